@@ -11,10 +11,16 @@ One "step" = one batch of 16 frames per GPU.  With N > 1 (launched by torch.dist
 one process per GPU) every rank processes its own 16 frames (weak scaling) and the 3x3
 thetas are all-gathered over RCCL each step.
 
-Prints ONE JSON line (rank 0) with the contract fields plus
+Prints ONE JSON line (rank 0).  A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps and
+prints the contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step, ...) and nothing else.  With
+--full the line also holds
   roofline     - live HIP-event timing of the DoubleConv 3x3 MFMA launches vs the matrix peak of the mode
+  kernel_groups, value_predict_sync - an unpipelined pass of the same K steps behind the timed region
   cpu_baseline - the CPU oracle (oracle/torch_ref.predict) timed on this box's host cores
-                 (rank 0, N == 1 only; reported baseline, not the target).
+                 (rank 0, N == 1 only; reported baseline, not the target)
+  device_calibration, per_rank, gather_check, parity, other_configs (C2d, C2 at batch 1 / 8 and in bf16x6 / fp32, C5,
+  C3, end to end from host frames).
+--dump-outputs DIR writes what the timed path returned in its last step as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -55,6 +61,29 @@ def usable_cores():
         except (OSError, ValueError, IndexError):
             pass
     return n
+
+
+DUMP_MAX_VALUES = 1 << 22        # per output array written by --dump-outputs (16 MiB in float32) ...
+DUMP_BUDGET_BYTES = 64 << 20     # ... and over all of them
+
+
+def dump_outputs(outdir, out):
+    """--dump-outputs: every array of `out` (what the timed path returned in its last step) as <outdir>/<name>.npy, float64
+    if it is float64, else float32 (the integer warp mask converts exactly).  An output of more than DUMP_MAX_VALUES values
+    (the logits: 14.7 M at 640x360 x 16) is written as a fixed sample of them: the values at DUMP_MAX_VALUES flat
+    positions drawn with seed 0, in increasing order, the same positions in every run of the same shape."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    left = DUMP_BUDGET_BYTES
+    for name in sorted(out):
+        a = out[name].detach().cpu().numpy()
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        if a.size > DUMP_MAX_VALUES:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_VALUES, replace=False))]
+        if a.nbytes > left:
+            raise SystemExit(f"--dump-outputs: {name} does not fit the {DUMP_BUDGET_BYTES >> 20} MiB budget")
+        left -= a.nbytes
+        np.save(os.path.join(outdir, name + ".npy"), a)
 
 
 def pmc_traffic(tag):
@@ -176,10 +205,11 @@ def c2_parity(net, dev):
     import numpy as np
     import torch
     from sfh_amd import synth
-    path = os.path.join(ROOT, "tests", "golden", "c2_640x360_b16.npz")
-    if not os.path.exists(path):
+    from oracle import golden
+    try:
+        g = golden.load(os.path.join(ROOT, "tests", "golden", "c2_640x360_b16.npz"))
+    except FileNotFoundError:
         return None
-    g = np.load(path)
     B, H, W = 16, 360, 640
     x = synth.frames_to_float(synth.synth_frames_u8(B, H, W, seed=0)).to(dev)
     with torch.no_grad():
@@ -281,6 +311,8 @@ def train_bench(args):
         loss = step()
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"loss": loss.detach().reshape(1)})
     return ({
         "metric": "training steps: frames/sec at %dx%d batch=%d (forward + losses + backward + clip + RMSprop)" % (W, H, B),
         "value": round(B * args.steps / el, 2), "unit": "frames/s", "n_gpus": 1, "steps": args.steps,
@@ -463,7 +495,7 @@ def extra_configs(args):
     del net, x, court, poi
     torch.cuda.empty_cache()
     a = copy.copy(args)
-    a.batch, a.width, a.height, a.steps, a.warmup, a.train_autograd = 16, 640, 360, 4, 2, False
+    a.batch, a.width, a.height, a.steps, a.warmup, a.train_autograd, a.dump_outputs = 16, 640, 360, 4, 2, False, None
     t = train_bench(a)
     res["C3_train_step_640x360_batch16"] = {k: t[k] for k in ("value", "unit", "ms_per_step", "steps", "warmup", "dtype",
                                                               "losses_and_optimizer", "peak_mem_gib", "final_loss",
@@ -492,7 +524,7 @@ def _run():
     ap.add_argument("--batch", type=int, default=16, help="frames per GPU per step")
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--height", type=int, default=360)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
     ap.add_argument("--cpu-frames", type=int, default=16,
                     help="frames of the same workload timed on the host cores for cpu_baseline (about 10 s)")
     ap.add_argument("--consistency", action="store_true",
@@ -522,7 +554,13 @@ def _run():
                     help="cpu: rehearsal of the multi-rank plumbing in the CPU tests (tests/test_sharding.py, gloo, a stand-in "
                          "model); the printed value then measures nothing")
     ap.add_argument("--no-extra-configs", action="store_true",
-                    help="skip the short C3 (training step) and C5 (1280x720) measurements appended at N=1")
+                    help="with --full: skip the short C3 (training step) and C5 (1280x720) measurements appended at N=1")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: device calibration, roofline and per-kernel figures, the unpipelined "
+                         "pass, CPU baseline, parity against the golden vector, per-rank figures, the exchange-step check and "
+                         "the other configurations (a plain run sets up, warms up, times --steps steps and prints the headline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_launch(args.gpus)
@@ -615,7 +653,8 @@ def _run():
             out = finish(pending.pop(0))
         return out
 
-    calib = device_calibration(dev) if on_gpu else None
+    full = args.full
+    calib = device_calibration(dev) if on_gpu and full else None
     bus = calib.get("pci") if calib else None
     with torch.no_grad():
         for k in range(args.warmup):
@@ -623,13 +662,13 @@ def _run():
         sync()
         if use_pg:
             dist.barrier()
-        # live HIP events around the launches of the dominant kernel (roofline); the other kernel groups are timed in the
-        # unpipelined pass behind the region when there is one (two event records per launch are not free: all 59 timed
-        # launches of a step cost about 0.2 ms of the step)
-        will_time_alone = not args.no_pipeline and not args.no_alone_pass
-        timer = engine.ConvTimer(only={"doubleconv3x3"} if will_time_alone else None)
+        # --full: live HIP events around the launches of the dominant kernel (roofline); the other kernel groups are timed
+        # in the unpipelined pass behind the region when there is one (two event records per launch are not free: all 59
+        # timed launches of a step cost about 0.2 ms of the step)
+        will_time_alone = full and not args.no_pipeline and not args.no_alone_pass
+        timer = engine.ConvTimer(only={"doubleconv3x3"} if will_time_alone else None) if full else None
         engine.PackedConv.timer = timer
-        power = PowerSampler(bus) if on_gpu else None
+        power = PowerSampler(bus) if on_gpu and full else None
         t0 = time.perf_counter()
         if power is not None:
             power.__enter__()
@@ -643,6 +682,49 @@ def _run():
         if power is not None:
             power.__exit__()
         engine.PackedConv.timer = None
+
+    # what the timed path returned in its last step (rank 0: its own frames), before anything else runs on the model
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
+    el = torch.tensor([elapsed], device=dev, dtype=torch.float64)
+    if use_pg:
+        dist.all_reduce(el, op=dist.ReduceOp.MAX)
+    elapsed = el.item()
+    frames_total = B * args.steps * world
+    fps = frames_total / elapsed
+    prec = net.precision
+
+    def headline():
+        """the contract fields of the result line (range counters as they stand when it is printed)"""
+        return {
+            "metric": "frames/sec at 640x360 batch=16 (1/2/4/8 GPU) + homography L1 vs ref",
+            "value": round(fps, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": {"bf16x6": "bf16x6->f32 (3-way bf16 split operands, 6 bf16 MFMA products, fp32 accumulate; fp32-equivalent)",
+                      "f16x3": "f16x3->f32 (2-way fp16 split operands = 22 significand bits, 3 fp16 MFMA products, fp32 "
+                               "accumulate; end-to-end error at the level of an fp32 run, see DESIGN.md section 2)"}.get(prec, "f32"),
+            "data": "synthetic",
+            "config": {"workload": f"predict(): UNet seg + ResNet34-STN + nearest warp, {W}x{H}, "
+                                   f"batch {B}/GPU, req_outputs=theta,warp_mask"
+                                   + (",consistency,poi" if args.consistency else ",consistency" if cons else ""),
+                       "frames_per_gpu_per_step": B, "global_batch": B * world,
+                       "pipeline": ("none: predict() per step" if args.no_pipeline else
+                                    "predict_async(): two batches in flight, ResNet-STN + warp of batch k on a side stream under the UNet of batch k + 1"),
+                       "precision": prec, "range_fallbacks": int(getattr(net, "range_fallbacks", 0)),
+                       "range_rescales": int(getattr(net, "range_rescales", 0)),
+                       "range_raises": int(getattr(net, "range_raises", 0)),
+                       "parallelism": (f"frame-sharded x{world}, all_gather_into_tensor(theta + consist_score) over "
+                                       + ("RCCL" if args.dist_backend == "nccl" else "gloo (REHEARSAL, ranks share a GPU)" if args.share_gpu else "gloo")
+                                       if world > 1 else
+                                       ("single GPU; exchange step forced through a one-rank " +
+                                        ("RCCL" if args.dist_backend == "nccl" else "gloo") + " process group (--force-collective)")
+                                       if use_pg else "single GPU")}}
+
+    if not full:
+        if rank == 0:
+            print(json.dumps(headline()), flush=True)
+        return
 
     # the exchange step, checked once outside the timed region: every rank holds world * B gathered rows, and its own
     # rows are the theta it computed in the last step
@@ -678,10 +760,6 @@ def _run():
             sync()
             engine.PackedConv.timer = None
         alone = (tm2.summary(), el2)
-    el = torch.tensor([elapsed], device=dev, dtype=torch.float64)
-    if use_pg:
-        dist.all_reduce(el, op=dist.ReduceOp.MAX)
-    elapsed = el.item()
     # per-rank figures: each rank's own step time and what its device sustains - a 4 % spread between the pool's devices
     # would otherwise read as a scaling loss (value = all frames / the SLOWEST rank's time)
     mine = {"rank": rank, "ms_per_step": round(own_elapsed / args.steps * 1e3, 3),
@@ -696,13 +774,10 @@ def _run():
     rms = sorted(r["ms_per_step"] for r in ranks)
     per_rank = {"ms_per_step_min": rms[0], "ms_per_step_median": rms[len(rms) // 2] if len(rms) % 2 else
                 round(0.5 * (rms[len(rms) // 2 - 1] + rms[len(rms) // 2]), 3), "ms_per_step_max": rms[-1], "ranks": ranks}
-    frames_total = B * args.steps * world
-    fps = frames_total / elapsed
 
     summ = timer.summary()
     n, fl, ms = summ.get("doubleconv3x3", (0, 0.0, 1.0))
     achieved = fl / (ms * 1e-3) / 1e12 if n else 0.0
-    prec = net.precision
     nprod = {"bf16x6": 6, "f16x3": 3}.get(prec)
     peak = {"bf16x6": BF16X6_PEAK_TFLOPS, "f16x3": F16X3_PEAK_TFLOPS}.get(prec, FP32_MFMA_PEAK_TFLOPS)
     x6 = nprod is not None
@@ -830,11 +905,8 @@ def _run():
         other_configs = extra_configs(args)
 
     if rank == 0:
-        line = {
-            "metric": "frames/sec at 640x360 batch=16 (1/2/4/8 GPU) + homography L1 vs ref",
-            "value": round(fps, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        line = headline()
+        line.update({
             "value_predict_sync": (round(B * args.steps / alone[1], 2) if alone is not None else round(fps, 2)) if world == 1 else None,
             "value_exact_operands": ((other_configs or {}).get("C2_640x360_batch16_bf16x6") or {}).get("value"),
             "value_exact_operands_note": "the same workload with every fp32 operand carried EXACTLY (bf16x6: three bf16 planes, six MFMA "
@@ -845,25 +917,6 @@ def _run():
                                                "pool's devices, which hold different clocks under an MFMA-dense load",
             "value_predict_sync_note": "frames/s of the drop-in predict() called per batch (no predict_async pipelining), "
                                        "same kernels, timed right after the headline region; N = 1 only",
-            "dtype": {"bf16x6": "bf16x6->f32 (3-way bf16 split operands, 6 bf16 MFMA products, fp32 accumulate; fp32-equivalent)",
-                      "f16x3": "f16x3->f32 (2-way fp16 split operands = 22 significand bits, 3 fp16 MFMA products, fp32 "
-                               "accumulate; end-to-end error at the level of an fp32 run, see DESIGN.md section 2)"}.get(prec, "f32"),
-            "data": "synthetic",
-            "config": {"workload": f"predict(): UNet seg + ResNet34-STN + nearest warp, {W}x{H}, "
-                                   f"batch {B}/GPU, req_outputs=theta,warp_mask"
-                                   + (",consistency,poi" if args.consistency else ",consistency" if cons else ""),
-                       "frames_per_gpu_per_step": B, "global_batch": B * world,
-                       "pipeline": ("none: predict() per step" if args.no_pipeline else
-                                    "predict_async(): two batches in flight, ResNet-STN + warp of batch k on a side stream under the UNet of batch k + 1"),
-                       "precision": prec, "range_fallbacks": int(getattr(net, "range_fallbacks", 0)),
-                       "range_rescales": int(getattr(net, "range_rescales", 0)),
-                       "range_raises": int(getattr(net, "range_raises", 0)),
-                       "parallelism": (f"frame-sharded x{world}, all_gather_into_tensor(theta + consist_score) over "
-                                       + ("RCCL" if args.dist_backend == "nccl" else "gloo (REHEARSAL, ranks share a GPU)" if args.share_gpu else "gloo")
-                                       if world > 1 else
-                                       ("single GPU; exchange step forced through a one-rank " +
-                                        ("RCCL" if args.dist_backend == "nccl" else "gloo") + " process group (--force-collective)")
-                                       if use_pg else "single GPU")},
             "roofline": roofline,
             "whole_step": {"algorithmic_gflop_per_step_per_gpu": round(step_gflop, 1), "tflops_per_gpu": round(whole_tf, 2),
                            "frac": round(whole_tf / mfma_peak, 4), "mfma_utilisation": round(whole_tf * (nprod or 1) / mfma_peak, 4),
@@ -878,7 +931,7 @@ def _run():
             "kernel_groups_measured_in": ("the unpipelined pass after the timed region (launches alone on the chip)"
                                           if alone is not None else "the timed region"),
             "other_configs": other_configs,
-        }
+        })
         print(json.dumps(line), flush=True)
 
 

@@ -1,7 +1,10 @@
 #!/bin/bash
 # Power / clock samples while bench.py runs (one gpurun call):  bash profiles/power_probe.sh [precision]
+# (bench.py --full: roofline is not in a plain run; the bench line goes to $OUT, default bench_runs/)
 export SFH_PRECISION=${1:-f16x3}
-python bench.py --no-cpu-baseline --no-extra-configs --steps 1200 --warmup 5 > gpurun_out/power_bench_$SFH_PRECISION.json 2> gpurun_out/power_bench.err &
+OUT=${OUT:-bench_runs}
+mkdir -p $OUT
+python bench.py --full --no-cpu-baseline --no-extra-configs --steps 1200 --warmup 5 > $OUT/power_bench_$SFH_PRECISION.json 2> $OUT/power_bench.err &
 BP=$!
 n=0
 while kill -0 $BP 2>/dev/null && [ $n -lt 400 ]; do
@@ -11,4 +14,4 @@ while kill -0 $BP 2>/dev/null && [ $n -lt 400 ]; do
   sleep 0.5
 done | awk '{ if ($NF+0 > 400) print }' | head -40
 wait $BP
-python -c "import json;d=json.loads(open('gpurun_out/power_bench_$SFH_PRECISION.json').read().strip().splitlines()[-1]);print(d['value'], d['ms_per_step'], d['roofline']['frac'])"
+python -c "import json;d=json.loads(open('$OUT/power_bench_$SFH_PRECISION.json').read().strip().splitlines()[-1]);print(d['value'], d['ms_per_step'], d['roofline']['frac'])"

@@ -6,7 +6,7 @@ TAG=${1:-r02h}
 ROOTD=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOTD/gpurun_out
 cd /tmp && export TMPDIR=/tmp
-ARGS="--steps 2 --warmup 1 --no-cpu-baseline --no-extra-configs"
+ARGS="--full --steps 2 --warmup 1 --no-cpu-baseline --no-extra-configs"
 rm -rf $OUT/${TAG}_sqA $OUT/${TAG}_sqB $OUT/${TAG}_tc
 timeout -k 10 300 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_LDS SQ_VALU_MFMA_BUSY_CYCLES --output-format csv -d $OUT/${TAG}_sqA -- python3 $ROOTD/bench.py $ARGS > $OUT/${TAG}_sqA.log 2>&1
 echo A

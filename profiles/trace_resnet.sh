@@ -4,7 +4,7 @@ TAG=${1:-r03}
 ROOTD=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOTD/gpurun_out
 cd /tmp && export TMPDIR=/tmp
-ARGS="--steps 3 --warmup 1 --no-cpu-baseline --no-extra-configs"
+ARGS="--full --steps 3 --warmup 1 --no-cpu-baseline --no-extra-configs"
 rm -rf $OUT/${TAG}_rn_split $OUT/${TAG}_rn_nosplit
 timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/${TAG}_rn_split -- python3 $ROOTD/bench.py $ARGS > $OUT/${TAG}_rn_split.log 2>&1
 export SFH_SPLITK=0

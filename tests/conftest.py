@@ -15,8 +15,8 @@ def pytest_configure(config):
 
 @pytest.fixture(scope="session")
 def golden_blocks():
-    import numpy as np
-    return np.load(os.path.join(GOLDEN, "blocks.npz"))
+    from oracle import golden
+    return golden.load(os.path.join(GOLDEN, "blocks.npz"))
 
 
 @pytest.fixture(scope="session")

@@ -23,7 +23,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-from oracle import train_ref, warp_ref  # noqa: E402
+from oracle import golden, train_ref, warp_ref  # noqa: E402
 from sfh_amd import synth  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -148,7 +148,7 @@ def _check_predict(tag, out, g, court, wh, nframes_golden):
 
 @pytest.mark.parametrize("precision", ["f16x3", "bf16x6", "fp32"])
 def test_c2_640x360_batch16_golden(precision):
-    g = np.load(os.path.join(GOLD, "c2_640x360_b16.npz"))
+    g = golden.load(os.path.join(GOLD, "c2_640x360_b16.npz"))
     net, _, court, _ = _net("ncaa_nc4_640x360", (640, 360), 16, precision)
     x = synth.frames_to_float(synth.synth_frames_u8(16, 360, 640, seed=0))
     with torch.no_grad():
@@ -167,7 +167,7 @@ def test_c2d_predict_py_default_geometry_unet640x360_warp1280x720(precision):
     the consistency score through the resized mask, POI; all of C2's logit checks as well."""
     from oracle import torch_ref
     from sfh_amd.reconstructor import Reconstructor
-    g2 = np.load(os.path.join(GOLD, "c2_640x360_b16.npz"))
+    g2 = golden.load(os.path.join(GOLD, "c2_640x360_b16.npz"))
     g = np.load(os.path.join(GOLD, "c2d_unet640x360_warp1280x720_b16.npz"))
     B, W, H, WW, WH = 16, 640, 360, 1280, 720
     court = synth.load_court_template("ncaa_nc4_1280x720", 4, B)
@@ -216,7 +216,7 @@ def test_c2d_predict_py_default_geometry_unet640x360_warp1280x720(precision):
 def test_c5_1280x720_batch16_pitch_template_poi(precision):
     """predict.py's HD configuration (predict.py:151-155,186-192): 16 frames in one call - whatever sub-batching
     the 32-bit tensor addressing needs happens inside predict()."""
-    g = np.load(os.path.join(GOLD, "c5_1280x720_b16.npz"))
+    g = golden.load(os.path.join(GOLD, "c5_1280x720_b16.npz"))
     net, _, court, _ = _net("pitch_v3_nc4_1280x720", (1280, 720), 16, precision)
     x = synth.frames_to_float(synth.synth_frames_u8(16, 720, 1280, seed=0))
     with torch.no_grad():
@@ -243,7 +243,7 @@ def test_theta_only_predict_640x360_b8(precision):
     bias: models/resnet.py:206-208) theta is the identity BIT FOR BIT whatever the conv stack computes."""
     from oracle import torch_ref
     from sfh_amd.reconstructor import Reconstructor
-    g = np.load(os.path.join(GOLD, "c2_640x360_b16.npz"))
+    g = golden.load(os.path.join(GOLD, "c2_640x360_b16.npz"))
     B, W, H = 8, 640, 360
     court = synth.load_court_template("ncaa_nc4_640x360", 4, B)
     poi = synth.load_court_poi("pitch", B)
@@ -386,7 +386,7 @@ def test_c3_batch16_forward_losses_and_running_stats(precision, monkeypatch):
     from sfh_amd import training
     from sfh_amd.reconstructor import Reconstructor
     monkeypatch.setenv("SFH_TRAIN_PRECISION", precision)
-    g = np.load(os.path.join(GOLD, "c3_fwd_640x360_b16.npz"))
+    g = golden.load(os.path.join(GOLD, "c3_fwd_640x360_b16.npz"))
     B, H, W = 16, 360, 640
     court = synth.load_court_template("ncaa_nc4_640x360", 4, B)
     poi = synth.load_court_poi("pitch", B)

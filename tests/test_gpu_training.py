@@ -6,7 +6,7 @@ import pytest
 import torch
 
 from sfh_amd import modules, synth
-from oracle import torch_ref, train_ref
+from oracle import golden, torch_ref, train_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -349,7 +349,7 @@ def test_full_training_forward_backward(T, prec, monkeypatch):
 @pytest.fixture(scope="module")
 def golden_train():
     import os
-    return np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "train_blocks.npz"))
+    return golden.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "train_blocks.npz"))
 
 
 def _golden_case(T, g, tag, mod, seed, build):

@@ -226,7 +226,7 @@ def _bench_main_worker(rank, world, port, q):
     bench = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(bench)
     sys.argv = ["bench.py", "--gpus", str(world), "--steps", "3", "--warmup", "1", "--device", "cpu", "--dist-backend", "gloo",
-                "--no-cpu-baseline", "--no-extra-configs"] + (["--force-collective"] if world == 1 else [])
+                "--full", "--no-cpu-baseline", "--no-extra-configs"] + (["--force-collective"] if world == 1 else [])
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
         bench.main()
@@ -315,13 +315,86 @@ def _bench_main_one_rank_worker(q):
     bench = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(bench)
     sys.argv = ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--device", "cpu", "--dist-backend", "gloo",
-                "--no-cpu-baseline", "--no-extra-configs", "--force-collective"]
+                "--full", "--no-cpu-baseline", "--no-extra-configs", "--force-collective"]
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
         bench.main()
     lines = [ln for ln in buf.getvalue().splitlines() if ln.startswith("{")]
     import torch.distributed as dist
     q.put((0, json.loads(lines[-1]) if lines else None, dist.is_initialized()))
+
+
+def _load_bench():
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_bench_plain_run_prints_the_headline_only_and_dumps_the_last_step(monkeypatch, tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` (CPU, the stand-in model): the line holds the contract fields and
+    nothing that --full measures; --dump-outputs writes the outputs of the last timed step as float32 .npy files, the
+    same in every run with the same arguments."""
+    import contextlib
+    import io
+    import json
+    import numpy as np
+    import sfh_amd.reconstructor as R
+    from sfh_amd import synth
+    monkeypatch.setattr(R, "Reconstructor", _StandInReconstructor)
+    real = synth.synth_frames_u8
+    monkeypatch.setattr(synth, "synth_frames_u8", lambda B, H, W, seed=0: real(B, 36, 64, seed=seed))
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
+        monkeypatch.delenv(k, raising=False)
+    bench = _load_bench()
+    lines, dumps = [], []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--device", "cpu",
+                                          "--dist-backend", "gloo", "--dump-outputs", str(d)])
+        buf = io.StringIO()
+        with contextlib.redirect_stdout(buf):
+            bench.main()
+        lines.append([json.loads(ln) for ln in buf.getvalue().splitlines() if ln.startswith("{")])
+        dumps.append({p.stem: np.load(p) for p in d.glob("*.npy")})
+    assert [len(x) for x in lines] == [1, 1]
+    line = lines[0][0]
+    assert set(line) == {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                         "vs_baseline", "dtype", "data", "config"}
+    assert line["metric"].startswith("frames/sec at 640x360 batch=16") and line["unit"] == "frames/s"
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["higher_is_better"] is True and line["n_gpus"] == 1
+    assert abs(line["value"] - 16 * 3 / (line["ms_per_step"] * 3e-3)) < 0.02 * line["value"]
+    assert line["dtype"].startswith("f16x3->f32") and line["config"]["parallelism"] == "single GPU"
+    assert set(dumps[0]) == {"theta", "logits"} and all(a.dtype == np.float32 for a in dumps[0].values())
+    # the third timed step runs batch 0 of the two resident batches (seed 0)
+    x = synth.frames_to_float(synth.synth_frames_u8(16, 360, 640, seed=0))
+    want = _StandInReconstructor(None, None).predict(x, consistency=False)
+    np.testing.assert_array_equal(dumps[0]["theta"], want["theta"].numpy())
+    np.testing.assert_array_equal(dumps[0]["logits"], want["logits"].numpy())
+    assert all(np.array_equal(dumps[0][k], dumps[1][k]) for k in dumps[0])
+
+
+def test_bench_dump_outputs_samples_large_arrays_at_fixed_positions(monkeypatch, tmp_path):
+    """dump_outputs: integer outputs as exact float32, float64 kept, an output above the per-array limit written as the
+    values at fixed seeded positions in increasing order, and the whole dump held to the budget."""
+    import numpy as np
+    bench = _load_bench()
+    monkeypatch.setattr(bench, "DUMP_MAX_VALUES", 100)
+    big = torch.arange(1000, dtype=torch.float32).reshape(10, 100)
+    out = {"big": big, "mask": torch.arange(12, dtype=torch.int32), "d": torch.ones(3, dtype=torch.float64)}
+    bench.dump_outputs(str(tmp_path / "a"), out)
+    bench.dump_outputs(str(tmp_path / "b"), out)
+    a = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in out}
+    b = np.load(tmp_path / "b" / "big.npy")
+    assert a["mask"].dtype == np.float32 and a["mask"].tolist() == list(range(12))
+    assert a["d"].dtype == np.float64 and a["d"].shape == (3,)
+    assert a["big"].dtype == np.float32 and a["big"].shape == (100,) and np.array_equal(a["big"], b)
+    assert (np.diff(a["big"]) > 0).all() and set(a["big"].tolist()) <= set(range(1000))
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 200)
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "c"), out)
 
 
 def _bench_main_raises_worker(q):

@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import post_ref, warp_ref
+from oracle import golden, post_ref, warp_ref
 from sfh_amd import synth
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -26,7 +26,7 @@ def _pin_thetas():
     a near-singular one (Z crosses zero inside the frame) and one that maps the whole frame out of bounds"""
     t = [np.eye(3, dtype=np.float32)] + [m for m in synth.REALISTIC_THETAS]
     for f in ("c2_640x360_b16.npz", "c5_1280x720_b16.npz"):
-        g = np.load(os.path.join(GOLDEN, f))
+        g = golden.load(os.path.join(GOLDEN, f))
         t += [m for m in g["theta"].reshape(-1, 3, 3)[:4]]
     sing = np.eye(3, dtype=np.float32)
     sing[2] = (0.9, 0.4, 1e-3)                     # Z = 0.9 x + 0.4 y + 0.001: zero along a line through the frame
