@@ -682,6 +682,40 @@ int sfh_rows_differ(const void* x, int64_t row_words, int rows, uint32_t* flag, 
 int sfh_stn_input_assemble(const float* logits, int nc, const float* frame, int cf, const float* uv, int cu, int batch, int H,
                            int W, int cs, float* dst, void* stream);
 
+/* Validation scores (eval.py:142-234, eval_reconstructor): slots of the fp64 accumulator vector that sfh_eval_batch adds one
+ * batch into.  The caller zero-fills it once per evaluation and writes len(loader) into SFH_EVAL_NBATCH; sfh_uv_loss (lambda
+ * 1) adds the uv score into SFH_EVAL_UV; SFH_EVAL_BAD mirrors the error flag.  Summed over ranks as one vector.            */
+#define SFH_EVAL_SEG 0
+#define SFH_EVAL_REC 1
+#define SFH_EVAL_UV 2
+#define SFH_EVAL_REPROJ 3
+#define SFH_EVAL_REPROJ_PX 4
+#define SFH_EVAL_CONSIST 5
+#define SFH_EVAL_NBATCH 6
+#define SFH_EVAL_FRAMES 7
+#define SFH_EVAL_BAD 8
+#define SFH_EVAL_SLOTS 9
+
+/* Workspace of sfh_eval_batch in doubles: 5 per frame row plus 7 per frame; -1 for a bad shape.                          */
+int64_t sfh_eval_workspace_doubles(int batch, int H, int W);
+
+/* One validation batch into acc (SFH_EVAL_* slots), deterministic (fixed-order fp64 sums, no atomics on any sum), no host
+ * synchronisation.  logits NCHW (B,nc,H,W) fp32, mask int64 (B,H,W), warp_mask fp32 (B,H,W); logits or warp_mask may be NULL
+ * (that score is skipped), the mask may be NULL only if both are.  Per pixel, lse = logsumexp over the nc logits:
+ *   seg     = lse - L[g], 0 and not counted where g == -100 (F.cross_entropy's ignore_index);
+ *   rec     = (warp - fp32(g) / nc)^2;
+ *   consist = lse - L[trunc(fp32(warp * nc))], 0 and not counted where that class is -100.
+ * weight (B) fp32 non-NULL: acc[SEG] += mean_b(weight_b * mean_px seg), acc[REC] likewise (models/losses.py:33-41); NULL:
+ * acc[SEG] += sum seg / counted pixels, acc[REC] += mean rec.  acc[CONSIST] += sum consist / counted pixels (if both logits and
+ * warp).  poi, gt_poi (B,npts,2), nonzeros (B,npts), num_nonzero (B), all fp32, all NULL or none: acc[REPROJ] += sum_b
+ * sum_n ||gt - poi|| * nonzeros / num_nonzero (models/losses.py:6-19, reduction 'sum') and acc[REPROJ_PX] += the same with x
+ * scaled by target_w and y by target_h in fp32 (eval.py:205-215).  acc[FRAMES] += B.  A mask id outside [0, nc) other than
+ * -100 ORs 1, a consistency class outside [0, nc) other than -100 (NaN included) ORs 2 into *flag (caller-zeroed, sticky;
+ * torch raises on both); acc[BAD] = *flag after the batch.  workspace: sfh_eval_workspace_doubles(batch, H, W); nc 1 .. 8. */
+int sfh_eval_batch(const float* logits, const int64_t* mask, const float* warp_mask, const float* weight, int nc, int batch,
+                   int H, int W, const float* poi, const float* gt_poi, const float* nonzeros, const float* num_nonzero, int npts,
+                   float target_w, float target_h, double* workspace, uint32_t* flag, double* acc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -159,6 +159,9 @@ SIGNATURES = {
     "sfh_warp_consistency_workspace_floats": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "sfh_warp_consistency_fwd": (C.c_int, [_p, _p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _p, C.c_int,
                                            C.c_int, C.c_int, _p, _p, _p, _p]),
+    "sfh_eval_workspace_doubles": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "sfh_eval_batch": (C.c_int, [_p, _p, _p, _p, C.c_int, C.c_int, C.c_int, C.c_int, _p, _p, _p, _p, C.c_int,
+                                 C.c_float, C.c_float, _p, _p, _p, _p]),
 }
 
 _lib = None

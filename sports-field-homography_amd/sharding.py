@@ -203,3 +203,15 @@ def allreduce_gradients(flat, group=None, force_collective=False):
         return 1.0
     dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=group)
     return 1.0 / world
+
+
+def allreduce_scores(vec, group=None, force_collective=False):
+    """Sum a small score accumulator (evaluation.eval_reconstructor: the fp64 vector of summed batch scores, batch and frame
+    counts) over the ranks in place - ONE all_reduce per evaluation, before the host divides.  Each rank has iterated its
+    own shard of the validation batches (DistributedSampler-style); without a peer (and without force_collective) the
+    vector is returned untouched."""
+    if not dist.is_initialized():
+        return vec
+    if _use_collective(dist.get_world_size(group), force_collective):
+        dist.all_reduce(vec, op=dist.ReduceOp.SUM, group=group)
+    return vec
