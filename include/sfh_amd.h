@@ -716,6 +716,38 @@ int sfh_eval_batch(const float* logits, const int64_t* mask, const float* warp_m
                    int H, int W, const float* poi, const float* gt_poi, const float* nonzeros, const float* num_nonzero, int npts,
                    float target_w, float target_h, double* workspace, uint32_t* flag, double* acc, void* stream);
 
+/* Training augmentation of a batch on the device (utils/augmentation.py: torchvision ColorJitter, GaussianBlur,
+ * RandomResizedCrop, RandomHorizontalFlip, UVHorizontalFlip, PoIHorizontalFlip), csrc/augment.hip.  Every random decision is
+ * made by the caller and arrives in `params`: device int32 (B,16) per sample = order[4] (the jitter op of slot 0..3: 0
+ * brightness, 1 contrast, 2 saturation, 3 hue), factor[4] per op (fp32 bits), enabled (bit op), sigma (fp32 bits, 0 = no
+ * blur), crop i, j, h, w, flip, 0.  The caller validates it (a permutation, finite factors, the crop inside the frame); the
+ * kernels clamp the crop so that no block can address outside the frame.  No atomics: results are bit-reproducible.      */
+
+/* Row partials of sfh_aug_gray_mean in doubles (batch * H); -1 for a bad shape.                                          */
+int64_t sfh_aug_workspace_doubles(int batch, int H);
+
+/* Contrast's mean, first stage (needed only when some sample has contrast enabled): per frame row, the sum in fp64 of
+ * gray = 0.2989 r + 0.587 g + 0.114 b of the frame (uint8 (B,H,W,3), / 255) after the ops that precede contrast in that
+ * sample's order -> workspace[b * H + y] (0 for a sample without contrast).                                               */
+int sfh_aug_gray_mean(const uint8_t* frames, const int32_t* params, int batch, int H, int W, double* workspace, void* stream);
+
+/* The fused pass: frames uint8 (B,H,W,3) -> image fp32 (B,3,H,W) = flip(resize(crop(blur(jitter(frames / 255))))) with
+ * torchvision.transforms.functional's tensor arithmetic in fp32: the jitter ops in the sample's order (contrast against the
+ * mean of the whole frame: the fixed-order sum of `workspace` / (H * W); workspace NULL = no sample has contrast on), a
+ * blur_k x blur_k Gaussian of the sample's sigma with reflect padding at the frame border (blur_k odd, 1 .. 11; 1 = none),
+ * bilinear align_corners=False resize of the crop to (H,W), horizontal flip.  masks uint8 (B,H,W) -> mask_out int64 and uv
+ * fp32 (B,uv_channels,H,W) -> uv_out through the same crop with legacy nearest (src = min(floor(dst * (float)in / out),
+ * in - 1)) and flip, uv channel 0 becoming (u > 0) - u under a flip; either pair may be NULL.  mean_out (B) fp32 or NULL:
+ * the contrast mean used per sample (0 where contrast is off).                                                            */
+int sfh_aug_apply(const uint8_t* frames, const uint8_t* masks, const float* uv, const int32_t* params, const double* workspace,
+                  int batch, int H, int W, int blur_k, int uv_channels, float* image, int64_t* mask_out, float* uv_out,
+                  float* mean_out, void* stream);
+
+/* poi (B,npts,2) / nonzeros (B,npts) fp32 of flipped samples through the involution perm (int32, npts): out[n] =
+ * (1 - poi[perm[n]].x, poi[perm[n]].y), nonzeros_out[n] = nonzeros[perm[n]]; other samples are copied.  nonzeros may be NULL. */
+int sfh_aug_poi_flip(const float* poi, const float* nonzeros, const int32_t* perm, const int32_t* params, int batch, int npts,
+                     float* poi_out, float* nonzeros_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -162,6 +162,10 @@ SIGNATURES = {
     "sfh_eval_workspace_doubles": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "sfh_eval_batch": (C.c_int, [_p, _p, _p, _p, C.c_int, C.c_int, C.c_int, C.c_int, _p, _p, _p, _p, C.c_int,
                                  C.c_float, C.c_float, _p, _p, _p, _p]),
+    "sfh_aug_workspace_doubles": (C.c_int64, [C.c_int, C.c_int]),
+    "sfh_aug_gray_mean": (C.c_int, [_p, _p, C.c_int, C.c_int, C.c_int, _p, _p]),
+    "sfh_aug_apply": (C.c_int, [_p, _p, _p, _p, _p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p, _p, _p, _p, _p]),
+    "sfh_aug_poi_flip": (C.c_int, [_p, _p, _p, _p, C.c_int, C.c_int, _p, _p, _p]),
 }
 
 _lib = None
