@@ -748,6 +748,41 @@ int sfh_aug_apply(const uint8_t* frames, const uint8_t* masks, const float* uv, 
 int sfh_aug_poi_flip(const float* poi, const float* nonzeros, const int32_t* perm, const int32_t* params, int batch, int npts,
                      float* poi_out, float* nonzeros_out, void* stream);
 
+/* Court overlay frames (viz_preds.py:117-146, utils/postprocess.py:21-65), csrc/overlay.hip.  `source` of both entries:   */
+#define SFH_OVERLAY_AUTO 0   /* per frame from score[b]: warp leg where score[b] < score_threshold, else segmentation leg */
+#define SFH_OVERLAY_WARP 1   /* every frame takes the warp leg (score may be NULL)                                         */
+#define SFH_OVERLAY_SEGM 2   /* every frame takes the segmentation leg (score may be NULL)                                 */
+#define SFH_OVERLAY_LABEL_MAX 32   /* glyphs of a label row (the L of sfh_overlay_annotate) at most                        */
+
+/* ONE launch: frames uint8 (B,H,W,3) -> out uint8 (B,H,W,3), out == frames allowed (a pixel depends on its own frame pixel
+ * only).  Per frame a class-id mask comes from one of two legs, chosen on the device:
+ *   warp leg: trunc(nearest homography warp of tmpl (ht x wt, batch stride tmpl_bstride floats, 0 = one shared image) by
+ *             theta[b] at (H,W) * out_scale) - the ids of sfh_homography_warp_fwd(mode 0, out_i32) for the same arguments;
+ *   segmentation leg: segm (B,hs,ws) int32 ids (segm_kind 0) / uint8 ids (1) or fp32 NCHW logits (B,nc,hs,ws) (2, first
+ *             maximum wins), resized to (H,W) with sfh_mask_format_fwd's INTER_NEAREST index rule; segm NULL: no mask.
+ * palette: HOST pointer to 8 x 3 bytes, ids outside 0..7 count as 0.  A pixel whose colour is (0,0,0) keeps the frame bytes,
+ * any other becomes (colour_c + frame_c) >> 1 per channel (= the reference's float64 colour * 0.5 + frame * 0.5 truncated).
+ * The blend is applied when the frame has a mask and (use_overlay_threshold == 0 or score[b] < overlay_threshold); otherwise
+ * the frame is copied.  score: device fp32 (B); required for SFH_OVERLAY_AUTO and with an overlay threshold.  A NaN score
+ * compares false everywhere.  theta / tmpl may be NULL for SFH_OVERLAY_SEGM.                                              */
+int sfh_overlay_render(const uint8_t* frames, uint8_t* out, int batch, int H, int W, const float* theta, const float* tmpl,
+                       int64_t tmpl_bstride, int ht, int wt, float out_scale, const void* segm, int segm_kind, int nc, int hs,
+                       int ws, const float* score, float score_threshold, int source, int use_overlay_threshold,
+                       float overlay_threshold, const uint8_t* palette, void* stream);
+
+/* ONE launch over out uint8 (B,H,W,3): POI markers and a label per frame; either part may be absent (poi / labels NULL).
+ * Markers: poi (B,npts,2) fp32 in [0,1]; centre = (rint(x * W), rint(y * H)), the product exact in fp64, ties to even; a
+ * filled disc dx^2 + dy^2 <= radius^2 of marker_color (HOST pointer, 3 bytes) clipped at the frame border; a NaN / inf
+ * centre draws nothing; radius 0 draws no markers.  Label: labels int8 (B,L) glyph codes of the 5x7 font in csrc/overlay.hip
+ * (0-9 digits, 10 '.', 11 '-', 12 '+', 13 'e', 14 ' ', 15 'n', 16 'a', 17 'i', 18 'f'; a negative code ends the row), L <=
+ * SFH_OVERLAY_LABEL_MAX, glyph cells of 6 x 7 font pixels of label_scale x label_scale frame pixels, top-left at (label_x,
+ * label_y), clipped; colour (0,255,0) where score[b] < score_threshold, else (0,0,255); with score NULL (forced source
+ * only) (0,255,0) for SFH_OVERLAY_WARP and (0,0,255) for SFH_OVERLAY_SEGM.  Deterministic: a later point index wins over an
+ * earlier one and the label is drawn last - every pixel has exactly one writer.                                           */
+int sfh_overlay_annotate(uint8_t* out, int batch, int H, int W, const float* poi, int npts, int radius,
+                         const uint8_t* marker_color, const int8_t* labels, int L, int label_x, int label_y, int label_scale,
+                         const float* score, float score_threshold, int source, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -166,6 +166,10 @@ SIGNATURES = {
     "sfh_aug_gray_mean": (C.c_int, [_p, _p, C.c_int, C.c_int, C.c_int, _p, _p]),
     "sfh_aug_apply": (C.c_int, [_p, _p, _p, _p, _p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p, _p, _p, _p, _p]),
     "sfh_aug_poi_flip": (C.c_int, [_p, _p, _p, _p, C.c_int, C.c_int, _p, _p, _p]),
+    "sfh_overlay_render": (C.c_int, [_p, _p, C.c_int, C.c_int, C.c_int, _p, _p, C.c_int64, C.c_int, C.c_int, C.c_float, _p,
+                                     C.c_int, C.c_int, C.c_int, C.c_int, _p, C.c_float, C.c_int, C.c_int, C.c_float, _p, _p]),
+    "sfh_overlay_annotate": (C.c_int, [_p, C.c_int, C.c_int, C.c_int, _p, C.c_int, C.c_int, _p, _p, C.c_int, C.c_int, C.c_int,
+                                       C.c_int, _p, C.c_float, C.c_int, _p]),
 }
 
 _lib = None

@@ -12,7 +12,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB = os.path.join(_HERE, "libsfh_amd.so")
 SOURCES = ["capi.hip", "conv_mfma.hip", "conv_s3.hip", "conv_c4h2.hip", "pointwise.hip", "warp.hip", "train.hip", "stem.hip",
            "wgrad_s3.hip", "probe.hip", "conv_small.hip", "conv_upfused.hip", "hostprep.hip",
-           "eval.hip", "augment.hip"]
+           "eval.hip", "augment.hip", "overlay.hip"]
 # warp.hip's coordinate arithmetic must not be contracted into FMAs (bit-exact nearest
 # sampling against oracle/warp_ref.py); the flag is harmless elsewhere.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off",
@@ -26,7 +26,9 @@ EXTRA_FLAGS = {"warp.hip": _NO_SLP, "conv_s3.hip": _NO_SLP, "conv_mfma.hip": _NO
                "conv_c4h2.hip": _NO_SLP, "conv_small.hip": _NO_SLP, "conv_upfused.hip": _NO_SLP,
                # augment.hip by the same reasoning, not by measurement: its hue leg (RGB -> HSV -> RGB, four IEEE divisions
                # per pixel) makes the staging loop VALU-issue-bound, the case the half-rate packed forms hurt
-               "augment.hip": _NO_SLP}
+               "augment.hip": _NO_SLP,
+               # overlay.hip's warp leg is the same coordinate arithmetic as warp.hip's, and as VALU-issue-bound
+               "overlay.hip": _NO_SLP}
 
 
 def _stale(target, deps):

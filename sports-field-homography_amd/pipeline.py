@@ -20,7 +20,9 @@ frame buffer has been read and may be refilled.
 
 Outputs and dtypes are those of predict.py:92-118 (``outputs.transfer_gpu_to_cpu`` is the synchronous version):
 ``segm_mask`` uint8 (B,H,W), ``warp_mask`` uint8 (B,H,W), ``theta`` float32 (B,1,3,3), ``consist_score`` float32 (B,),
-``poi`` float32 (B,N,2).
+``poi`` float32 (B,N,2).  With ``overlay=`` an ``OverlayRenderer`` and ``"overlay"`` requested, ``overlay`` uint8 (B,H,W,3): the
+uploaded frames at their decoded size with the court drawn over them (sfh_amd.visualize; viz_preds.py's frames, without
+the label - its text is the score, which is not on the host when the launch is enqueued).
 """
 import numpy as np
 import torch
@@ -57,13 +59,25 @@ class Ticket:
 
 
 class FramePipeline:
-    def __init__(self, net, batch, frame_hw, req_outputs=("theta", "warp_mask"), consistency=False, channels=3):
+    def __init__(self, net, batch, frame_hw, req_outputs=("theta", "warp_mask"), consistency=False, channels=3, overlay=None):
         """net: a Reconstructor on the GPU in eval mode; frame_hw = (H, W) of the DECODED frames (net.unet_size, or any
-        larger size: cv2.INTER_AREA's downscale runs on the GPU, engine.frames_u8_to_input); req_outputs as predict.py's --req_outputs."""
+        larger size: cv2.INTER_AREA's downscale runs on the GPU, engine.frames_u8_to_input); req_outputs as predict.py's --req_outputs.
+        overlay: a visualize.OverlayRenderer for the output "overlay" (its score is the consistency score: without
+        consistency the renderer must be source="warp" or "segm" and have no overlay threshold)."""
         self.net, self.B = net, int(batch)
         self.req = set(req_outputs)
         self.consistency = bool(consistency) or "consistency" in self.req
         self.poi = "poi" in self.req
+        self.overlay = None
+        if "overlay" in self.req:
+            if overlay is None:
+                raise ValueError('FramePipeline: the output "overlay" needs overlay=OverlayRenderer(...)')
+            if not self.consistency and (overlay.source == "auto" or overlay.overlay_threshold is not None):
+                raise ValueError('FramePipeline: without consistency=True there is no score - the OverlayRenderer must be '
+                                 'source="warp" or "segm" and have no overlay_threshold')
+            if channels != 3:
+                raise ValueError(f'FramePipeline: the output "overlay" needs 3-channel frames, not {channels}')
+            self.overlay = overlay
         p = next(net.parameters())
         if p.device.type != "cuda":
             raise RuntimeError("FramePipeline needs the model on the GPU (no CPU fallback)")
@@ -81,6 +95,9 @@ class FramePipeline:
             # buffers hold (or are receiving)
             s = {"u8": torch.empty((self.B, H, W, channels), dtype=torch.uint8, device=dev),
                  "consumed": None, "host": {}, "pending": None, "collected": None, "gen": 0}
+            if self.overlay is not None:
+                s["overlay"] = torch.empty((self.B, H, W, 3), dtype=torch.uint8, device=dev)
+                s["host"]["overlay"] = pin((self.B, H, W, 3), torch.uint8)
             if "segm_mask" in self.req:
                 s["host"]["segm_mask"] = pin((self.B, net.target_size[1], net.target_size[0]), torch.uint8)
             if "warp_mask" in self.req and net.warper:
@@ -146,6 +163,12 @@ class FramePipeline:
         for k in ("theta", "consist_score", "poi"):
             if k in s["host"]:
                 devout[k] = out[k]
+        if self.overlay is not None:
+            # drawn from the slot's uploaded frames: the next upload into them waits for this launch too
+            devout["overlay"] = self.overlay(s["u8"], out["theta"], score=out.get("consist_score"), segm=out.get("logits"),
+                                             poi=out.get("poi") if self.overlay.marker_radius > 0 else None, out=s["overlay"])
+            s["consumed"] = torch.cuda.Event()
+            s["consumed"].record(cur)
         ready = torch.cuda.Event()
         ready.record(cur)
         with torch.cuda.stream(self.d2h):
