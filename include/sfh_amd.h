@@ -140,7 +140,7 @@ typedef struct sfh_conv_desc {
   /* sfh_conv_s3_fwd, H2 sources: couts per workgroup. 0 = chosen by the launcher, 64 = the 4-wave workgroup
    * (256 pixels x 64 couts, two per CU), 128 = the 8-wave workgroup (256 pixels x 128 couts, one per CU, two LDS
    * buffers; needs stride 1, ksize 3 or 2, cout % 128 == 0 - per quadrant for the up-scatter conv -, at least 128
-   * input channels, no fused head). */
+   * input channels, no fused head).  Every other entry point (sfh_conv_small_fwd and sfh_conv_upfused_fwd included) ignores it. */
   int32_t wg_couts;
   /* kernels that split an fp32 source themselves (sfh_stem7x7_fwd): 0 or SFH_FMT_S3 = three bf16 planes, six products;
    * SFH_FMT_H2 = two fp16 planes, three products (weights from sfh_pack_stem_weights with the same format). */

@@ -48,7 +48,7 @@ print("composition identity (torch only): %.2e" % (ref2 - upart).abs().max().ite
 # (2) the HIP pair
 sk = E.f32_to_s3(skip.permute(0, 2, 3, 1).contiguous().cuda())
 xl = E.f32_to_s3(x.permute(0, 2, 3, 1).contiguous().cuda())
-k1 = PackedConv(conv.weight.detach()[:, :c0].contiguous(), None, None, 3, c0, relu=False, s3=True)
+k1 = PackedConv(conv.weight.detach()[:, :c0].contiguous(), None, None, 3, c0, relu=False, fmt="s3")
 k1.scale.copy_(fu.scale[:cout])
 part = torch.empty((B, 2 * h, 2 * w, cout), device="cuda")
 k1.run(sk, B, 2 * h, 2 * w, part)

@@ -15,7 +15,7 @@ B, cin, cout, h, w = 16, 512, 512, 45, 80
 for zero in (False, True):
     wt = torch.zeros(cout, cin, 3, 3, device="cuda") if zero else torch.randn(cout, cin, 3, 3, device="cuda") * 0.02
     x = torch.zeros(B, h, w, cin, device="cuda") if zero else torch.relu(torch.randn(B, h, w, cin, device="cuda"))
-    pc = E.PackedConv(wt, torch.zeros(cout, device="cuda"), None, 3, cin, s3=True)
+    pc = E.PackedConv(wt, torch.zeros(cout, device="cuda"), None, 3, cin, fmt="s3")
     xs = E.f32_to_s3(x); y = E.s3_empty(B, h, w, cout, "cuda")
     for _ in range(20): pc.run(xs, B, h, w, y)   # sustained load before timing
     t = bench(lambda: pc.run(xs, B, h, w, y), reps=20)

@@ -239,8 +239,8 @@ extern "C" int sfh_conv_upfused_fwd(const sfh_conv_desc* dp, void* stream_) {
               "conv_upfused_fwd: a tensor exceeds the 4 GiB descriptor range");
   g.bytes_skip = (unsigned)bs;
   g.bytes_low = (unsigned)bl;
-  g.xcd_order = d.wg_couts == 1 ? 0 : 1;     // (wg_couts = 1: the round-5 order, for same-device A/Bs)
-  const long nblocks = g.xcd_order ? (long)sfh_cdiv(g.ntiles, 8) * 8 * g.nblk : (long)g.ntiles * g.nblk;
+  g.xcd_order = 1;     // (sfh_conv_desc.wg_couts has no meaning here)
+  const long nblocks = (long)sfh_cdiv(g.ntiles, 8) * 8 * g.nblk;
   SFH_REQUIRE(nblocks < (1L << 31), "conv_upfused_fwd: grid too large");
   sfh_allow_big_lds((const void*)conv_upfused_kernel);
   hipLaunchKernelGGL(conv_upfused_kernel, dim3((unsigned)nblocks), dim3(256), SSLOTS * 16, (hipStream_t)stream_, d, g);

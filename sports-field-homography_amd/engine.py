@@ -1,440 +1,27 @@
 """Launch plans for the HIP hot path: weight packing, NHWC workspaces and the sequence
-of C-ABI calls that implements ``forward_unet`` / ``ResNetSTN`` / warp / POI / CE.
+of C-ABI calls that implements ``forward_unet`` / ``ResNetSTN`` / warp.
 
-PyTorch is used here for device memory (``torch.empty``), the current HIP stream and the
-parameter storage only; every arithmetic step is a call into ``libsfh_amd.so``.
+PyTorch is used here for device memory (``torch.empty``), the current HIP stream and the parameter storage only; every
+arithmetic step is a call into ``libsfh_amd.so``.  Host-prep helpers and format / layout wrappers: ``ops.py``; H2 range
+bookkeeping: ``h2ranges.py`` (both re-exported here).
 """
 import ctypes
-import math
 import os
-import threading
+from collections import namedtuple
 
 import torch
 
 from . import _lib
 from ._lib import ConvDesc
-
-BN_EPS = 1e-5
+from .h2ranges import FP16RangeExhausted, H2Ranges, _bits_to_float, _NoRanges  # noqa: F401
+from .ops import (PRECISIONS, _SPLIT, _SPLIT_DTYPES, _area_tab, _chan, _f32_to_split_into, _f32c,  # noqa: F401
+                  _fmt_code, _fmt_of, _hw, _ptr, _split_to_f32_into, _stream, _stream_scope, absminmax, absminmax_words,
+                  consistency_ce, f32_to_h2, f32_to_s3, f32_to_split, filled, frames_u8_to_input, h2_weight_exp,
+                  nchw_to_nhwc, nhwc_to_nchw, poi_project, resize_nchw, resolve_wexp, rows_all_equal, s3_empty, s3_to_f32,
+                  slice_in_channels, snapshot, split_empty, split_shape, stn_input_assemble, vec_op, weight_exps)
 
 # (tile id, rows, cols) of the stride-1 workgroup tiles; stride-2 tiles have half the rows.
 _TILES = ((_lib.TILE_8x32, 8, 32), (_lib.TILE_16x16, 16, 16), (_lib.TILE_32x8, 32, 8))
-
-
-# the HIP stream of the engine run() on this THREAD's stack (torch.cuda.current_stream() costs ~9 us per launch);
-# thread-local: another thread's run() - another model, device or torch.cuda.stream() context - has its own
-_STREAM_TLS = threading.local()
-
-
-def _stream():
-    stack = getattr(_STREAM_TLS, "stack", None)
-    if stack:
-        return stack[-1]
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-class _stream_scope:
-    """Resolve the current HIP stream once for all launches of one engine run (of the calling thread)."""
-
-    def __enter__(self):
-        stack = getattr(_STREAM_TLS, "stack", None)
-        if stack is None:
-            stack = _STREAM_TLS.stack = []
-        stack.append(ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-
-    def __exit__(self, *exc):
-        _STREAM_TLS.stack.pop()
-        return False
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _f32c(t, what):
-    if t.dtype != torch.float32 or not t.is_contiguous():
-        raise ValueError(f"{what}: expected a contiguous float32 tensor, got {t.dtype} "
-                         f"contiguous={t.is_contiguous()}")
-    if not t.is_cuda:
-        raise RuntimeError(f"{what}: tensor is on {t.device}; the HIP path needs a GPU tensor "
-                           "(there is no CPU fallback)")
-    return t
-
-
-# ---- engine-build helpers (csrc/hostprep.hip): the work around packing a checkpoint on this library's own kernels
-def filled(shape, dtype, device, value=0):
-    """torch.full / torch.zeros for 4-byte element types on this library's fill kernel"""
-    import struct
-    t = torch.empty(shape, dtype=dtype, device=device)
-    if t.element_size() != 4:
-        raise ValueError("filled: 4-byte element types only")
-    if t.numel():
-        word = struct.unpack("<I", struct.pack("<f" if dtype.is_floating_point else "<i", value))[0]
-        with torch.cuda.device(t.device):
-            _lib.check(_lib.load().sfh_fill_words(_ptr(t), t.numel(), word, _stream()), "fill_words")
-    return t
-
-
-_ABSMAX_TABLES = {}
-
-
-def absminmax_words(tensors):
-    """device int32 tensor of 2 words per tensor (sfh_multi_absminmax: bits of max |x|, 0x7FFFFFFF - bits of min |x|), no
-    read-back - for consumers that stay on the device (sfh_grad_scale)"""
-    import numpy as np
-    lib = _lib.load()
-    dev = tensors[0].device
-    for t in tensors:
-        _f32c(t, "absminmax operand")
-    # the (address, size) table lives on the device; a blocking upload would synchronise the caller's stream, so the table of
-    # a recurring set of tensors (a training step's gradient seeds come back at the same addresses) is uploaded once
-    key = (str(dev),) + tuple((t.data_ptr(), t.numel()) for t in tensors)
-    dtab = _ABSMAX_TABLES.get(key)
-    if dtab is None:
-        tab = np.array([(t.data_ptr(), t.numel()) for t in tensors], dtype=np.int64)
-        dtab = torch.from_numpy(tab.view(np.uint8).reshape(-1)).to(dev)
-        if len(_ABSMAX_TABLES) >= 16:
-            _ABSMAX_TABLES.pop(next(iter(_ABSMAX_TABLES)))
-        _ABSMAX_TABLES[key] = dtab
-    words = filled((2 * len(tensors),), torch.int32, dev)
-    _lib.check(lib.sfh_multi_absminmax(_ptr(dtab), len(tensors), _ptr(words), _stream()), "multi_absminmax")
-    return words
-
-
-def absminmax(tensors):
-    """[(max |x|, min |x|)] of float32 device tensors - ONE launch over all of them (sfh_multi_absminmax) and ONE
-    read-back, where torch would run an abs + a reduction + a host sync per tensor.  A non-finite element gives inf / nan."""
-    import numpy as np
-    if not tensors:
-        return []
-    w = absminmax_words(tensors).cpu().numpy().view(np.uint32)
-    mx = w[0::2].copy().view(np.float32)
-    mn = (np.uint32(0x7FFFFFFF) - w[1::2]).astype(np.uint32).view(np.float32)
-    return [(float(a), float(b)) for a, b in zip(mx, mn)]
-
-
-def h2_weight_exp(wmax, top=14):
-    """exponent e with max |w| * 2^e in [2^(top-1), 2^top) (include/sfh_amd.h, H2 weights); 0 for an all-zero tensor"""
-    import math
-    if not math.isfinite(wmax):
-        raise ValueError("conv weight holds non-finite values")
-    return max(-100, min(100, top - math.frexp(wmax)[1])) if wmax > 0 else 0
-
-
-def vec_op(a, b=None, op="scale", factor=1.0, out=None):
-    """out = a * factor ("scale"), a / b ("div") or a * b * factor ("mul") on the HIP helper kernel; b is indexed modulo
-    its length (a tiled operand); out may be a itself.  Small float32 vectors: a layer's folded scale / shift."""
-    lib = _lib.load()
-    code = {"scale": 0, "div": 1, "mul": 2}[op]
-    a = _f32c(a, "vec_op operand")
-    if out is None:
-        out = torch.empty_like(a)
-    if b is not None:
-        b = _f32c(b, "vec_op operand")
-    _lib.check(lib.sfh_vec_op(code, _ptr(a), _ptr(b) if b is not None else None, a.numel(), b.numel() if b is not None else 0,
-                              float(factor), _ptr(out), _stream()), "vec_op")
-    return out
-
-
-def snapshot(t):
-    """a private copy of a small float32 tensor (engines keep NO live reference to a parameter: load_state_dict writes
-    parameters in place, and an engine that finishes batches in flight must still see the weights it was built from)"""
-    return vec_op(_f32c(t.detach(), "snapshot operand"))
-
-
-def rows_all_equal(t):
-    """do all t[k] hold the bits of t[0]?  (4-byte elements, contiguous; one launch, one word read back)"""
-    lib = _lib.load()
-    if t.shape[0] <= 1:
-        return True
-    if not t.is_contiguous() or t.element_size() != 4 or not t.is_cuda:
-        raise ValueError("rows_all_equal: expected a contiguous GPU tensor of 4-byte elements")
-    flag = filled((1,), torch.int32, t.device)
-    _lib.check(lib.sfh_rows_differ(_ptr(t), t[0].numel(), t.shape[0], _ptr(flag), _stream()), "rows_differ")
-    return int(flag.cpu()[0]) == 0
-
-
-def stn_input_assemble(logits, frame, uv, cs):
-    """(B,H,W,cs) NHWC = cat((logits, frame, uv), 1) zero-padded (any of the three may be None): the ResNet-STN input of
-    the modes the fused OutConv epilogue does not cover (models/reconstructor.py:174-183,214)"""
-    lib = _lib.load()
-    srcs = [_f32c(t.contiguous(), "stn input source") if t is not None else None for t in (logits, frame, uv)]
-    ref = next(t for t in srcs if t is not None)
-    B, _, H, W = ref.shape
-    for t in srcs:
-        if t is not None and (t.shape[0], t.shape[2], t.shape[3]) != (B, H, W):
-            raise ValueError("stn_input_assemble: sources of different batch / size")
-    out = torch.empty((B, H, W, cs), dtype=torch.float32, device=ref.device)
-    ch = [t.shape[1] if t is not None else 0 for t in srcs]
-    _lib.check(lib.sfh_stn_input_assemble(_ptr(srcs[0]) if srcs[0] is not None else None, ch[0],
-                                          _ptr(srcs[1]) if srcs[1] is not None else None, ch[1],
-                                          _ptr(srcs[2]) if srcs[2] is not None else None, ch[2], B, H, W, cs, _ptr(out),
-                                          _stream()), "stn_input_assemble")
-    return out
-
-
-def slice_in_channels(w, c0, c1):
-    """w[:, c0:c1] of an OIHW weight as a contiguous tensor (sfh_copy2d_words)"""
-    lib = _lib.load()
-    w = _f32c(w.detach(), "conv weight")
-    cout, cin, kh, kw = w.shape
-    out = torch.empty((cout, c1 - c0, kh, kw), dtype=torch.float32, device=w.device)
-    _lib.check(lib.sfh_copy2d_words(ctypes.c_void_p(w.data_ptr() + 4 * c0 * kh * kw), cin * kh * kw, _ptr(out),
-                                    (c1 - c0) * kh * kw, (c1 - c0) * kh * kw, cout, _stream()), "copy2d_words")
-    return out
-
-
-# Split ("plane") activation formats of include/sfh_amd.h, identified by the tensor dtype:
-#   "s3": (B,H,C/32,3,4,W,8) bfloat16 - three bf16 planes, exact fp32 value            (precision "bf16x6")
-#   "h2": (B,H,C/32,2,4,W,8) float16  - two fp16 planes of v * 2^2, 22 significand bits (precision "f16x3")
-_SPLIT = {"s3": (torch.bfloat16, 3, _lib.FMT_S3), "h2": (torch.float16, 2, _lib.FMT_H2)}
-_SPLIT_DTYPES = {torch.bfloat16: "s3", torch.float16: "h2"}
-PRECISIONS = {"bf16x6": "s3", "f16x3": "h2", "fp32": None}
-
-
-def _fmt_of(t):
-    """"s3" / "h2" for a split tensor, None for fp32 NHWC"""
-    return _SPLIT_DTYPES.get(t.dtype)
-
-
-def _fmt_code(t):
-    f = _fmt_of(t)
-    return _SPLIT[f][2] if f else _lib.FMT_F32
-
-
-def _chan(t):
-    """channels per pixel of an activation tensor: fp32 NHWC (B,H,W,C) or split (B,H,C/32,planes,4,W,8)"""
-    return t.shape[2] * 32 if t.dtype in _SPLIT_DTYPES else t.shape[3]
-
-
-def _hw(t):
-    """(H, W) of an activation tensor in either format"""
-    return (t.shape[1], t.shape[5]) if t.dtype in _SPLIT_DTYPES else (t.shape[1], t.shape[2])
-
-
-def split_shape(fmt, b, h, w, c):
-    if c % 32:
-        raise ValueError(f"split-format tensors need a multiple of 32 channels, got {c}")
-    return (b, h, c // 32, _SPLIT[fmt][1], 4, w, 8)
-
-
-def s3_shape(b, h, w, c):
-    return split_shape("s3", b, h, w, c)
-
-
-def s3_empty(b, h, w, c, device):
-    """uninitialised split-bf16 activation tensor for c channels (c multiple of 32)"""
-    return torch.empty(s3_shape(b, h, w, c), dtype=torch.bfloat16, device=device)
-
-
-class FP16RangeExhausted(RuntimeError):
-    """an "f16x3" activation tensor is saturated and its exponent cannot be lowered any further"""
-
-
-class H2Ranges:
-    """Exponents and range words of the H2 (two-plane fp16, "f16x3") activation tensors of one model.
-
-    An H2 tensor stores u = v * 2^e and saturates beyond |v| = 65504 * 2^-e (include/sfh_amd.h); below |u| = 2^-3 its
-    low plane is an fp16 subnormal and the element keeps fewer than 22 bits.  Every tensor NAME has an exponent KEY -
-    tensors that enter one conv as its two sources share a key, and so do a conv output and the pooled copy its
-    producer writes - and a device word that the producing kernels raise (atomic max) to the largest bit pattern of
-    |v * 2^e| they produced, before saturation.  After a forward pass the host reads the words (`read`) and decides
-    in BOTH directions, one decision per key:
-
-    * a word above H2_LIMIT_BITS: the tensor was saturated; how far it overshot gives the exponent that fits (`lower`);
-    * every written word of a key below RAISE_BELOW (= 4: the largest element of the key's tensors sits within 2^5 of
-      the subnormal boundary, so a typical element, an order of magnitude below the peak, has lost bits - a "quiet"
-      layer): the exponent is RAISED so that the peak lands in [2^12, 2^13) like after `lower` (`quiet` / `raise_`).
-
-    The engines then repeat the pass from the first step that writes such a tensor.  Exponents start at the conventional
-    2; the state is sticky, shared by the UNet and ResNet engines of a Reconstructor and kept across engine rebuilds
-    (same model, new weights).  Hysteresis: the words are running maxima since the last reset (a reset happens only
-    together with a decision), so a key is raised only if EVERYTHING since then was quiet, and a key that `lower` has
-    touched is never raised above the exponent `lower` gave it until the weights change (`new_generation`)."""
-
-    LIMIT = _lib.H2_LIMIT_BITS
-    NONFINITE = 0x7F800000
-    DEFAULT = _lib.H2_ACT_EXP
-    MIN_EXP = -64
-    MAX_EXP = 48          # |v| down to 2^-36 reaches [2^12, 2^13); the kernels take -64 .. 64
-    RAISE_BELOW = 4.0     # stored peak |v * 2^e| below which a key counts as quiet (see above)
-
-    def __init__(self, device, capacity=1024):
-        self.device = device
-        self.words = filled((capacity,), torch.int32, device) if torch.device(device).type == "cuda" else \
-            torch.zeros(capacity, dtype=torch.int32, device=device)        # (CPU: the host-logic tests)
-        self.exps = {}     # key -> exponent (absent = DEFAULT)
-        self.slot = {}     # tensor name -> (key, word index)
-        self.peak = {}     # tensor name -> largest |v| seen so far (host side, from read())
-        self.ceiling = {}  # key -> exponent `lower` gave it in this weights generation: `raise_` never exceeds it
-        self._nwords = 0
-
-    def register(self, name, key=None, word_of=None):
-        """name: tensor; key: name of an already registered tensor whose exponent it shares; word_of: name of a
-        tensor whose word it shares (a pooled copy: its values are a subset of the other tensor's)."""
-        cur = self.slot.get(name)
-        k = self.slot[key][0] if key is not None else name
-        if cur is not None:
-            if cur[0] != k:
-                raise ValueError(f"H2 tensor {name!r} is tied to exponent key {cur[0]!r}, not {k!r}")
-            return
-        if word_of is not None:
-            idx = self.slot[word_of][1]
-        else:
-            idx = self._nwords
-            self._nwords += 1
-            if idx >= self.words.numel():
-                raise RuntimeError("H2Ranges: out of range words")
-        self.slot[name] = (k, idx)
-
-    def exp(self, name):
-        s = self.slot.get(name)
-        return self.exps.get(s[0], self.DEFAULT) if s is not None else self.DEFAULT
-
-    def key(self, name):
-        return self.slot[name][0]
-
-    def word_ptr(self, name):
-        s = self.slot.get(name)
-        return self.words.data_ptr() + 4 * s[1] if s is not None else None
-
-    def args(self, src=None, dst=None, res=None):
-        """keyword arguments of PackedConv.run / StemConv.run for a launch reading `src`, writing `dst` (+ residual)"""
-        return {"exp_src": self.exp(src), "exp_dst": self.exp(dst), "exp_res": self.exp(res),
-                "range_word": self.word_ptr(dst)}
-
-    def read(self):
-        """One device read-back: {tensor name: bit pattern of the largest |v * 2^e| since the words were zeroed}."""
-        n = self._nwords
-        if n == 0:
-            return {}
-        vals = self.words[:n].cpu().numpy().view("uint32")
-        out = {}
-        for name, (key, idx) in self.slot.items():
-            b = int(vals[idx])
-            out[name] = b
-            if 0 < b < self.NONFINITE:
-                v = _bits_to_float(b) * 2.0 ** -self.exps.get(key, self.DEFAULT)
-                if v > self.peak.get(name, 0.0):
-                    self.peak[name] = v
-        return out
-
-    def saturated(self, bits):
-        """names whose tensor left the fp16 range, and whether any of them holds a non-finite value"""
-        bad = [n for n, b in bits.items() if b > self.LIMIT]
-        return bad, any(bits[n] >= self.NONFINITE for n in bad)
-
-    def lower(self, bad, bits):
-        """Lower the exponents of the saturated tensors `bad` (names; bits = read()'s dict): ONE decision per exponent
-        key - a conv output and its pooled copy share word and key, a skip tensor and its up tensor share a key - from
-        the largest word of the key's tensors, converted with the exponent that was in force when the words were
-        written.  The new exponent puts the observed maximum into [2^12, 2^13) (8x headroom).  -> the set of keys.
-        Raises FP16RangeExhausted if a key cannot go lower (the caller falls back to the three-plane operands)."""
-        worst = {}
-        for n in bad:
-            key = self.slot[n][0]
-            worst[key] = max(worst.get(key, 0), bits[n])
-        before = {key: self.exps.get(key, self.DEFAULT) for key in worst}
-        for key, b in worst.items():
-            e = before[key]
-            vmax = _bits_to_float(b) * 2.0 ** -e
-            new = 13 - math.frexp(vmax)[1]                 # frexp: vmax = m * 2^x, 0.5 <= m < 1
-            new = max(self.MIN_EXP, min(new, e - 1))
-            if new >= e:
-                raise FP16RangeExhausted(f"H2 tensor group {key!r} is saturated at the lowest exponent {e}")
-            self.exps[key] = new
-            self.ceiling[key] = new
-        return set(worst)
-
-    def quiet(self, bits):
-        """The other direction (bits = read()'s dict of a pass WITHOUT saturated tensors): {key: larger exponent} for
-        every key whose written tensors all peaked below RAISE_BELOW in stored units - the largest word of the key,
-        converted with the exponent in force, goes to [2^12, 2^13).  A tensor whose word is still zero (a resumed pass
-        starts behind it) is judged by the peak it showed earlier in this weights generation; one that was never seen
-        says nothing, and a key with no seen tensor is left alone.  Never above the
-        exponent `lower` gave the key in this weights generation, never above MAX_EXP."""
-        top, skip = {}, set()
-        for n, b in bits.items():
-            s = self.slot.get(n)
-            if s is None:
-                continue
-            key = s[0]
-            if b > self.LIMIT:
-                skip.add(key)                              # saturated / non-finite: `lower`'s business
-                continue
-            if b:
-                stored = _bits_to_float(b)
-            else:
-                # not written since the words were zeroed (a resumed pass starts behind this tensor): what it showed
-                # BEFORE the reset still counts - its largest |v| of this weights generation, in today's stored units -
-                # so that a key shared by an early and a late tensor is never judged on the late one alone
-                v = self.peak.get(n)
-                if v is None:
-                    continue                               # never seen (or all zeros): says nothing
-                stored = v * 2.0 ** self.exps.get(key, self.DEFAULT)
-            top[key] = max(top.get(key, 0.0), stored)
-        plan = {}
-        for key, stored in top.items():
-            if key in skip or stored >= self.RAISE_BELOW or stored <= 0.0:
-                continue
-            e = self.exps.get(key, self.DEFAULT)
-            new = 13 - math.frexp(stored * 2.0 ** -e)[1]
-            new = min(new, self.MAX_EXP, self.ceiling.get(key, self.MAX_EXP))
-            if new > e:
-                plan[key] = new
-        return plan
-
-    def raise_(self, plan):
-        """apply quiet()'s plan -> the set of keys (the caller zeroes the words and repeats the pass from the first
-        launch that writes one of them)"""
-        self.exps.update(plan)
-        return set(plan)
-
-    def new_generation(self):
-        """The model's weights changed (or its mode): what the words and the `lower` ceilings say belongs to the old
-        weights.  The exponents stay - they are the best guess for the new weights - and are re-examined in both
-        directions by the first pass."""
-        self._zero_words()
-        self.ceiling.clear()
-        self.peak.clear()
-
-    def reset_words(self):
-        self._zero_words()
-
-    def _zero_words(self):
-        if self.words.is_cuda:
-            with torch.cuda.device(self.words.device):
-                _lib.check(_lib.load().sfh_fill_words(_ptr(self.words), self.words.numel(), 0, _stream()), "fill_words")
-        else:
-            self.words.zero_()
-
-    def headroom(self):
-        """{tensor name: 65504 * 2^-e / largest |v| seen} - how far each tensor is from saturating"""
-        return {n: 65504.0 * 2.0 ** -self.exp(n) / v for n, v in self.peak.items() if v > 0}
-
-
-def _bits_to_float(b):
-    import struct
-    return struct.unpack("<f", struct.pack("<I", b & 0xFFFFFFFF))[0]
-
-
-class _NoRanges:
-    """stands in for H2Ranges in the other precisions: default exponents, no words"""
-
-    def register(self, *a, **k):
-        pass
-
-    def exp(self, name):
-        return _lib.H2_ACT_EXP
-
-    def key(self, name):
-        return name
-
-    def word_ptr(self, name):
-        return None
-
-    def args(self, src=None, dst=None, res=None):
-        return {}
-
 
 # half-size tiles of the split-bf16 kernel (8 pixel groups): small maps and stride 2
 _TILES_S3_HALF = ((_lib.TILE_8x16, 8, 16), (_lib.TILE_16x8, 16, 8))
@@ -512,9 +99,13 @@ def choose_ksplit(batch, ho, wo, stride, cout, nstages, ksize=3, wg_slots=_WG_SL
     return max(1, min(wg_slots // (2 * wgs), nstages // 2, 8))
 
 
+ConvRecord = namedtuple("ConvRecord", "tag work e0 e1 executed nbytes")
+
+
 class ConvTimer:
     """Optional HIP-event timing of conv launches on the launch stream (used by bench.py for the
-    live roofline figure).  Records (tag, algorithmic FLOPs, start event, end event)."""
+    live roofline figure).  Records ConvRecord(tag, algorithmic work, start event, end event, executed FLOPs, bytes):
+    work = FLOPs of the conv launches, BYTES of the warp launches; executed / nbytes = None where a site has none."""
 
     def __init__(self, only=None):
         """only: set of tags to time (None = every launch).  bench.py times just the dominant kernel's launches inside the
@@ -527,32 +118,88 @@ class ConvTimer:
         return self.only is None or tag in self.only
 
     def summary(self):
-        """-> {tag: (launches, total_flops, total_ms)}; call after a device synchronize."""
+        """-> {tag: (launches, total work, total_ms)}; call after a device synchronize."""
         out = {}
         for rec in self.records:
-            tag, flops, e0, e1 = rec[:4]
-            n, f, t = out.get(tag, (0, 0.0, 0.0))
-            out[tag] = (n + 1, f + flops, t + e0.elapsed_time(e1))
+            n, f, t = out.get(rec.tag, (0, 0.0, 0.0))
+            out[rec.tag] = (n + 1, f + rec.work, t + rec.e0.elapsed_time(rec.e1))
         return out
 
     def traffic(self):
         """-> {tag: ALGORITHMIC HBM bytes of the launches}: every operand tensor read once, every result written once
         (sources at their stored width, packed weights, fp32 seed / residual where a launch has one) - the figure the
         counters' FETCH_SIZE + WRITE_SIZE are compared with (bench.py roofline.traffic_algorithmic)."""
-        out = {}
-        for rec in self.records:
-            if len(rec) > 5 and rec[5] is not None:
-                out[rec[0]] = out.get(rec[0], 0.0) + rec[5]
-        return out
+        return self._total("nbytes")
 
     def executed(self):
         """-> {tag: FLOPs the launches EXECUTED} where that differs from the algorithmic work they are credited with
         (the composed 2x2 Up conv runs 4 taps x 2C channels for the reference's 9 taps x C)."""
+        return self._total("executed")
+
+    def _total(self, field):
         out = {}
         for rec in self.records:
-            if len(rec) > 4 and rec[4] is not None:
-                out[rec[0]] = out.get(rec[0], 0.0) + rec[4]
+            v = getattr(rec, field)
+            if v is not None:
+                out[rec.tag] = out.get(rec.tag, 0.0) + v
         return out
+
+
+class _Timing:
+    """One timed launch: created = start event recorded; stop() records the end event, add() appends the ConvRecord."""
+    __slots__ = ("tm", "tag", "e0", "e1")
+
+    def __init__(self, tm, tag):
+        self.tm, self.tag = tm, tag
+        self.e0, self.e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        self.e0.record()
+
+    def stop(self):
+        self.e1.record()
+
+    def add(self, work, executed=None, nbytes=None):
+        self.tm.records.append(ConvRecord(self.tag, work, self.e0, self.e1, executed, nbytes))
+
+
+def _timed(tag):
+    """-> a started _Timing if the installed ConvTimer wants `tag`, else None (launch sites test `PackedConv.timer is
+    not None` themselves first: the untimed path pays that one test and no call)"""
+    tm = PackedConv.timer
+    return _Timing(tm, tag) if (tm is not None and tm.wants(tag)) else None
+
+
+def conv_work(batch, ho, wo, ksize, c0, c1, cout, cout_real, transposed=False, stem_cin=0, flops_per_out_pixel=None,
+              src_bpe=4, dst_bpe=4, src0_hw=(0, 0), src1_hw=None, weight_bytes=0, dst_pixels=0, pooled=False, head_nc=0,
+              extra_bytes=0):
+    """Roofline accounting of one PackedConv launch from plain numbers -> (flops, executed, nbytes).  flops: 2 * MACs of the
+    reference op (real cin, real taps); a fused Up conv (flops_per_out_pixel) is credited with the u-half of the reference's
+    3x3 conv, `executed` = what the composed conv really multiplies (4 quadrants x 4 taps x all low-resolution channels, 8/9
+    of the credit), else None.  nbytes: every operand read once, every result written once, at src_bpe / dst_bpe bytes per
+    element (4 for split-K slabs); dst_pixels = B * H * W as dst is written (0: a fused head consumed it)."""
+    kk = 49 if ksize == 4 else (4 if transposed else ksize * ksize)
+    cin = stem_cin if ksize == 4 else c0 + c1
+    flops, executed = 2.0 * batch * ho * wo * cout_real * kk * cin, None
+    if flops_per_out_pixel is not None:
+        executed = 2.0 * batch * ho * wo * cout * 4 * c0
+        flops = flops_per_out_pixel * batch * (2 * ho) * (2 * wo)
+    nbytes = batch * src0_hw[0] * src0_hw[1] * c0 * src_bpe + weight_bytes + dst_pixels * cout_real * dst_bpe + extra_bytes
+    if src1_hw is not None:
+        nbytes += batch * src1_hw[0] * src1_hw[1] * c1 * src_bpe
+    if pooled:      # the 2x2 max-pooled copy the epilogue writes beside dst
+        nbytes += batch * (ho // 2) * (wo // 2) * cout_real * dst_bpe
+    if head_nc:     # the fused OutConv's fp32 logits
+        nbytes += batch * ho * wo * head_nc * 4
+    return flops, executed, float(nbytes)
+
+
+def upfused_work(batch, H, W, skip_c0, cout, low_c0, low_hw, flops_per_out_pixel, weight_bytes):
+    """conv_work's counterpart for run_upfused -> (flops, executed, nbytes).  Credited like the two launches it replaces:
+    the whole reference conv over cat([skip, up]) (9 taps x (c_skip + c_up), c_up recovered from the composed conv's
+    flops_per_out_pixel); executed: 9 taps x the skip channels + 4 taps x all low-resolution channels; H2 tensors, 4 B."""
+    c_up = flops_per_out_pixel / (2.0 * cout * 9)
+    nbytes = (batch * H * W * (skip_c0 + cout) + batch * low_hw[0] * low_hw[1] * low_c0) * 4 + weight_bytes
+    return (2.0 * batch * H * W * cout * 9 * (skip_c0 + c_up), 2.0 * batch * H * W * cout * (9 * skip_c0 + 4 * low_c0),
+            float(nbytes))
 
 
 # conv_small.hip (12 x 20-pixel x 32-cout workgroups, halo + weights through LDS; bit-identical results) for 3x3 stride-1 H2
@@ -562,10 +209,9 @@ class ConvTimer:
 # with the threshold at 224 (layer4 only), 13.09 at 256.  SFH_SMALL_MAP=0 switches it off.
 _SMALL_MAP = os.environ.get("SFH_SMALL_MAP", "1") != "0"
 _SMALL_MAP_MAX = int(os.environ.get("SFH_SMALL_MAP_MAX", "256"))
-_SMALL_MAP_WS_ORDER = os.environ.get("SFH_SMALL_MAP_ORDER", "") == "weights"
-_SMALL_MAP_BUFFERS = int(os.environ.get("SFH_SMALL_MAP_BUFFERS", "0"))   # experiment: 1 / 2 = force one / two LDS buffers
 _W8_HALF = os.environ.get("SFH_W8_HALF", "1") != "0"
 _W8_HALF_ROUNDS = float(os.environ.get("SFH_W8_HALF_ROUNDS", "3"))   # rounds of 512 resident workgroups from which the shape is requested
+_BPE = {"h2": 4, "s3": 6, None: 4}   # stored bytes per activation element
 
 
 class LaunchOrder:
@@ -596,59 +242,103 @@ def _unit_epilogue(n, dev, scale=1.0):
     return v
 
 
-class PackedConv:
+class _H2Layer:
+    """What PackedConv and StemConv share: the folded per-channel epilogue (`scale`, `shift`) and, for H2 arithmetic, the
+    source exponent folded into `scale` (escale = the power of two the accumulator is multiplied with)."""
+    _shared_scale = False       # `scale` is a tensor shared with other layers (training): never rewritten in place
+
+    def _fold_epilogue(self, bias, bn, cout_real, rep, dev):
+        """scale / shift = bias and BatchNorm (either may be None) folded per channel, repeated rep times, then `escale`
+        multiplied into the scale (a power of two: exact)"""
+        self.scale, self.shift = (torch.empty(cout_real * rep, dtype=torch.float32, device=dev) for _ in range(2))
+        b = _f32c(bias.detach(), "conv bias") if bias is not None else None
+        bnt = (bn.weight, bn.bias, bn.running_mean, bn.running_var) if bn is not None else (None,) * 4
+        args = [_ptr(_f32c(t.detach(), "bn tensor")) if t is not None else None for t in bnt]
+        _lib.check(_lib.load().sfh_fold_bn(_ptr(b), *args, float(bn.eps) if bn is not None else 0.0, cout_real, rep,
+                                           _ptr(self.scale), _ptr(self.shift), _stream()), "fold_bn")
+        self._scale_by_escale()
+
+    def _scale_by_escale(self):
+        if self.escale != 1.0:
+            vec_op(self.scale, factor=self.escale, out=self.scale)
+
+    def _fold_exp_src(self, e):
+        """H2 layer: its sources now carry v * 2^e.  `scale` holds the factor 2^-(wexp + exp_src) that takes the
+        accumulator back to real units: multiply the difference in (a power of two: exact)."""
+        if e == self.exp_src:
+            return
+        if self._shared_scale:
+            raise ValueError("this layer's epilogue scale is shared with other layers: its source exponent is fixed")
+        f = 2.0 ** (self.exp_src - e)
+        vec_op(self.scale, factor=f, out=self.scale)
+        self.escale *= f
+        self.exp_src = e
+
+
+class PackedConv(_H2Layer):
     """One conv-shaped layer: fragment-ordered weights + folded per-channel epilogue."""
 
     timer = None   # set to a ConvTimer to time every launch (bench.py / profiling only)
-    order = None   # LaunchOrder of the owning engine (set by the engine); None = always forward
-    exp_src = _lib.H2_ACT_EXP   # H2 layers: exponent of the source tensors currently folded into `scale`
-    _shared_scale = False       # `scale` is a tensor shared with other layers (training): never rewritten in place
+
+    def _init_fields(self, tag, fmt, ksize, c0, c1, cout, cout_real, relu, stride, transposed, stem_cin):
+        """every attribute the class reads, with None / 0 / False where it does not apply"""
+        if fmt not in (None, "s3", "h2"):
+            raise ValueError(f"fmt={fmt!r}: expected None, 's3' or 'h2'")
+        self.tag, self.fmt = tag, fmt
+        self.ksize, self.c0, self.c1, self.cout, self.cout_real = ksize, c0, c1, cout, cout_real
+        self.relu, self.stride, self.transposed, self.stem_cin = relu, stride, transposed, stem_cin
+        self.c4, self.c4h2, self.escale = False, False, 1.0
+        self.exp_src = _lib.H2_ACT_EXP   # H2 layers: exponent of the source tensors currently folded into `scale`
+        self.wpacked = self.scale = self.shift = None
+        self.order = None                # LaunchOrder of the owning engine (set by the engine); None = always forward
+        self.overflow = None             # the owner's fp16-range word (set by the engine)
+        self._shared_scale = False
+        # fused_up only: border shifts, BatchNorm scale alone, credited work, seeded scale / shifts + their exponents, composed weights
+        self.shift_border = self.scale_bn = self.flops_per_out_pixel = None
+        self._seed_scale = self._seed_border = self._seed_key = self._w2 = None
+
+    @property
+    def s3(self):
+        """runs on the split-operand kernel"""
+        return self.fmt is not None
 
     def __init__(self, weight, bias, bn, ksize, c0, c1=0, relu=True, transposed=False, stride=1,
-                 stem_cin=0, tag="conv", s3=False, fmt=None, wexp=None, shared_unit_scale=False, frame_h2=False):
-        """fmt="s3" (or s3=True): sources are split-bf16 (S3) tensors and the contraction runs as six bf16 MFMAs
+                 stem_cin=0, tag="conv", fmt=None, wexp=None, shared_unit_scale=False, frame_h2=False, _geom=None):
+        """fmt="s3": sources are split-bf16 (S3) tensors and the contraction runs as six bf16 MFMAs
         per product; fmt="h2": two-plane fp16 (H2) sources, three fp16 MFMAs per product (both sfh_conv_s3_fwd);
         otherwise fp32 sources and fp32 MFMA (sfh_conv_fwd).  frame_h2 (with fmt=None, a 3x3 conv over <= 4 channels: the
         UNet's first layer): the source is the FH2 frame tensor of sfh_frame_to_h2 - held as a float32 (B,H,W,4) tensor, 16
-        bytes per pixel - and the contraction runs as three fp16 MFMAs per product (sfh_conv3x3_c4h2_fwd)."""
+        bytes per pixel - and the contraction runs as three fp16 MFMAs per product (sfh_conv3x3_c4h2_fwd).
+        _geom (fused_up / backward_data): (real couts, repeats, pack mode, aux) instead of what the weight's shape says;
+        pack mode None: the caller packs (finish_pack)."""
         lib = _lib.load()
-        self.tag = tag
-        self.fmt = fmt if fmt is not None else ("s3" if s3 else None)
-        if self.fmt not in (None, "s3", "h2"):
-            raise ValueError(f"fmt={fmt!r}: expected None, 's3' or 'h2'")
-        self.s3 = self.fmt is not None     # "runs on the split-operand kernel"
-        self.escale = 1.0
         dev = weight.device
         w = _f32c(weight.detach(), "conv weight")
-        self.ksize, self.c0, self.c1, self.relu, self.stride = ksize, c0, c1, relu, stride
-        self.transposed = transposed
         mode, aux = (1 if transposed else 0), 0
-        self.stem_cin = stem_cin
-        if stem_cin:  # 7x7 s2 stem re-expressed as a 4x4 conv over the space-to-depth input
-            cout = w.shape[0]
+        if _geom is not None:
+            cout, rep, mode, aux = _geom
+        elif stem_cin:  # 7x7 s2 stem re-expressed as a 4x4 conv over the space-to-depth input
+            cout, rep, mode, aux = w.shape[0], 1, 2, stem_cin
             assert ksize == 4 and tuple(w.shape[1:]) == (stem_cin, 7, 7) and c1 == 0
-            self.cout_real, self.cout = cout, cout
-            rep, mode, aux = 1, 2, stem_cin
         elif transposed:
-            cin, cout = w.shape[0], w.shape[1]
+            cin, cout, rep = w.shape[0], w.shape[1], 4
             assert ksize == 1 and cin == c0 and c1 == 0 and tuple(w.shape[2:]) == (2, 2)
-            self.cout_real, self.cout = cout, 4 * cout
-            rep = 4
         else:
-            cout, cin = w.shape[0], w.shape[1]
+            cout, cin, rep = w.shape[0], w.shape[1], 1
             assert cin == c0 + c1 and tuple(w.shape[2:]) == (ksize, ksize), (w.shape, c0, c1, ksize)
-            self.cout_real, self.cout = cout, cout
-            rep = 1
+        self._init_fields(tag, fmt, ksize, c0, c1, rep * cout, cout, relu, stride, transposed, stem_cin)
         if self.cout_real % 64:
             raise ValueError(f"conv with {self.cout_real} output channels: the MFMA kernel needs a multiple of 64")
         # 3x3 conv over <= 4 input channels (the UNet's first layer): tap-packed kernel
-        self.c4 = (not self.s3 and not stem_cin and not transposed and ksize == 3 and stride == 1
+        self.c4 = (_geom is None and not self.s3 and not stem_cin and not transposed and ksize == 3 and stride == 1
                    and c1 == 0 and c0 <= 4)
         self.c4h2 = bool(frame_h2) and self.c4
         if frame_h2 and not self.c4:
             raise ValueError("frame_h2 is the first-layer kernel: a 3x3 stride-1 conv over at most 4 channels, fmt=None")
-        if self.c4h2:
-            wx = int(wexp) if wexp is not None else h2_weight_exp(absminmax([w])[0][0])    # max |w| * 2^wx in [2^13, 2^14)
+        if mode is None:        # fused_up packs the composed weights itself (finish_pack)
+            pass
+        elif self.c4h2:
+            wx = resolve_wexp(w, wexp)    # max |w| * 2^wx in [2^13, 2^14)
             self.escale = 2.0 ** -(wx + _lib.H2_ACT_EXP)
             self.wpacked = torch.empty(lib.sfh_packed_c4h2_weight_bytes(self.cout), dtype=torch.uint8, device=dev)
             _lib.check(lib.sfh_pack_c4h2_weights(_ptr(w), _ptr(self.wpacked), c0, self.cout, wx, _stream()), "pack_c4h2_weights")
@@ -656,36 +346,25 @@ class PackedConv:
             self.wpacked = torch.empty((self.cout // 64) * 9 * 256, dtype=torch.float32, device=dev)
             _lib.check(lib.sfh_pack_c4_weights(_ptr(w), _ptr(self.wpacked), c0, self.cout, _stream()), "pack_c4_weights")
         elif self.s3:
-            if stem_cin:
-                mode, aux = 2, stem_cin
             self._pack_split(w, ksize, c0, c1, mode, aux, wexp)
         else:
             n = lib.sfh_packed_weight_floats(ksize, c0, c1, self.cout)
             if n <= 0:
-                raise ValueError(f"unsupported conv geometry ksize={ksize} c0={c0} c1={c1} cout={self.cout}")
+                raise ValueError(f"unsupported {'backward-data' if mode in (3, 4) else 'conv'} geometry ksize={ksize} "
+                                 f"c0={c0} c1={c1} cout={self.cout}")
             self.wpacked = torch.empty(n, dtype=torch.float32, device=dev)
             _lib.check(lib.sfh_pack_conv_weights(_ptr(w), _ptr(self.wpacked), ksize, c0, c1, self.cout,
                                                  mode, aux, _stream()), "pack_conv_weights")
-        b = _f32c(bias.detach(), "conv bias") if bias is not None else None
         if shared_unit_scale and bn is None:
             # training convs (one PackedConv per layer and step): no BatchNorm to fold - the scale is the layer's
             # power-of-two factor times ones, shared read-only between all layers of that size, the shift the bias
             # itself: no kernel launch here (a step builds 114 of these objects)
             self.scale, zeros = _unit_epilogue(self.cout, dev, self.escale)
+            b = _f32c(bias.detach(), "conv bias") if bias is not None else None
             self.shift = zeros if b is None else (b if rep == 1 else b.repeat(rep))
             self._shared_scale = True
-            return
-        self.scale = torch.empty(self.cout, dtype=torch.float32, device=dev)
-        self.shift = torch.empty(self.cout, dtype=torch.float32, device=dev)
-        if bn is not None:
-            args = [_f32c(t.detach(), "bn tensor") for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var)]
-            eps = float(bn.eps)
         else:
-            args, eps = [None] * 4, 0.0
-        _lib.check(lib.sfh_fold_bn(_ptr(b), *[_ptr(a) for a in args], eps, self.cout_real, rep,
-                                   _ptr(self.scale), _ptr(self.shift), _stream()), "fold_bn")
-        if self.escale != 1.0:
-            vec_op(self.scale, factor=self.escale, out=self.scale)     # a power of two: exact
+            self._fold_epilogue(bias, bn, self.cout_real, rep, dev)
 
     @property
     def stats_ok(self):
@@ -707,9 +386,7 @@ class PackedConv:
             raise ValueError(f"unsupported split-kernel conv geometry ksize={ksize} c0={c0} c1={c1} cout={self.cout}")
         self.wpacked = torch.empty(n, dtype=torch.uint8, device=w.device)
         if self.fmt == "h2":
-            if wexp is None:
-                wexp = h2_weight_exp(absminmax([w])[0][0])     # (callers that pack many layers pass it: one batched read-back)
-            wexp = max(-100, min(100, int(wexp)))
+            wexp = resolve_wexp(w, wexp)
             self.escale = 2.0 ** -(wexp + _lib.H2_ACT_EXP)
             _lib.check(lib.sfh_pack_h2_weights(_ptr(w), _ptr(self.wpacked), ksize, c0, c1, self.cout, mode, aux, wexp,
                                                _stream()), "pack_h2_weights")
@@ -722,8 +399,6 @@ class PackedConv:
         """The u-half of conv3x3(cat([skip, ConvTranspose2d(x)])) (+bias, BN, ReLU) as ONE 2x2 conv over the
         low-resolution x with quadrant scatter (sfh_compose_up_weights): takes x (S3), adds the fp32
         partial of the skip-half conv as residual and writes the activated S3 output.  Split-bf16 kernel only."""
-        lib = _lib.load()
-        self = cls.__new__(cls)
         wc = _f32c(conv.weight.detach(), "conv weight")
         wt = _f32c(up.weight.detach(), "up weight")
         bt = _f32c(up.bias.detach(), "up bias")
@@ -733,25 +408,16 @@ class PackedConv:
         assert cin == c0 + c1 and tuple(wc.shape[2:]) == (3, 3) and tuple(wt.shape[2:]) == (2, 2)
         if cout % 64 or cx % 32:
             raise ValueError("fused Up conv needs cout % 64 == 0 and a multiple of 32 low-resolution channels")
-        self.tag, self.s3, self.c4, self.stem_cin = tag, True, False, 0
-        self.fmt, self.escale = fmt, 1.0
-        self.ksize, self.c0, self.c1, self.relu, self.stride, self.transposed = 2, cx, 0, True, 1, True
-        self.cout, self.cout_real = 4 * cout, cout
+        # a 2x2 up-scatter conv over the cx low-resolution channels; BatchNorm folded (escale comes with finish_pack)
+        self = cls(wc, conv.bias, bn, 2, cx, relu=True, transposed=True, tag=tag, fmt=fmt, _geom=(cout, 4, None, 0))
         self.flops_per_out_pixel = 2.0 * cout * 9 * c1   # the part of the reference conv this launch stands for
-        self.scale = torch.empty(self.cout, dtype=torch.float32, device=dev)
-        self.shift = torch.empty(self.cout, dtype=torch.float32, device=dev)
-        args = [_f32c(t.detach(), "bn tensor") for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var)]
-        b = _f32c(conv.bias.detach(), "conv bias") if conv.bias is not None else None
-        _lib.check(lib.sfh_fold_bn(_ptr(b), *[_ptr(a) for a in args], float(bn.eps), cout, 4, _ptr(self.scale),
-                                   _ptr(self.shift), _stream()), "fold_bn")
-        w2 = torch.empty((4 * cout, cx, 2, 2), dtype=torch.float32, device=dev)
+        self._w2 = torch.empty((4 * cout, cx, 2, 2), dtype=torch.float32, device=dev)
         self.shift_border = torch.empty((16, 4 * cout), dtype=torch.float32, device=dev)
-        _lib.check(lib.sfh_compose_up_weights(_ptr(wc), cout, c0, c1, _ptr(wt), cx, _ptr(bt), _ptr(self.scale),
-                                              _ptr(self.shift), _ptr(w2), _ptr(self.shift_border), _stream()),
+        _lib.check(_lib.load().sfh_compose_up_weights(_ptr(wc), cout, c0, c1, _ptr(wt), cx, _ptr(bt), _ptr(self.scale),
+                                              _ptr(self.shift), _ptr(self._w2), _ptr(self.shift_border), _stream()),
                    "compose_up_weights")
         # the skip-half conv of the block applies the same BatchNorm scale to ITS accumulator (UNetEngine)
         self.scale_bn = snapshot(self.scale)
-        self._w2 = w2
         if not defer_pack:          # defer_pack: the engine packs all composed weights behind ONE batched |w| read-back
             self.finish_pack()
         return self
@@ -760,18 +426,14 @@ class PackedConv:
         """second half of fused_up(): pack the composed weights (H2: with exponent wexp, else from a read-back here)"""
         self._pack_split(self._w2, 2, self.c0, 0, 0, 0, wexp)
         self._w2 = None
-        if self.escale != 1.0:
-            vec_op(self.scale, factor=self.escale, out=self.scale)
+        self._scale_by_escale()
 
     @classmethod
-    def backward_data(cls, weight, ksize, transposed=False, tag="bwd_data", s3=False, fmt=None, wexp=None):
+    def backward_data(cls, weight, ksize, transposed=False, tag="bwd_data", fmt=None, wexp=None):
         """The conv that maps dz -> dx for a stride-1 nn.Conv2d (OIHW weight; taps flipped, channels
         swapped: pack mode 3) or for nn.ConvTranspose2d k2 s2 (IOHW weight; a 1x1 conv over
         space_to_depth2(dY): pack mode 4).  fp32 kernel; output channels padded to a multiple of 64."""
-        lib = _lib.load()
-        self = cls.__new__(cls)
-        w = _f32c(weight.detach(), "conv weight")
-        dev = w.device
+        w = weight.detach()
         if transposed:
             cin, cout = w.shape[0], w.shape[1]
             assert ksize == 1 and tuple(w.shape[2:]) == (2, 2)
@@ -780,64 +442,59 @@ class PackedConv:
             cout, cin = w.shape[0], w.shape[1]
             assert tuple(w.shape[2:]) == (ksize, ksize) and ksize in (1, 3)
             c0, mode, aux = cout, 3, cin
-        self.fmt = fmt if fmt is not None else ("s3" if s3 else None)
-        s3 = self.fmt is not None
-        self.tag, self.s3, self.c4, self.stem_cin = tag, s3, False, 0
-        self.escale = 1.0
-        self.ksize, self.c0, self.c1, self.relu, self.stride, self.transposed = ksize, c0, 0, False, 1, False
         if cin % 64:
             raise ValueError(f"backward-data conv needs a multiple of 64 input channels, got {cin}")
-        self.cout = self.cout_real = cin
-        if s3:
-            self._pack_split(w, ksize, c0, 0, mode, aux, wexp)
-        else:
-            n = lib.sfh_packed_weight_floats(ksize, c0, 0, self.cout)
-            if n <= 0:
-                raise ValueError(f"unsupported backward-data geometry ksize={ksize} c0={c0} cout={self.cout}")
-            self.wpacked = torch.empty(n, dtype=torch.float32, device=dev)
-            _lib.check(lib.sfh_pack_conv_weights(_ptr(w), _ptr(self.wpacked), ksize, c0, 0, self.cout, mode, aux,
-                                                 _stream()), "pack_conv_weights")
-        self.scale, self.shift = _unit_epilogue(self.cout, dev, self.escale)
-        self._shared_scale = True
-        return self
+        # no bias, no BatchNorm: the unit epilogue shared by every backward-data conv of that size
+        return cls(w, None, None, ksize, c0, relu=False, tag=tag, fmt=fmt, wexp=wexp, shared_unit_scale=True,
+                   _geom=(cin, 1, mode, aux))
 
-    def _fold_exp_src(self, e):
-        """H2 layer: its sources now carry v * 2^e.  `scale` holds the factor 2^-(wexp + exp_src) that takes the
-        accumulator back to real units: multiply the difference in (a power of two: exact)."""
-        if e == self.exp_src:
-            return
-        if self._shared_scale:
-            raise ValueError("this layer's epilogue scale is shared with other layers: its source exponent is fixed")
-        f = 2.0 ** (self.exp_src - e)
-        vec_op(self.scale, factor=f, out=self.scale)
-        self.escale *= f
-        self.exp_src = e
+    # ---- one launch: run() is the sequence of the steps below
+    def _out_geometry(self, H, W):
+        """-> output rows, columns and the shared zero rows per frame of the flattened tile grid"""
+        pad2 = self.ksize // 2 + (self.ksize - 1) // 2  # pad before + pad after
+        ho = (H + pad2 - self.ksize) // self.stride + 1
+        wo = (W + pad2 - self.ksize) // self.stride + 1
+        zr = self.ksize // 2
+        if self.fmt is not None:  # even rows per frame (fused 2x2 pool windows never straddle a tile edge)
+            zr += (ho + zr) & 1
+        return ho, wo, zr
 
-    def run(self, src0, batch, H, W, dst, src1=None, pool0=False, pad1=(0, 0), residual=None, tile=None,
-            dst_pool=None, up_dst=None, head=None, wg_couts=0, exp_src=None, exp_dst=None, exp_res=None,
-            range_word=None, ksplit=0, slabs=None, acc_init=None, scale=None, shift_border=None, stats=None, bwd=None,
-            small=None):
-        """src0/src1: NHWC float32 tensors, or split tensors of the layer's format (S3 bfloat16 / H2 float16);
-        dst/residual/dst_pool: float32 NHWC or the same split format (by dtype).  H, W: conv input frame.
-        H2 tensors: exp_src / exp_dst / exp_res = exponents of the sources / dst and dst_pool / an H2 residual
-        (None: the conventional SFH_H2_ACT_EXP), range_word: device address of dst's range word (H2Ranges).
-        ksplit > 1 (split-operand kernel, one source): the K loop is split over ksplit copies of the grid that write
-        fp32 partial slabs (`slabs`: float32 tensor (ksplit, B, Ho, Wo, cout)), and sfh_splitk_finish adds them up
-        with this layer's shift, residual and ReLU into dst - for grids that alone leave most of the chip idle.
-        acc_init (3x3 stride 1): float32 NHWC (B, H, W, cout) tensor the accumulators start from, in accumulator units
-        (sfh_conv_desc.acc_init); scale / shift_border: tensors used instead of the layer's own for this launch.
-        stats (training, H2 3x3 stride-1 layers with a plain fp32 dst): zero-filled float64 table (rows, 2, cout), rows a
-        power of two - the epilogue adds the per-wave sums of z and z^2 for batch-statistics BatchNorm into it
-        (sfh_conv_desc.stats_partial; PackedConv.stats_ok says whether a layer qualifies).  bwd (with stats, this launch
-        being a backward-data conv): (z, mean_invstd, gamma, beta) of the BatchNorm + ReLU layer whose only gradient dst
-        is - the table then receives sum g and sum g * xhat (sfh_conv_desc.bwd_z).
-        small: True / False forces / forbids the small-map kernel (sfh_conv_small_fwd: plain 3x3 stride-1 H2 launches, same
-        bits); None: the engine's rule - the standard grid is at most one workgroup per CU (one wave per SIMD)
-        and the finer tiling gives at least 1.2x the workgroups."""
-        lib = _lib.load()
-        d = ConvDesc()
-        if (self.fmt == "h2" or getattr(self, "c4h2", False)) and exp_src is not None:
-            self._fold_exp_src(int(exp_src))
+    def _pick_tile(self, batch, ho, wo, zr, wg_couts, plain):
+        """-> (tile id, wg_couts) where the caller names no tile; plain: no fused head, statistics or split-K"""
+        if self.fmt is None:
+            return choose_tile(batch, ho, wo, self.stride, zr), wg_couts
+        # 128 x 128 double-buffered workgroups (conv_s3.hip): measured +3 % for 128 / 256 input channels on grids of many
+        # rounds (64 -> 128: +4 %), slower for longer K or few rounds (profiles/r03_conv_rate_probe_w8half.txt)
+        if (_W8_HALF and plain and self.fmt == "h2" and self.ksize == 3 and self.stride == 1 and wg_couts == 0
+                and self.cout % 128 == 0 and 64 <= self.c0 + self.c1 <= 256):
+            nt = -(-(batch * (ho + zr)) // 8) * -(-wo // 16)
+            if nt * (self.cout // 128) >= _W8_HALF_ROUNDS * _WG_SLOTS:
+                return _lib.TILE_8x16, 128
+        return choose_tile_s3(batch, ho, wo, self.stride, zr, self.cout // 64, self.ksize), wg_couts
+
+    def _check_tensors(self, src0, src1, dst, dst_pool, residual, out_bhw):
+        """formats, destination shape and the 4 GiB range of the tensors of a launch -> format of dst"""
+        fmt, dfmt = self.fmt, _fmt_of(dst)
+        if _fmt_of(src0) != fmt or (src1 is not None and _fmt_of(src1) != fmt):
+            raise ValueError(f"layer of format {fmt} got a source of dtype {src0.dtype}")
+        if fmt is not None and dfmt not in (None, fmt):
+            raise ValueError(f"layer of format {fmt} cannot write a {dst.dtype} destination")
+        for t in (dst_pool, residual):
+            if t is not None and _fmt_of(t) not in (None, dfmt):
+                raise ValueError(f"dst_pool / residual of dtype {t.dtype} beside a {dst.dtype} destination")
+        if src1 is None and self.c1:
+            raise ValueError("layer was packed for two sources")
+        if (dst.shape[0],) + _hw(dst) != out_bhw or _chan(dst) < self.cout_real:
+            raise ValueError(f"conv dst shape {tuple(dst.shape)} does not match {out_bhw + (self.cout_real,)}")
+        for t in (dst, dst_pool, residual, src0, src1):
+            if t is not None and t.numel() * t.element_size() >= 0xFFFFFFF0:
+                raise ValueError(f"tensor of {t.numel() * t.element_size()} bytes exceeds the 4 GiB buffer-descriptor "
+                                 "range of the conv kernels; split the batch")
+        return dfmt
+
+    def _fill_desc(self, d, src0, src1, dst, dfmt, batch, H, W, pool0, pad1, residual, dst_pool, up_dst, head, exp_dst,
+                   exp_res, range_word, acc_init, scale, shift_border, stats, bwd):
+        """the descriptor of a plain launch (tile, wg_couts and reverse_tiles are run()'s)"""
         d.h2_exp_src = self.exp_src
         if exp_dst is not None:
             d.h2_exp_dst = int(exp_dst)
@@ -846,18 +503,11 @@ class PackedConv:
         d.src0 = src0.data_ptr()
         d.c0, d.cs0 = self.c0, _chan(src0)
         d.h0, d.w0 = _hw(src0)
-        if _fmt_of(src0) != self.fmt or (src1 is not None and _fmt_of(src1) != self.fmt):
-            raise ValueError(f"layer of format {self.fmt} got a source of dtype {src0.dtype}")
-        d.src_fmt = _fmt_code(src0)
-        d.dst_fmt = _fmt_code(dst)
-        if self.fmt is not None and _fmt_of(dst) not in (None, self.fmt):
-            raise ValueError(f"layer of format {self.fmt} cannot write a {dst.dtype} destination")
-        for t in (dst_pool, residual):
-            if t is not None and _fmt_of(t) not in (None, _fmt_of(dst)):
-                raise ValueError(f"dst_pool / residual of dtype {t.dtype} beside a {dst.dtype} destination")
-        ovf = getattr(self, "overflow", None)
-        d.h2_overflow = ovf.data_ptr() if (ovf is not None and _fmt_of(dst) == "h2") else None
-        d.h2_range = range_word if (range_word and _fmt_of(dst) == "h2") else None
+        d.src_fmt = _SPLIT[self.fmt][2] if self.fmt else _lib.FMT_F32
+        d.dst_fmt = _SPLIT[dfmt][2] if dfmt else _lib.FMT_F32
+        ovf = self.overflow
+        d.h2_overflow = ovf.data_ptr() if (ovf is not None and dfmt == "h2") else None
+        d.h2_range = range_word if (range_word and dfmt == "h2") else None
         if dst_pool is not None:
             d.dst_pool, d.pool_cs = dst_pool.data_ptr(), _chan(dst_pool)
         d.pool0 = 1 if pool0 else 0
@@ -866,32 +516,8 @@ class PackedConv:
             d.c1, d.cs1 = self.c1, _chan(src1)
             d.h1, d.w1 = _hw(src1)
             d.pad_top1, d.pad_left1 = pad1
-        else:
-            if self.c1:
-                raise ValueError("layer was packed for two sources")
-            d.src1 = None
         d.batch, d.H, d.W = batch, H, W
         d.ksize, d.stride = self.ksize, self.stride
-        pad2 = self.ksize // 2 + (self.ksize - 1) // 2  # pad before + pad after
-        ho = (H + pad2 - self.ksize) // self.stride + 1
-        wo = (W + pad2 - self.ksize) // self.stride + 1
-        zr = self.ksize // 2
-        if self.s3:  # even rows per frame (fused 2x2 pool windows never straddle a tile edge)
-            zr += (ho + zr) & 1
-        if tile is not None:
-            d.tile = tile
-        elif self.s3:
-            d.tile = choose_tile_s3(batch, ho, wo, self.stride, zr, self.cout // 64, self.ksize)
-            # 128 x 128 double-buffered workgroups (conv_s3.hip): measured +3 % for 128 / 256 input channels on grids of many
-            # rounds (64 -> 128: +4 %), slower for longer K or few rounds (profiles/r03_conv_rate_probe_w8half.txt)
-            if (_W8_HALF and self.fmt == "h2" and self.ksize == 3 and self.stride == 1 and wg_couts == 0 and head is None
-                    and stats is None and not (ksplit and ksplit > 1) and self.cout % 128 == 0
-                    and 64 <= self.c0 + self.c1 <= 256):
-                nt = -(-(batch * (ho + zr)) // 8) * -(-wo // 16)
-                if nt * (self.cout // 128) >= _W8_HALF_ROUNDS * _WG_SLOTS:
-                    d.tile, wg_couts = _lib.TILE_8x16, 128
-        else:
-            d.tile = choose_tile(batch, ho, wo, self.stride, zr)
         d.wpacked, d.shift = self.wpacked.data_ptr(), self.shift.data_ptr()
         d.scale = (scale if scale is not None else self.scale).data_ptr()
         d.cout, d.relu = self.cout, 1 if self.relu else 0
@@ -919,108 +545,123 @@ class PackedConv:
             d.head_stn = head["stn"].data_ptr() if head.get("stn") is not None else None
             d.head_frame = head["frame"].data_ptr() if head.get("frame") is not None else None
             d.head_skip_dst = 1 if head.get("skip_dst") else 0
-        d.reverse_tiles = 1 if (self.s3 and self.order is not None and self.order.next()) else 0
-        d.wg_couts = wg_couts   # 0: the launcher decides (sfh_conv_desc.wg_couts)
         d.residual = residual.data_ptr() if residual is not None else None
-        d.residual_f32 = 1 if (residual is not None and residual.dtype == torch.float32
-                               and dst.dtype in _SPLIT_DTYPES) else 0
-        sb = shift_border if shift_border is not None else getattr(self, "shift_border", None)
+        d.residual_f32 = 1 if (residual is not None and residual.dtype == torch.float32 and dfmt is not None) else 0
+        sb = shift_border if shift_border is not None else self.shift_border
         d.shift_border = sb.data_ptr() if sb is not None else None
         d.dst, d.dst_cs = dst.data_ptr(), _chan(dst)
         d.out_mode = _lib.OUT_UPSCATTER2 if self.transposed else _lib.OUT_NHWC
-        exp = (batch, 2 * ho, 2 * wo) if self.transposed else (batch, ho, wo)
         if up_dst is not None:   # fused Up block with F.pad: the destination is one row / column short of 2*H x 2*W
             d.up_dst_h, d.up_dst_w = up_dst
-            exp = (batch,) + tuple(up_dst)
-        if (dst.shape[0],) + _hw(dst) != exp or _chan(dst) < self.cout_real:
-            raise ValueError(f"conv dst shape {tuple(dst.shape)} does not match {exp + (self.cout_real,)}")
-        for t in (dst, dst_pool, residual, src0, src1):
-            if t is not None and t.numel() * t.element_size() >= 0xFFFFFFF0:
-                raise ValueError(f"tensor of {t.numel() * t.element_size()} bytes exceeds the 4 GiB buffer-descriptor "
-                                 "range of the conv kernels; split the batch")
-        fwd = lib.sfh_conv_s3_fwd if self.s3 else lib.sfh_conv_fwd
-        finish = None
-        if ksplit and ksplit > 1:
-            if not self.s3 or src1 is not None or dst_pool is not None or head is not None or self.transposed:
-                raise ValueError("split-K needs a plain single-source conv on the split-operand kernel")
-            if slabs is None or slabs.dtype != torch.float32 or tuple(slabs.shape) != (ksplit, batch, ho, wo, self.cout):
-                raise ValueError(f"split-K slabs must be a float32 tensor {(ksplit, batch, ho, wo, self.cout)}")
-            zero_shift = _unit_epilogue(self.cout, dst.device)[1]
-            d.dst, d.dst_cs, d.dst_fmt = slabs.data_ptr(), self.cout, _lib.FMT_F32
-            d.shift, d.relu, d.residual, d.residual_f32 = zero_shift.data_ptr(), 0, None, 0
-            d.h2_overflow = d.h2_range = None
-            d.ksplit, d.ksplit_stride = int(ksplit), slabs.stride(0) * 4
-            res_fmt = _fmt_code(residual) if residual is not None else 0
 
-            def finish():
-                _lib.check(lib.sfh_splitk_finish(
-                    _ptr(slabs), int(ksplit), slabs.stride(0) * 4, _ptr(self.shift), _ptr(residual), res_fmt,
-                    int(exp_res) if exp_res is not None else _lib.H2_ACT_EXP, 1 if self.relu else 0, batch * ho, wo,
-                    _chan(dst), _ptr(dst), _fmt_code(dst), int(exp_dst) if exp_dst is not None else _lib.H2_ACT_EXP,
-                    ctypes.c_void_p(ovf.data_ptr()) if (ovf is not None and _fmt_of(dst) == "h2") else None,
-                    ctypes.c_void_p(range_word) if (range_word and _fmt_of(dst) == "h2") else None, _stream()),
-                    "splitk_finish")
-            if _chan(dst) != self.cout:
-                raise ValueError("split-K writes all channels of dst")
-        small_ok = (self.fmt == "h2" and self.ksize == 3 and self.stride == 1 and not self.transposed and src1 is None
-                    and dst_pool is None and head is None and acc_init is None and stats is None and not (ksplit and ksplit > 1)
-                    and not d.residual_f32 and sb is None and not self.c4)
+    def _splitk(self, d, src1, dst, dfmt, dst_pool, head, residual, batch, ho, wo, ksplit, slabs, exp_dst, exp_res,
+                range_word):
+        """rewrite the descriptor for ksplit copies of the grid writing fp32 partial slabs -> the callable that adds them
+        up with this layer's shift, residual and ReLU into dst (sfh_splitk_finish)"""
+        lib = _lib.load()
+        if not self.s3 or src1 is not None or dst_pool is not None or head is not None or self.transposed:
+            raise ValueError("split-K needs a plain single-source conv on the split-operand kernel")
+        if slabs is None or slabs.dtype != torch.float32 or tuple(slabs.shape) != (ksplit, batch, ho, wo, self.cout):
+            raise ValueError(f"split-K slabs must be a float32 tensor {(ksplit, batch, ho, wo, self.cout)}")
+        if _chan(dst) != self.cout:
+            raise ValueError("split-K writes all channels of dst")
+        zero_shift = _unit_epilogue(self.cout, dst.device)[1]
+        d.dst, d.dst_cs, d.dst_fmt = slabs.data_ptr(), self.cout, _lib.FMT_F32
+        d.shift, d.relu, d.residual, d.residual_f32 = zero_shift.data_ptr(), 0, None, 0
+        d.h2_overflow = d.h2_range = None
+        d.ksplit, d.ksplit_stride = int(ksplit), slabs.stride(0) * 4
+        res_fmt = _fmt_code(residual) if residual is not None else 0
+        ovf = self.overflow
+
+        def finish():
+            _lib.check(lib.sfh_splitk_finish(
+                _ptr(slabs), int(ksplit), slabs.stride(0) * 4, _ptr(self.shift), _ptr(residual), res_fmt,
+                int(exp_res) if exp_res is not None else _lib.H2_ACT_EXP, 1 if self.relu else 0, batch * ho, wo,
+                _chan(dst), _ptr(dst), _fmt_code(dst), int(exp_dst) if exp_dst is not None else _lib.H2_ACT_EXP,
+                ctypes.c_void_p(ovf.data_ptr()) if (ovf is not None and dfmt == "h2") else None,
+                ctypes.c_void_p(range_word) if (range_word and dfmt == "h2") else None, _stream()),
+                "splitk_finish")
+        return finish
+
+    def _pick_kernel(self, d, src0, batch, ho, wo, zr, small, auto, plain):
+        """-> the sfh_*_fwd entry point of this launch.  small: True / False / None as run()'s; auto: the caller named
+        neither tile nor wg_couts; plain: one source and no pooled output / head / acc_init / statistics / split-K"""
+        lib = _lib.load()
+        small_ok = (plain and self.fmt == "h2" and self.ksize == 3 and self.stride == 1 and not self.transposed
+                    and not d.residual_f32 and not d.shift_border)
         if small and not small_ok:
             raise ValueError("the small-map kernel takes a plain 3x3 stride-1 H2 conv (one source, no pooled output / head / "
                              "acc_init / statistics / split-K)")
-        if small is None and small_ok and _SMALL_MAP and wg_couts == 0 and tile is None:
-            small = choose_small_map(batch, ho, wo, zr, self.cout, d.tile)
-        if small:
-            fwd = lib.sfh_conv_small_fwd
-            # 0: the launcher decides (two LDS buffers for grids of at most 256 workgroups); + 16 (experiment knob): keep the
-            # weight-stationary block order also where the layer's weights fit an XCD's L2
-            d.wg_couts = _SMALL_MAP_BUFFERS + (16 if _SMALL_MAP_WS_ORDER else 0)
         if self.c4:
-            if src0.shape[-1] != 4 or pool0 or dst_pool is not None:
+            if src0.shape[-1] != 4 or d.pool0 or d.dst_pool:
                 raise ValueError("the <=4-channel first-layer kernel needs an fp32 NHWC source with 4 stored channels")
-            fwd = lib.sfh_conv3x3_c4h2_fwd if self.c4h2 else lib.sfh_conv3x3_c4_fwd
             if self.c4h2:
                 d.src_fmt = _lib.FMT_FH2   # the (B,H,W,4) float32 tensor holds sfh_frame_to_h2's 16-byte pixels, not floats
-        tm = PackedConv.timer
-        if tm is not None and not tm.wants(self.tag):
-            tm = None
-        if tm is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        _lib.check(fwd(ctypes.byref(d), _stream()), "conv_s3_fwd" if self.s3 else "conv_fwd")
+                return lib.sfh_conv3x3_c4h2_fwd
+            return lib.sfh_conv3x3_c4_fwd
+        if small is None and small_ok and _SMALL_MAP and auto:
+            small = choose_small_map(batch, ho, wo, zr, self.cout, d.tile)
+        if small:
+            d.wg_couts = 0          # (the small-map launcher chooses its LDS buffering itself)
+            return lib.sfh_conv_small_fwd
+        return lib.sfh_conv_s3_fwd if self.fmt is not None else lib.sfh_conv_fwd
+
+    def run(self, src0, batch, H, W, dst, src1=None, pool0=False, pad1=(0, 0), residual=None, tile=None,
+            dst_pool=None, up_dst=None, head=None, wg_couts=0, exp_src=None, exp_dst=None, exp_res=None,
+            range_word=None, ksplit=0, slabs=None, acc_init=None, scale=None, shift_border=None, stats=None, bwd=None,
+            small=None):
+        """src0/src1: NHWC float32 tensors, or split tensors of the layer's format (S3 bfloat16 / H2 float16);
+        dst/residual/dst_pool: float32 NHWC or the same split format (by dtype).  H, W: conv input frame.
+        H2 tensors: exp_src / exp_dst / exp_res = exponents of the sources / dst and dst_pool / an H2 residual
+        (None: the conventional SFH_H2_ACT_EXP), range_word: device address of dst's range word (H2Ranges).
+        ksplit > 1 (split-operand kernel, one source): the K loop is split over ksplit copies of the grid that write
+        fp32 partial slabs (`slabs`: float32 tensor (ksplit, B, Ho, Wo, cout)), and sfh_splitk_finish adds them up
+        with this layer's shift, residual and ReLU into dst - for grids that alone leave most of the chip idle.
+        acc_init (3x3 stride 1): float32 NHWC (B, H, W, cout) tensor the accumulators start from, in accumulator units
+        (sfh_conv_desc.acc_init); scale / shift_border: tensors used instead of the layer's own for this launch.
+        stats (training, H2 3x3 stride-1 layers with a plain fp32 dst): zero-filled float64 table (rows, 2, cout), rows a
+        power of two - the epilogue adds the per-wave sums of z and z^2 for batch-statistics BatchNorm into it
+        (sfh_conv_desc.stats_partial; PackedConv.stats_ok says whether a layer qualifies).  bwd (with stats, this launch
+        being a backward-data conv): (z, mean_invstd, gamma, beta) of the BatchNorm + ReLU layer whose only gradient dst
+        is - the table then receives sum g and sum g * xhat (sfh_conv_desc.bwd_z).
+        small: True / False forces / forbids the small-map kernel (sfh_conv_small_fwd: plain 3x3 stride-1 H2 launches, same
+        bits); None: the engine's rule - the standard grid is at most one workgroup per CU (one wave per SIMD)
+        and the finer tiling gives at least 1.2x the workgroups."""
+        if (self.fmt == "h2" or self.c4h2) and exp_src is not None:
+            self._fold_exp_src(int(exp_src))
+        split_k = bool(ksplit and ksplit > 1)
+        ho, wo, zr = self._out_geometry(H, W)
+        out_bhw = (batch,) + (tuple(up_dst) if up_dst is not None else (2 * ho, 2 * wo) if self.transposed else (ho, wo))
+        dfmt = self._check_tensors(src0, src1, dst, dst_pool, residual, out_bhw)
+        d = ConvDesc()
+        auto = tile is None
+        if auto:
+            tile, wg_couts = self._pick_tile(batch, ho, wo, zr, wg_couts, head is None and stats is None and not split_k)
+        d.tile, d.wg_couts = tile, wg_couts   # wg_couts 0: the launcher decides (sfh_conv_desc.wg_couts)
+        self._fill_desc(d, src0, src1, dst, dfmt, batch, H, W, pool0, pad1, residual, dst_pool, up_dst, head, exp_dst, exp_res,
+                        range_word, acc_init, scale, shift_border, stats, bwd)
+        d.reverse_tiles = 1 if (self.fmt is not None and self.order is not None and self.order.next()) else 0
+        finish = self._splitk(d, src1, dst, dfmt, dst_pool, head, residual, batch, ho, wo, ksplit, slabs, exp_dst, exp_res,
+                              range_word) if split_k else None
+        fwd = self._pick_kernel(d, src0, batch, ho, wo, zr, small, auto and wg_couts == 0,
+                                src1 is None and dst_pool is None and head is None and acc_init is None and stats is None
+                                and not split_k)
+        t = _timed(self.tag) if PackedConv.timer is not None else None
+        _lib.check(fwd(ctypes.byref(d), _stream()), "conv_s3_fwd" if self.fmt is not None else "conv_fwd")
         if finish is not None:
             finish()
-        if tm is not None:
-            e1.record()
-            # algorithmic work: 2 * MACs of the reference op (real cin, real taps)
-            kk = 49 if self.ksize == 4 else (4 if self.transposed else self.ksize * self.ksize)
-            cin = self.stem_cin if self.ksize == 4 else self.c0 + self.c1
-            flops = 2.0 * batch * ho * wo * self.cout_real * kk * cin
-            fpp = getattr(self, "flops_per_out_pixel", None)
-            executed = None
-            if fpp is not None:   # fused Up conv: credited with the u-half of the reference's 3x3 conv only
-                # what the composed conv really multiplies: 4 quadrants x 4 taps x all low-resolution channels (8/9 of the credit)
-                executed = 2.0 * batch * ho * wo * self.cout * 4 * self.c0
-                flops = fpp * batch * (2 * ho) * (2 * wo)
-            bpe = {"h2": 4, "s3": 6}.get(self.fmt, 4)          # stored bytes per activation element
-            nbytes = batch * d.h0 * d.w0 * self.c0 * bpe + self.wpacked.numel() * self.wpacked.element_size()
-            if src1 is not None:
-                nbytes += batch * d.h1 * d.w1 * self.c1 * bpe
-            obpe = {"h2": 4, "s3": 6}.get(_fmt_of(dst), 4)
-            if not (head is not None and head.get("skip_dst")):
-                nbytes += exp[0] * exp[1] * exp[2] * self.cout_real * (4 if (ksplit and ksplit > 1) else obpe)
-            if dst_pool is not None:
-                nbytes += batch * (ho // 2) * (wo // 2) * self.cout_real * obpe
-            if head is not None:
-                nbytes += batch * ho * wo * head["nc"] * 4
-            for t in (residual, acc_init):
-                if t is not None:
-                    nbytes += t.numel() * t.element_size()
-            tm.records.append((self.tag, flops, e0, e1, executed, float(nbytes)))
+        if t is not None:
+            t.stop()
+            skip_dst = head is not None and head.get("skip_dst")
+            t.add(*conv_work(
+                batch, ho, wo, self.ksize, self.c0, self.c1, self.cout, self.cout_real, self.transposed, self.stem_cin,
+                self.flops_per_out_pixel, src_bpe=_BPE[self.fmt], dst_bpe=4 if split_k else _BPE[dfmt],
+                src0_hw=(d.h0, d.w0), src1_hw=(d.h1, d.w1) if src1 is not None else None,
+                weight_bytes=self.wpacked.numel() * self.wpacked.element_size(),
+                dst_pixels=0 if skip_dst else out_bhw[0] * out_bhw[1] * out_bhw[2], pooled=dst_pool is not None,
+                head_nc=head["nc"] if head is not None else 0,
+                extra_bytes=sum(x.numel() * x.element_size() for x in (residual, acc_init) if x is not None)))
         return dst
-
-
-_UPFUSED_LEGACY_ORDER = os.environ.get("SFH_UPFUSED_ORDER", "") == "legacy"
 
 
 def run_upfused(fu, sk, skip, ylow, dst, batch, H, W, exp_dst=None, range_word=None):
@@ -1028,7 +669,6 @@ def run_upfused(fu, sk, skip, ylow, dst, batch, H, W, exp_dst=None, range_word=N
     3x3 conv of the level (PackedConv.fused_up / the skip-half PackedConv) with fu._seed_scale / fu._seed_border up to date (the
     composed conv's scale and border shifts in sk's accumulator units, as the two-launch form passes them to its first launch);
     skip / ylow / dst: H2 tensors.  Bit-identical to fu.run(...part...) followed by sk.run(..., acc_init=part)."""
-    lib = _lib.load()
     d = ConvDesc()
     d.src0, d.c0, d.cs0 = skip.data_ptr(), sk.c0, _chan(skip)
     d.h0, d.w0 = _hw(skip)
@@ -1042,30 +682,18 @@ def run_upfused(fu, sk, skip, ylow, dst, batch, H, W, exp_dst=None, range_word=N
     d.dst, d.dst_cs = dst.data_ptr(), _chan(dst)
     d.src_fmt = d.dst_fmt = _lib.FMT_H2
     d.out_mode = _lib.OUT_NHWC
-    d.wg_couts = 1 if _UPFUSED_LEGACY_ORDER else 0      # experiment knob: 1 = the round-5 block order (no XCD-aware mapping)
     if exp_dst is not None:
         d.h2_exp_dst = int(exp_dst)
-    ovf = getattr(sk, "overflow", None)
-    d.h2_overflow = ovf.data_ptr() if ovf is not None else None
+    d.h2_overflow = sk.overflow.data_ptr() if sk.overflow is not None else None
     d.h2_range = range_word if range_word else None
     if (dst.shape[0],) + _hw(dst) != (batch, H, W) or _hw(skip) != (H, W) or _fmt_of(dst) != "h2" or _fmt_of(skip) != "h2":
         raise ValueError("run_upfused: skip and dst must be H2 tensors of the output's size")
-    tm = PackedConv.timer
-    if tm is not None and not tm.wants("upfused"):
-        tm = None
-    if tm is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    _lib.check(lib.sfh_conv_upfused_fwd(ctypes.byref(d), _stream()), "conv_upfused_fwd")
-    if tm is not None:
-        e1.record()
-        # credited like the two launches it replaces: the whole reference conv over cat([skip, up]) (9 taps x (c_skip + c_up))
-        c_up = fu.flops_per_out_pixel / (2.0 * sk.cout * 9)
-        # executed: 9 taps x the skip channels + 4 taps x all low-resolution channels (= 8/9 of the u-half's credit)
-        nbytes = (batch * H * W * (sk.c0 + sk.cout) + batch * d.h1 * d.w1 * fu.c0) * 4 \
-            + (sk.wpacked.numel() * sk.wpacked.element_size() + fu.wpacked.numel() * fu.wpacked.element_size())
-        tm.records.append(("upfused", 2.0 * batch * H * W * sk.cout * 9 * (sk.c0 + c_up), e0, e1,
-                           2.0 * batch * H * W * sk.cout * (9 * sk.c0 + 4 * fu.c0), float(nbytes)))
+    t = _timed("upfused") if PackedConv.timer is not None else None
+    _lib.check(_lib.load().sfh_conv_upfused_fwd(ctypes.byref(d), _stream()), "conv_upfused_fwd")
+    if t is not None:
+        t.stop()
+        t.add(*upfused_work(batch, H, W, sk.c0, sk.cout, fu.c0, (d.h1, d.w1), fu.flops_per_out_pixel,
+                            sk.wpacked.numel() * sk.wpacked.element_size() + fu.wpacked.numel() * fu.wpacked.element_size()))
     return dst
 
 
@@ -1089,7 +717,51 @@ class _Workspace:
         return cur[1]
 
 
-class UNetEngine:
+class _Engine:
+    """What the two engines share: precision, H2 range state, workspaces and the record / replay protocol - run() records
+    every launch as a step, so that the range guard can repeat the pass from the first one that writes a changed tensor."""
+
+    def __init__(self, device, precision, overflow, ranges):
+        if precision not in PRECISIONS:
+            raise ValueError(f"precision={precision!r}: expected one of {sorted(PRECISIONS)}")
+        self.device = device
+        self.ws = _Workspace(device)
+        self.fmt = fmt = PRECISIONS[precision]
+        self.s3 = fmt is not None          # split-format activations
+        self.overflow = overflow if fmt == "h2" else None
+        self.ranges = (ranges if ranges is not None else H2Ranges(device)) if fmt == "h2" else _NoRanges()
+        self.order = LaunchOrder()
+        self.steps = []            # launches of the last run(), in order: [(names of the H2 tensors written, fn)]
+        self._last_out = None
+
+    def _adopt(self, layers):
+        """self.L = layers, each launching in this engine's order and reporting to its overflow word"""
+        self.L = layers
+        for layer in layers.values():
+            layer.order = self.order
+            layer.overflow = self.overflow
+
+    def _do(self, outs, fn):
+        """record + execute one launch; outs = names of the H2 tensors it writes; everything that depends on an
+        exponent is looked up inside fn, i.e. again when the step is repeated"""
+        self.steps.append((tuple(outs), fn))
+        fn()
+
+    def first_step(self, keys):
+        """index of the first launch of the last run() that writes an H2 tensor whose exponent key is in `keys`"""
+        rg = self.ranges
+        return next((i for i, (outs, _) in enumerate(self.steps) if any(rg.key(n) in keys for n in outs)), None)
+
+    def rerun(self, first):
+        """Repeat the launches of the last run() from index `first` on (same buffers, same output tensors) with the
+        exponents H2Ranges holds NOW: what the range guard does after lowering the exponent of a saturated tensor."""
+        with _stream_scope():
+            for _, fn in self.steps[first:]:
+                fn()
+        return self._last_out
+
+
+class UNetEngine(_Engine):
     """forward_unet (models/reconstructor.py:132-158) on the HIP kernels."""
 
     def __init__(self, net, device, precision="bf16x6", overflow=None, ranges=None):
@@ -1098,6 +770,8 @@ class UNetEngine:
         activations, three fp16 MFMAs per product (22-bit operands; `ranges`: the model's H2Ranges - per-tensor
         exponents and the device words the kernels raise to the largest magnitude they produced; `overflow`:
         optional int32 device word OR-ed with 1 on any saturation); "fp32" - fp32 activations and fp32 MFMA."""
+        super().__init__(device, precision, overflow, ranges)
+        fmt, s3 = self.fmt, self.s3
         self.bilinear = bool(net.unet_bilinear)
         # fused Up levels where the composed 2x2 conv runs first (see run()) and the skip-half 3x3 conv finishes.  Round 2
         # (the partial added as a residual at the end of the 3x3 conv): none 629, {4} 634, {3,4} 638, all four 635 frames/s;
@@ -1105,25 +779,12 @@ class UNetEngine:
         # seeding 14.58 / 14.70, {3,4} seeded 14.58 / 14.66, {2,3,4} 14.60 / 14.57, all four 14.43 / 14.56
         self.up_swap = {int(c) for c in os.environ.get("SFH_UP_SWAP", "1234") if c.isdigit()}
         self.up_seed = {}          # level -> the skip-half conv starts from the partial (sfh_conv_desc.acc_init)
-        # level -> frames per band of the fused Up block's two launches (0 / absent: the whole batch per launch)
-        self.up_bands = {int(a): int(b) for a, b in (t.split(":") for t in os.environ.get("SFH_UP_BANDS", "").split(",") if t)}
         # levels whose fused Up block runs as ONE kernel (csrc/conv_upfused.hip, round 5; bit-identical to the two-launch
         # "swap + seed" form).  Same-device A/B at 640x360 x 16 (profiles/r05_ab_up_single.txt), ms per batch pipelined: none 13.13,
         # {4} 12.93, {3,4} 12.91-12.94, {2,3,4} 12.94, all four 13.15 (at long K a wave per parity class streams too many weights);
         # 1280x720: none 50.97, {3,4} 49.9.  SFH_UP_SINGLE="" switches it off.
         self.up_single = {int(c) for c in os.environ.get("SFH_UP_SINGLE", "34") if c.isdigit()}
-        if precision not in PRECISIONS:
-            raise ValueError(f"precision={precision!r}: expected one of {sorted(PRECISIONS)}")
-        self.device = device
-        self.ws = _Workspace(device)
         self.nc = net.mask_classes
-        self.fmt = fmt = PRECISIONS[precision]
-        self.s3 = fmt is not None          # split-format activations
-        s3 = self.s3
-        self.overflow = overflow if fmt == "h2" else None
-        self.ranges = (ranges if ranges is not None else H2Ranges(device)) if fmt == "h2" else _NoRanges()
-        self.steps = []            # launches of the last run(), in order: [(names of the H2 tensors written, fn)]
-        self._last_out = None
         L = {}
 
         # "f16x3": the 3-channel first layer too runs on the fp16 matrix cores, from a frame tensor split once (FH2)
@@ -1134,12 +795,9 @@ class UNetEngine:
         # the skip halves of the Up blocks' first convs (unet/unet_parts.py:67: cat([skip, up])) as tensors of their own
         skip_w = {i: slice_in_channels(up.conv.convs()[0][0].weight, 0, cin // 2) for i, cin, up in ups} if fuse_up else {}
         # "f16x3": the exponent of every weight tensor from ONE batched |w| reduction and one read-back
-        wx = {}
-        if fmt == "h2":
-            ws_ = [p.detach() for n, p in net.named_parameters()
-                   if p.dim() == 4 and not n.startswith("resnet_reg.") and p.is_contiguous()] + list(skip_w.values())
-            for w, (mx, _) in zip(ws_, absminmax(ws_)):
-                wx[w.data_ptr()] = h2_weight_exp(mx)
+        wx = weight_exps([p.detach() for n, p in net.named_parameters()
+                          if p.dim() == 4 and not n.startswith("resnet_reg.") and p.is_contiguous()]
+                         + list(skip_w.values())) if fmt == "h2" else {}
 
         def wexp(w):
             return wx.get(w.data_ptr())
@@ -1183,11 +841,7 @@ class UNetEngine:
                 # accumulator seeding (run()) divides by this scale: only where no channel's BatchNorm scale vanishes
                 smin = mm[len(fus) + k][1] * sk.escale
                 self.up_seed[i] = (os.environ.get("SFH_UP_SEED", "1") != "0") and 1e-30 < smin < float("inf")
-        self.L = L
-        self.order = LaunchOrder()
-        for layer in L.values():
-            layer.order = self.order
-            layer.overflow = self.overflow
+        self._adopt(L)
         # private copies: an engine holds NO live reference to a parameter (see snapshot())
         self.outc_w = snapshot(net.outc.conv.weight)
         self.outc_b = snapshot(net.outc.conv.bias)
@@ -1202,22 +856,6 @@ class UNetEngine:
         with _stream_scope():
             return self._run(x, want_stn_in, want_argmax, want_uv, stn_slot)
 
-    def first_step(self, keys):
-        """index of the first launch of the last run() that writes an H2 tensor whose exponent key is in `keys`"""
-        rg = self.ranges
-        for i, (outs, _) in enumerate(self.steps):
-            if any(rg.key(n) in keys for n in outs):
-                return i
-        return None
-
-    def rerun(self, first):
-        """Repeat the launches of the last run() from index `first` on (same buffers, same output tensors) with the
-        exponents H2Ranges holds NOW: what the range guard does after lowering the exponent of a saturated tensor."""
-        with _stream_scope():
-            for _, fn in self.steps[first:]:
-                fn()
-        return self._last_out
-
     def _run(self, x, want_stn_in, want_argmax, want_uv, stn_slot=0):
         """stn_slot: which of the STN-input buffers this pass writes (Reconstructor.predict_async alternates two, so that
         the ResNet of batch k can still read its input while the UNet of batch k + 1 writes the other)"""
@@ -1229,13 +867,8 @@ class UNetEngine:
         if H < 16 or W < 16:
             raise ValueError("frames smaller than 16x16 cannot pass four 2x2 poolings")
         ws, L, rg = self.ws, self.L, self.ranges
-        steps = self.steps = []
-
-        def do(outs, fn):
-            """record + execute one launch; outs = names of the H2 tensors it writes; everything that depends on an
-            exponent is looked up inside fn, i.e. again when the step is repeated"""
-            steps.append((tuple(outs), fn))
-            fn()
+        self.steps = []
+        do = self._do
 
         xin = ws.get("xin", (B, H, W, 4))
         first = (xin, None)
@@ -1311,7 +944,7 @@ class UNetEngine:
 
                 def level(y=y, ny=ny, skip=skip, nskip=nskip, part=part, mid=mid, nmid=nmid, fu=fu, sk=sk,
                           up_dst=up_dst, hs=hs, ws_=ws_, hy=hy, wy=wy, ey=ey, ex=ex, swap=i in self.up_swap,
-                          seed=self.up_seed.get(i, False), bands=self.up_bands.get(i, 0), single=i in self.up_single):
+                          seed=self.up_seed.get(i, False), single=i in self.up_single):
                     if swap and seed:
                         # as below, but the partial is written in the skip-half conv's ACCUMULATOR units (divided by its
                         # scale) and that conv STARTS from it (sfh_conv_desc.acc_init): sixteen loads in its prologue
@@ -1322,21 +955,16 @@ class UNetEngine:
                             fu._fold_exp_src(a_fu["exp_src"])
                             sk._fold_exp_src(a_sk["exp_src"])
                         key = (fu.exp_src, sk.exp_src)
-                        if getattr(fu, "_seed_key", None) != key:
+                        if fu._seed_key != key:
                             # (sk.scale is indexed modulo its length: the four sub-positions share it)
                             fu._seed_scale, fu._seed_border, fu._seed_key = (vec_op(fu.scale, sk.scale, "div"),
                                                                              vec_op(fu.shift_border, sk.scale, "div"), key)
-                        # frame bands (experiment, SFH_UP_BANDS="4:4" = level 4 in bands of 4 frames): the two launches of a
-                        # band run back to back, so that the band's fp32 partial is read back from the Infinity Cache
-                        if single and fu.fmt == "h2" and not bands:
+                        if single and fu.fmt == "h2":
                             run_upfused(fu, sk, skip, y, mid, B, hs, ws_, a_sk["exp_dst"], a_sk["range_word"])
                             return
-                        nb_ = bands if bands else B
-                        for b0 in range(0, B, nb_):
-                            b1 = min(B, b0 + nb_)
-                            fu.run(y[b0:b1], b1 - b0, hy + ey, wy + ex, part[b0:b1], up_dst=up_dst, scale=fu._seed_scale,
-                                   shift_border=fu._seed_border, **a_fu)
-                            sk.run(skip[b0:b1], b1 - b0, hs, ws_, mid[b0:b1], acc_init=part[b0:b1], **a_sk)
+                        fu.run(y, B, hy + ey, wy + ex, part, up_dst=up_dst, scale=fu._seed_scale,
+                               shift_border=fu._seed_border, **a_fu)
+                        sk.run(skip, B, hs, ws_, mid, acc_init=part, **a_sk)
                     elif swap:
                         # composed 2x2 conv first: it writes the 4 B fp32 partial instead of reading one and writing
                         # 6 B of S3; the MFMA-bound skip-half 3x3 conv then absorbs the residual, the ReLU and the split
@@ -1402,7 +1030,7 @@ class UNetEngine:
         return self.ranges.exp(out.get("x_top_name"))
 
 
-class StemConv:
+class StemConv(_H2Layer):
     """ResNetSTN stem (7x7 s2 conv + BatchNorm + ReLU) on the tap-packed split-bf16 kernel (csrc/stem.hip):
     reads the fp32 NHWC STN input (8 stored channels) directly, no space-to-depth copy."""
 
@@ -1422,11 +1050,8 @@ class StemConv:
         self.exp_src = _lib.H2_ACT_EXP     # h2: the input planes carry x * 2^exp_src (folded into `scale`)
         self.wpacked = torch.empty(lib.sfh_packed_stem_weight_bytes(), dtype=torch.uint8, device=dev)
         self.escale = 1.0
-        wexp_given, wexp = wexp, 0
+        wexp = resolve_wexp(w, wexp) if fmt == "h2" else 0
         if fmt == "h2":
-            if wexp_given is None:
-                wexp_given = h2_weight_exp(absminmax([w])[0][0])
-            wexp = max(-100, min(100, int(wexp_given)))
             self.escale = 2.0 ** -(wexp + _lib.H2_ACT_EXP)
         _lib.check(lib.sfh_pack_stem_weights(_ptr(w), _ptr(self.wpacked), cin, _SPLIT[fmt][2], wexp, _stream()),
                    "pack_stem_weights")
@@ -1435,25 +1060,15 @@ class StemConv:
             self.scale = torch.full((64,), float(self.escale), dtype=torch.float32, device=dev)
             self.shift = torch.zeros(64, dtype=torch.float32, device=dev)
             return
-        self.scale = torch.empty(64, dtype=torch.float32, device=dev)
-        self.shift = torch.empty(64, dtype=torch.float32, device=dev)
-        args = [_f32c(t.detach(), "bn tensor") for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var)]
-        _lib.check(lib.sfh_fold_bn(None, *[_ptr(a) for a in args], float(bn.eps), 64, 1, _ptr(self.scale),
-                                   _ptr(self.shift), _stream()), "fold_bn")
-        if self.escale != 1.0:
-            vec_op(self.scale, factor=self.escale, out=self.scale)
+        self._fold_epilogue(None, bn, 64, 1, dev)
 
     def run(self, x_nhwc8, B, H, W, dst, exp_src=None, range_word=None):
         """exp_src / range_word (h2 arithmetic): exponent of the split the kernel makes of its fp32 input, and the
         device word that receives the largest |x * 2^exp_src| (H2Ranges).  Built without a BatchNorm (bn=None) the
         launch writes the raw conv output (no ReLU)."""
-        lib = _lib.load()
         d = ConvDesc()
-        if self.fmt == "h2" and exp_src is not None and int(exp_src) != self.exp_src:
-            f = 2.0 ** (self.exp_src - int(exp_src))
-            vec_op(self.scale, factor=f, out=self.scale)
-            self.escale *= f
-            self.exp_src = int(exp_src)
+        if self.fmt == "h2" and exp_src is not None:
+            self._fold_exp_src(int(exp_src))
         d.h2_exp_src = self.exp_src
         d.h2_range = range_word if (range_word and self.fmt == "h2") else None
         d.src0, d.c0, d.cs0, d.h0, d.w0 = x_nhwc8.data_ptr(), self.cin, 8, H, W
@@ -1467,48 +1082,32 @@ class StemConv:
         ho, wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
         if tuple(dst.shape) != (B, ho, wo, 64) or tuple(x_nhwc8.shape) != (B, H, W, 8):
             raise ValueError(f"stem: shapes {tuple(x_nhwc8.shape)} -> {tuple(dst.shape)} do not match {(B, ho, wo, 64)}")
-        tm = PackedConv.timer
-        if tm is not None and not tm.wants(self.tag):
-            tm = None
-        if tm is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        _lib.check(lib.sfh_stem7x7_fwd(ctypes.byref(d), _stream()), "stem7x7_fwd")
-        if tm is not None:
-            e1.record()
-            tm.records.append((self.tag, 2.0 * B * ho * wo * 64 * 49 * self.cin, e0, e1))
+        t = _timed(self.tag) if PackedConv.timer is not None else None
+        _lib.check(_lib.load().sfh_stem7x7_fwd(ctypes.byref(d), _stream()), "stem7x7_fwd")
+        if t is not None:
+            t.stop()
+            t.add(2.0 * B * ho * wo * 64 * 49 * self.cin)
         return dst
 
 
-class ResNetEngine:
+class ResNetEngine(_Engine):
     """ResNetSTN forward (models/resnet.py:235-254) on the HIP kernels (BasicBlock and Bottleneck depths)."""
 
     def __init__(self, rn, in_channels, device, precision="bf16x6", overflow=None, ranges=None):
         """precision "bf16x6" / "f16x3": the 3x3 convs (stride 1 and 2) and the 1x1 stride-2 downsample convs run
         on the split-operand kernel with S3 / H2 activations; the stem stays on the fp32 kernel (or, with at most
         8 input channels, on the tap-packed split-bf16 stem kernel).  ranges / overflow: as UNetEngine."""
-        if precision not in PRECISIONS:
-            raise ValueError(f"precision={precision!r}: expected one of {sorted(PRECISIONS)}")
-        self.fmt = fmt = PRECISIONS[precision]
-        self.s3 = fmt is not None
-        s3 = self.s3
-        self.overflow = overflow if fmt == "h2" else None
-        self.ranges = (ranges if ranges is not None else H2Ranges(device)) if fmt == "h2" else _NoRanges()
-        self.steps = []
-        self._last_out = None
+        super().__init__(device, precision, overflow, ranges)
+        fmt, s3 = self.fmt, self.s3
         self.splitk = os.environ.get("SFH_SPLITK", "1") != "0"
-        self.device = device
-        self.ws = _Workspace(device)
         self.cin = in_channels
         self.cs_in = -(-in_channels // 4) * 4
         if (4 * self.cs_in) % 16:
             self.cs_in = -(-in_channels // 8) * 8
         L = {}
-        wx = {}
-        if fmt == "h2":       # every weight exponent from ONE batched |w| reduction and one read-back
-            ws_ = [p.detach() for p in rn.parameters() if p.dim() == 4 and p.is_contiguous()]
-            for w, (mx, _) in zip(ws_, absminmax(ws_)):
-                wx[w.data_ptr()] = h2_weight_exp(mx)
+        # "f16x3": every weight exponent from ONE batched |w| reduction and one read-back
+        wx = weight_exps([p.detach() for p in rn.parameters() if p.dim() == 4 and p.is_contiguous()]) if fmt == "h2" else {}
+
         def PC(w, *a, **k):      # (PackedConv with this engine's exponent table behind it)
             return PackedConv(w, *a, wexp=wx.get(w.data_ptr()), **k)
         # the stem stays on the fp32 kernel: the 16-tap split-bf16 instance spills registers and
@@ -1541,11 +1140,7 @@ class ResNetEngine:
                     L[name + ".down"] = PC(ds[0].weight, None, ds[1], 1, cin, relu=False, stride=blk.stride,
                                                    tag="resnet", fmt=fmt)
                 self.blocks.append((name, width, cout, blk.stride, blk.downsample is not None, hasattr(blk, "conv3")))
-        self.L = L
-        self.order = LaunchOrder()
-        for layer in L.values():
-            layer.order = self.order
-            layer.overflow = self.overflow
+        self._adopt(L)
         self.reg_w = snapshot(rn.reg.weight)
         self.reg_b = snapshot(rn.reg.bias)
 
@@ -1556,20 +1151,14 @@ class ResNetEngine:
         with _stream_scope():
             return self._run(y_nhwc, B, H, W, splitk)
 
-    first_step = UNetEngine.first_step
-    rerun = UNetEngine.rerun
-
     def _run(self, y_nhwc, B, H, W, splitk=None):
         lib = _lib.load()
         ws, L, rg = self.ws, self.L, self.ranges
         use_splitk = self.splitk and (splitk is None or bool(splitk))
         if y_nhwc.shape[3] != self.cs_in:
             raise ValueError(f"STN input has {y_nhwc.shape[3]} stored channels, engine expects {self.cs_in}")
-        steps = self.steps = []
-
-        def do(outs, fn):   # as UNetEngine._run
-            steps.append((tuple(outs), fn))
-            fn()
+        self.steps = []
+        do = self._do
 
         s3, fmt = self.s3, self.fmt
         H2, W2 = (H + 1) // 2, (W + 1) // 2
@@ -1584,7 +1173,7 @@ class ResNetEngine:
             do((), lambda: _lib.check(lib.sfh_space_to_depth2(_ptr(y_nhwc), _ptr(s2d), B, H, W, self.cs_in, _stream()),
                                       "space_to_depth2"))
             if L["stem"].s3:
-                s2d3 = ws.get("s2d.s3", s3_shape(B, H2, W2, 4 * self.cs_in), torch.bfloat16)
+                s2d3 = ws.get("s2d.s3", split_shape("s3", B, H2, W2, 4 * self.cs_in), torch.bfloat16)
                 do((), lambda: _lib.check(lib.sfh_f32_to_s3(_ptr(s2d), _ptr(s2d3), B * H2, W2, 4 * self.cs_in, _stream()),
                                           "f32_to_s3"))
                 s2d = s2d3
@@ -1652,195 +1241,33 @@ class ResNetEngine:
         return self._last_out
 
 
-def _split_to_f32_into(t, out, exp=_lib.H2_ACT_EXP):
-    """exp: exponent of an H2 tensor (ignored for S3)"""
-    lib = _lib.load()
-    B = t.shape[0]
-    H, W = _hw(t)
-    C = _chan(t)
-    if tuple(out.shape) != (B, H, W, C) or out.dtype != torch.float32:
-        raise ValueError(f"split_to_f32: destination {tuple(out.shape)} does not match {(B, H, W, C)}")
-    if _fmt_of(t) == "h2":
-        _lib.check(lib.sfh_h2_to_f32(_ptr(t), _ptr(out), B * H, W, C, int(exp), _stream()), "h2_to_f32")
-    else:
-        _lib.check(lib.sfh_s3_to_f32(_ptr(t), _ptr(out), B * H, W, C, _stream()), "s3_to_f32")
-    return out
-
-
-def _f32_to_split_into(t, out, overflow=None, exp=_lib.H2_ACT_EXP, range_word=None):
-    """H2 destinations: exp = the tensor's exponent, overflow / range_word: optional device words (OR 1 on
-    saturation / atomic max of |v * 2^exp|, see H2Ranges)"""
-    lib = _lib.load()
-    B, H, W, C = t.shape
-    if (out.shape[0],) + _hw(out) + (_chan(out),) != (B, H, W, C):
-        raise ValueError(f"f32_to_split: destination {tuple(out.shape)} does not match {(B, H, W, C)}")
-    if _fmt_of(out) == "h2":
-        _lib.check(lib.sfh_f32_to_h2(_ptr(t), _ptr(out), B * H, W, C, int(exp), _ptr(overflow),
-                                     ctypes.c_void_p(range_word) if range_word else None, _stream()), "f32_to_h2")
-    else:
-        _lib.check(lib.sfh_f32_to_s3(_ptr(t), _ptr(out), B * H, W, C, _stream()), "f32_to_s3")
-    return out
-
-
-def s3_to_f32(t, exp=_lib.H2_ACT_EXP):
-    """split tensor (S3: (B,H,C/32,3,4,W,8) bf16, exact sum of the planes; H2: (B,H,C/32,2,4,W,8) fp16 carrying
-    v * 2^exp) -> (B,H,W,C) float32."""
-    out = torch.empty((t.shape[0],) + _hw(t) + (_chan(t),), dtype=torch.float32, device=t.device)
-    return _split_to_f32_into(t, out, exp)
-
-
-def split_empty(fmt, b, h, w, c, device):
-    """uninitialised split-format activation tensor ("s3" or "h2") for c channels (c multiple of 32)"""
-    return torch.empty(split_shape(fmt, b, h, w, c), dtype=_SPLIT[fmt][0], device=device)
-
-
-def f32_to_split(t, fmt, overflow=None, exp=_lib.H2_ACT_EXP):
-    """(B,H,W,C) float32 -> split tensor of format "s3" or "h2" (h2: carrying v * 2^exp) """
-    t = _f32c(t, "nhwc tensor")
-    return _f32_to_split_into(t, split_empty(fmt, *t.shape, t.device), overflow, exp)
-
-
-def f32_to_h2(t, overflow=None, exp=_lib.H2_ACT_EXP, range_word=None):
-    """(B,H,W,C) float32 -> (B,H,C/32,2,4,W,8) fp16 two-plane tensor of v * 2^exp (include/sfh_amd.h, SFH_FMT_H2);
-    range_word: an int32 tensor whose first word receives the largest bit pattern of |v * 2^exp|."""
-    t = _f32c(t, "nhwc tensor")
-    B, H, W, C = t.shape
-    out = torch.empty(split_shape("h2", B, H, W, C), dtype=torch.float16, device=t.device)
-    return _f32_to_split_into(t, out, overflow, exp, range_word.data_ptr() if range_word is not None else None)
-
-
-def f32_to_s3(t):
-    """(B,H,W,C) float32 -> (B,H,C/32,3,4,W,8) bf16 split tensor."""
-    lib = _lib.load()
-    t = _f32c(t, "nhwc tensor")
-    B, H, W, C = t.shape
-    out = s3_empty(B, H, W, C, t.device)
-    _lib.check(lib.sfh_f32_to_s3(_ptr(t), _ptr(out), B * H, W, C, _stream()), "f32_to_s3")
-    return out
-
-
-_AREA_TABS = {}
-
-
-def _area_tab(ssize, dsize, device):
-    """device copies of one axis' INTER_AREA table (sfh_resize_area_tab: OpenCV's computeResizeAreaTab), cached per size pair"""
-    key = (ssize, dsize, str(device))
-    t = _AREA_TABS.get(key)
-    if t is None:
-        import numpy as np
-        lib = _lib.load()
-        cap = 2 * dsize + ssize
-        ofs, si, al = np.zeros(dsize + 1, np.int32), np.zeros(cap, np.int32), np.zeros(cap, np.float32)
-        n = lib.sfh_resize_area_tab(ssize, dsize, ofs.ctypes.data_as(ctypes.c_void_p), si.ctypes.data_as(ctypes.c_void_p),
-                                    al.ctypes.data_as(ctypes.c_void_p), cap)
-        if n < 0:
-            raise ValueError(f"no INTER_AREA table for {ssize} -> {dsize}")
-        t = _AREA_TABS[key] = tuple(torch.from_numpy(a).to(device) for a in (ofs, si[:max(n, 1)].copy(), al[:max(n, 1)].copy()))
-    return t
-
-
-def frames_u8_to_input(frames_u8, target_size=None):
-    """uint8 (B,H,W,C) decoded frames on the GPU -> float32 (B,C,H,W) in [0,1], bit-identical to the
-    reference dataset's `img.transpose((2,0,1)) / 255` (utils/dataset.py:154-159).  target_size = (W, H):
-    like VideoDataset.preprocess_img (utils/dataset.py:310-330) frames WIDER than the target are resized first with
-    cv2.INTER_AREA's rules: the integer factors 2 .. 16 take OpenCV's block-average fast paths (1280x720 -> 640x360 is the
-    2x2 special case, 1920x1080 -> 640x360 the 3x3 one), any other downscale (both factors >= 1, e.g. 1920x1080 -> 1024x576
-    or 1600x900 -> 640x360) the generic area tables (round 5).  Frames narrower than the target (the reference switches to
-    INTER_LINEAR there) are not on the HIP path."""
-    lib = _lib.load()
-    if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or not frames_u8.is_cuda:
-        raise ValueError("expected a uint8 (B,H,W,C) tensor on the GPU")
-    f = frames_u8.contiguous()
-    B, H, W, C = f.shape
-    if target_size is not None and (int(target_size[0]), int(target_size[1])) != (W, H):
-        tw, th = int(target_size[0]), int(target_size[1])
-        if tw <= 0 or th <= 0 or W <= tw or H < th:      # (W > tw: the reference's own test for INTER_AREA, utils/dataset.py:314)
-            raise NotImplementedError(f"GPU frame resize {W}x{H} -> {tw}x{th}: only downscales (cv2.INTER_AREA, the reference's choice "
-                                      "for frames wider than the target) are on the HIP path; resize on the host as utils/dataset.py does")
-        out = torch.empty((B, C, th, tw), dtype=torch.float32, device=f.device)
-        k = W // tw
-        if 2 <= k <= 16 and (k * tw, k * th) == (W, H):
-            _lib.check(lib.sfh_u8hwc_areak_to_f32nchw(_ptr(f), _ptr(out), B, C, th, tw, k, _stream()), "u8hwc_areak_to_f32nchw")
-            return out
-        if (tw * (W // tw), th * (H // th)) == (W, H):
-            # integer factors that differ per axis, or beyond 16: OpenCV's resizeAreaFast_ with a kx x ky block
-            kx, ky = W // tw, H // th
-            if kx > 64 or ky > 64:
-                raise NotImplementedError(f"GPU frame resize {W}x{H} -> {tw}x{th}: integer factors beyond 64 are not on the HIP path")
-            _lib.check(lib.sfh_u8hwc_areaxy_to_f32nchw(_ptr(f), _ptr(out), B, C, th, tw, kx, ky, _stream()), "u8hwc_areaxy_to_f32nchw")
-            return out
-        xo, xs, xa = _area_tab(W, tw, f.device)
-        yo, ys, yb = _area_tab(H, th, f.device)
-        _lib.check(lib.sfh_u8hwc_area_to_f32nchw(_ptr(f), _ptr(out), B, C, H, W, th, tw, _ptr(xo), _ptr(xs), _ptr(xa), _ptr(yo),
-                                                 _ptr(ys), _ptr(yb), _stream()), "u8hwc_area_to_f32nchw")
-        return out
-    out = torch.empty((B, C, H, W), dtype=torch.float32, device=f.device)
-    _lib.check(lib.sfh_u8hwc_to_f32nchw(_ptr(f), _ptr(out), B, C, H, W, _stream()), "u8hwc_to_f32nchw")
-    return out
-
-
-def resize_nchw(t, size_hw, mode, align_corners=False):
-    """F.interpolate(t, size=size_hw, mode=mode[, align_corners]) for NCHW float32 tensors."""
-    lib = _lib.load()
-    t = _f32c(t.contiguous(), "nchw tensor")
-    B, C, hs, ws = t.shape
-    hd, wd = size_hw
-    out = torch.empty((B, C, hd, wd), dtype=torch.float32, device=t.device)
-    _lib.check(lib.sfh_resize_nchw(_ptr(t), _ptr(out), B * C, hs, ws, hd, wd, 1 if mode == "bilinear" else 0,
-                                   1 if align_corners else 0, _stream()), "resize_nchw")
-    return out
-
-
-def nhwc_to_nchw(t, channels=None, exp=_lib.H2_ACT_EXP):
-    if t.dtype in _SPLIT_DTYPES:
-        t = s3_to_f32(t, exp)
-    lib = _lib.load()
-    B, H, W, cs = t.shape
-    C = cs if channels is None else channels
-    out = torch.empty((B, C, H, W), dtype=torch.float32, device=t.device)
-    _lib.check(lib.sfh_nhwc_to_nchw(_ptr(t), _ptr(out), B, C, H, W, cs, _stream()), "nhwc_to_nchw")
-    return out
-
-
-def nchw_to_nhwc(t, cs=None):
-    lib = _lib.load()
-    t = _f32c(t, "nchw tensor")
-    B, C, H, W = t.shape
-    cs = cs or -(-C // 4) * 4
-    out = torch.empty((B, H, W, cs), dtype=torch.float32, device=t.device)
-    _lib.check(lib.sfh_nchw_to_nhwc(_ptr(t), _ptr(out), B, C, H, W, cs, _stream()), "nchw_to_nhwc")
-    return out
+def _check_template(template, B, shared_template):
+    if template.dim() != 4 or template.shape[1] != 1:
+        raise ValueError(f"court template must be (B,1,H,W), got {tuple(template.shape)}")
+    if template.shape[0] < B and not shared_template:
+        raise ValueError(f"batch {B} exceeds the court template batch {template.shape[0]}")
 
 
 def homography_warp(theta, template, h, w, nearest, scale=None, want_f32=True, want_i32=False,
                     shared_template=False):
     """theta (B,1,3,3)|(B,3,3); template (>=B,1,ht,wt).  Returns (f32 or None, i32 or None)."""
-    lib = _lib.load()
     theta = _f32c(theta.reshape(-1, 3, 3).contiguous(), "theta")
     template = _f32c(template, "court template")
     B = theta.shape[0]
-    if template.dim() != 4 or template.shape[1] != 1:
-        raise ValueError(f"court template must be (B,1,H,W), got {tuple(template.shape)}")
-    if template.shape[0] < B and not shared_template:
-        raise ValueError(f"batch {B} exceeds the court template batch {template.shape[0]}")
+    _check_template(template, B, shared_template)
     ht, wt = template.shape[2], template.shape[3]
     out_f = torch.empty((B, h, w), dtype=torch.float32, device=theta.device) if want_f32 else None
     out_i = torch.empty((B, h, w), dtype=torch.int32, device=theta.device) if want_i32 else None
     bstride = 0 if shared_template else ht * wt
-    tm = PackedConv.timer
-    if tm is not None and not tm.wants("warp"):
-        tm = None
-    if tm is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    _lib.check(lib.sfh_homography_warp_fwd(_ptr(theta), _ptr(template), bstride, ht, wt, B, h, w,
+    t = _timed("warp") if PackedConv.timer is not None else None
+    _lib.check(_lib.load().sfh_homography_warp_fwd(_ptr(theta), _ptr(template), bstride, ht, wt, B, h, w,
                                            0 if nearest else 1, float(scale if scale is not None else 1.0),
                                            _ptr(out_f), _ptr(out_i), _stream()), "homography_warp")
-    if tm is not None:
-        e1.record()
+    if t is not None:
+        t.stop()
         # algorithmic BYTES (SURVEY.md 8d): every output once, the template once (per frame if not shared), theta
         nout = (1 if want_f32 else 0) + (1 if want_i32 else 0)
-        tm.records.append(("warp", float(B * h * w * 4 * nout + (1 if shared_template else B) * ht * wt * 4 + 36 * B), e0, e1))
+        t.add(float(B * h * w * 4 * nout + (1 if shared_template else B) * ht * wt * 4 + 36 * B))
     return out_f, out_i
 
 
@@ -1859,53 +1286,18 @@ def warp_consistency(theta, template, logits, scale, shared_template=False, warp
         raise ValueError(f"warp {w}x{h} against logits {wl}x{hl}: the fused kernel takes the same size or exactly twice it")
     if theta.shape[0] != B:
         raise ValueError(f"{theta.shape[0]} homographies for {B} frames of logits")
-    if template.dim() != 4 or template.shape[1] != 1:
-        raise ValueError(f"court template must be (B,1,H,W), got {tuple(template.shape)}")
-    if template.shape[0] < B and not shared_template:
-        raise ValueError(f"batch {B} exceeds the court template batch {template.shape[0]}")
+    _check_template(template, B, shared_template)
     ht, wt = template.shape[2], template.shape[3]
     dev = theta.device
     out_i = torch.empty((B, h, w), dtype=torch.int32, device=dev)
     partial = torch.empty(lib.sfh_warp_consistency_workspace_floats(B, h, w), dtype=torch.float32, device=dev)
     score = torch.empty(B, dtype=torch.float32, device=dev)
-    tm = PackedConv.timer
-    if tm is not None and not tm.wants("warp+ce"):
-        tm = None
-    if tm is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    t = _timed("warp+ce") if PackedConv.timer is not None else None
     _lib.check(lib.sfh_warp_consistency_fwd(_ptr(theta), _ptr(template), 0 if shared_template else ht * wt, ht, wt, B, h, w,
                                             float(scale), _ptr(logits), nc, hl, wl, _ptr(out_i), _ptr(partial), _ptr(score),
                                             _stream()), "warp_consistency")
-    if tm is not None:
-        e1.record()
+    if t is not None:
+        t.stop()
         # algorithmic BYTES: the logits once, the mask once, the template once (per frame if not shared), theta
-        tm.records.append(("warp+ce", float(B * (hl * wl * 4 * nc + h * w * 4) + (1 if shared_template else B) * ht * wt * 4 + 36 * B), e0, e1))
+        t.add(float(B * (hl * wl * 4 * nc + h * w * 4) + (1 if shared_template else B) * ht * wt * 4 + 36 * B))
     return out_i, score
-
-
-def poi_project(theta, poi, normalize=True):
-    lib = _lib.load()
-    theta = _f32c(theta.reshape(-1, 3, 3).contiguous(), "theta")
-    B = theta.shape[0]
-    if poi.shape[0] < B:
-        raise ValueError(f"batch {B} exceeds the court POI batch {poi.shape[0]}")
-    p = _f32c(poi[:B].contiguous(), "court_poi")
-    out = torch.empty_like(p)
-    _lib.check(lib.sfh_poi_project_fwd(_ptr(theta), _ptr(p), B, p.shape[1], 1 if normalize else 0,
-                                       _ptr(out), _stream()), "poi_project")
-    return out
-
-
-def consistency_ce(logits, mask_i32):
-    lib = _lib.load()
-    logits = _f32c(logits, "logits")
-    B, nc, H, W = logits.shape
-    if mask_i32.dtype != torch.int32 or not mask_i32.is_contiguous():
-        raise ValueError("warp mask must be a contiguous int32 tensor")
-    hm, wm = mask_i32.shape[1], mask_i32.shape[2]
-    partial = torch.empty(lib.sfh_ce_workspace_floats(B, H, W), dtype=torch.float32, device=logits.device)
-    score = torch.empty(B, dtype=torch.float32, device=logits.device)
-    _lib.check(lib.sfh_consistency_ce_fwd(_ptr(logits), _ptr(mask_i32), B, nc, H, W, hm, wm, _ptr(partial),
-                                          _ptr(score), _stream()), "consistency_ce")
-    return score

@@ -221,17 +221,14 @@ class Tape:
         """H2 mode: gradient scale for n_pixels = B*H*W and the weight exponents of all conv weights (one sync)."""
         if self.fmt != "h2":
             return
-        import math
         dev = next(net.parameters()).device
         # two words: [0] raised by the kernels; [1] = a copy of [0] taken behind the forward pass (mark_forward_done), so that
         # the one read-back at the end of the step can tell a forward overflow from a backward one
         self.overflow = E.filled((2,), torch.int32, dev)
         ws = [p for p in net.parameters() if p.dim() == 4]
         # one launch over all conv weights + one read-back (sfh_multi_absminmax)
-        for w, (m, _) in zip(ws, E.absminmax([w.detach() for w in ws])):
-            if not math.isfinite(m):
-                raise ValueError("a conv weight holds non-finite values")
-            self.wexp[id(w)] = (14 - math.frexp(m)[1]) if m > 0 else 0
+        ex = E.weight_exps([w.detach() for w in ws])      # (raises on a non-finite weight)
+        self.wexp.update((id(w), ex[w.data_ptr()]) for w in ws)
 
     def mark_forward_done(self):
         """H2: remember (on the device, no synchronisation) whether anything overflowed up to here"""

@@ -463,3 +463,73 @@ def test_trained_like_family_has_the_stated_statistics():
     net.load_state_dict(sd)                                 # and the layout is the checkpoint's (strict)
 
 
+
+
+def test_conv_work_pins_the_roofline_accounting():
+    """engine.conv_work / upfused_work: FLOPs, executed FLOPs and algorithmic bytes of a launch from plain numbers.  The
+    expected figures are worked out by hand from the formulas PackedConv.run and run_upfused have always used: 2 * MACs
+    of the reference op; every operand read once at its stored width (H2 4 B, S3 6 B, fp32 4 B per element), every
+    result written once."""
+    from sfh_amd import engine as E
+    wb = 147456     # packed-weight bytes of the layer (whatever the packer reports)
+    # plain 3x3 stride-1 H2 conv, 64 -> 64 channels, batch 1, 8x8
+    assert E.conv_work(1, 8, 8, 3, 64, 0, 64, 64, src_bpe=4, dst_bpe=4, src0_hw=(8, 8), weight_bytes=wb,
+                       dst_pixels=64) == (4718592.0, None, float(8 * 8 * 64 * 4 + wb + 8 * 8 * 64 * 4))
+    # fused Up conv (PackedConv.fused_up): 64 real couts (256 with the four quadrants), 128 low-resolution channels, 64 up
+    # channels, batch 2, 4x5 low-resolution pixels, fp32 partial as destination.  Credited 2 * cout * 9 * c1 per
+    # high-resolution pixel, executed 2 * B * ho * wo * (4 * cout) * 4 * cx = 8/9 of it
+    fpp = 2.0 * 64 * 9 * 64
+    got = E.conv_work(2, 4, 5, 2, 128, 0, 256, 64, transposed=True, flops_per_out_pixel=fpp, src0_hw=(4, 5),
+                      weight_bytes=wb, dst_pixels=2 * 8 * 10)
+    assert got == (11796480.0, 10485760.0, float(2 * 4 * 5 * 128 * 4 + wb + 2 * 8 * 10 * 64 * 4))
+    assert got[1] * 9 == got[0] * 8
+    # the one-launch fused Up block: 9 taps x (skip + up channels) credited, c_up = 64 recovered from fpp
+    assert E.upfused_work(2, 8, 10, 64, 64, 128, (4, 5), fpp, 2 * wb) == (
+        23592960.0, 22282240.0, float((2 * 8 * 10 * (64 + 64) + 2 * 4 * 5 * 128) * 4 + 2 * wb))
+    # two S3 sources, S3 destination with a pooled copy, a 1000-byte residual
+    assert E.conv_work(2, 16, 16, 3, 32, 32, 64, 64, src_bpe=6, dst_bpe=6, src0_hw=(16, 16), src1_hw=(16, 16),
+                       weight_bytes=wb, dst_pixels=2 * 256, pooled=True, extra_bytes=1000) == (
+        37748736.0, None, float(2 * 98304 + 196608 + 49152 + 1000 + wb))
+    # fused head that consumes dst in registers (4 classes of fp32 logits instead); split-K slabs are fp32 whatever dst is
+    assert E.conv_work(1, 8, 8, 3, 64, 0, 64, 64, src0_hw=(8, 8), weight_bytes=wb, dst_pixels=0, head_nc=4)[2] == \
+        float(16384 + wb + 64 * 4 * 4)
+    assert E.conv_work(1, 8, 8, 3, 64, 0, 64, 64, src_bpe=6, dst_bpe=4, src0_hw=(8, 8), weight_bytes=wb,
+                       dst_pixels=64)[2] == float(8 * 8 * 64 * 6 + wb + 16384)
+    # the 7x7 stride-2 stem as a 4x4 conv over the space-to-depth input: credited with 49 taps x the real channels
+    assert E.conv_work(2, 45, 80, 4, 32, 0, 64, 64, stem_cin=5, src0_hw=(45, 80), dst_pixels=0)[0] == \
+        2.0 * 2 * 45 * 80 * 64 * 49 * 5
+
+
+def test_conv_timer_records_have_one_shape():
+    """engine.ConvTimer over ConvRecord(tag, work, e0, e1, executed, nbytes): summary() sums launches, work and event
+    time per tag (the warp launches carry BYTES as their work); traffic() / executed() list only the tags whose records
+    carry nbytes / executed."""
+    from sfh_amd import engine as E
+
+    class Ev:
+        def __init__(self, t):
+            self.t = t
+
+        def elapsed_time(self, other):
+            return other.t - self.t
+
+    tm = E.ConvTimer(only={"doubleconv3x3", "fusedup2x2", "resnet", "warp", "warp+ce"})
+    assert tm.wants("warp") and not tm.wants("convT2x2") and E.ConvTimer().wants("anything")
+    R = E.ConvRecord
+    tm.records += [R("doubleconv3x3", 100.0, Ev(0.0), Ev(1.5), None, 4000.0),
+                   R("doubleconv3x3", 50.0, Ev(2.0), Ev(2.5), None, 1000.0),
+                   R("fusedup2x2", 90.0, Ev(0.0), Ev(1.0), 80.0, 300.0),
+                   R("resnet", 10.0, Ev(1.0), Ev(1.25), None, None),        # the stem: FLOPs only
+                   R("warp", 777.0, Ev(3.0), Ev(3.5), None, None),          # bytes in the work slot
+                   R("warp+ce", 999.0, Ev(4.0), Ev(4.25), None, None)]
+    assert tm.summary() == {"doubleconv3x3": (2, 150.0, 2.0), "fusedup2x2": (1, 90.0, 1.0), "resnet": (1, 10.0, 0.25),
+                            "warp": (1, 777.0, 0.5), "warp+ce": (1, 999.0, 0.25)}
+    assert tm.traffic() == {"doubleconv3x3": 5000.0, "fusedup2x2": 300.0}
+    assert tm.executed() == {"fusedup2x2": 80.0}
+    # no timer installed, or a tag it does not want: the launch sites get None (and record no event)
+    assert E.PackedConv.timer is None and E._timed("warp") is None
+    E.PackedConv.timer = tm
+    try:
+        assert E._timed("convT2x2") is None
+    finally:
+        E.PackedConv.timer = None
