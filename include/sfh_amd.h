@@ -783,6 +783,40 @@ int sfh_overlay_annotate(uint8_t* out, int batch, int H, int W, const float* poi
                          const uint8_t* marker_color, const int8_t* labels, int L, int label_x, int label_y, int label_scale,
                          const float* score, float score_threshold, int source, void* stream);
 
+/* Training labels from manual POI annotations (dataset_utils/preparation.py), csrc/prepare.hip.                           */
+#define SFH_PREP_MAX_POINTS 256   /* template points of a fit at most                                                       */
+#define SFH_PREP_JACOBI_SWEEPS 12 /* cyclic Jacobi sweeps over the 9 x 9 normal matrix                                      */
+
+/* ONE launch for any batch, everything fp64: per frame the homography court -> frame from the point pairs (court_poi[i] in
+ * [-1,1], 2 * manual_poi[b][i] - 1) of every point with manual x != -1 and y != -1 (calculate_homography's test).  Rule:
+ * Hartley normalisation of both sets (centroid to the origin, mean distance sqrt 2), the 9 x 9 matrix L^T L of the DLT rows
+ * (-x,-y,-1,0,0,0,ux,uy,u), (0,0,0,-x,-y,-1,vx,vy,v), its eigenvector of the smallest eigenvalue by SFH_PREP_JACOBI_SWEEPS
+ * cyclic Jacobi sweeps, denormalised and divided by h33; then `refine` damped Gauss-Newton steps on h11..h32 against the
+ * summed squared forward reprojection error in normalised frame coordinates (Marquardt scaling, lambda 1e-3, / 10 after an
+ * accepted and * 10 after a rejected step; a step is accepted only when it lowers the cost).  Sums over points: slot
+ * l = i mod 64 adds its points in index order, the 64 slots are combined by the butterfly l ^ 32, 16, 8, 4, 2, 1 - no
+ * atomics, the same bits every run.  Outputs per frame: theta_c2f (9, h33 = 1), theta = inverse(theta_c2f) / its last entry
+ * (frame -> court: Reconstructor.warp's convention), theta_f32 = theta rounded once (may be NULL), poi (npts,3): court
+ * points through theta_c2f with Kornia's s = 1 / (z + 1e-8) (|z| > 1e-8, else 1), then / 2 + 0.5, third column the flag of
+ * find_nonzero_points (0 where ignore_mask[i] != 0 or manual == (-1,-1)); num_nonzero = number of flags; rmse =
+ * sum(flag * |poi * norm - manual * norm|) / num_nonzero (calculate_reprojection_rmse; norm_w = norm_h = 1 for none);
+ * status 1, or 0 with every other output of the frame zero when fewer than 4 points are usable.  ignore_mask: device uint8
+ * (npts) or NULL.  npts <= SFH_PREP_MAX_POINTS.                                                                            */
+int sfh_prep_fit(const double* court_poi, const double* manual_poi, const uint8_t* ignore_mask, int batch, int npts,
+                 double norm_w, double norm_h, int refine, double* theta_c2f, double* theta, float* theta_f32, double* poi,
+                 int32_t* num_nonzero, double* rmse, int32_t* status, void* stream);
+
+/* ONE launch: the class-id label mask (B,H,W) uint8 of theta (B,9) fp32 - pixel = ids[tap], the tap being exactly the
+ * nearest tap of sfh_homography_warp_fwd(mode 0) on an hs x ws template (zero outside) - and, with want_uv, uv (B,H,W,3)
+ * uint16 = (id, u_tab[tap x], v_tab[tap y]), zero outside.  ids uint8 (hs,ws), u_tab uint16 (ws), v_tab uint16 (hs): device
+ * pointers.  W must be a multiple of 4 (every lane stores four pixels at once).                                            */
+int sfh_prep_render(const float* theta, const uint8_t* ids, int hs, int ws, const uint16_t* u_tab, const uint16_t* v_tab,
+                    int batch, int H, int W, int want_uv, uint8_t* mask, uint16_t* uv, void* stream);
+
+/* convert_rgb_to_onehot / generate_onehot: npix pixels of 3 bytes -> one byte each: k where the pixel equals colour k of
+ * the num_classes (4, 7, 8) table of sfh_mask_format_fwd's rgb mode (k >= 1), else the pixel's byte 0.                     */
+int sfh_prep_rgb_to_ids(const uint8_t* rgb, int64_t npix, int num_classes, uint8_t* ids, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -170,6 +170,9 @@ SIGNATURES = {
                                      C.c_int, C.c_int, C.c_int, C.c_int, _p, C.c_float, C.c_int, C.c_int, C.c_float, _p, _p]),
     "sfh_overlay_annotate": (C.c_int, [_p, C.c_int, C.c_int, C.c_int, _p, C.c_int, C.c_int, _p, _p, C.c_int, C.c_int, C.c_int,
                                        C.c_int, _p, C.c_float, C.c_int, _p]),
+    "sfh_prep_fit": (C.c_int, [_p, _p, _p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "sfh_prep_render": (C.c_int, [_p, _p, C.c_int, C.c_int, _p, _p, C.c_int, C.c_int, C.c_int, C.c_int, _p, _p, _p]),
+    "sfh_prep_rgb_to_ids": (C.c_int, [_p, C.c_int64, C.c_int, _p, _p]),
 }
 
 _lib = None

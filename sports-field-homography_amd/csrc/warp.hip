@@ -14,6 +14,7 @@
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 
 #include "common.h"
+#include "warp_coords.h"
 
 // waves a launch should put on the chip before a thread takes more rows (experiment knob of profiles/build_variant.py)
 #ifndef SFH_WARP_MIN_WAVES
@@ -21,30 +22,6 @@
 #endif
 
 namespace {
-
-struct Homog {
-  float t[9];
-};
-
-__device__ __forceinline__ void apply_h(const Homog& H, float x, float y, float& u, float& v) {
-  const float X = __fadd_rn(__fadd_rn(__fmul_rn(H.t[0], x), __fmul_rn(H.t[1], y)), H.t[2]);
-  const float Y = __fadd_rn(__fadd_rn(__fmul_rn(H.t[3], x), __fmul_rn(H.t[4], y)), H.t[5]);
-  const float Z = __fadd_rn(__fadd_rn(__fmul_rn(H.t[6], x), __fmul_rn(H.t[7], y)), H.t[8]);
-  const float s = (fabsf(Z) > 1e-8f) ? __fdiv_rn(1.0f, __fadd_rn(Z, 1e-8f)) : 1.0f;
-  u = __fmul_rn(s, X);
-  v = __fmul_rn(s, Y);
-}
-
-__device__ __forceinline__ float norm_axis(int i, int n) {
-  // create_meshgrid: (i/(n-1) - 0.5) * 2
-  return __fmul_rn(__fsub_rn(__fdiv_rn((float)i, (float)(n - 1)), 0.5f), 2.0f);
-}
-
-__device__ __forceinline__ float unnorm(float c, int size) {
-  // ATen CPU grid sampler, align_corners=False: fma(fl(c + 1), size/2, -0.5) - the rounding
-  // that reproduces torch's F.grid_sample bit for bit (see oracle/warp_ref.py:unnormalize).
-  return __builtin_fmaf(__fadd_rn(c, 1.0f), 0.5f * (float)size, -0.5f);
-}
 
 __device__ __forceinline__ float fetch(const float* __restrict__ tm, float fx, float fy, int wt, int ht) {
   // fx, fy are integral-valued floats (or NaN/inf): in range -> template value, else 0
@@ -77,49 +54,7 @@ __device__ __forceinline__ float fetch(const float* __restrict__ tm, float fx, f
 // Packed fp32 instructions (v_pk_add/mul/fma_f32, two rows per instruction) were measured SLOWER
 // (4.31 vs 4.72 TB/s at 640x360 B=1024): they issue at half rate here.
 
-// LEVEL 0: IEEE divisions (any theta); 1: fast reciprocal; 2: fast reciprocal and |Z| > 1e-8 everywhere
-template <int LEVEL>
-__device__ __forceinline__ float recip_rn(float z) {
-  if (LEVEL == 0) return __fdiv_rn(1.0f, z);
-  // caller guarantees |z| <= 2^60 (a tiny or zero z gives a result the caller discards)
-  float r = __builtin_amdgcn_rcpf(z);
-  float e = __builtin_fmaf(-z, r, 1.0f);
-  r = __builtin_fmaf(e, r, r);
-  e = __builtin_fmaf(-z, r, 1.0f);
-  return __builtin_fmaf(e, r, r);
-}
-
-// i / d for integral 0 <= i <= d < 2^14, rd = __fdiv_rn(1, d)
-__device__ __forceinline__ float div_small(float i, float d, float rd) {
-  const float q0 = __fmul_rn(i, rd);
-  return __builtin_fmaf(__builtin_fmaf(-q0, d, i), rd, q0);
-}
-
-template <bool SMALL>
-__device__ __forceinline__ float norm_axis2(int i, int n, float rd) {
-  const float q = SMALL ? div_small((float)i, (float)(n - 1), rd) : __fdiv_rn((float)i, (float)(n - 1));
-  return __fmul_rn(__fsub_rn(q, 0.5f), 2.0f);
-}
-
-__device__ __forceinline__ float tap_ld(__amdgpu_buffer_rsrc_t rs, unsigned off) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, (int)off, 0, 0));
-}
-
-constexpr unsigned kTapOOB = 0xFFFFFFFCu;   // beyond any descriptor's num_records: the load returns 0
-
-// rx, ry integral-valued floats -> byte offset of the tap or kTapOOB.  LEVEL 0 tolerates NaN / inf.
-template <int LEVEL>
-__device__ __forceinline__ unsigned tap_off(float rx, float ry, int wt, int ht) {
-  if (LEVEL == 0) {
-    const bool ok = (rx >= 0.f) & (rx <= (float)(wt - 1)) & (ry >= 0.f) & (ry <= (float)(ht - 1));
-    const float fi = __builtin_fmaf(ry, (float)wt, rx);             // exact: < 2^24 (checked by the launcher)
-    return ok ? ((unsigned)(int)fi << 2) : kTapOOB;
-  }
-  // finite coordinates: v_cvt_i32_f32 saturates, one unsigned compare per axis
-  const int ix = (int)rx, iy = (int)ry;
-  const bool ok = ((unsigned)ix < (unsigned)wt) & ((unsigned)iy < (unsigned)ht);
-  return ok ? (__umul24((unsigned)iy, (unsigned)wt) + (unsigned)ix) << 2 : kTapOOB;   // valid => iy, wt < 2^24
-}
+// recip_rn, div_small, norm_axis2, tap_ld, tap_off: warp_coords.h (shared with prepare.hip)
 
 // OUT: 0 = int32 mask only (predict), 1 = float only (forward / training), 2 = both
 template <int MODE, int J, int RPT, int OUT, int LEVEL, bool SMALL, bool NOLOAD = false>
