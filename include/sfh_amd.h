@@ -817,6 +817,48 @@ int sfh_prep_render(const float* theta, const uint8_t* ids, int hs, int ws, cons
  * the num_classes (4, 7, 8) table of sfh_mask_format_fwd's rgb mode (k >= 1), else the pixel's byte 0.                     */
 int sfh_prep_rgb_to_ids(const uint8_t* rgb, int64_t npix, int num_classes, uint8_t* ids, void* stream);
 
+/* Frame -> court mapping and top-view rectification (utils/transform.py, utils/court.py, utils/mapping_example.py),
+ * csrc/mapping.hip.  theta is frame -> court in the model's convention (Reconstructor.warp samples the court template into the
+ * frame with it); theta_c2f, its inverse, samples the frame into the court view and maps court points into the frame.     */
+
+/* theta (B,3,3) fp32 -> theta_c2f (B,3,3) fp32: the fp64 adjugate times the fp64 reciprocal of the determinant, every operation
+ * individually rounded, each entry rounded once to fp32 - the matrix sfh_poi_project_fwd applies.  status (B) uint8: 1 when
+ * every entry of theta is finite and the determinant is finite and non-zero; otherwise 0 and theta_c2f of that frame is all
+ * zeros.                                                                                                                   */
+int sfh_theta_invert(const float* theta, int batch, float* theta_c2f, uint8_t* status, void* stream);
+
+/* ONE launch: frames uint8 (B,H,W,3) -> top_view uint8 (B,hc,wc,3) and valid uint8 (B,hc,wc).  Court pixel (y, x) samples
+ * the frame at unnorm(apply_h(theta_c2f[b], norm_axis(x, wc), norm_axis(y, hc)), frame size): the pinned fp32 coordinate
+ * arithmetic of sfh_homography_warp_fwd with the frame as the sampled image.  mode 0: the nearest tap (round half to even;
+ * the reference's Warper); mode 1: the four bilinear taps blended in fp32 in the order ((t00 w00 + t01 w01) + t10 w10) + t11
+ * w11, rounded half to even and clamped to a byte.  Taps outside the frame give zero.  valid = 255 where the NEAREST tap lies
+ * inside the frame (both modes), else 0.  A frame with status[b] == 0, or, with score non-NULL, a score[b] that is NaN or
+ * above max_score, gives zeros and valid 0: decided on the device, no host read-back.  score (B) fp32 may be NULL (no gate).
+ * H * W < 2^24; hc, wc 2 .. 16384.                                                                                         */
+int sfh_topview_render(const uint8_t* frames, int batch, int H, int W, const float* theta_c2f, const uint8_t* status,
+                       const float* score, float max_score, int hc, int wc, int mode, uint8_t* top_view, uint8_t* valid,
+                       void* stream);
+
+/* ONE launch: the court mosaic of a clip.  For every used frame (the rule of sfh_topview_render) in batch order, the bytes of
+ * the nearest tap of every court pixel whose tap is valid are added to sum uint32 (hc,wc,3) and 1 to count uint32 (hc,wc);
+ * both persist across calls (the caller zeroes them once).  One thread owns one court pixel: no atomics, and the integer
+ * sums do not depend on how a clip is split into calls.  Limit: a pixel's count must stay below 2^32 / 255 frames.        */
+int sfh_topview_accumulate(const uint8_t* frames, int batch, int H, int W, const float* theta_c2f, const uint8_t* status,
+                           const float* score, float max_score, int hc, int wc, uint32_t* sum, uint32_t* count, void* stream);
+
+/* image uint8 (hc,wc,3) = (2 * sum + count) / (2 * count) in integers (the mean, halves up); 0 where count == 0.            */
+int sfh_topview_finish(const uint32_t* sum, const uint32_t* count, int hc, int wc, uint8_t* image, void* stream);
+
+/* ONE launch for any n: points (n,2) fp32 through thetas[frame_index[i]] of a table (nframes,3,3) fp32 holding theta (frame ->
+ * court) or theta_c2f (court -> frame): the caller picks the direction.  frame_index int32 (n), or NULL: every point uses
+ * row frame0.  Per point: (1) with in_w, in_h != 0 the normalisation (p / size - 0.5) * 2 in fp32 (utils/transform.py:38-39 on
+ * its float32 array; 0, 0 = already normalised); (2) X, Y, W = ((t0 x + t1 y) + t2) ... in fp64; (3) w' = 1 / W if |W| >
+ * FLT_EPSILON else 0 (cv2.perspectiveTransform's rule); (4) ((X w') / 2 + 0.5) * out_sx, likewise y with out_sy, rounded once
+ * to fp32.  Every fp64 operation is individually rounded.  flag (n) uint8: 0, with out = (0, 0), for a frame index outside
+ * [0, nframes), w' == 0 or a non-finite result; else 1.                                                                    */
+int sfh_map_points(const float* points, const int32_t* frame_index, int frame0, int64_t n, const float* thetas, int nframes,
+                   float in_w, float in_h, double out_sx, double out_sy, float* out, uint8_t* flag, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,3 +5,11 @@ All arithmetic runs in hand-written HIP kernels (``csrc/``) reached through the 
 library ``libsfh_amd.so`` (``include/sfh_amd.h``); there is no CPU or torch-op fallback.
 """
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    """``sfh_amd.mapping`` (frame <-> court mapping, top views) on first use: importing the package alone stays free of torch"""
+    if name == "mapping":
+        import importlib
+        return importlib.import_module(".mapping", __name__)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

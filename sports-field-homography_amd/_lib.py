@@ -173,6 +173,12 @@ SIGNATURES = {
     "sfh_prep_fit": (C.c_int, [_p, _p, _p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, _p, _p, _p, _p, _p, _p, _p, _p]),
     "sfh_prep_render": (C.c_int, [_p, _p, C.c_int, C.c_int, _p, _p, C.c_int, C.c_int, C.c_int, C.c_int, _p, _p, _p]),
     "sfh_prep_rgb_to_ids": (C.c_int, [_p, C.c_int64, C.c_int, _p, _p]),
+    "sfh_theta_invert": (C.c_int, [_p, C.c_int, _p, _p, _p]),
+    "sfh_topview_render": (C.c_int, [_p, C.c_int, C.c_int, C.c_int, _p, _p, _p, C.c_float, C.c_int, C.c_int, C.c_int, _p, _p, _p]),
+    "sfh_topview_accumulate": (C.c_int, [_p, C.c_int, C.c_int, C.c_int, _p, _p, _p, C.c_float, C.c_int, C.c_int, _p, _p, _p]),
+    "sfh_topview_finish": (C.c_int, [_p, _p, C.c_int, C.c_int, _p, _p]),
+    "sfh_map_points": (C.c_int, [_p, _p, C.c_int, C.c_int64, _p, C.c_int, C.c_float, C.c_float, C.c_double, C.c_double, _p, _p,
+                                 _p]),
 }
 
 _lib = None

@@ -12,7 +12,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB = os.path.join(_HERE, "libsfh_amd.so")
 SOURCES = ["capi.hip", "conv_mfma.hip", "conv_s3.hip", "conv_c4h2.hip", "pointwise.hip", "warp.hip", "train.hip", "stem.hip",
            "wgrad_s3.hip", "probe.hip", "conv_small.hip", "conv_upfused.hip", "hostprep.hip",
-           "eval.hip", "augment.hip", "overlay.hip", "prepare.hip"]
+           "eval.hip", "augment.hip", "overlay.hip", "prepare.hip", "mapping.hip"]
 # warp.hip's coordinate arithmetic must not be contracted into FMAs (bit-exact nearest
 # sampling against oracle/warp_ref.py); the flag is harmless elsewhere.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off",
@@ -30,7 +30,9 @@ EXTRA_FLAGS = {"warp.hip": _NO_SLP, "conv_s3.hip": _NO_SLP, "conv_mfma.hip": _NO
                # overlay.hip's warp leg is the same coordinate arithmetic as warp.hip's, and as VALU-issue-bound
                "overlay.hip": _NO_SLP,
                # prepare.hip's render kernel is warp.hip's coordinate arithmetic again (csrc/warp_coords.h)
-               "prepare.hip": _NO_SLP}
+               "prepare.hip": _NO_SLP,
+               # mapping.hip's top-view kernels are that coordinate arithmetic once more, sampling the frame instead
+               "mapping.hip": _NO_SLP}
 
 
 def _stale(target, deps):

@@ -424,31 +424,15 @@ __global__ void selftest_axis_kernel(int nmax, unsigned long long* bad) {
   if (c) atomicAdd(bad, c);
 }
 
-// inverse(theta) in fp64 (adjugate / determinant), rounded to fp32, then the same pinned
+// inverse(theta) in fp64 (adjugate / determinant: inverse_h33 of warp_coords.h), rounded to fp32, then the same pinned
 // fp32 point transform as the warp; one thread per point.
 __global__ void poi_kernel(const float* __restrict__ theta, const float* __restrict__ poi, int npts,
                            int normalize, float* __restrict__ out, int total) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= total) return;
   const int b = idx / npts;
-  double m[9];
-#pragma unroll
-  for (int k = 0; k < 9; ++k) m[k] = (double)theta[b * 9 + k];
-  const double c00 = m[4] * m[8] - m[5] * m[7];
-  const double c01 = m[5] * m[6] - m[3] * m[8];
-  const double c02 = m[3] * m[7] - m[4] * m[6];
-  const double det = m[0] * c00 + m[1] * c01 + m[2] * c02;
-  const double id = 1.0 / det;
   Homog Hi;
-  Hi.t[0] = (float)(c00 * id);
-  Hi.t[1] = (float)((m[2] * m[7] - m[1] * m[8]) * id);
-  Hi.t[2] = (float)((m[1] * m[5] - m[2] * m[4]) * id);
-  Hi.t[3] = (float)(c01 * id);
-  Hi.t[4] = (float)((m[0] * m[8] - m[2] * m[6]) * id);
-  Hi.t[5] = (float)((m[2] * m[3] - m[0] * m[5]) * id);
-  Hi.t[6] = (float)(c02 * id);
-  Hi.t[7] = (float)((m[1] * m[6] - m[0] * m[7]) * id);
-  Hi.t[8] = (float)((m[0] * m[4] - m[1] * m[3]) * id);
+  inverse_h33(theta + b * 9, Hi);
   float u, v;
   apply_h(Hi, poi[2 * idx], poi[2 * idx + 1], u, v);
   if (normalize) {

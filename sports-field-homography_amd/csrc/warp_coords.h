@@ -1,5 +1,5 @@
 // warp_coords.h - the pinned fp32 coordinate arithmetic of the homography warp, shared by every kernel that must land on
-// the same template tap as Reconstructor.warp() (warp.hip, prepare.hip).  Every operation is individually rounded, in the
+// the same template tap as Reconstructor.warp() (warp.hip, prepare.hip, mapping.hip).  Every operation is individually rounded, in the
 // order of oracle/warp_ref.py; the translation units that include this are compiled with -ffp-contract=off.
 #pragma once
 #include "common.h"
@@ -17,6 +17,29 @@ __device__ __forceinline__ void apply_h(const Homog& H, float x, float y, float&
   const float s = (fabsf(Z) > 1e-8f) ? __fdiv_rn(1.0f, __fadd_rn(Z, 1e-8f)) : 1.0f;
   u = __fmul_rn(s, X);
   v = __fmul_rn(s, Y);
+}
+
+// inverse(theta) in fp64: adjugate times the reciprocal of the determinant, every operation individually rounded, each
+// entry rounded once to fp32 (transform_poi's court -> frame matrix; sfh_theta_invert).  Returns the determinant.
+__device__ __forceinline__ double inverse_h33(const float* __restrict__ theta, Homog& Hi) {
+  double m[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) m[k] = (double)theta[k];
+  const double c00 = m[4] * m[8] - m[5] * m[7];
+  const double c01 = m[5] * m[6] - m[3] * m[8];
+  const double c02 = m[3] * m[7] - m[4] * m[6];
+  const double det = m[0] * c00 + m[1] * c01 + m[2] * c02;
+  const double id = 1.0 / det;
+  Hi.t[0] = (float)(c00 * id);
+  Hi.t[1] = (float)((m[2] * m[7] - m[1] * m[8]) * id);
+  Hi.t[2] = (float)((m[1] * m[5] - m[2] * m[4]) * id);
+  Hi.t[3] = (float)(c01 * id);
+  Hi.t[4] = (float)((m[0] * m[8] - m[2] * m[6]) * id);
+  Hi.t[5] = (float)((m[2] * m[3] - m[0] * m[5]) * id);
+  Hi.t[6] = (float)(c02 * id);
+  Hi.t[7] = (float)((m[1] * m[6] - m[0] * m[7]) * id);
+  Hi.t[8] = (float)((m[0] * m[4] - m[1] * m[3]) * id);
+  return det;
 }
 
 __device__ __forceinline__ float norm_axis(int i, int n) {

@@ -22,7 +22,9 @@ Outputs and dtypes are those of predict.py:92-118 (``outputs.transfer_gpu_to_cpu
 ``segm_mask`` uint8 (B,H,W), ``warp_mask`` uint8 (B,H,W), ``theta`` float32 (B,1,3,3), ``consist_score`` float32 (B,),
 ``poi`` float32 (B,N,2).  With ``overlay=`` an ``OverlayRenderer`` and ``"overlay"`` requested, ``overlay`` uint8 (B,H,W,3): the
 uploaded frames at their decoded size with the court drawn over them (sfh_amd.visualize; viz_preds.py's frames, without
-the label - its text is the score, which is not on the host when the launch is enqueued).
+the label - its text is the score, which is not on the host when the launch is enqueued).  With ``top_view=`` a
+``mapping.TopViewRenderer``, ``top_view`` uint8 (B,hc,wc,3) and ``top_view_valid`` uint8 (B,hc,wc): the uploaded frames
+rectified onto the court plane with the batch's own theta (sfh_amd.mapping).
 """
 import numpy as np
 import torch
@@ -59,11 +61,14 @@ class Ticket:
 
 
 class FramePipeline:
-    def __init__(self, net, batch, frame_hw, req_outputs=("theta", "warp_mask"), consistency=False, channels=3, overlay=None):
+    def __init__(self, net, batch, frame_hw, req_outputs=("theta", "warp_mask"), consistency=False, channels=3, overlay=None,
+                 top_view=None):
         """net: a Reconstructor on the GPU in eval mode; frame_hw = (H, W) of the DECODED frames (net.unet_size, or any
         larger size: cv2.INTER_AREA's downscale runs on the GPU, engine.frames_u8_to_input); req_outputs as predict.py's --req_outputs.
         overlay: a visualize.OverlayRenderer for the output "overlay" (its score is the consistency score: without
-        consistency the renderer must be source="warp" or "segm" and have no overlay threshold)."""
+        consistency the renderer must be source="warp" or "segm" and have no overlay threshold).
+        top_view: a mapping.TopViewRenderer for the outputs "top_view" and "top_view_valid" (its score is the consistency score:
+        a renderer with max_score needs consistency=True)."""
         self.net, self.B = net, int(batch)
         self.req = set(req_outputs)
         self.consistency = bool(consistency) or "consistency" in self.req
@@ -78,6 +83,14 @@ class FramePipeline:
             if channels != 3:
                 raise ValueError(f'FramePipeline: the output "overlay" needs 3-channel frames, not {channels}')
             self.overlay = overlay
+        self.top_view = None
+        if top_view is not None:
+            if channels != 3:
+                raise ValueError(f'FramePipeline: the output "top_view" needs 3-channel frames, not {channels}')
+            if top_view.max_score is not None and not self.consistency:
+                raise ValueError('FramePipeline: without consistency=True there is no score - the TopViewRenderer must have '
+                                 'no max_score')
+            self.top_view = top_view
         p = next(net.parameters())
         if p.device.type != "cuda":
             raise RuntimeError("FramePipeline needs the model on the GPU (no CPU fallback)")
@@ -98,6 +111,12 @@ class FramePipeline:
             if self.overlay is not None:
                 s["overlay"] = torch.empty((self.B, H, W, 3), dtype=torch.uint8, device=dev)
                 s["host"]["overlay"] = pin((self.B, H, W, 3), torch.uint8)
+            if self.top_view is not None:
+                wc, hc = self.top_view.out_size
+                s["top_view"] = {"top_view": torch.empty((self.B, hc, wc, 3), dtype=torch.uint8, device=dev),
+                                 "valid": torch.empty((self.B, hc, wc), dtype=torch.uint8, device=dev)}
+                s["host"]["top_view"] = pin((self.B, hc, wc, 3), torch.uint8)
+                s["host"]["top_view_valid"] = pin((self.B, hc, wc), torch.uint8)
             if "segm_mask" in self.req:
                 s["host"]["segm_mask"] = pin((self.B, net.target_size[1], net.target_size[0]), torch.uint8)
             if "warp_mask" in self.req and net.warper:
@@ -167,6 +186,12 @@ class FramePipeline:
             # drawn from the slot's uploaded frames: the next upload into them waits for this launch too
             devout["overlay"] = self.overlay(s["u8"], out["theta"], score=out.get("consist_score"), segm=out.get("logits"),
                                              poi=out.get("poi") if self.overlay.marker_radius > 0 else None, out=s["overlay"])
+            s["consumed"] = torch.cuda.Event()
+            s["consumed"].record(cur)
+        if self.top_view is not None:
+            # rectified from the slot's uploaded frames, like the overlay: the next upload into them waits for this launch
+            tv = self.top_view(s["u8"], out["theta"], score=out.get("consist_score"), out=s["top_view"])
+            devout["top_view"], devout["top_view_valid"] = tv["top_view"], tv["valid"]
             s["consumed"] = torch.cuda.Event()
             s["consumed"].record(cur)
         ready = torch.cuda.Event()
