@@ -859,6 +859,33 @@ int sfh_topview_finish(const uint32_t* sum, const uint32_t* count, int hc, int w
 int sfh_map_points(const float* points, const int32_t* frame_index, int frame0, int64_t n, const float* thetas, int nframes,
                    float in_w, float in_h, double out_sx, double out_sy, float* out, uint8_t* flag, void* stream);
 
+/* Standard PNG files from uint8 device images, csrc/pngenc.hip (the byte-exact rule: tests/pngenc_ref.py).  8-bit gray
+ * (C = 1) or RGB (C = 3), non-interlaced; every scanline filter 1 (Sub); the filtered stream cut into strips of
+ * max(1, min(SFH_PNG_STRIP_ROWS, SFH_PNG_MAX_ROW / (1 + W C))) rows, each strip one deflate block (fixed Huffman: maximal runs
+ * of equal bytes as a literal + distance-1 matches; or stored when that would be longer than the strip + 5 bytes) in one
+ * IDAT chunk; strips that are not the last end with an empty stored block so that they concatenate on byte boundaries.   */
+#define SFH_PNG_MAX_ROW 32768   /* bytes of a filtered scanline, 1 + W C, at most                                           */
+#define SFH_PNG_STRIP_ROWS 16   /* rows of a strip at most                                                                  */
+
+/* Upper bound of the file size of an H x W x C image: 8 + 25 + 12 + strips * (12 + 5) + H (1 + W C) + 2 + 4.  -1 for
+ * C other than 1, 3, non-positive sizes or a scanline above SFH_PNG_MAX_ROW.                                               */
+int64_t sfh_png_capacity(int H, int W, int C);
+/* bytes of the scratch buffer of sfh_png_encode / sfh_png_pack (16-byte aligned): per strip a 16-byte record and a slot  */
+int64_t sfh_png_scratch_bytes(int batch, int H, int W, int C);
+
+/* ONE launch, one workgroup per (image, strip): images uint8 (B,H,W) or (B,H,W,3) -> every strip's finished IDAT chunk
+ * (length, tag, data, CRC-32) in its slot of scratch, its byte count and Adler-32 partial sums in its record.  bgr != 0: a
+ * 3-channel image is BGR in memory (RGB in the file, cv2's convention); 0: RGB in memory.  No atomics on global memory.  */
+int sfh_png_encode(const uint8_t* images, int batch, int H, int W, int C, int bgr, uint8_t* scratch, int64_t scratch_bytes,
+                   void* stream);
+
+/* ONE launch, one workgroup per image: scratch of sfh_png_encode (same batch, H, W, C) -> the files.  compact == 0: file b
+ * starts at out + b * sfh_png_capacity; != 0: the files lie back to back.  offsets int64 (B + 1): start of every file,
+ * offsets[B] the end of the last (compact) or B * capacity; sizes int32 (B).  out_bytes >= B * capacity in both modes;
+ * nothing is written at or beyond offsets[b] + capacity of any file.                                                      */
+int sfh_png_pack(const uint8_t* scratch, int64_t scratch_bytes, int batch, int H, int W, int C, int compact, uint8_t* out,
+                 int64_t out_bytes, int64_t* offsets, int32_t* sizes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

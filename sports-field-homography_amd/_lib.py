@@ -179,6 +179,10 @@ SIGNATURES = {
     "sfh_topview_finish": (C.c_int, [_p, _p, C.c_int, C.c_int, _p, _p]),
     "sfh_map_points": (C.c_int, [_p, _p, C.c_int, C.c_int64, _p, C.c_int, C.c_float, C.c_float, C.c_double, C.c_double, _p, _p,
                                  _p]),
+    "sfh_png_capacity": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "sfh_png_scratch_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "sfh_png_encode": (C.c_int, [_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p, C.c_int64, _p]),
+    "sfh_png_pack": (C.c_int, [_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p, C.c_int64, _p, _p, _p]),
 }
 
 _lib = None

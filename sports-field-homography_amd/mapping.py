@@ -32,6 +32,7 @@ import torch
 
 from . import _lib
 from . import outputs as O
+from .pngenc import files_from_batch
 from .engine import _ptr
 
 MODES = {"nearest": 0, "bilinear": 1}
@@ -318,11 +319,12 @@ class CourtMosaic:
 
 
 def rectify_game(court_json, frames, dst_dir, out_size=(1280, 720), mode="nearest", max_score=None, batch=16, names=None,
-                 mosaic=True, device="cuda"):
+                 mosaic=True, device="cuda", png="host"):
     """The host driver, in the style of ``visualize.visualize``: frames - an iterable of host uint8 (H,W,3) arrays in the
     order of the predictions of ``court_json`` (names: their frame names, checked when given).  Writes
-    ``dst_dir/<name>.png`` (outputs.encode_png), the top view of every frame, and ``dst_dir/mosaic.png``.  Returns the list
-    of written paths."""
+    ``dst_dir/<name>.png`` (outputs.encode_png), the top view of every frame, and ``dst_dir/mosaic.png``.  png: "host"
+    (outputs.encode_png, the default) or "device" (sfh_amd.pngenc: the views are encoded on the GPU).  Returns the list of
+    written paths."""
     cm = CourtMapping(court_json, device=device)
     if names is not None:
         for k, (n, p) in enumerate(zip(names, cm.names)):
@@ -334,9 +336,9 @@ def rectify_game(court_json, frames, dst_dir, out_size=(1280, 720), mode="neares
     os.makedirs(dst_dir, exist_ok=True)
     written = []
 
-    def save(path, img):
+    def save(path, buf):
         with open(path, "wb") as f:
-            f.write(O.encode_png(img).tobytes())
+            f.write(buf.tobytes())
         written.append(path)
 
     def flush(chunk, first):
@@ -346,8 +348,8 @@ def rectify_game(court_json, frames, dst_dir, out_size=(1280, 720), mode="neares
         out = renderer(fr, theta, score=score)
         if mos is not None:
             mos.add(fr, theta, score=score)
-        for k, img in zip(cm.names[first:first + B], out["top_view"].cpu().numpy()):
-            save(os.path.join(dst_dir, f"{k}.png"), img)
+        for k, buf in zip(cm.names[first:first + B], files_from_batch(out["top_view"], 3, png)):
+            save(os.path.join(dst_dir, f"{k}.png"), buf)
 
     chunk, done = [], 0
     for fr in frames:
@@ -367,5 +369,5 @@ def rectify_game(court_json, frames, dst_dir, out_size=(1280, 720), mode="neares
     if done != len(cm):
         raise ValueError(f"rectify_game: {done} frames for {len(cm)} predictions")
     if mos is not None and done:
-        save(os.path.join(dst_dir, "mosaic.png"), mos.result()[0].cpu().numpy())
+        save(os.path.join(dst_dir, "mosaic.png"), files_from_batch(mos.result()[0][None], 3, png)[0])
     return written

@@ -221,6 +221,13 @@ class MaskPickleWriter:
     def write(self, name, mask):
         pickle.dump([name, encode_png(mask)], self._f)
 
+    def write_encoded(self, name, png_buf):
+        """a record whose PNG file exists already (sfh_amd.pngenc: encoded on the device): 1-D uint8 array or bytes"""
+        buf = np.frombuffer(png_buf, dtype=np.uint8) if isinstance(png_buf, (bytes, bytearray)) else np.asarray(png_buf)
+        if buf.dtype != np.uint8 or buf.ndim != 1 or bytes(buf[:8]) != _PNG_SIG:
+            raise ValueError("write_encoded: expected the bytes of a PNG file as a 1-D uint8 array")
+        pickle.dump([name, np.array(buf)], self._f)
+
     def close(self):
         if self._f is not None:
             self._f.close()

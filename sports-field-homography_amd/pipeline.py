@@ -25,12 +25,43 @@ uploaded frames at their decoded size with the court drawn over them (sfh_amd.vi
 the label - its text is the score, which is not on the host when the launch is enqueued).  With ``top_view=`` a
 ``mapping.TopViewRenderer``, ``top_view`` uint8 (B,hc,wc,3) and ``top_view_valid`` uint8 (B,hc,wc): the uploaded frames
 rectified onto the court plane with the batch's own theta (sfh_amd.mapping).
+
+With ``png=(names)`` the named image outputs (``segm_mask``, ``warp_mask``, ``overlay``, ``top_view``) are encoded on the device
+(sfh_amd.pngenc) and arrive as ``"<name>_png"``, a list of B 1-D uint8 arrays holding PNG files; the raw image is then not
+downloaded.  The files of a batch lie back to back behind their offsets and sizes in one device buffer, whose first
+``png_budget`` bytes of file data travel with the offsets in ONE non-blocking copy; ``get()`` reads ``offsets[B]`` and fetches what
+lies beyond the budget with one further, synchronous copy (label maps compress 18-70x: the default budget, an eighth of the
+raw size of the output, is not exceeded by them).
 """
 import numpy as np
 import torch
 
 from . import engine as E
 from . import outputs as O
+from . import pngenc as P
+
+PNG_OUTPUTS = ("segm_mask", "warp_mask", "overlay", "top_view")
+
+
+def png_head_bytes(batch):
+    """bytes of offsets int64 (B+1) and sizes int32 (B) in front of the file data, padded to 16"""
+    return (8 * (batch + 1) + 4 * batch + 15) // 16 * 16
+
+
+def png_files_from_head(head, batch, budget, fetch_rest):
+    """head: the downloaded first png_head_bytes(batch) + budget bytes of a PNG buffer (1-D uint8 array) -> list of `batch` 1-D
+    uint8 arrays.  fetch_rest(begin, end): the file data bytes [begin, end) as a 1-D uint8 array, called once and only when
+    offsets[batch] exceeds the budget."""
+    offsets = head[:8 * (batch + 1)].view(np.int64)
+    sizes = head[8 * (batch + 1):8 * (batch + 1) + 4 * batch].view(np.int32)
+    total = int(offsets[batch])
+    data = head[png_head_bytes(batch):]
+    if total > budget:
+        rest = np.asarray(fetch_rest(budget, total), dtype=np.uint8)
+        if rest.shape != (total - budget,):
+            raise RuntimeError(f"FramePipeline: overflow fetch returned {rest.shape}, expected ({total - budget},)")
+        data = np.concatenate([data[:budget], rest])
+    return P.split_files(data, offsets, sizes)
 
 
 # ONE copy stream per device, shared by every FramePipeline of the process, for uploads AND downloads.  HIP multiplexes streams
@@ -50,6 +81,11 @@ def _copy_stream(dev):
     return st
 
 
+def _copied(res):
+    """a result dict that outlives the slot's pinned buffers (the PNG lists are copies already)"""
+    return {k: (v if isinstance(v, list) else np.array(v)) for k, v in res.items()}
+
+
 class Ticket:
     """one submitted batch: which slot it uses, its generation on that slot, its own events"""
     __slots__ = ("slot", "gen", "uploaded", "downloaded", "handle", "dev", "fetched")
@@ -62,13 +98,15 @@ class Ticket:
 
 class FramePipeline:
     def __init__(self, net, batch, frame_hw, req_outputs=("theta", "warp_mask"), consistency=False, channels=3, overlay=None,
-                 top_view=None):
+                 top_view=None, png=None, png_budget=None):
         """net: a Reconstructor on the GPU in eval mode; frame_hw = (H, W) of the DECODED frames (net.unet_size, or any
         larger size: cv2.INTER_AREA's downscale runs on the GPU, engine.frames_u8_to_input); req_outputs as predict.py's --req_outputs.
         overlay: a visualize.OverlayRenderer for the output "overlay" (its score is the consistency score: without
         consistency the renderer must be source="warp" or "segm" and have no overlay threshold).
         top_view: a mapping.TopViewRenderer for the outputs "top_view" and "top_view_valid" (its score is the consistency score:
-        a renderer with max_score needs consistency=True)."""
+        a renderer with max_score needs consistency=True).
+        png: names among PNG_OUTPUTS to deliver as PNG files encoded on the device ("<name>_png") instead of raw images;
+        png_budget: bytes of file data per output and batch downloaded with the offsets (default: raw size / 8)."""
         self.net, self.B = net, int(batch)
         self.req = set(req_outputs)
         self.consistency = bool(consistency) or "consistency" in self.req
@@ -102,6 +140,30 @@ class FramePipeline:
         nc = net.mask_classes
         self.h2d = self.d2h = _copy_stream(dev)
         pin = lambda shape, dt: torch.empty(shape, dtype=dt).pin_memory()
+        self.png = tuple(png) if png else ()
+        for name in self.png:
+            if name not in PNG_OUTPUTS:
+                raise ValueError(f"FramePipeline: png output {name!r} (one of {PNG_OUTPUTS})")
+        # name -> (H, W, C) of every image output that can be encoded
+        shapes = {}
+        if "segm_mask" in self.req:
+            shapes["segm_mask"] = (net.target_size[1], net.target_size[0], 1)
+        if "warp_mask" in self.req and net.warper:
+            shapes["warp_mask"] = (wh, ww, 1)
+        if self.overlay is not None:
+            shapes["overlay"] = (H, W, 3)
+        if self.top_view is not None:
+            shapes["top_view"] = (self.top_view.out_size[1], self.top_view.out_size[0], 3)
+        self._png = {}
+        for name in self.png:
+            if name not in shapes:
+                raise ValueError(f"FramePipeline: png output {name!r} is not among this pipeline's outputs {sorted(shapes)}")
+            h, w, c = shapes[name]
+            budget = self.B * h * w * c // 8 if png_budget is None else int(png_budget)
+            if budget < 0:
+                raise ValueError(f"FramePipeline: png_budget {png_budget}")
+            enc = P.PngEncoder(h, w, c, self.B, bgr=True, device=dev)
+            self._png[name] = (enc, min(budget, self.B * enc.capacity))
         self.slots = []
         for _ in range(2):
             # pending: the ticket submitted on this slot and not yet collected; collected: the ticket whose results the host
@@ -110,16 +172,18 @@ class FramePipeline:
                  "consumed": None, "host": {}, "pending": None, "collected": None, "gen": 0}
             if self.overlay is not None:
                 s["overlay"] = torch.empty((self.B, H, W, 3), dtype=torch.uint8, device=dev)
-                s["host"]["overlay"] = pin((self.B, H, W, 3), torch.uint8)
+                if "overlay" not in self._png:
+                    s["host"]["overlay"] = pin((self.B, H, W, 3), torch.uint8)
             if self.top_view is not None:
                 wc, hc = self.top_view.out_size
                 s["top_view"] = {"top_view": torch.empty((self.B, hc, wc, 3), dtype=torch.uint8, device=dev),
                                  "valid": torch.empty((self.B, hc, wc), dtype=torch.uint8, device=dev)}
-                s["host"]["top_view"] = pin((self.B, hc, wc, 3), torch.uint8)
+                if "top_view" not in self._png:
+                    s["host"]["top_view"] = pin((self.B, hc, wc, 3), torch.uint8)
                 s["host"]["top_view_valid"] = pin((self.B, hc, wc), torch.uint8)
-            if "segm_mask" in self.req:
+            if "segm_mask" in self.req and "segm_mask" not in self._png:
                 s["host"]["segm_mask"] = pin((self.B, net.target_size[1], net.target_size[0]), torch.uint8)
-            if "warp_mask" in self.req and net.warper:
+            if "warp_mask" in self.req and net.warper and "warp_mask" not in self._png:
                 s["host"]["warp_mask"] = pin((self.B, wh, ww), torch.uint8)
             if "theta" in self.req:
                 s["host"]["theta"] = pin((self.B, 1, 3, 3), torch.float32)
@@ -127,6 +191,14 @@ class FramePipeline:
                 s["host"]["consist_score"] = pin((self.B,), torch.float32)
             if self.poi:
                 s["host"]["poi"] = pin((self.B,) + tuple(net.court_poi.shape[1:]), torch.float32)
+            # per PNG output: one device buffer [offsets | sizes | file data] and the pinned image of its first bytes
+            s["png"] = {}
+            for name, (enc, budget) in self._png.items():
+                hb = png_head_bytes(self.B)
+                blob = torch.empty(hb + self.B * enc.capacity, dtype=torch.uint8, device=dev)
+                batch_out = P.PngBatch(blob[hb:], blob[:8 * (self.B + 1)].view(torch.int64),
+                                       blob[8 * (self.B + 1):8 * (self.B + 1) + 4 * self.B].view(torch.int32))
+                s["png"][name] = {"blob": blob, "out": batch_out, "head": pin((hb + budget,), torch.uint8)}
             self.slots.append(s)
         self.k = 0
         self._nc = nc
@@ -175,9 +247,9 @@ class FramePipeline:
         t.handle = None
         cur = torch.cuda.current_stream(self.dev)
         devout = {}
-        if "segm_mask" in s["host"]:
+        if "segm_mask" in s["host"] or "segm_mask" in self._png:
             devout["segm_mask"] = O.format_masks(out["logits"], "gray", self._nc)          # uint8 arg-max (postprocess.py:7-18)
-        if "warp_mask" in s["host"]:
+        if "warp_mask" in s["host"] or "warp_mask" in self._png:
             devout["warp_mask"] = O.format_masks(out["warp_mask"].contiguous(), "gray", self._nc)   # int32 -> uint8 on the GPU
         for k in ("theta", "consist_score", "poi"):
             if k in s["host"]:
@@ -194,6 +266,9 @@ class FramePipeline:
             devout["top_view"], devout["top_view_valid"] = tv["top_view"], tv["valid"]
             s["consumed"] = torch.cuda.Event()
             s["consumed"].record(cur)
+        for name, (enc, _) in self._png.items():      # two launches per output; the raw image stays on the device
+            raw = devout.pop(name)
+            enc.encode(raw, out=s["png"][name]["out"])
         ready = torch.cuda.Event()
         ready.record(cur)
         with torch.cuda.stream(self.d2h):
@@ -201,6 +276,8 @@ class FramePipeline:
             for k, v in devout.items():
                 s["host"][k].copy_(v, non_blocking=True)
                 v.record_stream(self.d2h)
+            for name, pb in s["png"].items():
+                pb["head"].copy_(pb["blob"][:pb["head"].numel()], non_blocking=True)
             t.downloaded = torch.cuda.Event()
             t.downloaded.record(self.d2h)
         t.dev = devout
@@ -219,7 +296,13 @@ class FramePipeline:
         t.downloaded.synchronize()
         t.dev = None
         t.fetched = True
-        return {k: v.numpy() for k, v in s["host"].items()}
+        res = {k: v.numpy() for k, v in s["host"].items()}
+        for name, pb in s["png"].items():
+            budget = self._png[name][1]
+            # the slot's device buffer is rewritten only by the collect() of a later batch, which needs this get() first
+            res[name + "_png"] = png_files_from_head(pb["head"].numpy(), self.B, budget,
+                                                     lambda a, e, pb=pb: pb["out"].data[a:e].cpu().numpy())
+        return res
 
     def run(self, batches):
         """Generator over host uint8 batches -> result dicts (copies), two batches in flight.  The producer may hand over the
@@ -234,7 +317,7 @@ class FramePipeline:
         while fr is not None:
             t = self.submit(fr)
             if done is not None:
-                yield {k: np.array(v) for k, v in self.get(done).items()}
+                yield _copied(self.get(done))
                 done = None
             if prev is not None:
                 done = self.collect(prev)
@@ -242,6 +325,6 @@ class FramePipeline:
             self.wait_uploaded(t)
             fr = next(it, None)
         if done is not None:
-            yield {k: np.array(v) for k, v in self.get(done).items()}
+            yield _copied(self.get(done))
         if prev is not None:
-            yield {k: np.array(v) for k, v in self.get(self.collect(prev)).items()}
+            yield _copied(self.get(self.collect(prev)))

@@ -47,6 +47,7 @@ import torch
 
 from . import _lib
 from . import outputs as O
+from .pngenc import files_from_batch
 
 FOOTBALL_PITCH_IGNORE_POINTS = (12, 13, 16, 19, 20)      # dataset_utils/preparation.py:27
 MAX_VALUE_UINT16 = 65535
@@ -291,13 +292,14 @@ def to_batch(labels, frames=None, names=None):
 
 # ---------------------------------------------------------------------------------------------- dataset on disk
 def prepare_dataset(anno_dir, dst_dir, court_ids=None, court_poi=None, size=(640, 360), num_classes=4, uv=False,
-                    ignore_pts=None, refine=10, norm_size=None, batch=64, maker=None, device="cuda"):
+                    ignore_pts=None, refine=10, norm_size=None, batch=64, maker=None, device="cuda", png="host"):
     """Steps 1-5 and 7 of dataset_utils/preparation.py: reads one ``manual_anno.json`` per game directory of ``anno_dir``
     (``generate_requests``), batches the frames across games and writes per fitted frame, under ``dst_dir/<game>/``,
     ``<frame>.json`` = {theta (frame -> court, 3x3), poi (N,3: x, y, flag), reproj_mse} - the keys ``BasicDataset`` reads -,
     ``<frame>.png`` = the id mask (``outputs.encode_png``) and, with uv, ``<frame>.npy`` = uint16 (H,W,3) (id, u, v) (where
     the reference's reader expects a 16-bit TIFF: writing TIFF is out of scope).  maker: any object with ``LabelMaker.make``'s
-    contract (default: a LabelMaker built from the arguments).  Returns {"written": [game/frame, ..], "skipped": [..]};
+    contract (default: a LabelMaker built from the arguments).  png: "host" (outputs.encode_png, the default) or "device"
+    (sfh_amd.pngenc: the masks are encoded on the GPU).  Returns {"written": [game/frame, ..], "skipped": [..]};
     skipped = frames with fewer than 4 usable points (the reference's ``return None``), for which nothing is written."""
     if maker is None:
         maker = LabelMaker(court_ids, court_poi, size, num_classes, uv=uv, ignore_pts=ignore_pts, refine=refine,
@@ -311,7 +313,9 @@ def prepare_dataset(anno_dir, dst_dir, court_ids=None, court_poi=None, size=(640
         if len(shapes) != 1:
             raise ValueError(f"prepare_dataset: manual poi of different shapes in one run: {sorted(shapes)}")
         labels = maker.make(np.stack([p for _, _, p in chunk]))
-        host = {k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)) for k, v in labels.items()}
+        files = files_from_batch(labels["mask"], 1, png)
+        host = {k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)) for k, v in labels.items()
+                if k != "mask"}
         for k, (game, fid, _) in enumerate(chunk):
             key = f"{game}/{fid}"
             if int(host["status"][k]) != 1:
@@ -323,7 +327,7 @@ def prepare_dataset(anno_dir, dst_dir, court_ids=None, court_poi=None, size=(640
                 json.dump({"theta": host["theta"][k].reshape(3, 3).tolist(), "poi": host["poi"][k].tolist(),
                            "reproj_mse": float(host["reproj_mse"][k])}, f)
             with open(stem + ".png", "wb") as f:
-                f.write(O.encode_png(host["mask"][k]).tobytes())
+                f.write(files[k].tobytes())
             if "uv" in host:
                 np.save(stem + ".npy", host["uv"][k])
             written.append(key)
