@@ -886,6 +886,33 @@ int sfh_png_encode(const uint8_t* images, int batch, int H, int W, int C, int bg
 int sfh_png_pack(const uint8_t* scratch, int64_t scratch_bytes, int batch, int H, int W, int C, int compact, uint8_t* out,
                  int64_t out_bytes, int64_t* offsets, int32_t* sizes, void* stream);
 
+/* Baseline JFIF files from uint8 device images, csrc/jpegenc.hip (the byte-exact rule is libjpeg's with a restart interval of
+ * one MCU row, restated in tests/jpegenc_ref.py): gray (C = 1) or 4:2:0 YCbCr (C = 3), Annex K quantisation tables scaled by
+ * `quality` (1 .. 100, libjpeg's rule), Annex K Huffman tables, integer arithmetic only.                                  */
+#define SFH_JPEG_MAX_WIDTH 2048   /* pixels of an image row at most: an MCU row is encoded in one workgroup's LDS             */
+
+/* Upper bound of the file size of an H x W x C image: the header (334 bytes gray, 629 colour) + per MCU row (8 pixel rows
+ * gray, 16 colour) 2 * ceil(blocks * 1660 / 8) + 2, where 1660 = 22 + 63 * 26 bits is the longest code of a block (DC: an
+ * 11-bit code + 11 bits; every AC coefficient: a 16-bit code + 10 bits), the factor 2 is every byte stuffed and the 2 bytes
+ * are the RSTm / EOI marker.  -1 for C other than 1, 3, non-positive sizes, W above SFH_JPEG_MAX_WIDTH or H above 65535.   */
+int64_t sfh_jpeg_capacity(int H, int W, int C);
+/* bytes of the scratch buffer of sfh_jpeg_encode / sfh_jpeg_pack (16-byte aligned): per MCU row an 8-byte record
+ * {bytes, passes} and a slot of the interval's capacity                                                                    */
+int64_t sfh_jpeg_scratch_bytes(int batch, int H, int W, int C);
+
+/* ONE launch, one workgroup per (image, MCU row): images uint8 (B,H,W) or (B,H,W,3) -> every restart interval's entropy-coded
+ * bytes, stuffed, 1-padded and closed by RSTm (EOI in the last), in its slot of scratch.  bgr != 0: a 3-channel image is BGR
+ * in memory (cv2's convention); 0: RGB.  window_dwords: 0, or (tests only) the size of the LDS bit window, which an interval
+ * longer than it is emitted through in several passes; the record's second word counts them.  No atomics on global memory. */
+int sfh_jpeg_encode(const uint8_t* images, int batch, int H, int W, int C, int bgr, int quality, uint8_t* scratch,
+                    int64_t scratch_bytes, int window_dwords, void* stream);
+
+/* ONE launch, one workgroup per image: scratch of sfh_jpeg_encode (same batch, H, W, C, quality) -> the files.  compact == 0:
+ * file b starts at out + b * sfh_jpeg_capacity; != 0: the files lie back to back.  offsets int64 (B + 1), sizes int32 (B) as
+ * sfh_png_pack's.  out_bytes >= B * capacity in both modes; nothing is written at or beyond offsets[b] + capacity.        */
+int sfh_jpeg_pack(const uint8_t* scratch, int64_t scratch_bytes, int batch, int H, int W, int C, int quality, int compact,
+                  uint8_t* out, int64_t out_bytes, int64_t* offsets, int32_t* sizes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -183,6 +183,10 @@ SIGNATURES = {
     "sfh_png_scratch_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "sfh_png_encode": (C.c_int, [_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p, C.c_int64, _p]),
     "sfh_png_pack": (C.c_int, [_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p, C.c_int64, _p, _p, _p]),
+    "sfh_jpeg_capacity": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "sfh_jpeg_scratch_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "sfh_jpeg_encode": (C.c_int, [_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p, C.c_int64, C.c_int, _p]),
+    "sfh_jpeg_pack": (C.c_int, [_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p, C.c_int64, _p, _p, _p]),
 }
 
 _lib = None

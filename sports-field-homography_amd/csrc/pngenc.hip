@@ -23,10 +23,12 @@
 //   computes for itself from the meta records - no third launch, no communication between workgroups.
 // No global atomics anywhere; the same bytes every run.
 #include "common.h"
+#include "block_scan.h"
 
 namespace {
 
-constexpr int kThreads = 256;
+using namespace blockscan;
+constexpr int kThreads = kScanThreads;
 constexpr int kMaxRow = SFH_PNG_MAX_ROW;
 constexpr int kStripRows = SFH_PNG_STRIP_ROWS;
 constexpr uint32_t kPoly = 0xEDB88320u;
@@ -46,40 +48,6 @@ inline int round16(int v) { return (v + 15) & ~15; }
 inline int slot_stride(int R, int rowlen) { return round16(8 + 2 + 5 + R * rowlen + 4 + 4); }
 inline int raw_lds_bytes(int R, int rowlen) { return round16(R * rowlen + 4); }
 constexpr int kTableBytes = 256 * 4 + kThreads * 4 + 16;   // CRC table, CRC partials, the scans' four wave results
-
-enum { OP_SUM, OP_MAX, OP_MIN };
-template <int OP>
-__device__ __forceinline__ int op_apply(int a, int b) {
-  return OP == OP_SUM ? a + b : (OP == OP_MAX ? (a > b ? a : b) : (a < b ? a : b));
-}
-
-// exclusive scan over the 256 threads in thread order (REV: in reverse thread order); total: over all of them.
-// tmp: 4 ints of LDS.  Wave step: the 64-lane shuffle forms, then the four wave results through LDS.
-template <int OP, bool REV>
-__device__ __forceinline__ int block_scan_excl(int v, int ident, int* tmp, int& total) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  int inc = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int o = REV ? __shfl_down(inc, d) : __shfl_up(inc, d);
-    const bool ok = REV ? (lane + d < 64) : (lane >= d);
-    if (ok) inc = op_apply<OP>(inc, o);
-  }
-  int ex = REV ? __shfl_down(inc, 1) : __shfl_up(inc, 1);
-  if (lane == (REV ? 63 : 0)) ex = ident;
-  __syncthreads();
-  if (lane == (REV ? 0 : 63)) tmp[wv] = inc;
-  __syncthreads();
-  int pre = ident;
-  total = ident;
-#pragma unroll
-  for (int w = 0; w < kThreads / 64; ++w) {
-    const int x = tmp[w];
-    total = op_apply<OP>(total, x);
-    if (REV ? (w > wv) : (w < wv)) pre = op_apply<OP>(pre, x);
-  }
-  return op_apply<OP>(pre, ex);
-}
 
 // a * b mod P over GF(2), reflected representation (x^0 = 0x80000000): the operator of zlib's crc32_combine
 __device__ __forceinline__ uint32_t gf2_mulmod(uint32_t a, uint32_t b) {

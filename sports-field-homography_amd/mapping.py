@@ -32,7 +32,7 @@ import torch
 
 from . import _lib
 from . import outputs as O
-from .pngenc import files_from_batch
+from .jpegenc import image_files_from_batch
 from .engine import _ptr
 
 MODES = {"nearest": 0, "bilinear": 1}
@@ -319,12 +319,13 @@ class CourtMosaic:
 
 
 def rectify_game(court_json, frames, dst_dir, out_size=(1280, 720), mode="nearest", max_score=None, batch=16, names=None,
-                 mosaic=True, device="cuda", png="host"):
+                 mosaic=True, device="cuda", png="host", image_format="png", jpeg_quality=90):
     """The host driver, in the style of ``visualize.visualize``: frames - an iterable of host uint8 (H,W,3) arrays in the
     order of the predictions of ``court_json`` (names: their frame names, checked when given).  Writes
     ``dst_dir/<name>.png`` (outputs.encode_png), the top view of every frame, and ``dst_dir/mosaic.png``.  png: "host"
-    (outputs.encode_png, the default) or "device" (sfh_amd.pngenc: the views are encoded on the GPU).  Returns the list of
-    written paths."""
+    (outputs.encode_png, the default) or "device" (sfh_amd.pngenc: the views are encoded on the GPU).  image_format: "png",
+    or "jpeg" for ``<name>.jpeg`` and ``mosaic.jpeg`` at jpeg_quality (``png=`` then selects where the JPEG is encoded:
+    outputs.encode_jpeg or sfh_amd.jpegenc, the same bytes).  Returns the list of written paths."""
     cm = CourtMapping(court_json, device=device)
     if names is not None:
         for k, (n, p) in enumerate(zip(names, cm.names)):
@@ -348,8 +349,9 @@ def rectify_game(court_json, frames, dst_dir, out_size=(1280, 720), mode="neares
         out = renderer(fr, theta, score=score)
         if mos is not None:
             mos.add(fr, theta, score=score)
-        for k, buf in zip(cm.names[first:first + B], files_from_batch(out["top_view"], 3, png)):
-            save(os.path.join(dst_dir, f"{k}.png"), buf)
+        files, ext = image_files_from_batch(out["top_view"], 3, png, image_format, jpeg_quality)
+        for k, buf in zip(cm.names[first:first + B], files):
+            save(os.path.join(dst_dir, f"{k}.{ext}"), buf)
 
     chunk, done = [], 0
     for fr in frames:
@@ -369,5 +371,6 @@ def rectify_game(court_json, frames, dst_dir, out_size=(1280, 720), mode="neares
     if done != len(cm):
         raise ValueError(f"rectify_game: {done} frames for {len(cm)} predictions")
     if mos is not None and done:
-        save(os.path.join(dst_dir, "mosaic.png"), files_from_batch(mos.result()[0][None], 3, png)[0])
+        files, ext = image_files_from_batch(mos.result()[0][None], 3, png, image_format, jpeg_quality)
+        save(os.path.join(dst_dir, f"mosaic.{ext}"), files[0])
     return written

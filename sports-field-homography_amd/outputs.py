@@ -16,6 +16,7 @@ The reference encodes PNGs with OpenCV, which is absent here; ``encode_png``/``d
 small zlib PNG codec for 8-bit gray / 3-channel images.  3-channel arrays are treated as BGR like
 ``cv2.imencode``/``cv2.imdecode`` do (stored RGB in the file), so streams are interchangeable.
 """
+import io
 import json
 import os
 import pickle
@@ -197,6 +198,36 @@ def decode_png(buf):
     if nch == 3:
         return np.ascontiguousarray(out[:, :, ::-1])
     return np.ascontiguousarray(out[:, :, [2, 1, 0, 3]])
+
+
+def encode_jpeg(img, quality=90, restart_rows=1):
+    """8-bit gray (H,W) or BGR (H,W,3) array -> baseline JPEG file bytes as a 1-D uint8 array, through PIL's libjpeg: 4:2:0, the
+    standard Huffman tables - ``cv2.imencode('.jpg', img, [cv2.IMWRITE_JPEG_QUALITY, quality])`` with a restart marker every
+    ``restart_rows`` MCU rows (0: none, cv2's file exactly; 1: the bytes of ``sfh_amd.jpegenc``)."""
+    from PIL import Image
+    a = np.ascontiguousarray(img)
+    if a.dtype != np.uint8:
+        raise ValueError(f"encode_jpeg: dtype {a.dtype} (uint8 only)")
+    if isinstance(quality, bool) or int(quality) != quality or not 1 <= int(quality) <= 100:
+        raise ValueError(f"encode_jpeg: quality {quality!r} (an integer 1 .. 100)")
+    if a.ndim == 3 and a.shape[2] == 1:
+        a = a[:, :, 0]
+    kw = {"restart_marker_rows": int(restart_rows)} if restart_rows else {}
+    if a.ndim == 3 and a.shape[2] == 3:
+        a, kw["subsampling"] = np.ascontiguousarray(a[:, :, ::-1]), 2           # BGR in memory -> RGB for PIL
+    elif a.ndim != 2:
+        raise ValueError(f"encode_jpeg: shape {a.shape}")
+    buf = io.BytesIO()
+    Image.fromarray(a).save(buf, "JPEG", quality=int(quality), **kw)
+    return np.frombuffer(buf.getvalue(), dtype=np.uint8)
+
+
+def decode_jpeg(buf):
+    """JPEG file bytes -> uint8 (H,W) or BGR (H,W,3), as ``cv2.imdecode(buf, IMREAD_UNCHANGED)`` gives them (PIL's libjpeg)"""
+    from PIL import Image
+    im = Image.open(io.BytesIO(bytes(np.asarray(buf, dtype=np.uint8).reshape(-1))))
+    a = np.array(im)
+    return a if a.ndim == 2 else np.ascontiguousarray(a[:, :, ::-1])
 
 
 # --------------------------------------------------------------------- mask streams on disk

@@ -32,15 +32,21 @@ downloaded.  The files of a batch lie back to back behind their offsets and size
 ``png_budget`` bytes of file data travel with the offsets in ONE non-blocking copy; ``get()`` reads ``offsets[B]`` and fetches what
 lies beyond the budget with one further, synchronous copy (label maps compress 18-70x: the default budget, an eighth of the
 raw size of the output, is not exceeded by them).
+
+With ``jpeg=(names)`` the photographic outputs (``overlay``, ``top_view``) are encoded on the device as baseline JPEG files of
+quality ``jpeg_quality`` (sfh_amd.jpegenc) and arrive as ``"<name>_jpeg"`` in the same way, through the same single copy with a
+budget (``jpeg_budget``, default a quarter of the raw size) and the same overflow fetch.  Masks hold class ids and stay PNG.
 """
 import numpy as np
 import torch
 
 from . import engine as E
 from . import outputs as O
+from . import jpegenc as J
 from . import pngenc as P
 
 PNG_OUTPUTS = ("segm_mask", "warp_mask", "overlay", "top_view")
+JPEG_OUTPUTS = ("overlay", "top_view")
 
 
 def png_head_bytes(batch):
@@ -49,7 +55,7 @@ def png_head_bytes(batch):
 
 
 def png_files_from_head(head, batch, budget, fetch_rest):
-    """head: the downloaded first png_head_bytes(batch) + budget bytes of a PNG buffer (1-D uint8 array) -> list of `batch` 1-D
+    """head: the downloaded first png_head_bytes(batch) + budget bytes of a PNG or JPEG buffer (1-D uint8 array) -> list of `batch` 1-D
     uint8 arrays.  fetch_rest(begin, end): the file data bytes [begin, end) as a 1-D uint8 array, called once and only when
     offsets[batch] exceeds the budget."""
     offsets = head[:8 * (batch + 1)].view(np.int64)
@@ -98,7 +104,7 @@ class Ticket:
 
 class FramePipeline:
     def __init__(self, net, batch, frame_hw, req_outputs=("theta", "warp_mask"), consistency=False, channels=3, overlay=None,
-                 top_view=None, png=None, png_budget=None):
+                 top_view=None, png=None, png_budget=None, jpeg=None, jpeg_quality=90, jpeg_budget=None):
         """net: a Reconstructor on the GPU in eval mode; frame_hw = (H, W) of the DECODED frames (net.unet_size, or any
         larger size: cv2.INTER_AREA's downscale runs on the GPU, engine.frames_u8_to_input); req_outputs as predict.py's --req_outputs.
         overlay: a visualize.OverlayRenderer for the output "overlay" (its score is the consistency score: without
@@ -106,7 +112,9 @@ class FramePipeline:
         top_view: a mapping.TopViewRenderer for the outputs "top_view" and "top_view_valid" (its score is the consistency score:
         a renderer with max_score needs consistency=True).
         png: names among PNG_OUTPUTS to deliver as PNG files encoded on the device ("<name>_png") instead of raw images;
-        png_budget: bytes of file data per output and batch downloaded with the offsets (default: raw size / 8)."""
+        png_budget: bytes of file data per output and batch downloaded with the offsets (default: raw size / 8).
+        jpeg: names among JPEG_OUTPUTS to deliver as JPEG files of quality jpeg_quality encoded on the device ("<name>_jpeg")
+        instead of raw images; jpeg_budget as png_budget (default: raw size / 4).  A name may be in png or in jpeg, not both."""
         self.net, self.B = net, int(batch)
         self.req = set(req_outputs)
         self.consistency = bool(consistency) or "consistency" in self.req
@@ -154,16 +162,28 @@ class FramePipeline:
             shapes["overlay"] = (H, W, 3)
         if self.top_view is not None:
             shapes["top_view"] = (self.top_view.out_size[1], self.top_view.out_size[0], 3)
-        self._png = {}
-        for name in self.png:
+        self.jpeg = tuple(jpeg) if jpeg else ()
+        for name in self.jpeg:
+            if name not in JPEG_OUTPUTS:
+                raise ValueError(f"FramePipeline: jpeg output {name!r} (one of {JPEG_OUTPUTS})")
+            if name in self.png:
+                raise ValueError(f"FramePipeline: output {name!r} is named in both png= and jpeg=")
+        # name -> (encoder, budget, key suffix) of every output that leaves as files
+        self._coded = {}
+        for name in self.png + self.jpeg:
+            fmt = "png" if name in self.png else "jpeg"
             if name not in shapes:
-                raise ValueError(f"FramePipeline: png output {name!r} is not among this pipeline's outputs {sorted(shapes)}")
+                raise ValueError(f"FramePipeline: {fmt} output {name!r} is not among this pipeline's outputs {sorted(shapes)}")
             h, w, c = shapes[name]
-            budget = self.B * h * w * c // 8 if png_budget is None else int(png_budget)
+            given = png_budget if fmt == "png" else jpeg_budget
+            budget = self.B * h * w * c // (8 if fmt == "png" else 4) if given is None else int(given)
             if budget < 0:
-                raise ValueError(f"FramePipeline: png_budget {png_budget}")
-            enc = P.PngEncoder(h, w, c, self.B, bgr=True, device=dev)
-            self._png[name] = (enc, min(budget, self.B * enc.capacity))
+                raise ValueError(f"FramePipeline: {fmt}_budget {given}")
+            if fmt == "png":
+                enc = P.PngEncoder(h, w, c, self.B, bgr=True, device=dev)
+            else:
+                enc = J.JpegEncoder(h, w, c, self.B, quality=jpeg_quality, bgr=True, device=dev)
+            self._coded[name] = (enc, min(budget, self.B * enc.capacity), "_" + fmt)
         self.slots = []
         for _ in range(2):
             # pending: the ticket submitted on this slot and not yet collected; collected: the ticket whose results the host
@@ -172,18 +192,18 @@ class FramePipeline:
                  "consumed": None, "host": {}, "pending": None, "collected": None, "gen": 0}
             if self.overlay is not None:
                 s["overlay"] = torch.empty((self.B, H, W, 3), dtype=torch.uint8, device=dev)
-                if "overlay" not in self._png:
+                if "overlay" not in self._coded:
                     s["host"]["overlay"] = pin((self.B, H, W, 3), torch.uint8)
             if self.top_view is not None:
                 wc, hc = self.top_view.out_size
                 s["top_view"] = {"top_view": torch.empty((self.B, hc, wc, 3), dtype=torch.uint8, device=dev),
                                  "valid": torch.empty((self.B, hc, wc), dtype=torch.uint8, device=dev)}
-                if "top_view" not in self._png:
+                if "top_view" not in self._coded:
                     s["host"]["top_view"] = pin((self.B, hc, wc, 3), torch.uint8)
                 s["host"]["top_view_valid"] = pin((self.B, hc, wc), torch.uint8)
-            if "segm_mask" in self.req and "segm_mask" not in self._png:
+            if "segm_mask" in self.req and "segm_mask" not in self._coded:
                 s["host"]["segm_mask"] = pin((self.B, net.target_size[1], net.target_size[0]), torch.uint8)
-            if "warp_mask" in self.req and net.warper and "warp_mask" not in self._png:
+            if "warp_mask" in self.req and net.warper and "warp_mask" not in self._coded:
                 s["host"]["warp_mask"] = pin((self.B, wh, ww), torch.uint8)
             if "theta" in self.req:
                 s["host"]["theta"] = pin((self.B, 1, 3, 3), torch.float32)
@@ -191,9 +211,9 @@ class FramePipeline:
                 s["host"]["consist_score"] = pin((self.B,), torch.float32)
             if self.poi:
                 s["host"]["poi"] = pin((self.B,) + tuple(net.court_poi.shape[1:]), torch.float32)
-            # per PNG output: one device buffer [offsets | sizes | file data] and the pinned image of its first bytes
+            # per encoded output: one device buffer [offsets | sizes | file data] and the pinned image of its first bytes
             s["png"] = {}
-            for name, (enc, budget) in self._png.items():
+            for name, (enc, budget, _) in self._coded.items():
                 hb = png_head_bytes(self.B)
                 blob = torch.empty(hb + self.B * enc.capacity, dtype=torch.uint8, device=dev)
                 batch_out = P.PngBatch(blob[hb:], blob[:8 * (self.B + 1)].view(torch.int64),
@@ -247,9 +267,9 @@ class FramePipeline:
         t.handle = None
         cur = torch.cuda.current_stream(self.dev)
         devout = {}
-        if "segm_mask" in s["host"] or "segm_mask" in self._png:
+        if "segm_mask" in s["host"] or "segm_mask" in self._coded:
             devout["segm_mask"] = O.format_masks(out["logits"], "gray", self._nc)          # uint8 arg-max (postprocess.py:7-18)
-        if "warp_mask" in s["host"] or "warp_mask" in self._png:
+        if "warp_mask" in s["host"] or "warp_mask" in self._coded:
             devout["warp_mask"] = O.format_masks(out["warp_mask"].contiguous(), "gray", self._nc)   # int32 -> uint8 on the GPU
         for k in ("theta", "consist_score", "poi"):
             if k in s["host"]:
@@ -266,7 +286,7 @@ class FramePipeline:
             devout["top_view"], devout["top_view_valid"] = tv["top_view"], tv["valid"]
             s["consumed"] = torch.cuda.Event()
             s["consumed"].record(cur)
-        for name, (enc, _) in self._png.items():      # two launches per output; the raw image stays on the device
+        for name, (enc, _, _) in self._coded.items():   # two launches per output; the raw image stays on the device
             raw = devout.pop(name)
             enc.encode(raw, out=s["png"][name]["out"])
         ready = torch.cuda.Event()
@@ -298,9 +318,9 @@ class FramePipeline:
         t.fetched = True
         res = {k: v.numpy() for k, v in s["host"].items()}
         for name, pb in s["png"].items():
-            budget = self._png[name][1]
+            _, budget, suffix = self._coded[name]
             # the slot's device buffer is rewritten only by the collect() of a later batch, which needs this get() first
-            res[name + "_png"] = png_files_from_head(pb["head"].numpy(), self.B, budget,
+            res[name + suffix] = png_files_from_head(pb["head"].numpy(), self.B, budget,
                                                      lambda a, e, pb=pb: pb["out"].data[a:e].cpu().numpy())
         return res
 

@@ -68,7 +68,55 @@ class PngBatch:
         return split_files(data, off, sizes)
 
 
-class PngEncoder:
+class BatchEncoder:
+    """what the device encoders (PngEncoder, sfh_amd.jpegenc.JpegEncoder) share: the output buffers and the refusals of
+    ``encode``'s argument.  A subclass sets H, W, C, B, capacity, device and ``batch_type``."""
+    batch_type = PngBatch
+
+    def new_output(self):
+        return self.batch_type(torch.empty(self.B * self.capacity, dtype=torch.uint8, device=self.device),
+                               torch.empty(self.B + 1, dtype=torch.int64, device=self.device),
+                               torch.empty(self.B, dtype=torch.int32, device=self.device))
+
+    def _checked(self, images):
+        """-> the number of images.  What is wrong with the tensor itself (type, dtype, shape, contiguity) is a ValueError
+        wherever the tensor lies; a well-formed tensor that is not on the GPU is the RuntimeError of every HIP path."""
+        who = type(self).__name__
+        if not isinstance(images, torch.Tensor):
+            raise ValueError(f"{who}: expected a tensor, got {type(images).__name__}")
+        if images.dtype != torch.uint8:
+            raise ValueError(f"{who}: dtype {images.dtype} (uint8 only)")
+        want = (self.H, self.W) if self.C == 1 else (self.H, self.W, 3)
+        shape = tuple(images.shape)
+        if self.C == 1 and len(shape) == 4 and shape[3] == 1:
+            shape = shape[:3]
+        if len(shape) != len(want) + 1 or shape[1:] != want or not 1 <= shape[0] <= self.B:
+            raise ValueError(f"{who}: expected (b,{','.join(map(str, want))}) with b <= {self.B}, got {tuple(images.shape)}")
+        if not images.is_contiguous():
+            raise ValueError(f"{who}: expected a contiguous tensor")
+        if images.device.type != "cuda":
+            raise RuntimeError(f"{who}: device {images.device} - the HIP path has no CPU fallback")
+        return shape[0]
+
+
+def as_image_batch(t, who):
+    """how the one-off entry points read a tensor -> (batch tensor, channels, whether it was ONE image): a 2-D tensor and a 3-D
+    tensor whose last dimension is 3 are one image, any other 3-D tensor a batch of gray images, a 4-D tensor (B,H,W,1|3) a
+    batch"""
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{who}: expected a tensor, got {type(t).__name__}")
+    if t.dtype != torch.uint8:
+        raise ValueError(f"{who}: dtype {t.dtype} (uint8 only)")
+    single = t.dim() == 2 or (t.dim() == 3 and t.shape[2] == 3)
+    batch = t[None] if single else t
+    if batch.dim() == 3:
+        return batch, 1, single
+    if batch.dim() == 4 and batch.shape[3] in (1, 3):
+        return batch, int(batch.shape[3]), single
+    raise ValueError(f"{who}: shape {tuple(t.shape)}")
+
+
+class PngEncoder(BatchEncoder):
     """Encoder of batches of up to ``batch`` H x W images of ``channels`` (1 | 3) channels; owns the scratch, output, sizes and
     offsets buffers (``encode`` reuses them: a PngBatch is valid until the next call without ``out``).  bgr: 3-channel
     tensors are BGR in memory (cv2's convention, like ``outputs.encode_png``); False for RGB tensors."""
@@ -87,28 +135,6 @@ class PngEncoder:
             raise ValueError(f"PngEncoder: {self.B} images of {self.W}x{self.H}x{self.C}: encoded batch of 2 GiB or more")
         self.scratch = torch.empty(self.scratch_bytes, dtype=torch.uint8, device=self.device)
         self.out = self.new_output()
-
-    def new_output(self):
-        return PngBatch(torch.empty(self.B * self.capacity, dtype=torch.uint8, device=self.device),
-                        torch.empty(self.B + 1, dtype=torch.int64, device=self.device),
-                        torch.empty(self.B, dtype=torch.int32, device=self.device))
-
-    def _checked(self, images):
-        if not isinstance(images, torch.Tensor):
-            raise ValueError(f"PngEncoder: expected a tensor, got {type(images).__name__}")
-        if images.dtype != torch.uint8:
-            raise ValueError(f"PngEncoder: dtype {images.dtype} (uint8 only)")
-        if images.device.type != "cuda":
-            raise RuntimeError(f"PngEncoder: device {images.device} - the HIP path has no CPU fallback")
-        want = (self.H, self.W) if self.C == 1 else (self.H, self.W, 3)
-        shape = tuple(images.shape)
-        if self.C == 1 and len(shape) == 4 and shape[3] == 1:
-            shape = shape[:3]
-        if len(shape) != len(want) + 1 or shape[1:] != want or not 1 <= shape[0] <= self.B:
-            raise ValueError(f"PngEncoder: expected (b,{','.join(map(str, want))}) with b <= {self.B}, got {tuple(images.shape)}")
-        if not images.is_contiguous():
-            raise ValueError("PngEncoder: expected a contiguous tensor")
-        return shape[0]
 
     def encode(self, images_u8, out=None):
         """images_u8: uint8 (b,H,W[,3]) on the GPU, b <= batch -> PngBatch (of b files: offsets[:b+1], sizes[:b])"""
@@ -131,22 +157,7 @@ def encode_png_device(img_or_batch, bgr=True):
     """One-off: a uint8 GPU tensor (H,W) or (H,W,3) -> one 1-D uint8 numpy array; a batch -> a list of them.  A 3-D tensor
     whose last dimension is 3 is ONE colour image, any other 3-D tensor a batch of gray images, a 4-D tensor (B,H,W,1|3) a
     batch.  Synchronises (it returns host bytes)."""
-    t = img_or_batch
-    if not isinstance(t, torch.Tensor):
-        raise ValueError(f"encode_png_device: expected a tensor, got {type(t).__name__}")
-    if t.dtype != torch.uint8:
-        raise ValueError(f"encode_png_device: dtype {t.dtype} (uint8 only)")
-    single = t.dim() == 2 or (t.dim() == 3 and t.shape[2] == 3)
-    if single:
-        t = t[None]
-    if t.dim() == 3:
-        C = 1
-    elif t.dim() == 4 and t.shape[3] in (1, 3):
-        C = int(t.shape[3])
-    else:
-        raise ValueError(f"encode_png_device: shape {tuple(img_or_batch.shape)}")
-    if C not in (1, 3):
-        raise ValueError(f"encode_png_device: {C} channels")
+    t, C, single = as_image_batch(img_or_batch, "encode_png_device")
     enc = PngEncoder(t.shape[1], t.shape[2], C, t.shape[0], bgr=bgr, device=t.device)
     files = enc.encode(t.contiguous()).to_host()
     return files[0] if single else files

@@ -35,7 +35,7 @@ import torch
 
 from . import _lib
 from . import outputs as O
-from .pngenc import files_from_batch
+from .jpegenc import image_files_from_batch
 from .engine import _ptr
 
 SOURCES = {"auto": 0, "warp": 1, "segm": 2}     # SFH_OVERLAY_AUTO / WARP / SEGM
@@ -234,15 +234,17 @@ def _names_checked(names, pred_names, mask_names):
 
 
 def visualize(frames, preds_path, dst_dir, court_img, masks_path=None, mask_classes=4, score_threshold=0.1,
-              overlay_threshold=None, batch=16, names=None, renderer=None, device="cuda", png="host", **renderer_kw):
+              overlay_threshold=None, batch=16, names=None, renderer=None, device="cuda", png="host", image_format="png",
+              jpeg_quality=90, **renderer_kw):
     """viz_preds.py:78-152 without video decode and ffmpeg.  frames: an iterable of host uint8 (H,W,3) arrays in the order of
     the predictions (names: their frame names, checked against the predictions' when given; the reference asserts
     ``int(name) == frame number``); preds_path: a ``{game}_court.json`` (outputs.CourtJsonWriter); masks_path: the optional
     ``data.pkl`` mask stream (outputs.MaskPickleWriter) - without it frames on the segmentation leg are copied.  Renders in
     batches with the label ``'{:4f}'.format(score)`` and writes ``dst_dir/<name>.png`` (outputs.encode_png).  renderer: any
     callable with OverlayRenderer's call signature (default: an OverlayRenderer built from the arguments).  png: "host"
-    (outputs.encode_png, the default) or "device" (sfh_amd.pngenc: the frames are encoded on the GPU).  Returns the list of
-    written paths."""
+    (outputs.encode_png, the default) or "device" (sfh_amd.pngenc: the frames are encoded on the GPU).  image_format: "png",
+    or "jpeg" for ``dst_dir/<name>.jpeg`` at jpeg_quality, what the reference's predict.py:394 writes (``png=`` then selects
+    where the JPEG is encoded: outputs.encode_jpeg or sfh_amd.jpegenc, the same bytes).  Returns the list of written paths."""
     mapping, _ = O.load_court_mapping(preds_path)
     pred_names = list(mapping.keys())
     masks = None
@@ -274,8 +276,9 @@ def visualize(frames, preds_path, dst_dir, court_img, masks_path=None, mask_clas
                 raise ValueError("visualize: the mask stream must hold gray id masks of one size")
             segm = torch.from_numpy(np.ascontiguousarray(np.stack(dec))).to(device)
         out = renderer(fr, theta, score=score, segm=segm, labels=['{:4f}'.format(s) for s in scores])
-        for k, buf in zip(keys, files_from_batch(out, 3, png)):
-            path = os.path.join(dst_dir, f"{k}.png")
+        files, ext = image_files_from_batch(out, 3, png, image_format, jpeg_quality)
+        for k, buf in zip(keys, files):
+            path = os.path.join(dst_dir, f"{k}.{ext}")
             with open(path, "wb") as f:
                 f.write(buf.tobytes())
             written.append(path)
