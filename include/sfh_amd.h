@@ -913,6 +913,46 @@ int sfh_jpeg_encode(const uint8_t* images, int batch, int H, int W, int C, int b
 int sfh_jpeg_pack(const uint8_t* scratch, int64_t scratch_bytes, int batch, int H, int W, int C, int quality, int compact,
                   uint8_t* out, int64_t out_bytes, int64_t* offsets, int32_t* sizes, void* stream);
 
+/* Pillow's 8-bit image resize, csrc/resample.hip (the byte-exact rule is libImaging/Resample.c's, restated in
+ * tests/resample_ref.py): `Image.resize(size, filter)` of L and RGB images for the antialiased filters below - per axis a table
+ * of (xmin, n) and n coefficients in 22-bit fixed point per output index, a horizontal pass into uint8, then a vertical pass,
+ * each clamp((2^21 + sum pixel * k) >> 22, 0, 255) in 32-bit int - and the nearest resizes of the label side.                */
+#define SFH_FILTER_BOX 4        /* Pillow's numbering of Image.BOX, BILINEAR, BICUBIC                                           */
+#define SFH_FILTER_BILINEAR 2
+#define SFH_FILTER_BICUBIC 3
+#define SFH_NEAREST_PIL 0       /* Image.resize(.., NEAREST): a running fp64 sum x = a / 2, x += a with a = in / out            */
+#define SFH_NEAREST_CV2 1       /* cv2.INTER_NEAREST: min(floor(i * (1 / (out / in))), in - 1)                                  */
+#define SFH_RESAMPLE_MAX_TAPS 64   /* coefficients of one output index at most (bicubic: downscales up to 16x)                  */
+#define SFH_RESAMPLE_MAX_ROWS 64   /* source rows of one tile's uint8 intermediate in LDS                                       */
+
+/* SFH_RESAMPLE_MAX_TAPS, for callers that cannot read this header                                                            */
+int sfh_resample_max_taps(void);
+/* Host code, no device: the table of one axis.  bounds int32 (out, 2) = (xmin, n); coef int32 (out, ksize), row xx holding its
+ * n coefficients then zeros; returns the row stride ksize = 2 ceil(support * max(in / out, 1)) + 1 (Pillow's), or -1 for
+ * sizes <= 0, an unknown filter, a null pointer or cap < out * ksize (cap: the int32 elements `coef` has room for).         */
+int sfh_resample_tab(int in, int out, int filter, int32_t* bounds, int32_t* coef, int cap);
+/* Host code: output rows per tile for the vertical axis in -> out (16, 8, 4, 2 or 1: the largest whose source rows fit
+ * SFH_RESAMPLE_MAX_ROWS); -1 for bad arguments or when an output index has more than SFH_RESAMPLE_MAX_TAPS taps.            */
+int sfh_resample_tile_rows(int in, int out, int filter);
+/* Host code: idx int32 (out) = the source index of every output index under `rule`; returns out, or -1 for sizes <= 0, an
+ * unknown rule, a null pointer or cap < out.                                                                                */
+int sfh_nearest_tab(int in, int out, int rule, int32_t* idx, int cap);
+
+/* ONE launch, one workgroup per tile of tile_rows x 64 output pixels of one image, no atomics: src uint8 (B,Hs,Ws,C), C = 1 | 3
+ * -> dst_u8 uint8 (B,Hd,Wd,C) and / or dst_f32 float32 (B,C,Hd,Wd) = byte / 255 (sfh_u8hwc_to_f32nchw's rule), whichever is not
+ * NULL.  x* / y*: DEVICE copies of the tables of sfh_resample_tab for Ws -> Wd / Hs -> Hd with their row strides and the largest
+ * n of the axis (x*taps); an axis whose sizes are equal is skipped and its table may be NULL; equal sizes on both axes give a
+ * copy.  tile_rows: sfh_resample_tile_rows(Hs, Hd, filter).  -1 with nothing launched for null pointers, bad shapes and an
+ * axis with more than SFH_RESAMPLE_MAX_TAPS taps.                                                                            */
+int sfh_resample_u8(const uint8_t* src, uint8_t* dst_u8, float* dst_f32, int batch, int C, int Hs, int Ws, int Hd, int Wd,
+                    const int32_t* xbounds, const int32_t* xcoef, int xstride, int xtaps, const int32_t* ybounds,
+                    const int32_t* ycoef, int ystride, int ytaps, int tile_rows, void* stream);
+
+/* ONE launch: nearest resize through two DEVICE index tables (sfh_nearest_tab): src (B,Hs,Ws,C) -> dst (B,Hd,Wd,C) of uint8
+ * (elem_bytes 1, C = 1 | 3) or uint16 (elem_bytes 2, C = 3: the UV label).                                                   */
+int sfh_resize_gather(const void* src, void* dst, int batch, int C, int elem_bytes, int Hs, int Ws, int Hd, int Wd,
+                      const int32_t* yidx, const int32_t* xidx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

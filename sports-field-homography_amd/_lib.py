@@ -187,6 +187,13 @@ SIGNATURES = {
     "sfh_jpeg_scratch_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "sfh_jpeg_encode": (C.c_int, [_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p, C.c_int64, C.c_int, _p]),
     "sfh_jpeg_pack": (C.c_int, [_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p, C.c_int64, _p, _p, _p]),
+    "sfh_resample_max_taps": (C.c_int, []),
+    "sfh_resample_tab": (C.c_int, [C.c_int, C.c_int, C.c_int, _p, _p, C.c_int]),
+    "sfh_resample_tile_rows": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "sfh_nearest_tab": (C.c_int, [C.c_int, C.c_int, C.c_int, _p, C.c_int]),
+    "sfh_resample_u8": (C.c_int, [_p, _p, _p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p, _p, C.c_int, C.c_int,
+                                  _p, _p, C.c_int, C.c_int, C.c_int, _p]),
+    "sfh_resize_gather": (C.c_int, [_p, _p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p, _p, _p]),
 }
 
 _lib = None

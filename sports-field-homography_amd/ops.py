@@ -292,17 +292,25 @@ def _area_tab(ssize, dsize, device):
     return t
 
 
-def frames_u8_to_input(frames_u8, target_size=None):
+def frames_u8_to_input(frames_u8, target_size=None, resize="area"):
     """uint8 (B,H,W,C) decoded frames on the GPU -> float32 (B,C,H,W) in [0,1], bit-identical to the
     reference dataset's `img.transpose((2,0,1)) / 255` (utils/dataset.py:154-159).  target_size = (W, H):
     like VideoDataset.preprocess_img (utils/dataset.py:310-330) frames WIDER than the target are resized first with
     cv2.INTER_AREA's rules: the integer factors 2 .. 16 take OpenCV's block-average fast paths (1280x720 -> 640x360 is the
     2x2 special case, 1920x1080 -> 640x360 the 3x3 one), any other downscale (both factors >= 1, e.g. 1920x1080 -> 1024x576
     or 1600x900 -> 640x360) the generic area tables (round 5).  Frames narrower than the target (the reference switches to
-    INTER_LINEAR there) are not on the HIP path."""
+    INTER_LINEAR there) are not on the HIP path.
+    resize="pil": frames of another size are resized with Pillow's rule instead - `pil_img.resize(target_size)`, bicubic with
+    antialiasing, BasicDataset.preprocess_img's (utils/dataset.py:146-161) - for any size pair within sfh_amd.resample's tap
+    bound, upscales included."""
+    if resize not in ("area", "pil"):
+        raise ValueError(f'frames_u8_to_input: resize={resize!r} ("area" or "pil")')
     lib = _lib.load()
     if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or not frames_u8.is_cuda:
         raise ValueError("expected a uint8 (B,H,W,C) tensor on the GPU")
+    if resize == "pil" and target_size is not None and (int(target_size[0]), int(target_size[1])) != tuple(frames_u8.shape[2:0:-1]):
+        from . import resample
+        return resample.pil_resize_to_input(frames_u8.contiguous(), target_size)
     f = frames_u8.contiguous()
     B, H, W, C = f.shape
     if target_size is not None and (int(target_size[0]), int(target_size[1])) != (W, H):

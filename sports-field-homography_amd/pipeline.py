@@ -44,6 +44,7 @@ from . import engine as E
 from . import outputs as O
 from . import jpegenc as J
 from . import pngenc as P
+from . import resample as RS
 
 PNG_OUTPUTS = ("segm_mask", "warp_mask", "overlay", "top_view")
 JPEG_OUTPUTS = ("overlay", "top_view")
@@ -104,7 +105,7 @@ class Ticket:
 
 class FramePipeline:
     def __init__(self, net, batch, frame_hw, req_outputs=("theta", "warp_mask"), consistency=False, channels=3, overlay=None,
-                 top_view=None, png=None, png_budget=None, jpeg=None, jpeg_quality=90, jpeg_budget=None):
+                 top_view=None, png=None, png_budget=None, jpeg=None, jpeg_quality=90, jpeg_budget=None, resize="area"):
         """net: a Reconstructor on the GPU in eval mode; frame_hw = (H, W) of the DECODED frames (net.unet_size, or any
         larger size: cv2.INTER_AREA's downscale runs on the GPU, engine.frames_u8_to_input); req_outputs as predict.py's --req_outputs.
         overlay: a visualize.OverlayRenderer for the output "overlay" (its score is the consistency score: without
@@ -114,7 +115,13 @@ class FramePipeline:
         png: names among PNG_OUTPUTS to deliver as PNG files encoded on the device ("<name>_png") instead of raw images;
         png_budget: bytes of file data per output and batch downloaded with the offsets (default: raw size / 8).
         jpeg: names among JPEG_OUTPUTS to deliver as JPEG files of quality jpeg_quality encoded on the device ("<name>_jpeg")
-        instead of raw images; jpeg_budget as png_budget (default: raw size / 4).  A name may be in png or in jpeg, not both."""
+        instead of raw images; jpeg_budget as png_budget (default: raw size / 4).  A name may be in png or in jpeg, not both.
+        resize: how frames of another size than net.unet_size get there.  "area" (the default): cv2.INTER_AREA, VideoDataset's
+        rule, downscales only; overlay and top_view are drawn from the frames at their decoded size.  "pil": Pillow's
+        Image.resize (bicubic), BasicDataset's rule (sfh_amd.resample), any size pair within its tap bound; overlay and top_view
+        are drawn from the RESIZED frames, as they are when the same frames come resized from the host."""
+        if resize not in ("area", "pil"):
+            raise ValueError(f'FramePipeline: resize={resize!r} ("area" or "pil")')
         self.net, self.B = net, int(batch)
         self.req = set(req_outputs)
         self.consistency = bool(consistency) or "consistency" in self.req
@@ -144,6 +151,12 @@ class FramePipeline:
         H, W = int(frame_hw[0]), int(frame_hw[1])
         tw, th = net.unet_size
         self.target = None if (W, H) == (tw, th) else (tw, th)
+        self.resampler = None
+        if resize == "pil" and self.target is not None:
+            self.resampler = RS.resampler((H, W), (th, tw), channels)
+            vh, vw = th, tw                               # the size of the frames overlay and top_view see
+        else:
+            vh, vw = H, W
         wh, ww = net._warp_hw
         nc = net.mask_classes
         self.h2d = self.d2h = _copy_stream(dev)
@@ -159,7 +172,7 @@ class FramePipeline:
         if "warp_mask" in self.req and net.warper:
             shapes["warp_mask"] = (wh, ww, 1)
         if self.overlay is not None:
-            shapes["overlay"] = (H, W, 3)
+            shapes["overlay"] = (vh, vw, 3)
         if self.top_view is not None:
             shapes["top_view"] = (self.top_view.out_size[1], self.top_view.out_size[0], 3)
         self.jpeg = tuple(jpeg) if jpeg else ()
@@ -191,9 +204,9 @@ class FramePipeline:
             s = {"u8": torch.empty((self.B, H, W, channels), dtype=torch.uint8, device=dev),
                  "consumed": None, "host": {}, "pending": None, "collected": None, "gen": 0}
             if self.overlay is not None:
-                s["overlay"] = torch.empty((self.B, H, W, 3), dtype=torch.uint8, device=dev)
+                s["overlay"] = torch.empty((self.B, vh, vw, 3), dtype=torch.uint8, device=dev)
                 if "overlay" not in self._coded:
-                    s["host"]["overlay"] = pin((self.B, H, W, 3), torch.uint8)
+                    s["host"]["overlay"] = pin((self.B, vh, vw, 3), torch.uint8)
             if self.top_view is not None:
                 wc, hc = self.top_view.out_size
                 s["top_view"] = {"top_view": torch.empty((self.B, hc, wc, 3), dtype=torch.uint8, device=dev),
@@ -241,7 +254,11 @@ class FramePipeline:
             t.uploaded = torch.cuda.Event()
             t.uploaded.record(self.h2d)
         cur.wait_event(t.uploaded)
-        x = E.frames_u8_to_input(s["u8"], self.target)
+        if self.resampler is not None:
+            s["frames"], x = self.resampler.both(s["u8"])     # one launch: the resized bytes for overlay / top_view and / 255
+        else:
+            s["frames"] = s["u8"]
+            x = E.frames_u8_to_input(s["u8"], self.target)
         s["consumed"] = torch.cuda.Event()
         s["consumed"].record(cur)
         t.handle = self.net.predict_async(x, consistency=self.consistency, project_poi=self.poi)
@@ -276,13 +293,13 @@ class FramePipeline:
                 devout[k] = out[k]
         if self.overlay is not None:
             # drawn from the slot's uploaded frames: the next upload into them waits for this launch too
-            devout["overlay"] = self.overlay(s["u8"], out["theta"], score=out.get("consist_score"), segm=out.get("logits"),
+            devout["overlay"] = self.overlay(s["frames"], out["theta"], score=out.get("consist_score"), segm=out.get("logits"),
                                              poi=out.get("poi") if self.overlay.marker_radius > 0 else None, out=s["overlay"])
             s["consumed"] = torch.cuda.Event()
             s["consumed"].record(cur)
         if self.top_view is not None:
             # rectified from the slot's uploaded frames, like the overlay: the next upload into them waits for this launch
-            tv = self.top_view(s["u8"], out["theta"], score=out.get("consist_score"), out=s["top_view"])
+            tv = self.top_view(s["frames"], out["theta"], score=out.get("consist_score"), out=s["top_view"])
             devout["top_view"], devout["top_view_valid"] = tv["top_view"], tv["valid"]
             s["consumed"] = torch.cuda.Event()
             s["consumed"].record(cur)

@@ -250,12 +250,16 @@ def split_uv(uv_u16):
         np.moveaxis((a[..., 1:3] / float(MAX_VALUE_UINT16)).astype(np.float32), -1, -3))
 
 
-def to_batch(labels, frames=None, names=None):
+def to_batch(labels, frames=None, names=None, frame_resize=None):
     """labels: the dict of ``LabelMaker.make`` (tensors on any device); frames: uint8 (B,H,W,3) or None; names: B frame
     names or None (then indices).  Returns (batch, dropped): the frames with status 1 as BatchAugment, TrainStep and
     eval_reconstructor take them - frames_u8 and image float32 (B,3,H,W) = / 255 (when frames are given), mask_u8, mask
     int64, uv float32 (B,2,H,W) (when labels hold uv), poi (B,N,2), nonzeros (B,N) float32, num_nonzero (B,) float32, weight
-    (B,1) float32 (preprocess_weight of reproj_mse), theta float32 (B,3,3), name - and the names of the dropped frames."""
+    (B,1) float32 (preprocess_weight of reproj_mse), theta float32 (B,3,3), name - and the names of the dropped frames.
+    frame_resize="pil": frames of another size than the labels are resized on the device with Pillow's rule
+    (BasicDataset.preprocess_img's `pil_img.resize`, sfh_amd.resample) instead of refused; frames_u8 holds the resized bytes."""
+    if frame_resize not in (None, "pil"):
+        raise ValueError(f'to_batch: frame_resize={frame_resize!r} (None or "pil")')
     status = labels["status"].cpu().numpy()
     B = int(status.shape[0])
     names = list(range(B)) if names is None else list(names)
@@ -282,11 +286,17 @@ def to_batch(labels, frames=None, names=None):
         batch["uv"] = split_uv(sel(labels["uv"].view(torch.int16)).view(torch.uint16))[1]
     if frames is not None:
         if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[0] != B \
-                or tuple(frames.shape[1:3]) != tuple(labels["mask"].shape[1:]) or frames.shape[3] != 3:
+                or frames.shape[3] != 3 \
+                or (frame_resize is None and tuple(frames.shape[1:3]) != tuple(labels["mask"].shape[1:])):
             raise ValueError(f"frames: expected uint8 ({B},H,W,3) of the labels' size, got {tuple(getattr(frames, 'shape', ()))}")
         fr = sel(frames.to(dev)).contiguous()
+        if tuple(fr.shape[1:3]) != tuple(labels["mask"].shape[1:]):
+            from . import resample
+            hd, wd = (int(v) for v in labels["mask"].shape[1:])
+            fr, batch["image"] = resample.resampler(tuple(int(v) for v in fr.shape[1:3]), (hd, wd), 3).both(fr)
+        else:
+            batch["image"] = (fr.permute(0, 3, 1, 2).to(torch.float32) / 255).contiguous()      # utils/dataset.py:154-159
         batch["frames_u8"] = fr
-        batch["image"] = (fr.permute(0, 3, 1, 2).to(torch.float32) / 255).contiguous()      # utils/dataset.py:154-159
     return batch, dropped
 
 
@@ -334,27 +344,45 @@ def prepare_dataset(anno_dir, dst_dir, court_ids=None, court_poi=None, size=(640
     return {"written": written, "skipped": skipped}
 
 
-def read_dataset(dst_dir, keys, use_uv=False, device="cpu"):
+def read_dataset(dst_dir, keys, use_uv=False, device="cpu", size=None):
     """``BasicDataset.__getitem__``'s label side (utils/dataset.py:240-289, anno_keys = theta, poi, reproj_mse; no resize: the
     labels are written at the target size) for the frames ``keys`` (``game/frame``) of a tree written by ``prepare_dataset``,
-    collated: the entries ``to_batch`` returns for the same frames (without frames_u8 / image)."""
+    collated: the entries ``to_batch`` returns for the same frames (without frames_u8 / image).
+    size=(W, H): the labels at another size than the written one, as ``BasicDataset`` resizes them - the mask with
+    ``Image.NEAREST`` (preprocess_mask), the uint16 UV label with cv2.INTER_NEAREST before it is split (preprocess_uv_mask) - on
+    the device (``resample.resize_nearest``): ``device`` must then be a GPU."""
+    if size is not None:
+        size = (int(size[0]), int(size[1]))
+        if torch.device(device).type != "cuda":
+            raise ValueError(f"read_dataset: size={size} resizes on the device; device={device!r} is not a GPU")
+        from . import resample
     masks, uvs, pois, nzs, thetas, ws = [], [], [], [], [], []
     for key in keys:
         stem = os.path.join(dst_dir, *str(key).split("/"))
         with open(stem + ".json", "r") as f:
             anno = json.load(f)
-        if use_uv:
+        if use_uv and size is not None:
+            lab = torch.from_numpy(np.ascontiguousarray(np.load(stem + ".npy")).view(np.int16)).to(device).view(torch.uint16)
+            m, uvp = split_uv(resample.resize_nearest(lab[None], (size[1], size[0]), rule="cv2")[0])
+            uvs.append(uvp)
+            masks.append(m.contiguous())
+            m = None
+        elif use_uv:
             m, uvp = split_uv(np.load(stem + ".npy"))
             uvs.append(torch.from_numpy(uvp))
         else:
             m = O.decode_png(np.fromfile(stem + ".png", dtype=np.uint8))
-        masks.append(torch.from_numpy(np.ascontiguousarray(m)))
+        if m is not None:
+            masks.append(torch.from_numpy(np.ascontiguousarray(m)))
         p = torch.from_numpy(np.asarray(anno["poi"], dtype="float")).type(torch.FloatTensor)
         pois.append(p[:, :2])
         nzs.append(p[:, 2])
         thetas.append(torch.from_numpy(np.asarray(anno["theta"], dtype="float")).type(torch.FloatTensor))
         ws.append(torch.from_numpy(preprocess_weight(np.asarray([anno["reproj_mse"]], dtype="float"))))
-    batch = {"name": [str(k) for k in keys], "mask_u8": torch.stack(masks).to(device),
+    mask_u8 = torch.stack(masks).to(device)
+    if size is not None and not use_uv:
+        mask_u8 = resample.resize_nearest(mask_u8.contiguous(), (size[1], size[0]), rule="pil")
+    batch = {"name": [str(k) for k in keys], "mask_u8": mask_u8,
              "poi": torch.stack(pois).contiguous().to(device), "nonzeros": torch.stack(nzs).contiguous().to(device),
              "theta": torch.stack(thetas).to(device), "weight": torch.stack(ws).to(device)}
     batch["mask"] = batch["mask_u8"].to(torch.int64)
