@@ -257,6 +257,16 @@ int64_t sfh_packed_c4h2_weight_bytes(int cout);
 int sfh_pack_c4h2_weights(const float* w, void* packed, int cin, int cout, int wexp, void* stream);
 int sfh_conv3x3_c4h2_fwd(const sfh_conv_desc* d, void* stream);
 
+/* The UNet's first DoubleConv in "f16x3" arithmetic - conv3x3(<= 4 -> 64) + BatchNorm + ReLU + conv3x3(64 -> 64) + BatchNorm +
+ * ReLU, unet/unet_parts.py:14-21 - as ONE launch: the 64-channel intermediate is produced and consumed in LDS and never
+ * written to memory.  inc0 = the descriptor sfh_conv3x3_c4h2_fwd would take for the first conv (FH2 frame source, cout 64,
+ * dst_fmt H2; h2_exp_dst = the intermediate's exponent, h2_range / h2_overflow = the intermediate's words, which receive what
+ * that launch would leave; dst is not used), inc3 = the descriptor sfh_conv_s3_fwd would take for the second conv (H2, ksize 3,
+ * stride 1, c0 = cout = 64, tile SFH_TILE_8x32, h2_exp_src = inc0's h2_exp_dst, optional dst_pool, reverse_tiles; no second
+ * source / residual / head / acc_init / split-K / statistics; src0 is not used).  Same products in the same order per output
+ * element as the two launches: dst, dst_pool and all four range / overflow words are bit-identical. */
+int sfh_conv_inc_fused_fwd(const sfh_conv_desc* inc0, const sfh_conv_desc* inc3, void* stream);
+
 /* Number of floats of the packed weight buffer for a conv with the given geometry. */
 int64_t sfh_packed_weight_floats(int ksize, int c0, int c1, int cout_virtual);
 

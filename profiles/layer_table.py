@@ -34,14 +34,18 @@ if any('conv_upfused' in r['Kernel_Name'] for r in step):
         i = names.index(lv + ".fuse")
         L[i:i + 2] = [(lv + ".one", g)]
         names = [n for n, _ in L]
+if any('conv_inc_fused' in r['Kernel_Name'] for r in step):
+    # the first DoubleConv is ONE kernel (csrc/conv_inc_fused.hip), credited with both convs it stands for
+    L[0:2] = [("inc.one", gm(3, 64, 360, 640) + gm(64, 64, 360, 640))]
 dur = lambda r: (int(r['End_Timestamp']) - int(r['Start_Timestamp'])) / 1e6
-is_conv = lambda n: 'conv_mfma' in n or 'conv_s3' in n or 'conv_upfused' in n or 'conv_small' in n or 'conv3x3_c4' in n or 'stem7x7' in n   # (c4: also conv3x3_c4h2)
+is_conv = lambda n: 'conv_mfma' in n or 'conv_s3' in n or 'conv_upfused' in n or 'conv_inc_fused' in n or 'conv_small' in n or 'conv3x3_c4' in n or 'stem7x7' in n   # (c4: also conv3x3_c4h2)
 convs = [r for r in step if is_conv(r['Kernel_Name'])]
 tot = 0
 for (nm, g), r in zip(L, convs[:len(L)]):
     d = dur(r)
     m_ = re.search(r'Cfg<([^>]*)>', r['Kernel_Name'])
-    cfg = m_.group(1) if m_ else ('single-kernel Up' if 'upfused' in r['Kernel_Name'] else 'c4 tap-packed')
+    cfg = m_.group(1) if m_ else ('single-kernel Up' if 'upfused' in r['Kernel_Name'] else
+                              'single-kernel inc' if 'inc_fused' in r['Kernel_Name'] else 'c4 tap-packed')
     print(f"{nm:6s} cfg<{cfg:22s}> {d:7.3f} ms {2*g*B/d:7.1f} TFLOP/s grid={r.get('Grid_Size_X')} vgpr={r.get('VGPR_Count')} lds={r.get('LDS_Block_Size')}")
     tot += d
 print(f"UNet conv launches: {tot:.3f} ms")

@@ -48,6 +48,8 @@ def group(name, resnet=False):
         return "s3_resnet" if resnet else "s3_conv3x3"
     if "conv_upfused_kernel" in name:    # round 5: composed 2x2 + skip-half 3x3 of a fused Up block in one kernel (u3, u4)
         return "s3_upfused"
+    if "conv_inc_fused_kernel" in name:  # the first DoubleConv (frame -> 64 -> 64) in one kernel
+        return "s3_incfused"
     if "stem7x7" in name:
         return "s3_stem7x7"
     if "conv3x3_c4" in name:

@@ -26,7 +26,7 @@ def label(n):
     m = re.search(r"S3Cfg<([^>]*)>, (true|false)", n)
     if m:
         return f"conv_s3 S3Cfg<{m.group(1)}> DB={m.group(2)}"
-    for k in ("conv_upfused_kernel", "conv_small_kernel", "conv3x3_c4h2_kernel", "stem7x7_kernel", "outconv_kernel", "warp"):
+    for k in ("conv_upfused_kernel", "conv_inc_fused_kernel", "conv_small_kernel", "conv3x3_c4h2_kernel", "stem7x7_kernel", "outconv_kernel", "warp"):
         if k in n:
             return k
     return None

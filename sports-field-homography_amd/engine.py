@@ -697,6 +697,75 @@ def run_upfused(fu, sk, skip, ylow, dst, batch, H, W, exp_dst=None, range_word=N
     return dst
 
 
+def inc_fused_ok(l0, l3):
+    """can the pair (first conv over the FH2 frame, second conv) of a DoubleConv run as ONE launch (run_inc_fused)?"""
+    return (l0.c4h2 and l3.fmt == "h2" and l0.cout == l0.cout_real == 64 and l3.cout == l3.cout_real == 64 and l3.c0 == 64
+            and l3.c1 == 0 and l3.ksize == 3 and l3.stride == 1 and not l3.transposed and l0.wpacked is not None)
+
+
+def run_inc_fused(l0, l3, frame, dst, batch, H, W, dst_pool=None, exp_frame=None, exp_mid=None, exp_dst=None,
+                  range_mid=None, range_dst=None):
+    """The UNet's first DoubleConv as ONE launch (sfh_conv_inc_fused_fwd, csrc/conv_inc_fused.hip): l0 = the first-layer
+    PackedConv over the FH2 frame tensor (frame_h2=True, 64 couts), l3 = the 64 -> 64 H2 conv behind it; frame: the float32
+    (B,H,W,4) tensor of sfh_frame_to_h2; dst / dst_pool: H2 tensors.  The 64-channel intermediate exists in LDS only; its
+    exponent (exp_mid) and range word (range_mid) are used and written as by the two launches.  Bit-identical to
+    l0.run(frame, ..., mid) followed by l3.run(mid, ..., dst, dst_pool=dst_pool)."""
+    if not inc_fused_ok(l0, l3):
+        raise ValueError("run_inc_fused: needs the FH2 first-layer conv (<= 4 -> 64 channels) and a plain 64 -> 64 3x3 H2 conv")
+    if (tuple(frame.shape) != (batch, H, W, 4) or frame.dtype != torch.float32 or _fmt_of(dst) != "h2"
+            or (dst.shape[0],) + _hw(dst) != (batch, H, W) or _chan(dst) < 64):
+        raise ValueError("run_inc_fused: frame must be the float32 (B,H,W,4) FH2 tensor, dst an H2 tensor of the frame's size")
+    if dst_pool is not None and (_fmt_of(dst_pool) != "h2" or (dst_pool.shape[0],) + _hw(dst_pool) != (batch, H // 2, W // 2)
+                                 or _chan(dst_pool) < 64):
+        raise ValueError("run_inc_fused: dst_pool must be an H2 tensor of half the frame's size")
+    for t in (frame, dst, dst_pool):
+        if t is not None and t.numel() * t.element_size() >= 0xFFFFFFF0:
+            raise ValueError("run_inc_fused: a tensor exceeds the 4 GiB buffer-descriptor range of the conv kernels; split the batch")
+    if exp_frame is not None:
+        l0._fold_exp_src(int(exp_frame))
+    if exp_mid is not None:
+        l3._fold_exp_src(int(exp_mid))
+    ovf = l3.overflow
+    d0, d3 = ConvDesc(), ConvDesc()
+    for d, layer in ((d0, l0), (d3, l3)):
+        d.batch, d.H, d.W, d.h0, d.w0, d.ksize, d.stride = batch, H, W, H, W, 3, 1
+        d.wpacked, d.scale, d.shift = layer.wpacked.data_ptr(), layer.scale.data_ptr(), layer.shift.data_ptr()
+        d.cout, d.relu, d.out_mode = 64, 1 if layer.relu else 0, _lib.OUT_NHWC
+        d.h2_exp_src, d.dst_fmt = layer.exp_src, _lib.FMT_H2
+        d.h2_overflow = ovf.data_ptr() if ovf is not None else None
+    d0.src0, d0.c0, d0.cs0, d0.src_fmt = frame.data_ptr(), l0.c0, 4, _lib.FMT_FH2
+    d0.h2_exp_dst = l3.exp_src
+    d0.h2_range = range_mid if range_mid else None
+    d3.c0, d3.cs0, d3.src_fmt = 64, 64, _lib.FMT_H2
+    d3.dst, d3.dst_cs = dst.data_ptr(), _chan(dst)
+    if dst_pool is not None:
+        d3.dst_pool, d3.pool_cs = dst_pool.data_ptr(), _chan(dst_pool)
+    if exp_dst is not None:
+        d3.h2_exp_dst = int(exp_dst)
+    d3.h2_range = range_dst if range_dst else None
+    d3.tile = _lib.TILE_8x32
+    # one launch where the two-launch form asks the order once too (the first-layer kernel has no tile direction)
+    d3.reverse_tiles = 1 if (l3.order is not None and l3.order.next()) else 0
+    t = _timed("incfused") if PackedConv.timer is not None else None
+    _lib.check(_lib.load().sfh_conv_inc_fused_fwd(ctypes.byref(d0), ctypes.byref(d3), _stream()), "conv_inc_fused_fwd")
+    if t is not None:
+        t.stop()
+        t.add(*inc_fused_work(batch, H, W, l0.c0, sum(x.wpacked.numel() * x.wpacked.element_size() for x in (l0, l3)),
+                              dst_pool is not None))
+    return dst
+
+
+def inc_fused_work(batch, H, W, c0, weight_bytes, pooled):
+    """conv_work's counterpart for run_inc_fused -> (flops, executed, nbytes).  Credited with both reference convs (9 taps x
+    c0 -> 64 and 9 taps x 64 -> 64; the halo pixels of the first one that neighbouring workgroups recompute are not counted);
+    bytes: the 16-byte FH2 frame pixels in, the H2 output (4 B per element) and its pooled copy out, the weights."""
+    flops = 2.0 * batch * H * W * 64 * 9 * (c0 + 64)
+    nbytes = batch * H * W * (16 + 64 * 4) + weight_bytes
+    if pooled:
+        nbytes += batch * (H // 2) * (W // 2) * 64 * 4
+    return flops, None, float(nbytes)
+
+
 class _Workspace:
     """Named activation buffers, one per name: a call with another shape (a different batch size, the tail
     chunk of a sub-batched call) replaces the buffer instead of keeping a second full activation set in HBM."""
@@ -790,6 +859,10 @@ class UNetEngine(_Engine):
         # "f16x3": the 3-channel first layer too runs on the fp16 matrix cores, from a frame tensor split once (FH2)
         self.frame_h2 = fmt == "h2" and os.environ.get("SFH_INC0_H2", "1") != "0"
 
+        # the first DoubleConv (frame -> 64 -> 64) as ONE launch (csrc/conv_inc_fused.hip; bit-identical to the two launches):
+        # the 0.94 GB intermediate of a 640x360 x 16 batch never leaves LDS.  Inference only - this engine; a training tape keeps
+        # the intermediate for its backward pass.  SFH_FUSE_INC=0 restores the two launches.
+        self.fuse_inc = self.frame_h2 and os.environ.get("SFH_FUSE_INC", "1") != "0"
         fuse_up = not self.bilinear and s3 and os.environ.get("SFH_FUSE_UP", "1") != "0"
         ups = [(i, cin, getattr(net, f"up{i}")) for i, cin in enumerate((1024, 512, 256, 128), start=1)]
         # the skip halves of the Up blocks' first convs (unet/unet_parts.py:67: cat([skip, up])) as tensors of their own
@@ -898,11 +971,22 @@ class UNetEngine(_Engine):
         def dconv(name, src0, h, w, cout, src1=None, pool0=False, pad1=(0, 0), want_pool=False, out_f32=False, head=None):
             """src0 / src1: (tensor, name) pairs"""
             (t0, n0), (t1, _) = src0, (src1 if src1 is not None else (None, None))
-            mid, nmid = act(name + ".mid", (B, h, w), L[name + ".0"].cout_real)
+            l0, l3 = L[name + ".0"], L[name + ".3"]
+            fuse = (self.fuse_inc and name == "inc" and t1 is None and head is None and not pool0 and not out_f32
+                    and inc_fused_ok(l0, l3))
+            if fuse:    # "inc.mid" keeps its exponent and range word (the range guard reads them) but has no buffer
+                rg.register(name + ".mid")
+                mid, nmid = None, name + ".mid"
+            else:
+                mid, nmid = act(name + ".mid", (B, h, w), l0.cout_real)
             out, nout = act(name + ".out", (B, h, w), cout, f32=out_f32)
             pooled, npool = (act(name + ".pool", (B, h // 2, w // 2), cout, key=nout, word_of=nout)
                              if (want_pool and s3) else (None, None))
-            l0, l3 = L[name + ".0"], L[name + ".3"]
+            if fuse:
+                do((nmid, nout), lambda: run_inc_fused(
+                    l0, l3, t0, out, B, h, w, dst_pool=pooled, exp_frame=rg.exp(n0), exp_mid=rg.exp(nmid), exp_dst=rg.exp(nout),
+                    range_mid=rg.word_ptr(nmid), range_dst=rg.word_ptr(nout)))
+                return (out, nout), (pooled, npool)
             do((nmid,) if nmid else (), lambda: l0.run(t0, B, h, w, mid, src1=t1, pool0=pool0, pad1=pad1, **rg.args(n0, nmid)))
             do((nout,) if nout else (), lambda: l3.run(mid, B, h, w, out, dst_pool=pooled, head=head, **rg.args(nmid, nout)))
             return (out, nout), (pooled, npool)
