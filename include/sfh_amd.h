@@ -923,6 +923,100 @@ int sfh_jpeg_encode(const uint8_t* images, int batch, int H, int W, int C, int b
 int sfh_jpeg_pack(const uint8_t* scratch, int64_t scratch_bytes, int batch, int H, int W, int C, int quality, int compact,
                   uint8_t* out, int64_t out_bytes, int64_t* offsets, int32_t* sizes, void* stream);
 
+/* Baseline JFIF files -> uint8 device frames, csrc/jpegdec.hip with the decode core csrc/jpegdec_core.h (the byte-exact rule is
+ * libjpeg's - jidctint's "islow" IDCT, the triangle h2v2 upsampler, the 16-bit fixed-point YCbCr -> RGB tables - restated in
+ * tests/jpegdec_ref.py, which tests/test_jpegdec_host.py holds to PIL's bytes).  Admitted: SOF0, 8 bits, one interleaved scan
+ * (Ss, Se, Ah/Al = 0, 63, 0), gray or YCbCr at 4:2:0 or 4:4:4, any 8-bit quantisation and any Huffman tables, any restart
+ * interval.  Everything else is refused on the host, with nothing launched: -1 and one of the reasons below; a reason of 100 or
+ * more names a well-formed file that needs something not built.                                                              */
+#define SFH_JPEG_R_OK 0
+#define SFH_JPEG_R_TRUNCATED 1        /* the bytes end inside the header                                                       */
+#define SFH_JPEG_R_NOT_JPEG 2         /* no SOI                                                                                */
+#define SFH_JPEG_R_MARKER 3           /* a marker that may not stand where it stands, or fill bytes inside entropy-coded data  */
+#define SFH_JPEG_R_BAD_SOF 4
+#define SFH_JPEG_R_BAD_TABLE 5        /* a DQT / DHT segment that defines no valid table, or a table used but not defined      */
+#define SFH_JPEG_R_BAD_SOS 6
+#define SFH_JPEG_R_RESTART 7          /* RSTm out of sequence, or not as many as the restart interval asks for                 */
+#define SFH_JPEG_R_SIZE 8             /* width, height or channels other than the decoder's                                    */
+#define SFH_JPEG_R_TOO_LONG 9         /* more bytes than the decoder's max_file_bytes                                          */
+#define SFH_JPEG_R_PROGRESSIVE 100
+#define SFH_JPEG_R_ARITHMETIC 101
+#define SFH_JPEG_R_PRECISION 102      /* 12-bit samples                                                                        */
+#define SFH_JPEG_R_DQT16 103          /* 16-bit quantisation tables                                                            */
+#define SFH_JPEG_R_COMPONENTS 104     /* 2 or 4 components                                                                     */
+#define SFH_JPEG_R_COLORSPACE 105     /* 3 components that are RGB by libjpeg's rule                                           */
+#define SFH_JPEG_R_SAMPLING 106       /* 4:2:2, 4:4:0, 4:1:1, ...                                                              */
+#define SFH_JPEG_R_NONINTERLEAVED 107 /* more than one scan                                                                    */
+#define SFH_JPEG_R_DNL 108            /* DNL, or a height of 0                                                                 */
+#define SFH_JPEG_R_SOF_TYPE 109       /* extended sequential, lossless, hierarchical                                           */
+
+/* One Huffman table in the form the kernel reads: look[b] = length << 8 | symbol of the code of at most 8 bits that the byte b
+ * starts with (0: none); a longer code c of length l is valid iff c <= maxcode[l] (-1: no code of that length) and its symbol
+ * is vals[c + valoff[l]]; maxcode[0] = -1, maxcode[17] = INT32_MAX; vals in code order.                                      */
+typedef struct sfh_jpeg_hufftab {
+  uint16_t look[256];
+  int32_t maxcode[18];
+  int32_t valoff[18];
+  uint8_t vals[256];
+} sfh_jpeg_hufftab;
+
+/* The parse of one file (7920 bytes).  hsamp, vsamp: sampling of component 0 (2, 2: 4:2:0; 1, 1: 4:4:4 and gray).  qsel / dcsel /
+ * acsel: table of every component.  quant: natural (row-major) order.  scan_begin / scan_end: the entropy-coded bytes.
+ * file_pos, file_bytes, seg_pos, nsub: filled by sfh_jpeg_dec_stage only - where the file and its segment table lie in the
+ * staging buffer and the subsequences of its segments together.                                                             */
+typedef struct sfh_jpeg_info {
+  int32_t width, height, ncomp, hsamp, vsamp;
+  int32_t mcus_x, mcus_y, blocks_per_mcu;
+  int32_t restart_interval, nsegments;
+  int32_t scan_begin, scan_end;
+  int32_t reason;
+  int32_t qsel[3], dcsel[3], acsel[3];
+  int32_t file_pos, file_bytes, seg_pos, nsub;
+  int32_t reserved[2];
+  uint16_t quant[4][64];
+  sfh_jpeg_hufftab dc[4], ac[4];
+} sfh_jpeg_info;
+
+/* Host code, no device: walks the markers of host_bytes[0, n) -> host_info, and the segments of the scan (the bytes between
+ * RSTm markers, found by a scan for FF D0..D7; a file without DRI is one segment) as int32 quadruples {first byte, end byte,
+ * first MCU, 0} in host_segs, as many as seg_cap admits (host_segs may be NULL with seg_cap 0); host_info->nsegments counts all.
+ * 0, or -1 with host_info->reason = SFH_JPEG_R_*.                                                                            */
+int sfh_jpeg_parse(const uint8_t* host_bytes, int64_t n, sfh_jpeg_info* host_info, int32_t* host_segs, int64_t seg_cap);
+
+/* bytes of the staging buffer (pinned host memory and its device copy, 16-byte aligned) and of the device scratch buffer of a
+ * decoder of `batch` H x W x C files of at most max_file_bytes; -1 for bad arguments (subseq_bits: a multiple of 32 in
+ * 32 .. 65536) and for buffers of 2 GiB or more.                                                                             */
+int64_t sfh_jpeg_dec_staging_bytes(int batch, int H, int W, int C, int64_t max_file_bytes);
+int64_t sfh_jpeg_dec_scratch_bytes(int batch, int H, int W, int C, int64_t max_file_bytes, int subseq_bits);
+
+/* Host code, no device: parses `batch` files and packs the batch into host_staging - a 64-byte head {magic, batch, largest
+ * segment count, subseq_bits, used bytes}, the sfh_jpeg_info of every file, every file's segment table (the fourth word of a
+ * quadruple: the segment's first subsequence slot), the files at 16-byte aligned positions - for ONE copy to the device.
+ * Returns the bytes used, or -1 with *host_reason = SFH_JPEG_R_* and *host_index = the file refused (a file whose size or
+ * channels are not H, W, C: SFH_JPEG_R_SIZE; longer than max_file_bytes: SFH_JPEG_R_TOO_LONG).                               */
+int64_t sfh_jpeg_dec_stage(const uint8_t* const* host_files, const int64_t* host_sizes, int batch, int H, int W, int C,
+                           int64_t max_file_bytes, int subseq_bits, uint8_t* host_staging, int64_t staging_bytes,
+                           int32_t* host_reason, int32_t* host_index);
+
+/* One hipMemsetAsync (coefficients and segment records) and ONE launch, one workgroup per (image, segment): `staged`, the device
+ * copy of host_staging (which is read here for its head only) -> the quantised coefficients of every block as int16 in natural
+ * order, MCU order, in scratch, and per segment a record {rounds, status}.  The segment's bits are cut into subsequences of
+ * subseq_bits bits; a bounded fixed-point iteration over their exit states (bit position, block in the MCU, zig-zag index) finds
+ * every subsequence's true entry state in at most as many rounds as there are subsequences, whatever the bytes are; a last pass
+ * scatters the coefficients.  Reads are clamped to the segment's bytes, writes to its blocks; status != 0 (JD_E_* of
+ * csrc/jpegdec_core.h): an invalid code, a run past coefficient 63, bits that end early, blocks left over.  No global atomics,
+ * no waiting between workgroups.                                                                                             */
+int sfh_jpeg_entropy_decode(const uint8_t* host_staging, const uint8_t* staged, int64_t staged_bytes, int batch, int H, int W,
+                            int C, int64_t max_file_bytes, int subseq_bits, uint8_t* scratch, int64_t scratch_bytes, void* stream);
+
+/* THREE launches (two for gray): the segment records -> status int32 (B) (the OR over the image's segments) and rounds int32 (B)
+ * (their largest round count); dequantisation and jidctint's IDCT of every block into planes in scratch (gray: into out); the
+ * h2v2 triangle upsampling and YCbCr -> RGB into out uint8 (B,H,W,3) (bgr != 0: BGR in memory) or (B,H,W).  An image whose
+ * status is not 0 comes back as zeros.                                                                                       */
+int sfh_jpeg_decode_pixels(const uint8_t* staged, int batch, int H, int W, int C, int hsamp, int bgr, int64_t max_file_bytes,
+                           int subseq_bits, uint8_t* scratch, int64_t scratch_bytes, uint8_t* out, int32_t* status,
+                           int32_t* rounds, void* stream);
+
 /* Pillow's 8-bit image resize, csrc/resample.hip (the byte-exact rule is libImaging/Resample.c's, restated in
  * tests/resample_ref.py): `Image.resize(size, filter)` of L and RGB images for the antialiased filters below - per axis a table
  * of (xmin, n) and n coefficients in 22-bit fixed point per output index, a horizontal pass into uint8, then a vertical pass,

@@ -188,6 +188,14 @@ SIGNATURES = {
     "sfh_jpeg_scratch_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "sfh_jpeg_encode": (C.c_int, [_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p, C.c_int64, C.c_int, _p]),
     "sfh_jpeg_pack": (C.c_int, [_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p, C.c_int64, _p, _p, _p]),
+    "sfh_jpeg_parse": (C.c_int, [_p, C.c_int64, _p, _p, C.c_int64]),
+    "sfh_jpeg_dec_staging_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64]),
+    "sfh_jpeg_dec_scratch_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int]),
+    "sfh_jpeg_dec_stage": (C.c_int64, [_p, _p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, _p, C.c_int64, _p, _p]),
+    "sfh_jpeg_entropy_decode": (C.c_int, [_p, _p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, _p, C.c_int64,
+                                          _p]),
+    "sfh_jpeg_decode_pixels": (C.c_int, [_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, _p, C.c_int64,
+                                         _p, _p, _p, _p]),
     "sfh_resample_max_taps": (C.c_int, []),
     "sfh_resample_tab": (C.c_int, [C.c_int, C.c_int, C.c_int, _p, _p, C.c_int]),
     "sfh_resample_tile_rows": (C.c_int, [C.c_int, C.c_int, C.c_int]),

@@ -18,7 +18,7 @@ back in ``data``, as ``pngenc``'s do.
 
 Stated deviations: restart markers are added, so a file is larger than ``cv2.imwrite``'s by the 6-byte DRI segment and 2 bytes
 plus at most 7 padding bits per MCU row; the Huffman tables are Annex K's, not optimised; there is no 4:4:4, no 4:2:2 and no
-progressive mode; there is no decoder on the device.  JPEG is for photographs: masks and labels hold class ids and stay PNG.
+progressive mode; the decoder is ``sfh_amd.jpegdec``.  JPEG is for photographs: masks and labels hold class ids and stay PNG.
 """
 
 import torch

@@ -33,6 +33,7 @@ import torch
 from . import _lib
 from . import outputs as O
 from .jpegenc import image_files_from_batch
+from .jpegdec import frames_from_files
 from .engine import _ptr
 
 MODES = {"nearest": 0, "bilinear": 1}
@@ -319,13 +320,17 @@ class CourtMosaic:
 
 
 def rectify_game(court_json, frames, dst_dir, out_size=(1280, 720), mode="nearest", max_score=None, batch=16, names=None,
-                 mosaic=True, device="cuda", png="host", image_format="png", jpeg_quality=90):
+                 mosaic=True, device="cuda", png="host", image_format="png", jpeg_quality=90,
+                 frames_format="array"):
     """The host driver, in the style of ``visualize.visualize``: frames - an iterable of host uint8 (H,W,3) arrays in the
     order of the predictions of ``court_json`` (names: their frame names, checked when given).  Writes
     ``dst_dir/<name>.png`` (outputs.encode_png), the top view of every frame, and ``dst_dir/mosaic.png``.  png: "host"
     (outputs.encode_png, the default) or "device" (sfh_amd.pngenc: the views are encoded on the GPU).  image_format: "png",
     or "jpeg" for ``<name>.jpeg`` and ``mosaic.jpeg`` at jpeg_quality (``png=`` then selects where the JPEG is encoded:
-    outputs.encode_jpeg or sfh_amd.jpegenc, the same bytes).  Returns the list of written paths."""
+    outputs.encode_jpeg or sfh_amd.jpegenc, the same bytes).  frames_format: "array", or "jpeg" for an iterable of JPEG files as
+    bytes, decoded on the GPU (sfh_amd.jpegdec) to the pixels PIL gives.  Returns the list of written paths."""
+    if frames_format not in ("array", "jpeg"):
+        raise ValueError(f'rectify_game: frames_format={frames_format!r} ("array" or "jpeg")')
     cm = CourtMapping(court_json, device=device)
     if names is not None:
         for k, (n, p) in enumerate(zip(names, cm.names)):
@@ -344,7 +349,10 @@ def rectify_game(court_json, frames, dst_dir, out_size=(1280, 720), mode="neares
 
     def flush(chunk, first):
         B = len(chunk)
-        fr = torch.from_numpy(np.ascontiguousarray(np.stack(chunk))).to(tabs["theta"].device)
+        if frames_format == "jpeg":
+            fr = frames_from_files(chunk, tabs["theta"].device)     # decoded on the GPU (sfh_amd.jpegdec): only the files are uploaded
+        else:
+            fr = torch.from_numpy(np.ascontiguousarray(np.stack(chunk))).to(tabs["theta"].device)
         theta, score = tabs["theta"][first:first + B], tabs["scores"][first:first + B]
         out = renderer(fr, theta, score=score)
         if mos is not None:
@@ -357,8 +365,11 @@ def rectify_game(court_json, frames, dst_dir, out_size=(1280, 720), mode="neares
     for fr in frames:
         if done + len(chunk) >= len(cm):
             raise ValueError(f"rectify_game: more frames than the {len(cm)} predictions")
-        a = np.asarray(fr)
-        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or (chunk and a.shape != chunk[0].shape):
+        a = np.frombuffer(fr, np.uint8) if isinstance(fr, (bytes, bytearray, memoryview)) else np.asarray(fr)
+        if frames_format == "jpeg":
+            if a.dtype != np.uint8 or a.ndim != 1:
+                raise ValueError(f"rectify_game: with frames_format='jpeg' a frame is the bytes of a JPEG file, got {a.dtype} {a.shape}")
+        elif a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or (chunk and a.shape != chunk[0].shape):
             raise ValueError(f"rectify_game: frames must be uint8 (H,W,3) arrays of one size, got {a.dtype} {a.shape}")
         chunk.append(a)
         if len(chunk) == batch:

@@ -43,6 +43,7 @@ import torch
 from . import engine as E
 from . import outputs as O
 from . import jpegenc as J
+from . import jpegdec as JD
 from . import pngenc as P
 from . import resample as RS
 
@@ -105,7 +106,8 @@ class Ticket:
 
 class FramePipeline:
     def __init__(self, net, batch, frame_hw, req_outputs=("theta", "warp_mask"), consistency=False, channels=3, overlay=None,
-                 top_view=None, png=None, png_budget=None, jpeg=None, jpeg_quality=90, jpeg_budget=None, resize="area"):
+                 top_view=None, png=None, png_budget=None, jpeg=None, jpeg_quality=90, jpeg_budget=None, resize="area",
+                 jpeg_in_max_bytes=None):
         """net: a Reconstructor on the GPU in eval mode; frame_hw = (H, W) of the DECODED frames (net.unet_size, or any
         larger size: cv2.INTER_AREA's downscale runs on the GPU, engine.frames_u8_to_input); req_outputs as predict.py's --req_outputs.
         overlay: a visualize.OverlayRenderer for the output "overlay" (its score is the consistency score: without
@@ -119,7 +121,10 @@ class FramePipeline:
         resize: how frames of another size than net.unet_size get there.  "area" (the default): cv2.INTER_AREA, VideoDataset's
         rule, downscales only; overlay and top_view are drawn from the frames at their decoded size.  "pil": Pillow's
         Image.resize (bicubic), BasicDataset's rule (sfh_amd.resample), any size pair within its tap bound; overlay and top_view
-        are drawn from the RESIZED frames, as they are when the same frames come resized from the host."""
+        are drawn from the RESIZED frames, as they are when the same frames come resized from the host.
+        jpeg_in_max_bytes: the longest file ``submit_jpeg`` admits (default: jpegenc.jpeg_capacity of the frame size); it sizes
+        the decoders' buffers, which are allocated at the first ``submit_jpeg``."""
+        self.jpeg_in_max_bytes = jpeg_in_max_bytes
         if resize not in ("area", "pil"):
             raise ValueError(f'FramePipeline: resize={resize!r} ("area" or "pil")')
         self.net, self.B = net, int(batch)
@@ -254,6 +259,42 @@ class FramePipeline:
             t.uploaded = torch.cuda.Event()
             t.uploaded.record(self.h2d)
         cur.wait_event(t.uploaded)
+        return self._forward(s, t, cur)
+
+    def submit_jpeg(self, files):
+        """files: B JPEG files of the pipeline's frame size as bytes / 1-D uint8 arrays (or a jpegenc.JpegBatch), in the place of
+        ``submit``'s decoded frames: the files and their parse tables are uploaded in one copy, decoded on the compute stream
+        into the slot's frame buffer (sfh_amd.jpegdec: PIL's pixels, in BGR order), and then runs exactly what ``submit``
+        runs.  The headers are parsed here, on the host: a refused file raises before anything is enqueued.  The files are
+        copied into the slot's pinned staging buffer before this returns, so they need not outlive the call."""
+        s = self.slots[self.k % 2]
+        if s["pending"] is not None:
+            raise RuntimeError("FramePipeline: collect() the batch submitted two calls ago before reusing its slot")
+        if "jpegdec" not in s:
+            _, H, W, C = s["u8"].shape
+            s["jpegdec"] = JD.JpegDecoder(H, W, C, self.B, bgr=True, max_file_bytes=self.jpeg_in_max_bytes, device=self.dev)
+        dec = s["jpegdec"]
+        n = len(files.sizes) if isinstance(files, J.JpegBatch) else len(files)
+        if n != self.B:
+            raise ValueError(f"FramePipeline.submit_jpeg: {n} files for a batch of {self.B}")
+        dec.stage(files)                                  # host only; raises for a refused file
+        self.k += 1
+        s["gen"] += 1
+        t = Ticket(s, s["gen"])
+        cur = torch.cuda.current_stream(self.dev)
+        with torch.cuda.stream(self.h2d):
+            if getattr(dec, "decoded", None) is not None:
+                self.h2d.wait_event(dec.decoded)          # the slot's previous decode has read the device copy of the files
+            dec.upload()
+            t.uploaded = torch.cuda.Event()
+            t.uploaded.record(self.h2d)
+        cur.wait_event(t.uploaded)
+        dec.decode_staged(out=s["u8"])                    # on cur: ordered behind every launch that read s["u8"]
+        dec.decoded = torch.cuda.Event()
+        dec.decoded.record(cur)
+        return self._forward(s, t, cur)
+
+    def _forward(self, s, t, cur):
         if self.resampler is not None:
             s["frames"], x = self.resampler.both(s["u8"])     # one launch: the resized bytes for overlay / top_view and / 255
         else:
@@ -341,8 +382,9 @@ class FramePipeline:
                                                      lambda a, e, pb=pb: pb["out"].data[a:e].cpu().numpy())
         return res
 
-    def run(self, batches):
-        """Generator over host uint8 batches -> result dicts (copies), two batches in flight.  The producer may hand over the
+    def run(self, batches, jpeg=False):
+        """Generator over host uint8 batches (jpeg=True: over lists of B JPEG files, through ``submit_jpeg``) -> result dicts
+        (copies), two batches in flight.  The producer may hand over the
         SAME pinned buffer every time: the next item is pulled from `batches` only after the upload of the batch just
         submitted has read its buffer (wait_uploaded) - with the one copy stream per device that upload queues behind the
         download of the batch two submissions back, so without the wait a producer that refills one buffer would overwrite
@@ -352,7 +394,7 @@ class FramePipeline:
         it = iter(batches)
         fr = next(it, None)
         while fr is not None:
-            t = self.submit(fr)
+            t = self.submit_jpeg(fr) if jpeg else self.submit(fr)
             if done is not None:
                 yield _copied(self.get(done))
                 done = None
