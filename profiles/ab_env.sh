@@ -1,6 +1,8 @@
 #!/bin/bash
 # A/B of ENVIRONMENT variants of the product library on ONE device (one gpurun call): alternating bench runs.
 #   bash profiles/ab_env.sh <rounds> <name>=<ENV=VAL[,ENV=VAL...]|-> ...      ("-" = no extra environment)
+# the launch-plan options travel in ONE variable whose pairs are joined by ":" (sfh_amd.options), e.g.
+#   bash profiles/ab_env.sh 3 base=- two=SFH_OPTIONS=fuse_inc=0 both=SFH_OPTIONS=fuse_inc=0:up_single=4,SFH_PRECISION=bf16x6
 # prints value / ms per step / unpipelined ms / per-group ms for every run
 # (bench.py --full: the unpipelined pass and kernel_groups are not in a plain run; results go to $OUT, default bench_runs/)
 R=$1; shift

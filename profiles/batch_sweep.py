@@ -1,5 +1,5 @@
 """predict() at 640x360 over batch sizes (latency of one batch, frames/s), default f16x3 arithmetic; with
-SFH_SPLITK=0 the small-batch split-K of the ResNet layers is off.  GPU box only.
+SFH_OPTIONS=splitk=0 the small-batch split-K of the ResNet layers is off.  GPU box only.
 usage: python profiles/batch_sweep.py [B ...]"""
 import os
 import sys

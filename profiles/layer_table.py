@@ -24,7 +24,7 @@ if any('S3Cfg<2,' in r['Kernel_Name'] for r in step):
     # (u1 / u2: .a / .b in launch order - cfg<2, …> is the composed 2x2 launch, cfg<3, …> the skip half)
     L = L[:10] + [("u1.a", gm(512, 512, 45, 80)), ("u1.b", gm(512, 512, 45, 80)), ("u1.3", gm(512, 512, 45, 80)),
                   ("u2.a", gm(256, 256, 90, 160)), ("u2.b", gm(256, 256, 90, 160)), ("u2.3", gm(256, 256, 90, 160)),
-                  # u3 / u4: the composed 2x2 conv runs first, the skip-half 3x3 conv finishes (engine.UNetEngine.up_swap)
+                  # u3 / u4: the composed 2x2 conv runs first, the skip-half 3x3 conv finishes (as at every fused level since round 3)
                   ("u3.fuse", gm(128, 128, 180, 320)), ("u3.skip", gm(128, 128, 180, 320)), ("u3.3", gm(128, 128, 180, 320)),
                   ("u4.fuse", gm(64, 64, 360, 640)), ("u4.skip", gm(64, 64, 360, 640)), ("u4.3", gm(64, 64, 360, 640))]
 if any('conv_upfused' in r['Kernel_Name'] for r in step):

@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp
 ARGS="--full --steps 3 --warmup 1 --no-cpu-baseline --no-extra-configs"
 rm -rf $OUT/${TAG}_rn_split $OUT/${TAG}_rn_nosplit
 timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/${TAG}_rn_split -- python3 $ROOTD/bench.py $ARGS > $OUT/${TAG}_rn_split.log 2>&1
-export SFH_SPLITK=0
+export SFH_OPTIONS=splitk=0
 timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/${TAG}_rn_nosplit -- python3 $ROOTD/bench.py $ARGS > $OUT/${TAG}_rn_nosplit.log 2>&1
 cd $ROOTD
 for v in split nosplit; do

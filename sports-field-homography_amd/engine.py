@@ -6,7 +6,6 @@ arithmetic step is a call into ``libsfh_amd.so``.  Host-prep helpers and format 
 bookkeeping: ``h2ranges.py`` (both re-exported here).
 """
 import ctypes
-import os
 from collections import namedtuple
 
 import torch
@@ -14,6 +13,7 @@ import torch
 from . import _lib
 from ._lib import ConvDesc
 from .h2ranges import FP16RangeExhausted, H2Ranges, _bits_to_float, _NoRanges  # noqa: F401
+from .options import Options
 from .ops import (PRECISIONS, _SPLIT, _SPLIT_DTYPES, _area_tab, _chan, _f32_to_split_into, _f32c,  # noqa: F401
                   _fmt_code, _fmt_of, _hw, _ptr, _split_to_f32_into, _stream, _stream_scope, absminmax, absminmax_words,
                   consistency_ce, f32_to_h2, f32_to_s3, f32_to_split, filled, frames_u8_to_input, h2_weight_exp,
@@ -206,11 +206,9 @@ def upfused_work(batch, H, W, skip_c0, cout, low_c0, low_hw, flops_per_out_pixel
 # launches whose standard grid is at most one workgroup per CU, i.e. one wave per SIMD (_SMALL_MAP_MAX workgroups): ResNet layer4
 # at batch 16 (192 workgroups -> 256: 79 -> 50 us per launch, profiles/r05_small_map_probe.txt), layer3 (240 -> 512: equal
 # alone, +0.2 % under the pipeline), small batches.  Same-device A/B (profiles/r05_ab_small_map.txt): 13.31 -> 13.19 ms per batch
-# with the threshold at 224 (layer4 only), 13.09 at 256.  SFH_SMALL_MAP=0 switches it off.
-_SMALL_MAP = os.environ.get("SFH_SMALL_MAP", "1") != "0"
-_SMALL_MAP_MAX = int(os.environ.get("SFH_SMALL_MAP_MAX", "256"))
-_W8_HALF = os.environ.get("SFH_W8_HALF", "1") != "0"
-_W8_HALF_ROUNDS = float(os.environ.get("SFH_W8_HALF_ROUNDS", "3"))   # rounds of 512 resident workgroups from which the shape is requested
+# with the threshold at 224 (layer4 only), 13.09 at 256.
+_SMALL_MAP_MAX = 256
+_W8_HALF_ROUNDS = 3   # rounds of 512 resident workgroups from which the 128 x 128 workgroup shape is requested
 _BPE = {"h2": 4, "s3": 6, None: 4}   # stored bytes per activation element
 
 
@@ -219,12 +217,11 @@ class LaunchOrder:
     alternating ("snake", sfh_conv_desc.reverse_tiles), so that a launch starts on what the same XCD wrote
     last.  Per owner, not process-wide: the order a model sees does not depend on what else ran."""
 
-    def __init__(self, snake=None):
-        self.snake = (os.environ.get("SFH_SNAKE", "1") != "0") if snake is None else bool(snake)
+    def __init__(self):
         self._flip = False
 
     def next(self):
-        r = self.snake and self._flip
+        r = self._flip
         self._flip = not self._flip
         return r
 
@@ -465,7 +462,7 @@ class PackedConv(_H2Layer):
             return choose_tile(batch, ho, wo, self.stride, zr), wg_couts
         # 128 x 128 double-buffered workgroups (conv_s3.hip): measured +3 % for 128 / 256 input channels on grids of many
         # rounds (64 -> 128: +4 %), slower for longer K or few rounds (profiles/r03_conv_rate_probe_w8half.txt)
-        if (_W8_HALF and plain and self.fmt == "h2" and self.ksize == 3 and self.stride == 1 and wg_couts == 0
+        if (plain and self.fmt == "h2" and self.ksize == 3 and self.stride == 1 and wg_couts == 0
                 and self.cout % 128 == 0 and 64 <= self.c0 + self.c1 <= 256):
             nt = -(-(batch * (ho + zr)) // 8) * -(-wo // 16)
             if nt * (self.cout // 128) >= _W8_HALF_ROUNDS * _WG_SLOTS:
@@ -599,7 +596,7 @@ class PackedConv(_H2Layer):
                 d.src_fmt = _lib.FMT_FH2   # the (B,H,W,4) float32 tensor holds sfh_frame_to_h2's 16-byte pixels, not floats
                 return lib.sfh_conv3x3_c4h2_fwd
             return lib.sfh_conv3x3_c4_fwd
-        if small is None and small_ok and _SMALL_MAP and auto:
+        if small is None and small_ok and auto:
             small = choose_small_map(batch, ho, wo, zr, self.cout, d.tile)
         if small:
             d.wg_couts = 0          # (the small-map launcher chooses its LDS buffering itself)
@@ -790,10 +787,11 @@ class _Engine:
     """What the two engines share: precision, H2 range state, workspaces and the record / replay protocol - run() records
     every launch as a step, so that the range guard can repeat the pass from the first one that writes a changed tensor."""
 
-    def __init__(self, device, precision, overflow, ranges):
+    def __init__(self, device, precision, overflow, ranges, options):
         if precision not in PRECISIONS:
             raise ValueError(f"precision={precision!r}: expected one of {sorted(PRECISIONS)}")
         self.device = device
+        self.options = options if options is not None else Options()
         self.ws = _Workspace(device)
         self.fmt = fmt = PRECISIONS[precision]
         self.s3 = fmt is not None          # split-format activations
@@ -833,37 +831,36 @@ class _Engine:
 class UNetEngine(_Engine):
     """forward_unet (models/reconstructor.py:132-158) on the HIP kernels."""
 
-    def __init__(self, net, device, precision="bf16x6", overflow=None, ranges=None):
+    def __init__(self, net, device, precision="bf16x6", overflow=None, ranges=None, options=None):
         """precision: "bf16x6" - activations in split-bf16 (S3) format, contractions as six bf16
         MFMAs per product with fp32 accumulation (fp32-equivalent accuracy); "f16x3" - two-plane fp16 (H2)
         activations, three fp16 MFMAs per product (22-bit operands; `ranges`: the model's H2Ranges - per-tensor
         exponents and the device words the kernels raise to the largest magnitude they produced; `overflow`:
-        optional int32 device word OR-ed with 1 on any saturation); "fp32" - fp32 activations and fp32 MFMA."""
-        super().__init__(device, precision, overflow, ranges)
-        fmt, s3 = self.fmt, self.s3
+        optional int32 device word OR-ed with 1 on any saturation); "fp32" - fp32 activations and fp32 MFMA.
+        options: the model's Options record (None: the defaults)."""
+        super().__init__(device, precision, overflow, ranges, options)
+        fmt, s3, options = self.fmt, self.s3, self.options
         self.bilinear = bool(net.unet_bilinear)
-        # fused Up levels where the composed 2x2 conv runs first (see run()) and the skip-half 3x3 conv finishes.  Round 2
+        # In every fused Up level the composed 2x2 conv runs first (see run()) and the skip-half 3x3 conv finishes.  Round 2
         # (the partial added as a residual at the end of the 3x3 conv): none 629, {4} 634, {3,4} 638, all four 635 frames/s;
         # round 3 (the 3x3 conv STARTS from the partial, sfh_conv_desc.acc_init), one device, ms per batch: {3,4} without
         # seeding 14.58 / 14.70, {3,4} seeded 14.58 / 14.66, {2,3,4} 14.60 / 14.57, all four 14.43 / 14.56
-        self.up_swap = {int(c) for c in os.environ.get("SFH_UP_SWAP", "1234") if c.isdigit()}
         self.up_seed = {}          # level -> the skip-half conv starts from the partial (sfh_conv_desc.acc_init)
-        # levels whose fused Up block runs as ONE kernel (csrc/conv_upfused.hip, round 5; bit-identical to the two-launch
-        # "swap + seed" form).  Same-device A/B at 640x360 x 16 (profiles/r05_ab_up_single.txt), ms per batch pipelined: none 13.13,
-        # {4} 12.93, {3,4} 12.91-12.94, {2,3,4} 12.94, all four 13.15 (at long K a wave per parity class streams too many weights);
-        # 1280x720: none 50.97, {3,4} 49.9.  SFH_UP_SINGLE="" switches it off.
-        self.up_single = {int(c) for c in os.environ.get("SFH_UP_SINGLE", "34") if c.isdigit()}
+        # options.up_single: levels whose fused Up block runs as ONE kernel (csrc/conv_upfused.hip, round 5; bit-identical to the
+        # two-launch seeded form).  Same-device A/B at 640x360 x 16 (profiles/r05_ab_up_single.txt), ms per batch pipelined: none
+        # 13.13, {4} 12.93, {3,4} 12.91-12.94, {2,3,4} 12.94, all four 13.15 (at long K a wave per parity class streams too many
+        # weights); 1280x720: none 50.97, {3,4} 49.9.
         self.nc = net.mask_classes
         L = {}
 
         # "f16x3": the 3-channel first layer too runs on the fp16 matrix cores, from a frame tensor split once (FH2)
-        self.frame_h2 = fmt == "h2" and os.environ.get("SFH_INC0_H2", "1") != "0"
+        self.frame_h2 = fmt == "h2"
 
         # the first DoubleConv (frame -> 64 -> 64) as ONE launch (csrc/conv_inc_fused.hip; bit-identical to the two launches):
         # the 0.94 GB intermediate of a 640x360 x 16 batch never leaves LDS.  Inference only - this engine; a training tape keeps
-        # the intermediate for its backward pass.  SFH_FUSE_INC=0 restores the two launches.
-        self.fuse_inc = self.frame_h2 and os.environ.get("SFH_FUSE_INC", "1") != "0"
-        fuse_up = not self.bilinear and s3 and os.environ.get("SFH_FUSE_UP", "1") != "0"
+        # the intermediate for its backward pass.  options.fuse_inc = False restores the two launches.
+        self.fuse_inc = self.frame_h2 and options.fuse_inc
+        fuse_up = not self.bilinear and s3 and options.fuse_up
         ups = [(i, cin, getattr(net, f"up{i}")) for i, cin in enumerate((1024, 512, 256, 128), start=1)]
         # the skip halves of the Up blocks' first convs (unet/unet_parts.py:67: cat([skip, up])) as tensors of their own
         skip_w = {i: slice_in_channels(up.conv.convs()[0][0].weight, 0, cin // 2) for i, cin, up in ups} if fuse_up else {}
@@ -906,6 +903,7 @@ class UNetEngine(_Engine):
             mm = absminmax([f._w2 for f in fus] + [f.scale_bn for f in fus])
             for k, (i, cin, up) in enumerate(ups):
                 fu, sk = fus[k], L[f"up{i}.skip"]
+                fu.relu, sk.relu = False, True      # the composed 2x2 conv runs first, the skip-half conv activates
                 fu.finish_pack(h2_weight_exp(mm[k][0]) if fmt == "h2" else None)
                 cout = up.conv.convs()[0][0].out_channels
                 # the partial enters the fused conv's epilogue as a residual, i.e. after the BatchNorm scale:
@@ -913,8 +911,10 @@ class UNetEngine(_Engine):
                 vec_op(fu.scale_bn[:cout], factor=sk.escale, out=sk.scale)
                 # accumulator seeding (run()) divides by this scale: only where no channel's BatchNorm scale vanishes
                 smin = mm[len(fus) + k][1] * sk.escale
-                self.up_seed[i] = (os.environ.get("SFH_UP_SEED", "1") != "0") and 1e-30 < smin < float("inf")
+                self.up_seed[i] = 1e-30 < smin < float("inf")
         self._adopt(L)
+        # OutConv (+ the STN input) rides in the epilogue of the last 3x3 conv (run() drops it when something else needs y)
+        self.fuse_head = s3 and L["up4.conv.3"].cout_real == 64 and options.fuse_head
         # private copies: an engine holds NO live reference to a parameter (see snapshot())
         self.outc_w = snapshot(net.outc.conv.weight)
         self.outc_b = snapshot(net.outc.conv.bias)
@@ -1004,14 +1004,12 @@ class UNetEngine(_Engine):
             feats.append(f)
             pooled.append(p)
         y, ny = feats[4]
-        # OutConv (+ the STN input) rides in the epilogue of the last 3x3 conv when nothing else needs y
         logits = torch.empty((B, self.nc, H, W), dtype=torch.float32, device=x.device)
         if want_stn_in and self.nc + 3 > 8:
             raise NotImplementedError("mask_classes > 5 with resnet_input='img+mask' needs a wider STN input buffer")
         stn_in = ws.get("stn_in" if not stn_slot else f"stn_in{stn_slot}", (B, H, W, 8), zero=True) if want_stn_in else None
         head = None
-        if (s3 and not want_argmax and not (want_uv and self.outuv is not None)
-                and L["up4.conv.3"].cout_real == 64 and os.environ.get("SFH_FUSE_HEAD", "1") != "0"):
+        if self.fuse_head and not want_argmax and not (want_uv and self.outuv is not None):
             head = {"w": self.outc_w, "b": self.outc_b, "nc": self.nc, "logits": logits, "stn": stn_in,
                     "frame": xin if want_stn_in else None, "skip_dst": True}
         for i in range(1, 5):
@@ -1027,13 +1025,12 @@ class UNetEngine(_Engine):
                 up_dst = (hs, ws_) if (ey or ex) else None
 
                 def level(y=y, ny=ny, skip=skip, nskip=nskip, part=part, mid=mid, nmid=nmid, fu=fu, sk=sk,
-                          up_dst=up_dst, hs=hs, ws_=ws_, hy=hy, wy=wy, ey=ey, ex=ex, swap=i in self.up_swap,
-                          seed=self.up_seed.get(i, False), single=i in self.up_single):
-                    if swap and seed:
+                          up_dst=up_dst, hs=hs, ws_=ws_, hy=hy, wy=wy, ey=ey, ex=ex,
+                          seed=self.up_seed.get(i, False), single=i in self.options.up_single):
+                    if seed:
                         # as below, but the partial is written in the skip-half conv's ACCUMULATOR units (divided by its
                         # scale) and that conv STARTS from it (sfh_conv_desc.acc_init): sixteen loads in its prologue
                         # instead of sixteen dependent reads at its end
-                        fu.relu, sk.relu = False, True
                         a_fu, a_sk = rg.args(ny, None), rg.args(nskip, nmid)
                         if fu.fmt == "h2":      # bring both scales up to date with the exponents before dividing them
                             fu._fold_exp_src(a_fu["exp_src"])
@@ -1049,16 +1046,11 @@ class UNetEngine(_Engine):
                         fu.run(y, B, hy + ey, wy + ex, part, up_dst=up_dst, scale=fu._seed_scale,
                                shift_border=fu._seed_border, **a_fu)
                         sk.run(skip, B, hs, ws_, mid, acc_init=part, **a_sk)
-                    elif swap:
+                    else:
                         # composed 2x2 conv first: it writes the 4 B fp32 partial instead of reading one and writing
                         # 6 B of S3; the MFMA-bound skip-half 3x3 conv then absorbs the residual, the ReLU and the split
-                        fu.relu, sk.relu = False, True
                         fu.run(y, B, hy + ey, wy + ex, part, up_dst=up_dst, **rg.args(ny, None))
                         sk.run(skip, B, hs, ws_, mid, residual=part, **rg.args(nskip, nmid))
-                    else:
-                        fu.relu, sk.relu = True, False
-                        sk.run(skip, B, hs, ws_, part, **rg.args(nskip, None))
-                        fu.run(y, B, hy + ey, wy + ex, mid, residual=part, up_dst=up_dst, **rg.args(ny, nmid))
                 do((nmid,) if nmid else (), level)
                 ymid, l3 = mid, L[f"up{i}.conv.3"]
                 y, ny = act(f"up{i}.conv.out", (B, hs, ws_), cout, f32=(i == 4))
@@ -1177,13 +1169,12 @@ class StemConv(_H2Layer):
 class ResNetEngine(_Engine):
     """ResNetSTN forward (models/resnet.py:235-254) on the HIP kernels (BasicBlock and Bottleneck depths)."""
 
-    def __init__(self, rn, in_channels, device, precision="bf16x6", overflow=None, ranges=None):
+    def __init__(self, rn, in_channels, device, precision="bf16x6", overflow=None, ranges=None, options=None):
         """precision "bf16x6" / "f16x3": the 3x3 convs (stride 1 and 2) and the 1x1 stride-2 downsample convs run
         on the split-operand kernel with S3 / H2 activations; the stem stays on the fp32 kernel (or, with at most
-        8 input channels, on the tap-packed split-bf16 stem kernel).  ranges / overflow: as UNetEngine."""
-        super().__init__(device, precision, overflow, ranges)
+        8 input channels, on the tap-packed split-bf16 stem kernel).  ranges / overflow / options: as UNetEngine."""
+        super().__init__(device, precision, overflow, ranges, options)
         fmt, s3 = self.fmt, self.s3
-        self.splitk = os.environ.get("SFH_SPLITK", "1") != "0"
         self.cin = in_channels
         self.cs_in = -(-in_channels // 4) * 4
         if (4 * self.cs_in) % 16:
@@ -1199,8 +1190,7 @@ class ResNetEngine(_Engine):
         L["stem"] = PC(rn.conv0.weight, None, rn.bn1, 4, 4 * self.cs_in, stem_cin=in_channels, tag="resnet")
         # bf16x6 mode with <= 8 input channels (every resnet_input mode but img+mask+uv): the tap-packed stem kernel
         self.stem7 = (StemConv(rn.conv0, rn.bn1, in_channels, fmt=fmt, overflow=self.overflow, wexp=wx.get(rn.conv0.weight.data_ptr()))
-                      if (s3 and self.cs_in == 8 and rn.conv0.out_channels == 64
-                                                                  and os.environ.get("SFH_STEM7", "1") != "0") else None)
+                      if (s3 and self.cs_in == 8 and rn.conv0.out_channels == 64) else None)
         self.blocks = []
         for li in range(1, 5):
             for bi, blk in enumerate(getattr(rn, f"layer{li}")):
@@ -1238,7 +1228,7 @@ class ResNetEngine(_Engine):
     def _run(self, y_nhwc, B, H, W, splitk=None):
         lib = _lib.load()
         ws, L, rg = self.ws, self.L, self.ranges
-        use_splitk = self.splitk and (splitk is None or bool(splitk))
+        use_splitk = self.options.splitk and (splitk is None or bool(splitk))
         if y_nhwc.shape[3] != self.cs_in:
             raise ValueError(f"STN input has {y_nhwc.shape[3]} stored channels, engine expects {self.cs_in}")
         self.steps = []

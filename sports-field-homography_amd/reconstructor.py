@@ -16,6 +16,7 @@ import torch.nn as nn
 
 from . import engine as E
 from .modules import DoubleConv, Down, Up, OutConv, resnet_stn
+from .options import Options
 
 
 class Input(Enum):
@@ -58,11 +59,11 @@ torch.nn.modules.module.register_module_module_registration_hook(_count_registra
 _PIPE_STREAMS = {}
 
 
-def _pipe_streams(dev, prio):
-    key = (dev.index if dev.index is not None else torch.cuda.current_device(), prio)
+def _pipe_streams(dev):
+    key = dev.index if dev.index is not None else torch.cuda.current_device()
     st = _PIPE_STREAMS.get(key)
     if st is None:
-        st = _PIPE_STREAMS[key] = (torch.cuda.Stream(dev, priority=prio), torch.cuda.Stream(dev))
+        st = _PIPE_STREAMS[key] = (torch.cuda.Stream(dev), torch.cuda.Stream(dev))
     return st
 
 
@@ -182,6 +183,9 @@ class Reconstructor(nn.Module):
         #   "fp32"            = fp32 MFMA throughout.
         # Plain attribute (or env SFH_PRECISION) so the constructor signature stays the reference's.
         self.precision = os.environ.get("SFH_PRECISION", "f16x3")
+        # The launch-plan choices that are still open (options.py; env SFH_OPTIONS, read here and nowhere else).  Part of the
+        # engine stamp: assigning another record rebuilds the engines and drops captured graphs.
+        self.options = Options.from_env()
         self._engines = None       # (UNetEngine | None, ResNetEngine | None)
         self._engines_by_precision = {}
         self._h2_ranges = None     # engine.H2Ranges: exponents + device range words of the "f16x3" activations
@@ -193,8 +197,8 @@ class Reconstructor(nn.Module):
         # caller that pipelines several batches then asks range_overflowed() itself once it has synchronised
         self.range_guard = True
         # predict(consistency=True) with a nearest warp of the logits' size: warp + consistency CE as one kernel (False: the two
-        # separate kernels; env SFH_FUSE_WARP_CE=0)
-        self.fuse_warp_ce = os.environ.get("SFH_FUSE_WARP_CE", "1") != "0"
+        # separate kernels)
+        self.fuse_warp_ce = True
         # predict() through predict_replay() (one HIP-graph launch per batch, same bits) for batches of at most
         # graph_replay_max_batch frames; off by default: it returns the caller's thread, not GPU time
         self.graph_replay = False
@@ -237,7 +241,7 @@ class Reconstructor(nn.Module):
             ver += t._version
         if lst:
             dev = lst[-1].device
-        return (dev, ver, self.training, self.precision, self._weights_generation)
+        return (dev, ver, self.training, self.precision, self._weights_generation, self.options)
 
     def _apply(self, fn, *args, **kwargs):
         # .to() / .cuda() / .float(): buffers are REPLACED by nn.Module._apply - drop the cached tensor list
@@ -298,8 +302,8 @@ class Reconstructor(nn.Module):
                     if self._h2_ranges is None or self._h2_ranges.device != dev:
                         self._h2_ranges = E.H2Ranges(dev)
                     rg = self._h2_ranges
-                un = E.UNetEngine(self, dev, precision, ranges=rg) if self.use_unet else None
-                rn = (E.ResNetEngine(self.resnet_reg, self._stn_in_channels, dev, precision, ranges=rg)
+                un = E.UNetEngine(self, dev, precision, ranges=rg, options=self.options) if self.use_unet else None
+                rn = (E.ResNetEngine(self.resnet_reg, self._stn_in_channels, dev, precision, ranges=rg, options=self.options)
                       if self.use_resnet else None)
             eng = self._engines_by_precision[precision] = (un, rn)
         self._engines = eng
@@ -717,9 +721,7 @@ class Reconstructor(nn.Module):
         dev = x.device
         if p is None or p["device"] != dev:
             with torch.cuda.device(dev):
-                # experiment knob: HIP priority of the side stream (negative = higher than the caller's default stream)
-                prio = int(os.environ.get("SFH_SIDE_PRIO", "0"))
-                side, copy = _pipe_streams(dev, prio)
+                side, copy = _pipe_streams(dev)
                 p = self.__dict__["_pipe"] = {"device": dev, "side": side, "copy": copy,
                                               "slot": 0, "stem_read": [None, None], "inflight": []}
         cur = torch.cuda.current_stream(dev)

@@ -25,6 +25,7 @@ import torch
 from . import _lib
 from . import engine as E
 from .engine import PackedConv, _ptr, _stream
+from .options import Options
 
 BN_MOMENTUM = 0.1  # nn.BatchNorm2d default, unchanged by the reference
 
@@ -158,7 +159,8 @@ def _warn_range_fallback():
 class Tape:
     """Backward closures in forward order + gradients of activations by tensor identity."""
 
-    def __init__(self, fmt="env"):
+    def __init__(self, fmt="env", options=None):
+        self.options = options if options is not None else Options()     # (None: the defaults, not the environment)
         self.ops = []
         self.grads = {}
         self.param_grads = {}
@@ -269,24 +271,15 @@ class Tape:
 
 
 # --------------------------------------------------------------------------------------- layers
-STATS_IN_EPILOGUE = os.environ.get("SFH_TRAIN_STATS_EPILOGUE", "1") != "0"
-BWD_SUMS_IN_EPILOGUE = os.environ.get("SFH_TRAIN_BWD_SUMS_EPILOGUE", "1") != "0"
-# ConvTranspose2d backward: bias gradient + space-to-depth + split copy in one pass (sfh_s2d_split_colsum)
-S2D_FUSED = os.environ.get("SFH_TRAIN_S2D_FUSED", "1") != "0"
+# Options.train_one_pass (tape.options) stands for five one-pass forms; False takes the separate passes of each:
+#   ConvTranspose2d backward: bias gradient + space-to-depth + split copy in one pass (sfh_s2d_split_colsum);
+#   encoder skip tensors: BatchNorm + ReLU + MaxPool2d(2) in one forward pass (split copies only), max-pool backward + the
+#     BatchNorm backward sums in one backward pass (sfh_bn_apply_pool / sfh_pool2_bwd_bn_reduce);
+#   first layer: BatchNorm backward applied inside the backward-filter kernel (sfh_conv_wgrad_c4_bn);
+#   layers whose only consumer is an Up block's ConvTranspose2d: split copy only, backward sums from that conv's backward-data
+#     launch;
+#   the last DoubleConv's BatchNorm backward sums from the OutConv backward pass (sfh_outconv_bwd_bn).
 S2D_ROWS = 32
-# encoder skip tensors: BatchNorm + ReLU + MaxPool2d(2) in one forward pass (split copies only), max-pool backward +
-# the BatchNorm backward sums in one backward pass (sfh_bn_apply_pool / sfh_pool2_bwd_bn_reduce)
-POOL_FUSED = os.environ.get("SFH_TRAIN_POOL_FUSED", "1") != "0"
-# first layer: BatchNorm backward applied inside the backward-filter kernel (sfh_conv_wgrad_c4_bn)
-C4_BN_FUSED = os.environ.get("SFH_TRAIN_C4_BN_FUSED", "1") != "0"
-# layers whose only consumer is an Up block's ConvTranspose2d: split copy only, backward sums from that conv's backward-data launch
-UP_SUMS_FUSED = os.environ.get("SFH_TRAIN_UP_SUMS_FUSED", "1") != "0"
-# the last DoubleConv's BatchNorm backward sums from the OutConv backward pass (sfh_outconv_bwd_bn)
-OUTCONV_SUMS_FUSED = os.environ.get("SFH_TRAIN_OUTCONV_SUMS_FUSED", "1") != "0"
-# TrainStep: the backward pass's power-of-two gradient scale chosen on the device (sfh_grad_scale), no read-back mid-step
-DEVICE_GRAD_SCALE = os.environ.get("SFH_TRAIN_DEVICE_GRAD_SCALE", "1") != "0"
-# BatchNorm forward: the sum of a conv epilogue's table and the finalize step in one launch (sfh_bn_finalize_partials)
-FINALIZE_FUSED = os.environ.get("SFH_TRAIN_FINALIZE_FUSED", "1") != "0"
 STATS_ROWS = 2048   # most rows of the table a conv epilogue adds its per-wave BatchNorm sums into (sfh_conv_desc.stats_partial)
 
 
@@ -302,17 +295,14 @@ def _bn_forward(lib, z, bn, relu, residual, tape, want_s3=True, want_f32=True, s
     if nbt is not None and (nbt.dtype != torch.int64 or not nbt.is_cuda):
         raise ValueError("BatchNorm num_batches_tracked must be an int64 tensor on the GPU")
     # (the kernels also advance nn.BatchNorm2d's step counter: one launch per layer less)
-    if stats is not None and FINALIZE_FUSED:
+    if stats is not None:
         # the conv that wrote z left the per-wave sums: no pass over z, and table sum + finalize are one launch
         _lib.check(lib.sfh_bn_finalize_partials(_ptr(stats), stats.shape[0], npix, C, float(bn.eps), BN_MOMENTUM,
                                                 _ptr(bn.running_mean), _ptr(bn.running_var), _ptr(mi), _ptr(nbt), _stream()),
                    "bn_finalize_partials")
     else:
         acc = tape.zeros((2 * C,), z, torch.float64)
-        if stats is not None:
-            _lib.check(lib.sfh_bn_stats_partials(_ptr(stats), stats.shape[0], C, _ptr(acc), _stream()), "bn_stats_partials")
-        else:
-            _lib.check(lib.sfh_bn_stats(_ptr(z), npix, C, _ptr(acc), _stream()), "bn_stats")
+        _lib.check(lib.sfh_bn_stats(_ptr(z), npix, C, _ptr(acc), _stream()), "bn_stats")
         _lib.check(lib.sfh_bn_finalize(_ptr(acc), npix, C, float(bn.eps), BN_MOMENTUM, _ptr(bn.running_mean),
                                        _ptr(bn.running_var), _ptr(mi), _ptr(nbt), _stream()), "bn_finalize")
     if pool:
@@ -452,7 +442,7 @@ def conv_bn_act(tape, names, conv, bn, srcs, B, H, W, relu=True, residual=None, 
     z = _empty((B, ho, wo, cout), t0)
     # BatchNorm's batch sums ride in the conv epilogue where the kernel offers it (H2, 3x3, stride 1)
     stats = None
-    if s3 and pc.stats_ok and STATS_IN_EPILOGUE:
+    if s3 and pc.stats_ok:
         rows = 64
         while rows < STATS_ROWS and rows * 1024 < B * ho * wo:   # about a quarter as many rows as pixel tiles
             rows *= 2
@@ -469,7 +459,7 @@ def conv_bn_act(tape, names, conv, bn, srcs, B, H, W, relu=True, residual=None, 
                             want_f32=f32_out or residual is not None, stats=stats)
     if relu and residual is None:
         tape.bn_layers[id(y)] = {"z": z, "mi": mi, "bn": bn}
-    if not pool and not f32_out and residual is None and relu and BWD_SUMS_IN_EPILOGUE:
+    if not pool and not f32_out and residual is None and relu:
         tape.single_consumer[id(y)] = {"z": z, "mi": mi, "bn": bn}
 
     def backward():
@@ -486,8 +476,8 @@ def conv_bn_act(tape, names, conv, bn, srcs, B, H, W, relu=True, residual=None, 
         ent = tape.single_consumer.pop(id(y), None)
         # the first layer (three channels stored as four, nothing upstream): its BatchNorm backward rides in the
         # backward-filter kernel's tile load - no dz tensor
-        c4_bn = (C4_BN_FUSED and not need_dx and not s3 and relu and residual is None and t1 is None and ks == 3
-                 and stride == 1 and c0 <= 4 and t0.shape[3] == 4 and cout % 4 == 0)
+        c4_bn = (tape.options.train_one_pass and not need_dx and not s3 and relu and residual is None and t1 is None
+                 and ks == 3 and stride == 1 and c0 <= 4 and t0.shape[3] == 4 and cout % 4 == 0)
         if c4_bn:
             _, dgamma, dbeta, _, acc = _bn_backward(lib, tape, dy, y, z, mi, bn, relu, False, apply=False,
                                                     sums_table=ent.get("table") if ent is not None else None,
@@ -643,7 +633,7 @@ def conv_transpose2x2(tape, names, up, x):
         g = tape.param_grads
         wsrc = [(x, cin, 0, 0, 0)]
         wg_s3 = s3 and wgrad_s3_ok(1, 1, 4 * cout, wsrc)
-        if wg_s3 and cout % 8 == 0 and S2D_FUSED:
+        if wg_s3 and cout % 8 == 0 and tape.options.train_one_pass:
             # one pass over du: bias gradient + the split copy of s (nobody reads s itself: backward-filter and
             # backward-data take the split copy)
             table = tape.zeros((S2D_ROWS, cout), x, torch.float64)     # (rows: see sfh_s2d_split_colsum)
@@ -723,7 +713,8 @@ def out_conv(tape, names, oc, y, B, H, W, frame_nhwc=None, stn_cs=0, sole_consum
         acc_w = tape.zeros((nc * cin,), y, torch.float64)
         acc_b = tape.zeros((nc,), y, torch.float64)
         dy = _empty(y.shape, y)
-        ent = tape.bn_layers.get(id(y)) if (sole_consumer and OUTCONV_SUMS_FUSED and tape.peek_grad(y) is None) else None
+        fused = sole_consumer and tape.options.train_one_pass and tape.peek_grad(y) is None
+        ent = tape.bn_layers.get(id(y)) if fused else None
         if ent is not None:
             sb = ent["bn"]
             acc_bn = tape.zeros((2 * cin,), y, torch.float64)
@@ -765,12 +756,12 @@ class UNetTrainer:
             y1 = conv_bn_act(tape, names, cv1, bn1, srcs, B, h, w, need_dx=need_dx, f32_out=mid_f32)
             # pool: this block's output is a skip tensor (consumers: MaxPool2d(2), and an Up block's conv with all its
             # channels - conv and backward-filter read the split copy) - BatchNorm, ReLU and pooling in one pass
-            pool = (pool and POOL_FUSED and tape.use_s3 and cv2.out_channels % 64 == 0 and CAPTURE is None
+            pool = (pool and tape.options.train_one_pass and tape.use_s3 and cv2.out_channels % 64 == 0 and CAPTURE is None
                     and not net.unet_bilinear and h >= 2 and w >= 2)
             # to_up: the only consumer is an Up block's ConvTranspose2d (forward, backward-filter and backward-data read
             # the split copy; its backward-data launch leaves this layer's BatchNorm backward sums)
-            to_up = (to_up and UP_SUMS_FUSED and tape.use_s3 and cv2.out_channels % 64 == 0 and CAPTURE is None and not net.unet_bilinear
-                     and not pool)
+            to_up = (to_up and tape.options.train_one_pass and tape.use_s3 and cv2.out_channels % 64 == 0 and CAPTURE is None
+                     and not net.unet_bilinear and not pool)
             out = conv_bn_act(tape, names, cv2, bn2, [(y1, y1.shape[3], 0, 0)], B, h, w, s3_out=s3_out, pool=pool,
                               f32_out=not to_up)
             return out if pool else (out, None)
@@ -825,7 +816,7 @@ class ResNetTrainer:
         _lib.check(lib.sfh_space_to_depth2(_ptr(stn_in), _ptr(s2d), B, H, W, cs, st()), "space_to_depth2")
         w0 = rn.conv0.weight.detach()
         z0 = _empty((B, H2, W2, 64), stn_in)
-        if tape.fmt is not None and cs == 8 and w0.shape[0] == 64 and os.environ.get("SFH_TRAIN_STEM7", "1") != "0":
+        if tape.fmt is not None and cs == 8 and w0.shape[0] == 64:
             # the tap-packed stem kernel of the inference path (csrc/stem.hip: 0.16 ms against 0.63 ms for the 4x4 fp32 conv
             # over the space-to-depth copy), in the tape's arithmetic, writing the raw conv output z
             E.StemConv(rn.conv0, None, cin, tag="train_fwd", fmt=tape.fmt, overflow=tape.overflow,
@@ -1124,7 +1115,7 @@ class _TrainForward(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, net, info, x, *params):
-        tape = Tape()
+        tape = Tape(options=net.options)
         x = E._f32c(x.detach(), "input frames")
         ctx.snap_gen = None
         if tape.fmt == "h2":
@@ -1140,7 +1131,7 @@ class _TrainForward(torch.autograd.Function):
                 snap.restore()
                 _warn_range_fallback()
                 net.__dict__["train_range_fallbacks"] = net.__dict__.get("train_range_fallbacks", 0) + 1
-                tape = Tape(fmt="s3")
+                tape = Tape(fmt="s3", options=net.options)
                 f = run_forward(net, tape, x)
         else:
             f = run_forward(net, tape, x)
@@ -1179,7 +1170,7 @@ class _TrainForward(torch.autograd.Function):
             snap.restore()
             _warn_range_fallback()
             net.__dict__["train_range_fallbacks"] = net.__dict__.get("train_range_fallbacks", 0) + 1
-            tape = Tape(fmt="s3")
+            tape = Tape(fmt="s3", options=net.options)
             g = attempt(tape, run_forward(net, tape, ctx.x))
             net.invalidate_engines()
         names = _Names(net)
@@ -1370,7 +1361,7 @@ class TrainStep:
         if not (net.use_unet and net.use_resnet and net.warper) or mode not in ("IMG_AND_MASK", "IMG_AND_MASK_AND_UV"):
             raise NotImplementedError("TrainStep covers the reference's training configurations: UNet + ResNetSTN + warper "
                                       "with resnet_input 'img+mask', or 'img+mask+uv' with the uv head")
-        tape = Tape(fmt=fmt)
+        tape = Tape(fmt=fmt, options=net.options)
         tape.gshift = self.grad_scale_shift
         B, _, H, W = x.shape
         x = E._f32c(x, "input frames")
@@ -1417,8 +1408,7 @@ class TrainStep:
                                            1 if self.uv_loss == "MSE" else 0, _ptr(duv),
                                            ctypes.c_void_p(losses.data_ptr() + 32), st), "uv_loss")
             dheads.append(duv)
-        g = run_backward(net, tape, f, dheads, theta_gradient(net, f, None, dpoi, dwarp), unscale=False,
-                         device_scale=DEVICE_GRAD_SCALE)
+        g = run_backward(net, tape, f, dheads, theta_gradient(net, f, None, dpoi, dwarp), unscale=False, device_scale=True)
         srcs = []
         for p, dst in zip(self.params, self.grads):
             src = g[self.names(p)]

@@ -1,7 +1,7 @@
 """The single-kernel Up block against the two-launch form over a range of frame sizes (odd widths / heights at several levels,
 sizes below one 16 x 32 tile, non-multiples of the tile): logits and theta must be identical bit for bit at every level set.
 usage: python tests/probes/upfused_sizes_probe.py"""
-import os, sys
+import dataclasses, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
 import sfh_amd  # noqa
@@ -20,9 +20,7 @@ for (w, h) in ((100, 60), (136, 90), (72, 56), (200, 120), (330, 180), (64, 48),
     x = synth.smooth_frames(B, h, w, seed=3).cuda()
     outs = {}
     for single in ((), (3, 4), (1, 2, 3, 4)):
-        net.invalidate_engines()
-        un, _ = net._get_engines()
-        un.up_single = set(single)
+        net.options = dataclasses.replace(net.options, up_single=frozenset(single))
         with torch.no_grad():
             o = net.predict(x, consistency=False)
         outs[single] = (o["logits"].clone(), o["theta"].clone())

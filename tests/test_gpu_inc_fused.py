@@ -1,8 +1,10 @@
-"""The UNet's first DoubleConv as ONE launch (csrc/conv_inc_fused.hip, engine.run_inc_fused; SFH_FUSE_INC) against the two
+"""The UNet's first DoubleConv as ONE launch (csrc/conv_inc_fused.hip, engine.run_inc_fused; Options.fuse_inc) against the two
 launches it replaces (sfh_conv3x3_c4h2_fwd writing the 64-channel H2 intermediate, sfh_conv_s3_fwd reading it back): the fused
 kernel performs the same products in the same order per output element, so everything it leaves must have the same BITS - the
 full-resolution output planes, the pooled output planes, and the range / overflow words of the intermediate (which no longer
 exists as a tensor) and of the output."""
+import dataclasses
+
 import pytest
 import torch
 
@@ -109,32 +111,83 @@ def test_nan_pixel_and_saturation_behave_identically():
     assert words[0] >= H2Ranges.NONFINITE and words[2] == 1
 
 
-def test_predict_is_unchanged_by_the_switch(monkeypatch):
-    """predict() on 2 frames of 64x96 with SFH_FUSE_INC on (the default) and off: logits, theta and warp_mask equal; the
-    fused launch really ran in the first and not in the second."""
-    from sfh_amd import engine as E
+def _model(B, H, W):
     from sfh_amd.reconstructor import Reconstructor
-    B, H, W = 2, 64, 96
     court = synth.load_court_template("ncaa_nc4_640x360", 4, B)[:, :, :H, :W].contiguous()
     poi = synth.load_court_poi("pitch", B)
     net = Reconstructor(court.cuda(), poi.cuda(), target_size=(W, H), unet_size=(W, H), warp_size=(W, H),
                         warp_with_nearest=True)
     net.load_state_dict(synth.synth_state_dict(net.state_dict(), 19))
-    net.cuda().eval()
-    x = synth.smooth_frames(B, H, W, seed=19).cuda()
+    return net.cuda().eval()
+
+
+def _count_fused_calls(monkeypatch):
+    from sfh_amd import engine as E
     calls = []
     real = E.run_inc_fused
     monkeypatch.setattr(E, "run_inc_fused", lambda *a, **k: (calls.append(1), real(*a, **k))[1])
+    return calls
+
+
+def test_predict_is_unchanged_by_the_switch(monkeypatch):
+    """predict() on 2 frames of 64x96 with Options.fuse_inc on (the default) and off: logits, theta and warp_mask equal; the
+    fused launch really ran in the first and not in the second."""
+    B, H, W = 2, 64, 96
+    net = _model(B, H, W)
+    x = synth.smooth_frames(B, H, W, seed=19).cuda()
+    calls = _count_fused_calls(monkeypatch)
     outs, ncalls = {}, {}
     for sw in ("1", "0"):
-        monkeypatch.setenv("SFH_FUSE_INC", sw)
-        net.invalidate_engines()
+        net.options = dataclasses.replace(net.options, fuse_inc=sw == "1")
         del calls[:]
         with torch.no_grad():
             outs[sw] = net.predict(x, consistency=True)
         torch.cuda.synchronize()
         ncalls[sw] = len(calls)
+        assert net._get_engines()[0].options.fuse_inc == (sw == "1")
         assert net._get_engines()[0].fuse_inc == (sw == "1")
     assert ncalls["1"] >= 1 and ncalls["0"] == 0
     for k in ("logits", "theta", "warp_mask"):
         assert torch.equal(outs["1"][k], outs["0"][k]), k
+
+
+def test_options_are_per_model_and_part_of_the_engine_stamp(monkeypatch):
+    """Two models of one process with the same weights, one with fuse_inc = False: equal bits, the fused launch runs for one and
+    not for the other.  Assigning another record to a model that has run - no invalidate_engines() - rebuilds its engines (the
+    next predict() makes no fused call) and voids its captured graphs (predict_replay() captures anew, on the fused launch
+    again once the option is back): always the same bits."""
+    B, H, W = 2, 64, 96
+    a, b = _model(B, H, W), _model(B, H, W)
+    b.options = dataclasses.replace(b.options, fuse_inc=False)
+    x = synth.smooth_frames(B, H, W, seed=19).cuda()
+    calls = _count_fused_calls(monkeypatch)
+
+    def run(net, how="predict"):
+        del calls[:]
+        with torch.no_grad():
+            out = getattr(net, how)(x, consistency=True)
+        torch.cuda.synchronize()
+        return {k: out[k].clone() for k in ("logits", "theta", "warp_mask")}, len(calls)
+
+    def same(o, ref):
+        return all(torch.equal(o[k], ref[k]) for k in ref)
+
+    ref, na = run(a)
+    ob, nb = run(b)
+    assert na >= 1 and nb == 0 and same(ob, ref)
+    assert a.options.fuse_inc and not b.options.fuse_inc          # neither model changed the other's record
+    a.options = dataclasses.replace(a.options, fuse_inc=False)
+    oa, na = run(a)
+    assert na == 0 and same(oa, ref)
+    # graph replay: the capture of one setting is never replayed under another
+    a.options = dataclasses.replace(a.options, fuse_inc=True)
+    a.graph_replay = True
+    o1, n1 = run(a, "predict_replay")          # eager pass + capture: the fused launch is recorded
+    o2, _ = run(a, "predict_replay")
+    assert n1 >= 1 and same(o1, ref) and same(o2, ref)
+    a.options = dataclasses.replace(a.options, fuse_inc=False)
+    o3, n3 = run(a, "predict_replay")          # captures anew, without the fused launch
+    assert n3 == 0 and same(o3, ref) and not a._get_engines()[0].fuse_inc
+    a.options = dataclasses.replace(a.options, fuse_inc=True)
+    o4, n4 = run(a, "predict_replay")          # and anew with it: run_inc_fused is counted again
+    assert n4 >= 1 and same(o4, ref)

@@ -1,6 +1,7 @@
 """GPU parity tests: the HIP path (through the C ABI) against the CPU oracle and the
 committed golden vectors.  Tolerances (BASELINE.json north_star): homography and warp
 within 1e-4 abs, nearest-mode warp / argmax / POI pixel integer-exact."""
+import dataclasses
 import json
 import math
 import os
@@ -697,7 +698,7 @@ def test_warp_consistency_fused_kernel_with_a_warp_twice_the_logits_size(E, size
 
 @pytest.mark.parametrize("wh", [(112, 90), (640, 360), (160, 96)])
 def test_single_kernel_up_block_gives_the_two_launch_bits(E, wh):
-    """Round 5 (csrc/conv_upfused.hip; the engine's default for levels 3 and 4, SFH_UP_SINGLE): the first conv of a fused Up block as ONE kernel -
+    """Round 5 (csrc/conv_upfused.hip; the engine's default for levels 3 and 4, Options.up_single): the first conv of a fused Up block as ONE kernel -
     the composed 2x2 conv over the low-resolution tensor and the skip-half 3x3 conv accumulate into the same registers, a wave per
     output-parity class - against the two-launch form (fp32 partial + acc_init): same products in the same order per output =>
     identical logits and theta, at every level, incl. the level whose skip tensor is one row larger than twice the low-resolution
@@ -708,9 +709,7 @@ def test_single_kernel_up_block_gives_the_two_launch_bits(E, wh):
     x = synth.smooth_frames(2, wh[1], wh[0], seed=19).cuda()
     outs = {}
     for single in ((), (4,), (1, 2, 3, 4)):
-        net.invalidate_engines()
-        un, _ = net._get_engines()
-        un.up_single = set(single)
+        net.options = dataclasses.replace(net.options, up_single=frozenset(single))
         with torch.no_grad():
             outs[single] = net.predict(x, consistency=False)
     for single in ((4,), (1, 2, 3, 4)):
@@ -1346,9 +1345,9 @@ def test_non_finite_frame_gives_non_finite_outputs_like_torch(E, precision):
 
 @pytest.mark.parametrize("precision", ["f16x3", "bf16x6"])
 @pytest.mark.parametrize("size", [(96, 128), (90, 112), (54, 72)])
-def test_fused_up_block_vs_unfused_and_oracle(E, monkeypatch, size, precision):
+def test_fused_up_block_vs_unfused_and_oracle(E, size, precision):
     """Up blocks without F.pad run as skip-half conv + composed 2x2 quadrant conv over the low-resolution
-    tensor (ConvTranspose2d folded into the consumer conv); with SFH_FUSE_UP=0 as ConvTranspose2d + conv over
+    tensor (ConvTranspose2d folded into the consumer conv); with Options.fuse_up = False as ConvTranspose2d + conv over
     the concatenation.  Both against the oracle, and against each other, incl. the image borders."""
     from sfh_amd.reconstructor import Reconstructor
     # 96x128: no level needs F.pad; 90x112: 5->10 vs 11 and 22->44 vs 45 (one padded row); 54x72: 27 rows, 9 cols
@@ -1358,9 +1357,9 @@ def test_fused_up_block_vs_unfused_and_oracle(E, monkeypatch, size, precision):
     x = synth.smooth_frames(B, H, W, seed=37)
     outs = {}
     for flag in ("1", "0"):
-        monkeypatch.setenv("SFH_FUSE_UP", flag)
         net = Reconstructor(court.cuda(), poi.cuda(), target_size=(W, H), unet_size=(W, H), warp_size=(W, H),
                             warp_with_nearest=True)
+        net.options = dataclasses.replace(net.options, fuse_up=flag == "1")
         sd = synth.synth_state_dict(net.state_dict(), 37)
         net.load_state_dict(sd)
         net.cuda().eval()
@@ -1382,7 +1381,7 @@ def test_fused_up_block_vs_unfused_and_oracle(E, monkeypatch, size, precision):
 
 @pytest.mark.parametrize("precision", ["f16x3", "bf16x6"])
 @pytest.mark.parametrize("size", [(90, 112), (48, 64)])
-def test_fused_outconv_head_vs_outconv_kernel(E, monkeypatch, size, precision):
+def test_fused_outconv_head_vs_outconv_kernel(E, size, precision):
     """OutConv + cat((logits, x)) in the epilogue of the last 3x3 conv against the separate OutConv kernel."""
     from sfh_amd.reconstructor import Reconstructor
     B, (H, W) = 2, size
@@ -1391,8 +1390,8 @@ def test_fused_outconv_head_vs_outconv_kernel(E, monkeypatch, size, precision):
     x = synth.smooth_frames(B, H, W, seed=41)
     res = {}
     for flag in ("1", "0"):
-        monkeypatch.setenv("SFH_FUSE_HEAD", flag)
         net = Reconstructor(court.cuda(), poi.cuda(), target_size=(W, H), unet_size=(W, H), warp_size=(W, H))
+        net.options = dataclasses.replace(net.options, fuse_head=flag == "1")
         sd = synth.synth_state_dict(net.state_dict(), 41)
         net.load_state_dict(sd)
         net.cuda().eval()

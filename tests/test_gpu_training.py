@@ -1,4 +1,5 @@
 """Training-mode parity: HIP forward/backward vs torch autograd over the CPU oracle."""
+import dataclasses
 import warnings
 
 import numpy as np
@@ -1134,12 +1135,8 @@ def test_fused_training_passes_give_the_gradients_of_the_separate_ones(T, prec, 
     monkeypatch.setattr(T._lib, "check", lambda rc, tag="": (tags.append(tag), real(rc, tag))[1])
 
     def grads(fused):
-        monkeypatch.setattr(T, "POOL_FUSED", fused)
-        monkeypatch.setattr(T, "S2D_FUSED", fused)
-        monkeypatch.setattr(T, "C4_BN_FUSED", fused)
-        monkeypatch.setattr(T, "UP_SUMS_FUSED", fused)
-        monkeypatch.setattr(T, "OUTCONV_SUMS_FUSED", fused)
         net = Reconstructor(court, poi, target_size=(W, H), unet_size=(W, H), warp_size=(W, H))
+        net.options = dataclasses.replace(net.options, train_one_pass=fused)
         net.load_state_dict(synth.synth_state_dict(net.state_dict(), 3))
         net.cuda().train()
         ts = T.TrainStep(net, lr=1e-4)
