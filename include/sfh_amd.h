@@ -1017,6 +1017,75 @@ int sfh_jpeg_decode_pixels(const uint8_t* staged, int batch, int H, int W, int C
                            int subseq_bits, uint8_t* scratch, int64_t scratch_bytes, uint8_t* out, int32_t* status,
                            int32_t* rounds, void* stream);
 
+/* Standard PNG files -> uint8 device images, csrc/pngdec.hip with the decode core csrc/pngdec_core.h (the pixels are those of
+ * outputs.decode_png, which tests/test_pngdec_host.py holds to PIL's).  Admitted: non-interlaced 8-bit files of colour type 0, 2
+ * and 6, all five scanline filters, any number of IDAT chunks cut anywhere, stored, fixed and dynamic blocks, a zlib header with
+ * CM = 8, a window of at most 32 KB and no preset dictionary; ancillary chunks are skipped.  Everything else is refused on the
+ * host, with nothing launched: -1 and one of the reasons below; a reason of 100 or more names a well-formed file that needs
+ * something not built.                                                                                                       */
+#define SFH_PNG_R_OK 0
+#define SFH_PNG_R_TRUNCATED 1         /* the bytes end before IHDR is complete                                                 */
+#define SFH_PNG_R_NOT_PNG 2           /* no PNG signature                                                                      */
+#define SFH_PNG_R_CRC 3               /* a chunk whose CRC-32 is not the one stored                                            */
+#define SFH_PNG_R_BAD_IHDR 4          /* IHDR missing, not first, repeated, or with values the format does not have            */
+#define SFH_PNG_R_IDAT_ORDER 5        /* IDAT chunks that are not consecutive                                                  */
+#define SFH_PNG_R_NO_IDAT 6
+#define SFH_PNG_R_NO_IEND 7           /* the chunks end without IEND                                                           */
+#define SFH_PNG_R_ZLIB 8              /* a zlib header that is not CM 8, window <= 32 KB, check bits right                      */
+#define SFH_PNG_R_ZLIB_DICT 9         /* a preset dictionary                                                                   */
+#define SFH_PNG_R_CRITICAL 10         /* a critical chunk that is not IHDR, PLTE, IDAT, IEND                                   */
+#define SFH_PNG_R_SIZE 11             /* width, height or channels other than the decoder's                                    */
+#define SFH_PNG_R_TOO_LONG 12         /* more bytes than the decoder's max_file_bytes                                          */
+#define SFH_PNG_R_BIT_DEPTH 100       /* 1, 2, 4 or 16 bits                                                                    */
+#define SFH_PNG_R_PALETTE 101
+#define SFH_PNG_R_GRAY_ALPHA 102
+#define SFH_PNG_R_INTERLACE 103       /* Adam7                                                                                 */
+#define SFH_PNG_R_APNG 104
+#define SFH_PNG_DEC_MAX_SEGMENTS 1024 /* IDAT chunks of a file that the segmented leg is tried on at most                      */
+
+/* The parse of one file (64 bytes).  channels: 1, 3, 4.  idat_bytes: of all IDAT bodies together; cmf, flg: their first two
+ * bytes; adler: their last four, big endian.  file_pos, file_bytes, range_pos, joined_pos: filled by sfh_png_dec_stage only -
+ * where the file, its range table and the table of every body's offset in the joined bodies lie in the staging buffer.      */
+typedef struct sfh_png_info {
+  int32_t width, height, channels, bit_depth, color_type, interlace;
+  int32_t nidat, idat_bytes, cmf, flg;
+  uint32_t adler;
+  int32_t reason;
+  int32_t file_pos, file_bytes, range_pos, joined_pos;
+} sfh_png_info;
+
+/* Host code, no device: checks the signature, walks the chunks of host_bytes[0, n) and verifies every chunk's CRC-32 with a
+ * table, reads IHDR and the zlib header -> host_info, and the IDAT bodies as int32 pairs {first byte, end byte} in host_ranges,
+ * as many as range_cap admits (host_ranges may be NULL with range_cap 0); host_info->nidat counts all.  0, or -1 with
+ * host_info->reason = SFH_PNG_R_*.                                                                                           */
+int sfh_png_parse(const uint8_t* host_bytes, int64_t n, sfh_png_info* host_info, int32_t* host_ranges, int64_t range_cap);
+
+/* bytes of the staging buffer (pinned host memory and its device copy, 16-byte aligned) and of the device scratch buffer of a
+ * decoder of `batch` H x W x C files (C = 1, 3, 4) of at most max_file_bytes; -1 for bad arguments, a filtered stream
+ * H (1 + W C) of 2 GiB or more and for buffers of 2 GiB (staging) / 4 GiB (scratch) or more.                                 */
+int64_t sfh_png_dec_staging_bytes(int batch, int H, int W, int C, int64_t max_file_bytes);
+int64_t sfh_png_dec_scratch_bytes(int batch, int H, int W, int C);
+
+/* Host code, no device: parses `batch` files and packs the batch into host_staging - a 64-byte head {magic, batch, largest
+ * IDAT count, used bytes}, the sfh_png_info of every file, every file's range table and joined offsets, the files at 16-byte
+ * aligned positions - for ONE copy to the device.  Returns the bytes used, or -1 with *host_reason = SFH_PNG_R_* and
+ * *host_index = the file refused.                                                                                           */
+int64_t sfh_png_dec_stage(const uint8_t* const* host_files, const int64_t* host_sizes, int batch, int H, int W, int C,
+                          int64_t max_file_bytes, uint8_t* host_staging, int64_t staging_bytes, int32_t* host_reason,
+                          int32_t* host_index);
+
+/* `staged`, the device copy of host_staging (which is read here for its head only) -> out uint8 (B,H,W) or (B,H,W,C) (bgr != 0:
+ * BGR(A) in memory), status int32 (B) (the PD_E_* bits of csrc/pngdec_core.h; such an image comes back as zeros) and segmented
+ * int32 (B) (1: the image's filtered stream came from the segmented leg).  One small memset, then: when a file of the batch has
+ * 2 .. SFH_PNG_DEC_MAX_SEGMENTS IDAT chunks and serial_only == 0, the segmented leg - count pass, one workgroup per (image,
+ * chunk); acceptance, on the device; write pass; Adler-32 partials; verdict - and then always the serial leg - inflate, one
+ * workgroup per image, which exits at once for an accepted image; Adler-32 partials; verdict - and the two unfilter kernels, of
+ * which exactly one does an image's work.  5 or 10 launches, no global atomics, no workgroup waits for another, no host
+ * synchronisation.                                                                                                           */
+int sfh_png_decode(const uint8_t* host_staging, const uint8_t* staged, int64_t staged_bytes, int batch, int H, int W, int C,
+                   int bgr, int64_t max_file_bytes, int serial_only, uint8_t* scratch, int64_t scratch_bytes, uint8_t* out,
+                   int32_t* status, int32_t* segmented, void* stream);
+
 /* Pillow's 8-bit image resize, csrc/resample.hip (the byte-exact rule is libImaging/Resample.c's, restated in
  * tests/resample_ref.py): `Image.resize(size, filter)` of L and RGB images for the antialiased filters below - per axis a table
  * of (xmin, n) and n coefficients in 22-bit fixed point per output index, a horizontal pass into uint8, then a vertical pass,

@@ -13,7 +13,7 @@ LIB = os.path.join(_HERE, "libsfh_amd.so")
 SOURCES = ["capi.hip", "conv_mfma.hip", "conv_s3.hip", "conv_c4h2.hip", "pointwise.hip", "warp.hip", "train.hip", "stem.hip",
            "wgrad_s3.hip", "probe.hip", "conv_small.hip", "conv_upfused.hip", "conv_inc_fused.hip", "hostprep.hip",
            "eval.hip", "augment.hip", "overlay.hip", "prepare.hip", "mapping.hip", "pngenc.hip", "jpegenc.hip", "resample.hip",
-           "jpegdec.hip"]
+           "jpegdec.hip", "pngdec.hip"]
 # warp.hip's coordinate arithmetic must not be contracted into FMAs (bit-exact nearest
 # sampling against oracle/warp_ref.py); the flag is harmless elsewhere.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off",
@@ -47,7 +47,7 @@ def _stale(target, deps):
 def build(force=False, verbose=True):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "conv_epilogue.h"), os.path.join(CSRC, "warp_coords.h"), os.path.join(CSRC, "block_scan.h"),
-               os.path.join(CSRC, "jpegdec_core.h"),
+               os.path.join(CSRC, "jpegdec_core.h"), os.path.join(CSRC, "pngdec_core.h"),
                os.path.join(os.path.dirname(_HERE), "include", "sfh_amd.h")]
     objs = []
     procs = []

@@ -33,6 +33,7 @@ import torch
 from . import _lib
 from . import outputs as O
 from .jpegenc import image_files_from_batch
+from . import pngdec
 from .jpegdec import frames_from_files
 from .engine import _ptr
 
@@ -328,9 +329,10 @@ def rectify_game(court_json, frames, dst_dir, out_size=(1280, 720), mode="neares
     (outputs.encode_png, the default) or "device" (sfh_amd.pngenc: the views are encoded on the GPU).  image_format: "png",
     or "jpeg" for ``<name>.jpeg`` and ``mosaic.jpeg`` at jpeg_quality (``png=`` then selects where the JPEG is encoded:
     outputs.encode_jpeg or sfh_amd.jpegenc, the same bytes).  frames_format: "array", or "jpeg" for an iterable of JPEG files as
-    bytes, decoded on the GPU (sfh_amd.jpegdec) to the pixels PIL gives.  Returns the list of written paths."""
-    if frames_format not in ("array", "jpeg"):
-        raise ValueError(f'rectify_game: frames_format={frames_format!r} ("array" or "jpeg")')
+    bytes, decoded on the GPU (sfh_amd.jpegdec) to the pixels PIL gives, or "png" for PNG files (sfh_amd.pngdec).  Returns the
+    list of written paths."""
+    if frames_format not in ("array", "jpeg", "png"):
+        raise ValueError(f'rectify_game: frames_format={frames_format!r} ("array", "jpeg" or "png")')
     cm = CourtMapping(court_json, device=device)
     if names is not None:
         for k, (n, p) in enumerate(zip(names, cm.names)):
@@ -351,6 +353,8 @@ def rectify_game(court_json, frames, dst_dir, out_size=(1280, 720), mode="neares
         B = len(chunk)
         if frames_format == "jpeg":
             fr = frames_from_files(chunk, tabs["theta"].device)     # decoded on the GPU (sfh_amd.jpegdec): only the files are uploaded
+        elif frames_format == "png":
+            fr = pngdec.frames_from_files(chunk, tabs["theta"].device)
         else:
             fr = torch.from_numpy(np.ascontiguousarray(np.stack(chunk))).to(tabs["theta"].device)
         theta, score = tabs["theta"][first:first + B], tabs["scores"][first:first + B]
@@ -366,9 +370,10 @@ def rectify_game(court_json, frames, dst_dir, out_size=(1280, 720), mode="neares
         if done + len(chunk) >= len(cm):
             raise ValueError(f"rectify_game: more frames than the {len(cm)} predictions")
         a = np.frombuffer(fr, np.uint8) if isinstance(fr, (bytes, bytearray, memoryview)) else np.asarray(fr)
-        if frames_format == "jpeg":
+        if frames_format != "array":
             if a.dtype != np.uint8 or a.ndim != 1:
-                raise ValueError(f"rectify_game: with frames_format='jpeg' a frame is the bytes of a JPEG file, got {a.dtype} {a.shape}")
+                raise ValueError(f"rectify_game: with frames_format={frames_format!r} a frame is the bytes of a {frames_format.upper()} "
+                                 f"file, got {a.dtype} {a.shape}")
         elif a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or (chunk and a.shape != chunk[0].shape):
             raise ValueError(f"rectify_game: frames must be uint8 (H,W,3) arrays of one size, got {a.dtype} {a.shape}")
         chunk.append(a)

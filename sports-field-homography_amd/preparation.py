@@ -344,19 +344,26 @@ def prepare_dataset(anno_dir, dst_dir, court_ids=None, court_poi=None, size=(640
     return {"written": written, "skipped": skipped}
 
 
-def read_dataset(dst_dir, keys, use_uv=False, device="cpu", size=None):
+def read_dataset(dst_dir, keys, use_uv=False, device="cpu", size=None, decode="host"):
     """``BasicDataset.__getitem__``'s label side (utils/dataset.py:240-289, anno_keys = theta, poi, reproj_mse; no resize: the
     labels are written at the target size) for the frames ``keys`` (``game/frame``) of a tree written by ``prepare_dataset``,
     collated: the entries ``to_batch`` returns for the same frames (without frames_u8 / image).
     size=(W, H): the labels at another size than the written one, as ``BasicDataset`` resizes them - the mask with
     ``Image.NEAREST`` (preprocess_mask), the uint16 UV label with cv2.INTER_NEAREST before it is split (preprocess_uv_mask) - on
-    the device (``resample.resize_nearest``): ``device`` must then be a GPU."""
+    the device (``resample.resize_nearest``): ``device`` must then be a GPU.
+    decode: "host" (outputs.decode_png, the default) or "device" - the mask files of all keys in one sfh_amd.pngdec decode, only
+    the files are uploaded: ``device`` must then be a GPU."""
+    if decode not in ("host", "device"):
+        raise ValueError(f'read_dataset: decode={decode!r} ("host" or "device")')
+    if decode == "device" and torch.device(device).type != "cuda":
+        raise ValueError(f"read_dataset: decode='device' decodes on the device; device={device!r} is not a GPU")
     if size is not None:
         size = (int(size[0]), int(size[1]))
         if torch.device(device).type != "cuda":
             raise ValueError(f"read_dataset: size={size} resizes on the device; device={device!r} is not a GPU")
         from . import resample
     masks, uvs, pois, nzs, thetas, ws = [], [], [], [], [], []
+    mask_files = []
     for key in keys:
         stem = os.path.join(dst_dir, *str(key).split("/"))
         with open(stem + ".json", "r") as f:
@@ -370,6 +377,9 @@ def read_dataset(dst_dir, keys, use_uv=False, device="cpu", size=None):
         elif use_uv:
             m, uvp = split_uv(np.load(stem + ".npy"))
             uvs.append(torch.from_numpy(uvp))
+        elif decode == "device":
+            m = None
+            mask_files.append(np.fromfile(stem + ".png", dtype=np.uint8))
         else:
             m = O.decode_png(np.fromfile(stem + ".png", dtype=np.uint8))
         if m is not None:
@@ -379,7 +389,11 @@ def read_dataset(dst_dir, keys, use_uv=False, device="cpu", size=None):
         nzs.append(p[:, 2])
         thetas.append(torch.from_numpy(np.asarray(anno["theta"], dtype="float")).type(torch.FloatTensor))
         ws.append(torch.from_numpy(preprocess_weight(np.asarray([anno["reproj_mse"]], dtype="float"))))
-    mask_u8 = torch.stack(masks).to(device)
+    if mask_files:
+        from . import pngdec
+        mask_u8 = pngdec.masks_from_files(mask_files, device)
+    else:
+        mask_u8 = torch.stack(masks).to(device)
     if size is not None and not use_uv:
         mask_u8 = resample.resize_nearest(mask_u8.contiguous(), (size[1], size[0]), rule="pil")
     batch = {"name": [str(k) for k in keys], "mask_u8": mask_u8,

@@ -36,6 +36,7 @@ import torch
 from . import _lib
 from . import outputs as O
 from .jpegenc import image_files_from_batch
+from . import pngdec
 from .jpegdec import frames_from_files
 from .engine import _ptr
 
@@ -236,7 +237,7 @@ def _names_checked(names, pred_names, mask_names):
 
 def visualize(frames, preds_path, dst_dir, court_img, masks_path=None, mask_classes=4, score_threshold=0.1,
               overlay_threshold=None, batch=16, names=None, renderer=None, device="cuda", png="host", image_format="png",
-              jpeg_quality=90, frames_format="array", **renderer_kw):
+              jpeg_quality=90, frames_format="array", masks_decode="host", **renderer_kw):
     """viz_preds.py:78-152 without video decode and ffmpeg.  frames: an iterable of host uint8 (H,W,3) arrays in the order of
     the predictions (names: their frame names, checked against the predictions' when given; the reference asserts
     ``int(name) == frame number``); preds_path: a ``{game}_court.json`` (outputs.CourtJsonWriter); masks_path: the optional
@@ -246,10 +247,13 @@ def visualize(frames, preds_path, dst_dir, court_img, masks_path=None, mask_clas
     (outputs.encode_png, the default) or "device" (sfh_amd.pngenc: the frames are encoded on the GPU).  image_format: "png",
     or "jpeg" for ``dst_dir/<name>.jpeg`` at jpeg_quality, what the reference's predict.py:394 writes (``png=`` then selects
     where the JPEG is encoded: outputs.encode_jpeg or sfh_amd.jpegenc, the same bytes).  frames_format: "array", or "jpeg" for
-    an iterable of JPEG files as bytes, decoded on the GPU (sfh_amd.jpegdec) to the pixels PIL gives.  Returns the list of
-    written paths."""
-    if frames_format not in ("array", "jpeg"):
-        raise ValueError(f'visualize: frames_format={frames_format!r} ("array" or "jpeg")')
+    an iterable of JPEG files as bytes, decoded on the GPU (sfh_amd.jpegdec) to the pixels PIL gives, or "png" for PNG files
+    (sfh_amd.pngdec).  masks_decode: "host" (outputs.decode_png, the default) or "device" (the masks of a batch in one
+    sfh_amd.pngdec decode: only the files are uploaded).  Returns the list of written paths."""
+    if frames_format not in ("array", "jpeg", "png"):
+        raise ValueError(f'visualize: frames_format={frames_format!r} ("array", "jpeg" or "png")')
+    if masks_decode not in ("host", "device"):
+        raise ValueError(f'visualize: masks_decode={masks_decode!r} ("host" or "device")')
     mapping, _ = O.load_court_mapping(preds_path)
     pred_names = list(mapping.keys())
     masks = None
@@ -271,6 +275,8 @@ def visualize(frames, preds_path, dst_dir, court_img, masks_path=None, mask_clas
         B = len(chunk)
         if frames_format == "jpeg":
             fr = frames_from_files(chunk, device)     # decoded on the GPU (sfh_amd.jpegdec): only the files are uploaded
+        elif frames_format == "png":
+            fr = pngdec.frames_from_files(chunk, device)
         else:
             fr = torch.from_numpy(np.ascontiguousarray(np.stack(chunk))).to(device)
         keys = pred_names[first:first + B]
@@ -278,7 +284,9 @@ def visualize(frames, preds_path, dst_dir, court_img, masks_path=None, mask_clas
         scores = [mapping[k][2] for k in keys]
         score = torch.tensor(scores, dtype=torch.float32).to(device)
         segm = None
-        if masks is not None:
+        if masks is not None and masks_decode == "device":
+            segm = pngdec.masks_from_files(masks[first:first + B], device)
+        elif masks is not None:
             dec = [O.decode_png(m) for m in masks[first:first + B]]
             if any(d.ndim != 2 or d.shape != dec[0].shape for d in dec):
                 raise ValueError("visualize: the mask stream must hold gray id masks of one size")
@@ -296,9 +304,10 @@ def visualize(frames, preds_path, dst_dir, court_img, masks_path=None, mask_clas
         if done + len(chunk) >= len(pred_names):
             raise ValueError(f"visualize: more frames than the {len(pred_names)} predictions")
         a = np.frombuffer(fr, np.uint8) if isinstance(fr, (bytes, bytearray, memoryview)) else np.asarray(fr)
-        if frames_format == "jpeg":
+        if frames_format != "array":
             if a.dtype != np.uint8 or a.ndim != 1:
-                raise ValueError(f"visualize: with frames_format='jpeg' a frame is the bytes of a JPEG file, got {a.dtype} {a.shape}")
+                raise ValueError(f"visualize: with frames_format={frames_format!r} a frame is the bytes of a {frames_format.upper()} "
+                                 f"file, got {a.dtype} {a.shape}")
         elif a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or (chunk and a.shape != chunk[0].shape):
             raise ValueError(f"visualize: frames must be uint8 (H,W,3) arrays of one size, got {a.dtype} {a.shape}")
         chunk.append(a)
