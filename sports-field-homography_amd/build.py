@@ -3,6 +3,7 @@
 Plain ``hipcc -c`` per source + one link; no torch C++ ABI, no cmake.  Called by
 ``__graft_entry__.build()`` and usable stand-alone: ``python -m sfh_amd.build``.
 """
+import glob
 import os
 import subprocess
 import sys
@@ -46,9 +47,7 @@ def _stale(target, deps):
 
 def build(force=False, verbose=True):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "conv_epilogue.h"), os.path.join(CSRC, "warp_coords.h"), os.path.join(CSRC, "block_scan.h"),
-               os.path.join(CSRC, "jpegdec_core.h"), os.path.join(CSRC, "pngdec_core.h"),
-               os.path.join(os.path.dirname(_HERE), "include", "sfh_amd.h")]
+    headers = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(os.path.dirname(_HERE), "include", "sfh_amd.h")]
     objs = []
     procs = []
     for s in SOURCES:

@@ -22,6 +22,7 @@
 // sfh_jpeg_info (7920 bytes) and a few words.  No global atomics; no workgroup waits for another.
 #include "common.h"
 #include "block_scan.h"
+#include "codec_host.h"
 #include "jpegdec_core.h"
 
 namespace {
@@ -29,9 +30,6 @@ namespace {
 using namespace blockscan;
 constexpr int kThreads = kScanThreads;
 constexpr uint32_t kMagic = 0x4a444543u;   // "JDEC"
-constexpr int kHeadBytes = 64;
-
-inline int64_t round16(int64_t v) { return (v + 15) & ~(int64_t)15; }
 
 struct DecGeom {
   int mcus_x16, mcus_y16, mcus_x8, mcus_y8;
@@ -74,7 +72,7 @@ bool dec_geom(int batch, int H, int W, int C, int64_t max_file_bytes, int subseq
   g->planes = o;
   o += round16((int64_t)batch * 3 * g->plane);
   g->total = o;
-  g->staging = kHeadBytes + (int64_t)batch * ((int64_t)sizeof(sfh_jpeg_info) + 16 * g->max_mcus + round16(max_file_bytes) + 16);
+  g->staging = kStageHeadBytes + (int64_t)batch * ((int64_t)sizeof(sfh_jpeg_info) + 16 * g->max_mcus + round16(max_file_bytes) + 16);
   return g->total < ((int64_t)1 << 31) * 2 && g->staging < ((int64_t)1 << 31);
 }
 
@@ -105,7 +103,7 @@ DecArgs dec_args(const DecGeom& g, int H, int W, int C, int subseq_bits) {
 }
 
 __device__ __forceinline__ const sfh_jpeg_info* staged_info(const uint8_t* staged, int b) {
-  return reinterpret_cast<const sfh_jpeg_info*>(staged + kHeadBytes) + b;
+  return reinterpret_cast<const sfh_jpeg_info*>(staged + kStageHeadBytes) + b;
 }
 
 __global__ __launch_bounds__(kThreads) void jpeg_entropy_kernel(const uint8_t* __restrict__ staged, DecArgs a,
@@ -270,7 +268,6 @@ __global__ __launch_bounds__(kThreads) void jpeg_status_kernel(const uint8_t* __
   }
 }
 
-__device__ __forceinline__ int descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
 __device__ __forceinline__ int clamp255(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
 
 // one pass of jidctint.c (CONST_BITS 13, PASS1_BITS 2) over 8 values; N: the descale (11: the column pass, 18: the row pass)
@@ -496,37 +493,22 @@ extern "C" int64_t sfh_jpeg_dec_stage(const uint8_t* const* host_files, const in
                                       int64_t max_file_bytes, int subseq_bits, uint8_t* host_staging, int64_t staging_bytes,
                                       int32_t* host_reason, int32_t* host_index) {
   DecGeom g;
-  if (!host_files || !host_sizes || !host_staging || !host_reason || !host_index ||
-      !dec_geom(batch, H, W, C, max_file_bytes, subseq_bits, &g) || staging_bytes < g.staging || ((uintptr_t)host_staging & 15)) {
-    sfh_set_error("jpeg_dec_stage: null pointer, bad shape or a staging buffer that is too small or not 16-byte aligned");
-    if (host_reason) *host_reason = SFH_JPEG_R_OK;
-    return -1;
-  }
-  *host_reason = SFH_JPEG_R_OK;
-  *host_index = -1;
-  sfh_jpeg_info* infos = reinterpret_cast<sfh_jpeg_info*>(host_staging + kHeadBytes);
-  int64_t pos = kHeadBytes + (int64_t)batch * (int64_t)sizeof(sfh_jpeg_info);
+  const int64_t need = dec_geom(batch, H, W, C, max_file_bytes, subseq_bits, &g) ? g.staging : -1;
+  if (!stage_begin("jpeg_dec_stage", host_files, host_sizes, host_staging, staging_bytes, need, host_reason, host_index)) return -1;
+  sfh_jpeg_info* infos = reinterpret_cast<sfh_jpeg_info*>(host_staging + kStageHeadBytes);
+  int64_t pos = kStageHeadBytes + (int64_t)batch * (int64_t)sizeof(sfh_jpeg_info);
   int max_seg = 0, hsamp = 0;
   for (int b = 0; b < batch; ++b) {
     sfh_jpeg_info* info = infos + b;
     int32_t* segs = reinterpret_cast<int32_t*>(host_staging + pos);
-    int reason = SFH_JPEG_R_OK;
-    if (!host_files[b] || host_sizes[b] < 0) {
-      reason = SFH_JPEG_R_TRUNCATED;
-    } else if (host_sizes[b] > max_file_bytes) {
-      reason = SFH_JPEG_R_TOO_LONG;
-    } else if (jd_parse(host_files[b], host_sizes[b], info, segs, g.max_mcus)) {
-      reason = info->reason;
-    } else if (info->width != W || info->height != H || info->ncomp != C || info->nsegments > g.max_mcus ||
-               (b > 0 && info->hsamp != hsamp)) {
-      reason = SFH_JPEG_R_SIZE;
+    int reason = stage_file_reason(host_files[b], host_sizes[b], max_file_bytes, SFH_JPEG_R_TRUNCATED, SFH_JPEG_R_TOO_LONG);
+    if (reason == SFH_JPEG_R_OK) {
+      if (jd_parse(host_files[b], host_sizes[b], info, segs, g.max_mcus)) reason = info->reason;
+      else if (info->width != W || info->height != H || info->ncomp != C || info->nsegments > g.max_mcus ||
+               (b > 0 && info->hsamp != hsamp))
+        reason = SFH_JPEG_R_SIZE;
     }
-    if (reason != SFH_JPEG_R_OK) {
-      *host_reason = reason;
-      *host_index = b;
-      sfh_set_error("jpeg_dec_stage: file %d refused, reason %d", b, reason);
-      return -1;
-    }
+    if (reason != SFH_JPEG_R_OK) return stage_refuse_file("jpeg_dec_stage", b, reason, host_reason, host_index);
     hsamp = info->hsamp;
     int64_t nsub = 0;
     for (int s = 0; s < info->nsegments; ++s) {
@@ -538,20 +520,8 @@ extern "C" int64_t sfh_jpeg_dec_stage(const uint8_t* const* host_files, const in
     pos += 16 * (int64_t)info->nsegments;
     max_seg = info->nsegments > max_seg ? info->nsegments : max_seg;
   }
-  for (int b = 0; b < batch; ++b) {
-    sfh_jpeg_info* info = infos + b;
-    info->file_pos = (int32_t)pos;
-    info->file_bytes = (int32_t)host_sizes[b];
-    memcpy(host_staging + pos, host_files[b], (size_t)host_sizes[b]);
-    const int64_t end = round16(pos + host_sizes[b]) + 16;
-    memset(host_staging + pos + host_sizes[b], 0, (size_t)(end - pos - host_sizes[b]));
-    pos = end;
-  }
-  uint32_t* head = reinterpret_cast<uint32_t*>(host_staging);
-  memset(head, 0, kHeadBytes);
-  head[0] = kMagic;
-  head[1] = (uint32_t)batch;
-  head[2] = (uint32_t)max_seg;
+  pos = stage_copy_files(infos, host_files, host_sizes, batch, host_staging, pos);
+  uint32_t* head = stage_head(host_staging, kMagic, batch, max_seg);
   head[3] = (uint32_t)subseq_bits;
   head[4] = (uint32_t)pos;
   head[5] = (uint32_t)hsamp;
@@ -563,16 +533,12 @@ extern "C" int sfh_jpeg_entropy_decode(const uint8_t* host_staging, const uint8_
                                        int64_t scratch_bytes, void* stream) {
   DecGeom g;
   SFH_REQUIRE(dec_geom(batch, H, W, C, max_file_bytes, subseq_bits, &g), "jpeg_entropy_decode: batch %d image %dx%dx%d", batch, W, H, C);
-  SFH_REQUIRE(host_staging && staged && scratch, "jpeg_entropy_decode: null pointer (host_staging, staged, scratch)");
-  SFH_REQUIRE((((uintptr_t)staged | (uintptr_t)scratch) & 15) == 0, "jpeg_entropy_decode: staged and scratch must be 16-byte aligned");
+  if (int rc = decode_begin("jpeg_entropy_decode", "sfh_jpeg_dec_stage", host_staging, staged, staged_bytes, scratch, scratch_bytes,
+                            g.total, kMagic, batch, g.max_mcus, 4))
+    return rc;
   const uint32_t* head = reinterpret_cast<const uint32_t*>(host_staging);
-  SFH_REQUIRE(head[0] == kMagic && head[1] == (uint32_t)batch && head[3] == (uint32_t)subseq_bits && head[2] >= 1 &&
-                  (int64_t)head[2] <= g.max_mcus,
-              "jpeg_entropy_decode: host_staging is not what sfh_jpeg_dec_stage left for this batch and subsequence size");
-  SFH_REQUIRE(staged_bytes >= (int64_t)head[4], "jpeg_entropy_decode: staged buffer of %lld bytes, %lld used", (long long)staged_bytes,
-              (long long)head[4]);
-  SFH_REQUIRE(scratch_bytes >= g.total, "jpeg_entropy_decode: scratch of %lld bytes, %lld needed", (long long)scratch_bytes,
-              (long long)g.total);
+  SFH_REQUIRE(head[3] == (uint32_t)subseq_bits, "jpeg_entropy_decode: host_staging was staged for subsequences of %u bits, not %d",
+              head[3], subseq_bits);
   const hipError_t e = hipMemsetAsync(scratch, 0, (size_t)g.clear_bytes, (hipStream_t)stream);
   if (e != hipSuccess) {
     sfh_set_error("jpeg_entropy_decode: hipMemsetAsync: %s", hipGetErrorString(e));

@@ -17,17 +17,7 @@
 #include <string.h>
 
 #include "../../include/sfh_amd.h"
-
-#if defined(__HIPCC__)
-#define SFH_HD __host__ __device__ inline
-#else
-#define SFH_HD inline
-#endif
-
-// zig-zag position -> natural (row-major) index
-constexpr uint8_t kJdNatural[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                    41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                    30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+#include "codec_common.h"
 
 enum { JD_E_CODE = 1, JD_E_RUN = 2, JD_E_EOF = 4, JD_E_BLOCKS = 8 };   // status bits of a segment
 
@@ -252,7 +242,7 @@ SFH_HD int jd_final_lane(const JdCtx& c, int32_t subseq_bits, int32_t nsub, int 
       jd_step(c, s, e);
       if (ab >= 0 && ab < nblocks) {
         err |= e.err;
-        if (e.k >= 0) coef[(int64_t)ab * 64 + kJdNatural[e.k & 63]] = (int16_t)e.value;
+        if (e.k >= 0) coef[(int64_t)ab * 64 + kJpegNatural[e.k & 63]] = (int16_t)e.value;
       }
       ab += e.done;
     }
@@ -298,8 +288,6 @@ inline bool build_huff(const uint8_t* bits, const uint8_t* vals, int nvals, sfh_
   return true;
 }
 
-inline int be16(const uint8_t* p) { return (p[0] << 8) | p[1]; }
-
 }  // namespace jdparse
 
 // bytes[0, n) -> info, and up to seg_cap segments {first byte, end byte, first MCU, 0} as int32 quadruples in segs (may be null
@@ -323,7 +311,7 @@ inline int jd_parse(const uint8_t* bytes, int64_t n, sfh_jpeg_info* info, int32_
     const int m = bytes[i++];
     if (m == 0xD8 || m == 0xD9 || m == 0x01 || m == 0x00 || (m >= 0xD0 && m <= 0xD7)) return fail(info, SFH_JPEG_R_MARKER);
     if (i + 2 > n) return fail(info, SFH_JPEG_R_TRUNCATED);
-    const int len = be16(bytes + i);
+    const int len = get_be16(bytes + i);
     if (len < 2 || i + len > n) return fail(info, SFH_JPEG_R_TRUNCATED);
     const uint8_t* b = bytes + i + 2;
     const int bl = len - 2;
@@ -335,8 +323,8 @@ inline int jd_parse(const uint8_t* bytes, int64_t n, sfh_jpeg_info* info, int32_
       if (sof) return fail(info, SFH_JPEG_R_MARKER);
       if (bl < 6) return fail(info, SFH_JPEG_R_TRUNCATED);
       if (b[0] != 8) return fail(info, b[0] == 12 ? SFH_JPEG_R_PRECISION : SFH_JPEG_R_BAD_SOF);
-      info->height = be16(b + 1);
-      info->width = be16(b + 3);
+      info->height = get_be16(b + 1);
+      info->width = get_be16(b + 3);
       info->ncomp = b[5];
       if (info->width == 0) return fail(info, SFH_JPEG_R_BAD_SOF);
       if (info->height == 0) return fail(info, SFH_JPEG_R_DNL);
@@ -358,7 +346,7 @@ inline int jd_parse(const uint8_t* bytes, int64_t n, sfh_jpeg_info* info, int32_
         if (tq > 3 || pq > 1) return fail(info, SFH_JPEG_R_BAD_TABLE);
         if (pq == 1) return fail(info, SFH_JPEG_R_DQT16);
         if (o + 65 > bl) return fail(info, SFH_JPEG_R_TRUNCATED);
-        for (int z = 0; z < 64; ++z) info->quant[tq][kJdNatural[z]] = b[o + 1 + z];
+        for (int z = 0; z < 64; ++z) info->quant[tq][kJpegNatural[z]] = b[o + 1 + z];
         have_q[tq] = true;
         o += 65;
       }
@@ -381,7 +369,7 @@ inline int jd_parse(const uint8_t* bytes, int64_t n, sfh_jpeg_info* info, int32_
       }
     } else if (m == 0xDD) {
       if (bl != 2) return fail(info, SFH_JPEG_R_MARKER);
-      info->restart_interval = be16(b);
+      info->restart_interval = get_be16(b);
     } else if (m == 0xE0) {
       if (bl >= 5 && memcmp(b, "JFIF", 5) == 0) jfif = true;
     } else if (m == 0xEE) {

@@ -23,11 +23,13 @@
 //   the images before it, which every workgroup computes for itself from the meta records - no third launch.
 // No global atomics anywhere; the same bytes every run.
 #include "common.h"
-#include "block_scan.h"
+#include "codec_common.h"
+#include "codec_host.h"
+#include "codec_pack.h"
 
 namespace {
 
-using namespace blockscan;
+using namespace codecpack;
 constexpr int kThreads = kScanThreads;
 constexpr int kMaxWidth = SFH_JPEG_MAX_WIDTH;
 constexpr int kCoefStride = 66;               // int16 per block: 64 coefficients, the block's bit length, one spare = 33 dwords
@@ -37,9 +39,6 @@ constexpr int kCoefStride = 66;               // int16 per block: 64 coefficient
 constexpr int kBlockMaxBits = 22 + 63 * 26;
 constexpr int kMinRegion = 1536;              // bytes of the samples / window + staging region at least
 
-constexpr uint8_t kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                 41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 constexpr uint8_t kBaseLuma[64] = {16, 11, 10, 16, 24,  40,  51,  61,  12, 12, 14, 19, 26,  58,  60,  55,
                                    14, 13, 16, 24, 40,  57,  69,  56,  14, 17, 22, 29, 51,  87,  80,  62,
                                    18, 22, 37, 56, 68,  109, 103, 77,  24, 35, 55, 64, 81,  104, 113, 92,
@@ -118,8 +117,7 @@ void make_tables(int quality, JpegTables* t) {
   }
 }
 
-inline int round16(int v) { return (v + 15) & ~15; }
-inline int64_t meta_bytes(int64_t intervals) { return (intervals * 8 + 15) & ~(int64_t)15; }   // {bytes, passes} per interval
+inline int64_t meta_bytes(int64_t intervals) { return round16(intervals * 8); }   // {bytes, passes} per interval
 inline int mcu_size(int C) { return C == 3 ? 16 : 8; }
 inline int blocks_per_row(int W, int C) { return sfh_cdiv(W, mcu_size(C)) * (C == 3 ? 6 : 1); }
 // bytes of an interval at most: its blocks at kBlockMaxBits, every byte stuffed, the marker
@@ -152,7 +150,7 @@ void make_header(int H, int W, int C, int quality, JpegHead* h) {
   p = put_segment(p, 0xE0, jfif, 14);
   for (int c = 0; c < (C == 3 ? 2 : 1); ++c) {
     body[0] = (uint8_t)c;
-    for (int i = 0; i < 64; ++i) body[1 + i] = (uint8_t)quant_entry((c ? kBaseChroma : kBaseLuma)[kZigzag[i]], quality);
+    for (int i = 0; i < 64; ++i) body[1 + i] = (uint8_t)quant_entry((c ? kBaseChroma : kBaseLuma)[kJpegNatural[i]], quality);
     p = put_segment(p, 0xDB, body, 65);
   }
   int n = 0;
@@ -194,8 +192,6 @@ void make_header(int H, int W, int C, int quality, JpegHead* h) {
   p = put_segment(p, 0xDA, body, n);
   h->n = (int)(p - h->b);
 }
-
-__device__ __forceinline__ int descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
 
 // one pass of jfdctint.c (CONST_BITS 13, PASS1_BITS 2) over 8 values; FIRST: the row pass
 template <bool FIRST>
@@ -412,7 +408,7 @@ __global__ __launch_bounds__(kThreads) void jpeg_encode_kernel(const uint8_t* __
     const uint16_t* dv = lt->div[bp.tab];
 #pragma unroll
     for (int z = 0; z < 64; ++z) {
-      const int i = kZigzag[z];
+      const int i = kJpegNatural[z];
       const int c = d[i];
       const uint32_t q = __umulhi((uint32_t)(c < 0 ? -c : c) + ((uint32_t)dv[i] >> 1), recip[i]);
       cf[z] = (int16_t)(c < 0 ? -(int)q : (int)q);
@@ -527,15 +523,9 @@ __global__ __launch_bounds__(kThreads) void jpeg_pack_kernel(const uint32_t* __r
   int* tmp = reinterpret_cast<int*>(jpeg_lds);                                // kPackLdsBytes of dynamic LDS: the scan's 4 ints,
   int* off_s = tmp + 4;                                                       // offset and byte count of kThreads intervals
   int* cnt_s = off_s + kThreads;
-  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const int t = threadIdx.x;
   const int b = blockIdx.x;
-  int base = b * capacity;
-  if (compact) {
-    int part = 0;
-    for (int i = t; i < b * nrows; i += kThreads) part += (int)meta[(size_t)i * 2];
-    block_scan_excl<OP_SUM, false>(part, 0, tmp, base);
-    base += b * head.n;
-  }
+  const int base = compact ? bytes_before<2>(meta, b * nrows, tmp) + b * head.n : b * capacity;
   uint8_t* dst = out + base;
   for (int i = t; i < head.n; i += kThreads) dst[i] = head.b[i];
   int pos = head.n;
@@ -549,29 +539,10 @@ __global__ __launch_bounds__(kThreads) void jpeg_pack_kernel(const uint32_t* __r
     cnt_s[t] = cnt;
     __syncthreads();
     const int nhere = nrows - s0 < kThreads ? nrows - s0 : kThreads;
-    for (int j = wv; j < nhere; j += kThreads / 64) {                         // a wave copies an interval
-      const uint8_t* src = slots + ((size_t)b * nrows + s0 + j) * (size_t)stride;
-      uint8_t* d = dst + off_s[j];
-      const int n = cnt_s[j];
-      int headb = (int)((4u - (uint32_t)(uintptr_t)d) & 3u);
-      if (headb > n) headb = n;
-      if (lane < headb) d[lane] = src[lane];
-      const int nw = (n - headb) / 4;
-      for (int w = lane; w < nw; w += 64) {                                   // aligned dword stores, byte loads
-        const uint8_t* sp = src + headb + 4 * w;
-        *reinterpret_cast<uint32_t*>(d + headb + 4 * w) =
-            (uint32_t)sp[0] | ((uint32_t)sp[1] << 8) | ((uint32_t)sp[2] << 16) | ((uint32_t)sp[3] << 24);
-      }
-      const int done = headb + 4 * nw;
-      if (lane < n - done) d[done + lane] = src[done + lane];
-    }
+    copy_slots(slots + ((size_t)b * nrows + s0) * (size_t)stride, (size_t)stride, nhere, dst, off_s, cnt_s);
     pos += tot;
   }
-  if (t == 0) {
-    sizes[b] = pos;
-    offsets[b] = base;
-    if (b == batch - 1) offsets[batch] = compact ? (int64_t)base + pos : (int64_t)batch * capacity;
-  }
+  if (t == 0) write_index(b, batch, base, pos, capacity, compact, offsets, sizes);
 }
 
 int jpeg_check(const char* who, int batch, int H, int W, int C, int quality) {
@@ -579,11 +550,7 @@ int jpeg_check(const char* who, int batch, int H, int W, int C, int quality) {
   SFH_REQUIRE(H > 0 && W > 0 && H <= 65535, "%s: image %dx%d", who, W, H);
   SFH_REQUIRE(W <= kMaxWidth, "%s: width %d (at most %d)", who, W, kMaxWidth);
   SFH_REQUIRE(quality >= 1 && quality <= 100, "%s: quality %d (1 .. 100)", who, quality);
-  SFH_REQUIRE(batch > 0 && batch <= 65535, "%s: batch %d (1 .. 65535)", who, batch);
-  const int64_t cap = sfh_jpeg_capacity(H, W, C);
-  SFH_REQUIRE(cap * batch < ((int64_t)1 << 31) && sfh_jpeg_scratch_bytes(batch, H, W, C) < ((int64_t)1 << 32),
-              "%s: %d images of %dx%dx%d: encoded batch of 2 GiB or more", who, batch, W, H, C);
-  return SFH_OK;
+  return enc_batch_check(who, batch, H, W, C, sfh_jpeg_capacity(H, W, C), sfh_jpeg_scratch_bytes(batch, H, W, C));
 }
 
 }  // namespace
@@ -609,9 +576,7 @@ extern "C" int sfh_jpeg_encode(const uint8_t* images, int batch, int H, int W, i
                                int64_t scratch_bytes, int window_dwords, void* stream) {
   if (int rc = jpeg_check("jpeg_encode", batch, H, W, C, quality)) return rc;
   SFH_REQUIRE(images && scratch, "jpeg_encode: null pointer (images, scratch)");
-  SFH_REQUIRE(((uintptr_t)scratch & 15) == 0, "jpeg_encode: scratch must be 16-byte aligned");
-  SFH_REQUIRE(scratch_bytes >= sfh_jpeg_scratch_bytes(batch, H, W, C), "jpeg_encode: scratch of %lld bytes, %lld needed",
-              (long long)scratch_bytes, (long long)sfh_jpeg_scratch_bytes(batch, H, W, C));
+  if (int rc = enc_scratch_check("jpeg_encode", scratch, scratch_bytes, sfh_jpeg_scratch_bytes(batch, H, W, C))) return rc;
   const int region = region_bytes(W, C);
   const int winmax = window_words(region);
   SFH_REQUIRE(window_dwords >= 0 && window_dwords <= winmax, "jpeg_encode: window of %d dwords (0: the default, at most %d)",
@@ -634,9 +599,7 @@ extern "C" int sfh_jpeg_pack(const uint8_t* scratch, int64_t scratch_bytes, int 
                              int compact, uint8_t* out, int64_t out_bytes, int64_t* offsets, int32_t* sizes, void* stream) {
   if (int rc = jpeg_check("jpeg_pack", batch, H, W, C, quality)) return rc;
   SFH_REQUIRE(scratch && out && offsets && sizes, "jpeg_pack: null pointer (scratch, out, offsets, sizes)");
-  SFH_REQUIRE(((uintptr_t)scratch & 15) == 0, "jpeg_pack: scratch must be 16-byte aligned");
-  SFH_REQUIRE(scratch_bytes >= sfh_jpeg_scratch_bytes(batch, H, W, C), "jpeg_pack: scratch of %lld bytes, %lld needed",
-              (long long)scratch_bytes, (long long)sfh_jpeg_scratch_bytes(batch, H, W, C));
+  if (int rc = enc_scratch_check("jpeg_pack", scratch, scratch_bytes, sfh_jpeg_scratch_bytes(batch, H, W, C))) return rc;
   const int64_t cap = sfh_jpeg_capacity(H, W, C);
   SFH_REQUIRE(out_bytes >= cap * batch, "jpeg_pack: output of %lld bytes, %lld needed (batch * jpeg_capacity)",
               (long long)out_bytes, (long long)(cap * batch));

@@ -23,6 +23,7 @@
 // workgroup waits for another; no host synchronisation.
 #include "common.h"
 #include "block_scan.h"
+#include "codec_host.h"
 #include "pngdec_core.h"
 
 namespace {
@@ -30,14 +31,11 @@ namespace {
 using namespace blockscan;
 constexpr int kThreads = kScanThreads;
 constexpr uint32_t kMagic = 0x50444543u;   // "PDEC"
-constexpr int kHeadBytes = 64;
 constexpr int kAdlerChunk = 16384;         // bytes of one workgroup of png_adler_kernel: 256 threads x 64
 constexpr int kRowsPerGroup = 8;
 constexpr int kPixPerThread = 8;
 constexpr int kCtlInts = 8;                // per image: accepted, serial status, mode, ...
 enum { CTL_ACCEPTED = 0, CTL_SERIAL_STATUS = 1, CTL_MODE = 2 };
-
-inline int64_t round16(int64_t v) { return (v + 15) & ~(int64_t)15; }
 
 struct PngGeom {
   int64_t total;         // bytes of an image's filtered stream
@@ -70,7 +68,7 @@ bool png_geom(int batch, int H, int W, int C, int64_t max_file_bytes, PngGeom* g
   if (max_file_bytes < 0) return true;                   // the scratch alone
   if (max_file_bytes < 8 || max_file_bytes >= ((int64_t)1 << 28)) return false;
   g->range_cap = max_file_bytes / 12 + 1;
-  g->staging = kHeadBytes + (int64_t)batch * ((int64_t)sizeof(sfh_png_info) + 12 * g->range_cap + 16 + round16(max_file_bytes) + 16);
+  g->staging = kStageHeadBytes + (int64_t)batch * ((int64_t)sizeof(sfh_png_info) + 12 * g->range_cap + 16 + round16(max_file_bytes) + 16);
   return g->staging < ((int64_t)1 << 31);
 }
 
@@ -99,7 +97,7 @@ PngArgs png_args(const PngGeom& g, int H, int W, int C, int bgr) {
 }
 
 __device__ __forceinline__ const sfh_png_info* staged_info(const uint8_t* staged, int b) {
-  return reinterpret_cast<const sfh_png_info*>(staged + kHeadBytes) + b;
+  return reinterpret_cast<const sfh_png_info*>(staged + kStageHeadBytes) + b;
 }
 __device__ __forceinline__ int32_t* ctl_of(uint8_t* scratch, const PngArgs& a, int b) {
   return reinterpret_cast<int32_t*>(scratch + a.ctl) + (int64_t)b * kCtlInts;
@@ -428,36 +426,20 @@ extern "C" int64_t sfh_png_dec_stage(const uint8_t* const* host_files, const int
                                      int64_t max_file_bytes, uint8_t* host_staging, int64_t staging_bytes, int32_t* host_reason,
                                      int32_t* host_index) {
   PngGeom g;
-  if (!host_files || !host_sizes || !host_staging || !host_reason || !host_index || max_file_bytes < 0 ||
-      !png_geom(batch, H, W, C, max_file_bytes, &g) || staging_bytes < g.staging || ((uintptr_t)host_staging & 15)) {
-    sfh_set_error("png_dec_stage: null pointer, bad shape or a staging buffer that is too small or not 16-byte aligned");
-    if (host_reason) *host_reason = SFH_PNG_R_OK;
-    return -1;
-  }
-  *host_reason = SFH_PNG_R_OK;
-  *host_index = -1;
-  sfh_png_info* infos = reinterpret_cast<sfh_png_info*>(host_staging + kHeadBytes);
-  int64_t pos = kHeadBytes + (int64_t)batch * (int64_t)sizeof(sfh_png_info);
+  const int64_t need = max_file_bytes >= 0 && png_geom(batch, H, W, C, max_file_bytes, &g) ? g.staging : -1;
+  if (!stage_begin("png_dec_stage", host_files, host_sizes, host_staging, staging_bytes, need, host_reason, host_index)) return -1;
+  sfh_png_info* infos = reinterpret_cast<sfh_png_info*>(host_staging + kStageHeadBytes);
+  int64_t pos = kStageHeadBytes + (int64_t)batch * (int64_t)sizeof(sfh_png_info);
   int max_idat = 0;
   for (int b = 0; b < batch; ++b) {
     sfh_png_info* info = infos + b;
     int32_t* ranges = reinterpret_cast<int32_t*>(host_staging + pos);
-    int reason = SFH_PNG_R_OK;
-    if (!host_files[b] || host_sizes[b] < 0) {
-      reason = SFH_PNG_R_TRUNCATED;
-    } else if (host_sizes[b] > max_file_bytes) {
-      reason = SFH_PNG_R_TOO_LONG;
-    } else if (pd_parse(host_files[b], host_sizes[b], info, ranges, g.range_cap)) {
-      reason = info->reason;
-    } else if (info->width != W || info->height != H || info->channels != C || info->nidat > g.range_cap) {
-      reason = SFH_PNG_R_SIZE;
+    int reason = stage_file_reason(host_files[b], host_sizes[b], max_file_bytes, SFH_PNG_R_TRUNCATED, SFH_PNG_R_TOO_LONG);
+    if (reason == SFH_PNG_R_OK) {
+      if (pd_parse(host_files[b], host_sizes[b], info, ranges, g.range_cap)) reason = info->reason;
+      else if (info->width != W || info->height != H || info->channels != C || info->nidat > g.range_cap) reason = SFH_PNG_R_SIZE;
     }
-    if (reason != SFH_PNG_R_OK) {
-      *host_reason = reason;
-      *host_index = b;
-      sfh_set_error("png_dec_stage: file %d refused, reason %d", b, reason);
-      return -1;
-    }
+    if (reason != SFH_PNG_R_OK) return stage_refuse_file("png_dec_stage", b, reason, host_reason, host_index);
     info->range_pos = (int32_t)pos;
     pos += 8 * (int64_t)info->nidat;
     int32_t* joined = reinterpret_cast<int32_t*>(host_staging + pos);
@@ -470,21 +452,8 @@ extern "C" int64_t sfh_png_dec_stage(const uint8_t* const* host_files, const int
     pos = round16(pos + 4 * (int64_t)info->nidat);
     max_idat = info->nidat > max_idat ? info->nidat : max_idat;
   }
-  for (int b = 0; b < batch; ++b) {
-    sfh_png_info* info = infos + b;
-    info->file_pos = (int32_t)pos;
-    info->file_bytes = (int32_t)host_sizes[b];
-    memcpy(host_staging + pos, host_files[b], (size_t)host_sizes[b]);
-    const int64_t end = round16(pos + host_sizes[b]) + 16;
-    memset(host_staging + pos + host_sizes[b], 0, (size_t)(end - pos - host_sizes[b]));
-    pos = end;
-  }
-  uint32_t* head = reinterpret_cast<uint32_t*>(host_staging);
-  memset(head, 0, kHeadBytes);
-  head[0] = kMagic;
-  head[1] = (uint32_t)batch;
-  head[2] = (uint32_t)max_idat;
-  head[3] = (uint32_t)pos;
+  pos = stage_copy_files(infos, host_files, host_sizes, batch, host_staging, pos);
+  stage_head(host_staging, kMagic, batch, max_idat)[3] = (uint32_t)pos;
   return pos;
 }
 
@@ -493,14 +462,11 @@ extern "C" int sfh_png_decode(const uint8_t* host_staging, const uint8_t* staged
                               int32_t* status, int32_t* segmented, void* stream) {
   PngGeom g;
   SFH_REQUIRE(max_file_bytes >= 0 && png_geom(batch, H, W, C, max_file_bytes, &g), "png_decode: batch %d image %dx%dx%d", batch, W, H, C);
-  SFH_REQUIRE(host_staging && staged && scratch && out && status && segmented, "png_decode: null pointer");
-  SFH_REQUIRE((((uintptr_t)staged | (uintptr_t)scratch) & 15) == 0, "png_decode: staged and scratch must be 16-byte aligned");
+  SFH_REQUIRE(out && status && segmented, "png_decode: null pointer (out, status, segmented)");
+  if (int rc = decode_begin("png_decode", "sfh_png_dec_stage", host_staging, staged, staged_bytes, scratch, scratch_bytes, g.bytes,
+                            kMagic, batch, g.range_cap, 3))
+    return rc;
   const uint32_t* head = reinterpret_cast<const uint32_t*>(host_staging);
-  SFH_REQUIRE(head[0] == kMagic && head[1] == (uint32_t)batch && head[2] >= 1 && (int64_t)head[2] <= g.range_cap,
-              "png_decode: host_staging is not what sfh_png_dec_stage left for this batch");
-  SFH_REQUIRE(staged_bytes >= (int64_t)head[3], "png_decode: staged buffer of %lld bytes, %lld used", (long long)staged_bytes,
-              (long long)head[3]);
-  SFH_REQUIRE(scratch_bytes >= g.bytes, "png_decode: scratch of %lld bytes, %lld needed", (long long)scratch_bytes, (long long)g.bytes);
   hipStream_t st = (hipStream_t)stream;
   const PngArgs a = png_args(g, H, W, C, bgr ? 1 : 0);
   const hipError_t e = hipMemsetAsync(scratch + g.ctl, 0, (size_t)batch * kCtlInts * 4, st);

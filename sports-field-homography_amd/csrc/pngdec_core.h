@@ -21,12 +21,7 @@
 #include <string.h>
 
 #include "../../include/sfh_amd.h"
-
-#if defined(__HIPCC__)
-#define SFH_HD __host__ __device__ inline
-#else
-#define SFH_HD inline
-#endif
+#include "codec_common.h"
 
 #if defined(__HIP_DEVICE_COMPILE__)
 #define PD_LANES_BEGIN(lane) \
@@ -64,26 +59,6 @@ enum {
 
 // ------------------------------------------------------------------------------------------------------------ the host parse
 
-SFH_HD uint32_t pd_be32(const uint8_t* p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
-
-struct PdCrcTable {
-  uint32_t t[256];
-  PdCrcTable() {
-    for (uint32_t n = 0; n < 256; ++n) {
-      uint32_t c = n;
-      for (int k = 0; k < 8; ++k) c = (c & 1u) ? (0xEDB88320u ^ (c >> 1)) : (c >> 1);
-      t[n] = c;
-    }
-  }
-};
-
-inline uint32_t pd_crc32(const uint8_t* p, int64_t n) {
-  static const PdCrcTable tab;
-  uint32_t c = 0xFFFFFFFFu;
-  for (int64_t i = 0; i < n; ++i) c = tab.t[(c ^ p[i]) & 255u] ^ (c >> 8);
-  return c ^ 0xFFFFFFFFu;
-}
-
 // Host code: the parse of sfh_png_parse.  ranges: int32 pairs, as many as `cap` admits (may be null with cap 0).
 inline int pd_parse(const uint8_t* d, int64_t n, sfh_png_info* info, int32_t* ranges, int64_t cap) {
   memset(info, 0, sizeof(*info));
@@ -103,16 +78,16 @@ inline int pd_parse(const uint8_t* d, int64_t n, sfh_png_info* info, int32_t* ra
   uint8_t head[2] = {0, 0}, tail[4] = {0, 0, 0, 0};      // the first two and the last four bytes of the joined bodies
   while (!have_iend) {
     if (n - pos < 12) return refuse(have_ihdr ? SFH_PNG_R_NO_IEND : SFH_PNG_R_TRUNCATED);
-    const uint32_t len = pd_be32(d + pos);
+    const uint32_t len = get_be32(d + pos);
     const uint8_t* tag = d + pos + 4;
     if (len > 0x7FFFFFFFu || (int64_t)len > n - pos - 12) return refuse(have_ihdr ? SFH_PNG_R_NO_IEND : SFH_PNG_R_TRUNCATED);
     const uint8_t* body = d + pos + 8;
-    if (pd_crc32(tag, 4 + (int64_t)len) != pd_be32(body + len)) return refuse(SFH_PNG_R_CRC);
+    if (host_crc32(tag, 4 + (int64_t)len) != get_be32(body + len)) return refuse(SFH_PNG_R_CRC);
     const bool is_idat = !memcmp(tag, "IDAT", 4);
     if (!have_ihdr) {
       if (memcmp(tag, "IHDR", 4) || len != 13) return refuse(SFH_PNG_R_BAD_IHDR);
       have_ihdr = true;
-      const uint32_t w = pd_be32(body), h = pd_be32(body + 4);
+      const uint32_t w = get_be32(body), h = get_be32(body + 4);
       const int depth = body[8], ctype = body[9], comp = body[10], filt = body[11], lace = body[12];
       if (w == 0 || h == 0 || w > 0x7FFFFFFFu || h > 0x7FFFFFFFu || comp != 0 || filt != 0 || lace > 1 ||
           !(ctype == 0 || ctype == 2 || ctype == 3 || ctype == 4 || ctype == 6) ||

@@ -23,11 +23,13 @@
 //   computes for itself from the meta records - no third launch, no communication between workgroups.
 // No global atomics anywhere; the same bytes every run.
 #include "common.h"
-#include "block_scan.h"
+#include "codec_common.h"
+#include "codec_host.h"
+#include "codec_pack.h"
 
 namespace {
 
-using namespace blockscan;
+using namespace codecpack;
 constexpr int kThreads = kScanThreads;
 constexpr int kMaxRow = SFH_PNG_MAX_ROW;
 constexpr int kStripRows = SFH_PNG_STRIP_ROWS;
@@ -43,7 +45,6 @@ inline int strip_rows(int W, int C) {
   const int r = kMaxRow / (1 + W * C);
   return r < 1 ? 1 : (r > kStripRows ? kStripRows : r);
 }
-inline int round16(int v) { return (v + 15) & ~15; }
 // a strip's slot in the scratch buffer: chunk header 8, zlib header 2, stored header 5, the bytes, Adler 4, CRC 4
 inline int slot_stride(int R, int rowlen) { return round16(8 + 2 + 5 + R * rowlen + 4 + 4); }
 inline int raw_lds_bytes(int R, int rowlen) { return round16(R * rowlen + 4); }
@@ -341,29 +342,16 @@ __global__ __launch_bounds__(kThreads) void png_encode_kernel(const uint8_t* __r
   }
 }
 
-__device__ __forceinline__ void put_be32(uint8_t* o, uint32_t v) {
-  o[0] = (uint8_t)(v >> 24);
-  o[1] = (uint8_t)(v >> 16);
-  o[2] = (uint8_t)(v >> 8);
-  o[3] = (uint8_t)v;
-}
-
 __global__ __launch_bounds__(kThreads) void png_pack_kernel(const uint32_t* __restrict__ meta, const uint8_t* __restrict__ slots,
                                                             int batch, int H, int rowlen, int R, int nstrips, int stride,
                                                             int capacity, int compact, PngHead head, uint8_t* __restrict__ out,
                                                             int64_t* __restrict__ offsets, int32_t* __restrict__ sizes) {
   __shared__ int tmp[4];
   __shared__ int off_s[kThreads], cnt_s[kThreads];
-  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const int t = threadIdx.x;
   const int b = blockIdx.x;
   // where the image starts
-  int base = b * capacity;
-  if (compact) {
-    int part = 0;
-    for (int i = t; i < b * nstrips; i += kThreads) part += (int)meta[(size_t)i * 4];
-    block_scan_excl<OP_SUM, false>(part, 0, tmp, base);
-    base += b * kFixedFile;
-  }
+  const int base = compact ? bytes_before<4>(meta, b * nstrips, tmp) + b * kFixedFile : b * capacity;
   uint8_t* dst = out + base;
   if (t < 33) dst[t] = head.b[t];
   int pos = 33;                                   // bytes of the file so far
@@ -388,22 +376,7 @@ __global__ __launch_bounds__(kThreads) void png_pack_kernel(const uint32_t* __re
     cnt_s[t] = (live && s == nstrips - 1) ? cnt - 8 : cnt;      // the last chunk's Adler and CRC are written below
     __syncthreads();
     const int nhere = nstrips - s0 < kThreads ? nstrips - s0 : kThreads;
-    for (int j = wv; j < nhere; j += kThreads / 64) {             // a wave copies a strip
-      const uint8_t* src = slots + ((size_t)b * nstrips + s0 + j) * (size_t)stride;
-      uint8_t* d = dst + off_s[j];
-      const int n = cnt_s[j];
-      int headb = (int)((4u - (uint32_t)(uintptr_t)d) & 3u);
-      if (headb > n) headb = n;
-      if (lane < headb) d[lane] = src[lane];
-      const int nw = (n - headb) / 4;
-      for (int w = lane; w < nw; w += 64) {                       // aligned dword stores, byte loads
-        const uint8_t* sp = src + headb + 4 * w;
-        *reinterpret_cast<uint32_t*>(d + headb + 4 * w) =
-            (uint32_t)sp[0] | ((uint32_t)sp[1] << 8) | ((uint32_t)sp[2] << 16) | ((uint32_t)sp[3] << 24);
-      }
-      const int done = headb + 4 * nw;
-      if (lane < n - done) d[done + lane] = src[done + lane];
-    }
+    copy_slots(slots + ((size_t)b * nstrips + s0) * (size_t)stride, (size_t)stride, nhere, dst, off_s, cnt_s);
     pos += tot;
   }
   if (t == 0) {
@@ -417,30 +390,15 @@ __global__ __launch_bounds__(kThreads) void png_pack_kernel(const uint32_t* __re
     put_be32(dst + pos - 4, ~reg);
     const uint8_t iend[12] = {0, 0, 0, 0, 'I', 'E', 'N', 'D', 0xAE, 0x42, 0x60, 0x82};
     for (int i = 0; i < 12; ++i) dst[pos + i] = iend[i];
-    sizes[b] = pos + 12;
-    offsets[b] = base;
-    if (b == batch - 1) offsets[batch] = compact ? (int64_t)base + pos + 12 : (int64_t)batch * capacity;
+    write_index(b, batch, base, pos + 12, capacity, compact, offsets, sizes);
   }
-}
-
-uint32_t host_crc32(const uint8_t* p, int n) {
-  uint32_t c = 0xFFFFFFFFu;
-  for (int i = 0; i < n; ++i) {
-    c ^= p[i];
-    for (int k = 0; k < 8; ++k) c = (c >> 1) ^ ((c & 1u) ? kPoly : 0u);
-  }
-  return ~c;
 }
 
 int png_check(const char* who, int batch, int H, int W, int C) {
   SFH_REQUIRE(C == 1 || C == 3, "%s: %d channels (1 gray, 3 colour)", who, C);
   SFH_REQUIRE(H > 0 && W > 0, "%s: image %dx%d", who, W, H);
   SFH_REQUIRE((int64_t)1 + (int64_t)W * C <= kMaxRow, "%s: a scanline of 1 + %d * %d bytes (at most %d)", who, W, C, kMaxRow);
-  SFH_REQUIRE(batch > 0 && batch <= 65535, "%s: batch %d (1 .. 65535)", who, batch);
-  const int64_t cap = sfh_png_capacity(H, W, C);
-  SFH_REQUIRE(cap * batch < ((int64_t)1 << 31) && sfh_png_scratch_bytes(batch, H, W, C) < ((int64_t)1 << 32),
-              "%s: %d images of %dx%dx%d: encoded batch of 2 GiB or more", who, batch, W, H, C);
-  return SFH_OK;
+  return enc_batch_check(who, batch, H, W, C, sfh_png_capacity(H, W, C), sfh_png_scratch_bytes(batch, H, W, C));
 }
 
 }  // namespace
@@ -469,9 +427,7 @@ extern "C" int sfh_png_encode(const uint8_t* images, int batch, int H, int W, in
                               int64_t scratch_bytes, void* stream) {
   if (int rc = png_check("png_encode", batch, H, W, C)) return rc;
   SFH_REQUIRE(images && scratch, "png_encode: null pointer (images, scratch)");
-  SFH_REQUIRE(((uintptr_t)scratch & 15) == 0, "png_encode: scratch must be 16-byte aligned");
-  SFH_REQUIRE(scratch_bytes >= sfh_png_scratch_bytes(batch, H, W, C), "png_encode: scratch of %lld bytes, %lld needed",
-              (long long)scratch_bytes, (long long)sfh_png_scratch_bytes(batch, H, W, C));
+  if (int rc = enc_scratch_check("png_encode", scratch, scratch_bytes, sfh_png_scratch_bytes(batch, H, W, C))) return rc;
   const int rowlen = 1 + W * C, R = strip_rows(W, C), nstrips = sfh_cdiv(H, R);
   const int stride = slot_stride(R, rowlen), raw_bytes = raw_lds_bytes(R, rowlen);
   const size_t lds = (size_t)raw_bytes + stride + 16 + kTableBytes;
@@ -487,9 +443,7 @@ extern "C" int sfh_png_pack(const uint8_t* scratch, int64_t scratch_bytes, int b
                             uint8_t* out, int64_t out_bytes, int64_t* offsets, int32_t* sizes, void* stream) {
   if (int rc = png_check("png_pack", batch, H, W, C)) return rc;
   SFH_REQUIRE(scratch && out && offsets && sizes, "png_pack: null pointer (scratch, out, offsets, sizes)");
-  SFH_REQUIRE(((uintptr_t)scratch & 15) == 0, "png_pack: scratch must be 16-byte aligned");
-  SFH_REQUIRE(scratch_bytes >= sfh_png_scratch_bytes(batch, H, W, C), "png_pack: scratch of %lld bytes, %lld needed",
-              (long long)scratch_bytes, (long long)sfh_png_scratch_bytes(batch, H, W, C));
+  if (int rc = enc_scratch_check("png_pack", scratch, scratch_bytes, sfh_png_scratch_bytes(batch, H, W, C))) return rc;
   const int64_t cap = sfh_png_capacity(H, W, C);
   SFH_REQUIRE(out_bytes >= cap * batch, "png_pack: output of %lld bytes, %lld needed (batch * png_capacity)",
               (long long)out_bytes, (long long)(cap * batch));
@@ -498,16 +452,11 @@ extern "C" int sfh_png_pack(const uint8_t* scratch, int64_t scratch_bytes, int b
   const uint8_t sig[8] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1A, '\n'};
   for (int i = 0; i < 8; ++i) head.b[i] = sig[i];
   uint8_t* p = head.b + 8;
-  const uint8_t ihdr[21] = {0, 0, 0, 13, 'I', 'H', 'D', 'R',
-                            (uint8_t)(W >> 24), (uint8_t)(W >> 16), (uint8_t)(W >> 8), (uint8_t)W,
-                            (uint8_t)(H >> 24), (uint8_t)(H >> 16), (uint8_t)(H >> 8), (uint8_t)H,
-                            8, (uint8_t)(C == 1 ? 0 : 2), 0, 0, 0};
+  const uint8_t ihdr[21] = {0, 0, 0, 13, 'I', 'H', 'D', 'R', 0, 0, 0, 0, 0, 0, 0, 0, 8, (uint8_t)(C == 1 ? 0 : 2), 0, 0, 0};
   for (int i = 0; i < 21; ++i) p[i] = ihdr[i];
-  const uint32_t crc = host_crc32(p + 4, 17);
-  p[21] = (uint8_t)(crc >> 24);
-  p[22] = (uint8_t)(crc >> 16);
-  p[23] = (uint8_t)(crc >> 8);
-  p[24] = (uint8_t)crc;
+  put_be32(p + 8, (uint32_t)W);
+  put_be32(p + 12, (uint32_t)H);
+  put_be32(p + 21, host_crc32(p + 4, 17));
   const uint32_t* meta = reinterpret_cast<const uint32_t*>(scratch);
   const uint8_t* slots = scratch + (size_t)batch * nstrips * 16;
   hipLaunchKernelGGL(png_pack_kernel, dim3((unsigned)batch), dim3(kThreads), 0, (hipStream_t)stream, meta, slots, batch, H, rowlen,

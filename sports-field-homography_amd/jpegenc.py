@@ -24,7 +24,7 @@ progressive mode; the decoder is ``sfh_amd.jpegdec``.  JPEG is for photographs: 
 import torch
 
 from . import _lib
-from .pngenc import BatchEncoder, PngBatch, _ptr, _stream, as_image_batch, files_from_batch
+from ._codec import BatchEncoder, JpegBatch, as_image_batch, image_files_from_batch, ptr, stream  # noqa: F401 (re-exported)
 
 MAX_WIDTH = 2048
 
@@ -43,11 +43,6 @@ def jpeg_capacity(H, W, C):
     return int(cap)
 
 
-class JpegBatch(PngBatch):
-    """the encoded files of one batch on the device: ``data`` uint8, file b = data[offsets[b] : offsets[b] + sizes[b]];
-    ``to_host()`` -> list of B 1-D uint8 numpy arrays (synchronises)"""
-
-
 def _check_quality(quality, who):
     if isinstance(quality, bool) or int(quality) != quality or not 1 <= int(quality) <= 100:
         raise ValueError(f"{who}: quality {quality!r} (an integer 1 .. 100)")
@@ -60,41 +55,27 @@ class JpegEncoder(BatchEncoder):
     3-channel tensors are BGR in memory (cv2's convention, like ``PngEncoder``); False for RGB tensors."""
     batch_type = JpegBatch
 
+    capacity_of = staticmethod(jpeg_capacity)
+
     def __init__(self, H, W, channels=3, batch=1, quality=90, bgr=True, compact=True, device="cuda", _window_dwords=0):
-        self.H, self.W, self.C, self.B = int(H), int(W), int(channels), int(batch)
-        if self.B < 1:
-            raise ValueError(f"JpegEncoder: batch {batch}")
-        self.quality = _check_quality(quality, "JpegEncoder")
-        self.capacity = jpeg_capacity(self.H, self.W, self.C)
-        self.bgr, self.compact = bool(bgr), bool(compact)
+        if int(batch) >= 1:                       # the batch refusal comes first, as in every encoder
+            self.quality = _check_quality(quality, "JpegEncoder")
         self._window = int(_window_dwords)        # tests only: a smaller LDS bit window, to reach the multi-pass branch
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError(f"JpegEncoder: device {self.device} - the HIP path has no CPU fallback")
-        self.scratch_bytes = int(_lib.load().sfh_jpeg_scratch_bytes(self.B, self.H, self.W, self.C))
-        if self.scratch_bytes < 0 or self.scratch_bytes >= 2 ** 32 or self.capacity * self.B >= 2 ** 31:
-            raise ValueError(f"JpegEncoder: {self.B} images of {self.W}x{self.H}x{self.C}: encoded batch of 2 GiB or more")
-        self.scratch = torch.empty(self.scratch_bytes, dtype=torch.uint8, device=self.device)
+        super().__init__(H, W, channels, batch, bgr, compact, device)
         self.intervals = -(-self.H // (16 if self.C == 3 else 8))
-        self.out = self.new_output()
         self._last = 0                            # images of the last encode
 
-    def encode(self, images_u8, out=None):
-        """images_u8: uint8 (b,H,W[,3]) on the GPU, b <= batch -> JpegBatch (of b files: offsets[:b+1], sizes[:b])"""
-        b = self._checked(images_u8)
-        out = self.out if out is None else out
+    def scratch_bytes_of(self, lib):
+        return lib.sfh_jpeg_scratch_bytes(self.B, self.H, self.W, self.C)
+
+    def _launch(self, images_u8, b, out, dev):
         lib = _lib.load()
-        dev = images_u8.device
-        with torch.cuda.device(dev):
-            _lib.check(lib.sfh_jpeg_encode(_ptr(images_u8), b, self.H, self.W, self.C, int(self.bgr), self.quality,
-                                           _ptr(self.scratch), self.scratch_bytes, self._window, _stream(dev)), "jpeg_encode")
-            _lib.check(lib.sfh_jpeg_pack(_ptr(self.scratch), self.scratch_bytes, b, self.H, self.W, self.C, self.quality,
-                                         int(self.compact), _ptr(out.data), out.data.numel(), _ptr(out.offsets), _ptr(out.sizes),
-                                         _stream(dev)), "jpeg_pack")
+        _lib.check(lib.sfh_jpeg_encode(ptr(images_u8), b, self.H, self.W, self.C, int(self.bgr), self.quality,
+                                       ptr(self.scratch), self.scratch_bytes, self._window, stream(dev)), "jpeg_encode")
+        _lib.check(lib.sfh_jpeg_pack(ptr(self.scratch), self.scratch_bytes, b, self.H, self.W, self.C, self.quality,
+                                     int(self.compact), ptr(out.data), out.data.numel(), ptr(out.offsets), ptr(out.sizes),
+                                     stream(dev)), "jpeg_pack")
         self._last = b
-        if b == self.B:
-            return out
-        return JpegBatch(out.data, out.offsets[:b + 1], out.sizes[:b])
 
     def passes(self):
         """-> int64 array (b, intervals): through how many LDS bit windows every restart interval of the last ``encode`` was
@@ -129,12 +110,3 @@ def jpeg_files_from_batch(images, channels, where="host", quality=90):
         raise RuntimeError('png="device" needs the images on the GPU - the HIP path has no CPU fallback')
     enc = JpegEncoder(images.shape[1], images.shape[2], channels, images.shape[0], quality=quality, device=images.device)
     return enc.encode(images.contiguous()).to_host()
-
-
-def image_files_from_batch(images, channels, where="host", image_format="png", jpeg_quality=90):
-    """the ``image_format=`` / ``png=`` switches of the host drivers together -> (list of B files, file extension)"""
-    if image_format == "png":
-        return files_from_batch(images, channels, where), "png"
-    if image_format == "jpeg":
-        return jpeg_files_from_batch(images, channels, where, jpeg_quality), "jpeg"     # the reference's extension
-    raise ValueError(f'image_format={image_format!r} ("png" or "jpeg")')

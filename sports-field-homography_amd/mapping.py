@@ -24,7 +24,6 @@ Stated deviations from the reference:
 * points: ``cv2.perspectiveTransform`` rounds to float32 before ``/ 2 + 0.5``; ``sfh_map_points`` carries fp64 to the end and
   rounds once.  Drawing markers on the court image (mapping_example.py's ``cv2.circle``) is not reproduced.
 """
-import ctypes
 import os
 
 import numpy as np
@@ -32,10 +31,7 @@ import torch
 
 from . import _lib
 from . import outputs as O
-from .jpegenc import image_files_from_batch
-from . import pngdec
-from .jpegdec import frames_from_files
-from .engine import _ptr
+from ._codec import frames_from_files, image_files_from_batch, ptr as _ptr, stream as _stream
 
 MODES = {"nearest": 0, "bilinear": 1}
 
@@ -59,10 +55,6 @@ UNITS = {
     "meters": CourtSizes.COURT_IN_METERS,
     "feet": (CourtSizes.COURT_IN_METERS[0] * CourtSizes.METERS2FEET, CourtSizes.COURT_IN_METERS[1] * CourtSizes.METERS2FEET),
 }
-
-
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def _need_gpu(t, what):
@@ -351,10 +343,8 @@ def rectify_game(court_json, frames, dst_dir, out_size=(1280, 720), mode="neares
 
     def flush(chunk, first):
         B = len(chunk)
-        if frames_format == "jpeg":
-            fr = frames_from_files(chunk, tabs["theta"].device)     # decoded on the GPU (sfh_amd.jpegdec): only the files are uploaded
-        elif frames_format == "png":
-            fr = pngdec.frames_from_files(chunk, tabs["theta"].device)
+        if frames_format != "array":              # decoded on the GPU (sfh_amd.jpegdec, pngdec): only the files are uploaded
+            fr = frames_from_files(chunk, tabs["theta"].device, frames_format)
         else:
             fr = torch.from_numpy(np.ascontiguousarray(np.stack(chunk))).to(tabs["theta"].device)
         theta, score = tabs["theta"][first:first + B], tabs["scores"][first:first + B]

@@ -32,7 +32,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .pngenc import PngBatch, _ptr, _stream
+from ._codec import BatchDecoder, PngBatch, as_bytes_array, ptr, refuse, stream
 
 REASONS = {1: "the bytes end inside the header", 2: "no PNG signature: not a PNG file", 3: "a chunk CRC mismatch",
            4: "a missing or malformed IHDR chunk", 5: "IDAT chunks that are not consecutive", 6: "no IDAT chunk",
@@ -58,23 +58,6 @@ class PngInfo(ctypes.Structure):
 assert ctypes.sizeof(PngInfo) == 64
 
 
-def _refuse(reason, who, index=None):
-    what = REASONS.get(int(reason), f"reason {reason}")
-    where = "" if index is None or index < 0 else f" (file {index})"
-    if reason >= 100:
-        raise NotImplementedError(f"{who}: {what} is not built{where}")
-    raise ValueError(f"{who}: {what}{where}")
-
-
-def _as_bytes_array(f, who):
-    if isinstance(f, (bytes, bytearray, memoryview)):
-        return np.frombuffer(f, dtype=np.uint8)
-    a = np.asarray(f)
-    if a.dtype != np.uint8 or a.ndim != 1:
-        raise ValueError(f"{who}: a file is bytes or a 1-D uint8 array, not {a.dtype} {a.shape}")
-    return np.ascontiguousarray(a)
-
-
 def png_file_capacity(H, W, C):
     """the default ``max_file_bytes``: the filtered stream in stored blocks (5 bytes per 65535), chunk framing and 64 KB of
     ancillary chunks - every file a deflater makes of an H x W x C image fits, a file with more metadata needs the argument"""
@@ -86,163 +69,69 @@ def parse_png(data):
     """the host parse of one file as a dict (no device needed): size, channels, bit depth, colour type, the zlib header's two
     bytes, the Adler-32 that ends the joined IDAT bodies, their byte count and the bodies [(first byte, end byte)].  Every
     chunk's CRC-32 is verified.  Raises what ``PngDecoder.decode`` raises for a refused file."""
-    a = _as_bytes_array(data, "parse_png")
+    a = as_bytes_array(data, "parse_png")
     lib = _lib.load()
     info = PngInfo()
     src = a.ctypes.data_as(ctypes.c_void_p)
     if lib.sfh_png_parse(src, a.size, ctypes.byref(info), None, 0) != 0:
-        _refuse(info.reason, "parse_png")
+        refuse(REASONS, info.reason, "parse_png")
     ranges = np.zeros((info.nidat, 2), dtype=np.int32)
     if lib.sfh_png_parse(src, a.size, ctypes.byref(info), ranges.ctypes.data_as(ctypes.c_void_p), info.nidat) != 0:
-        _refuse(info.reason, "parse_png")
+        refuse(REASONS, info.reason, "parse_png")
     return {"width": info.width, "height": info.height, "channels": info.channels, "bit_depth": info.bit_depth,
             "color_type": info.color_type, "interlace": info.interlace, "nidat": info.nidat, "idat_bytes": info.idat_bytes,
             "cmf": info.cmf, "flg": info.flg, "adler": int(info.adler), "idat": [(int(a0), int(a1)) for a0, a1 in ranges]}
 
 
-class PngDecoder:
+class PngDecoder(BatchDecoder):
     """Decoder of batches of up to ``batch`` PNG files of H x W pixels and ``channels`` (1 | 3 | 4) channels; owns the pinned
     staging buffer, its device copy, the scratch, the images and the per-image results - every buffer is allocated once, and the
     images ``decode`` returns without ``out`` are valid until the next call.  bgr: 3- and 4-channel images come out BGR(A) in
-    memory (cv2's convention, like ``outputs.decode_png``); False for the file's order."""
+    memory (cv2's convention, like ``outputs.decode_png``); False for the file's order.
+
+    ``stage`` verifies every chunk's CRC-32.  ``decode_staged``: one small memset and 5 launches on the current stream, 10 when
+    a file of the batch has more than one IDAT chunk.  ``status`` bits: 1 (an over-subscribed or incomplete code-length set, or
+    none for end-of-block), 2 (symbols 286 / 287, distance codes 30 / 31, bits that are no code, block type 3), 4 (a distance
+    beyond the bytes produced), 8 (a stored block with LEN != ~NLEN), 16 (output short of or beyond H (1 + W C)), 32 (the bits
+    end early), 64 (a filter byte above 4), 128 (an Adler-32 mismatch)."""
+    NAME, REASONS, batch_type = "png", REASONS, PngBatch
+    CHANNELS, LIMITS = (1, 3, 4), "1, 3 or 4 channels"
+    MIN_FILE_BYTES, CORRUPT = 8, "compressed"
+    default_max_file_bytes = staticmethod(png_file_capacity)
 
     def __init__(self, H, W, channels=1, batch=1, bgr=True, max_file_bytes=None, device="cuda", _serial_only=False):
-        self.H, self.W, self.C, self.B = int(H), int(W), int(channels), int(batch)
-        if self.B < 1:
-            raise ValueError(f"PngDecoder: batch {batch}")
-        if self.C not in (1, 3, 4) or self.H < 1 or self.W < 1:
-            raise ValueError(f"PngDecoder: image {self.W}x{self.H}x{self.C} (1, 3 or 4 channels)")
-        self.max_file_bytes = png_file_capacity(self.H, self.W, self.C) if max_file_bytes is None else int(max_file_bytes)
-        self.bgr = bool(bgr)
         self.serial_only = bool(_serial_only)              # tests: the serial leg on files the segmented leg would take
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError(f"PngDecoder: device {self.device} - the HIP path has no CPU fallback")
-        lib = _lib.load()
-        self.staging_bytes = int(lib.sfh_png_dec_staging_bytes(self.B, self.H, self.W, self.C, self.max_file_bytes))
-        self.scratch_bytes = int(lib.sfh_png_dec_scratch_bytes(self.B, self.H, self.W, self.C))
-        if self.staging_bytes < 0 or self.scratch_bytes < 0:
-            raise ValueError(f"PngDecoder: {self.B} files of {self.W}x{self.H}x{self.C}, at most {self.max_file_bytes} bytes each: "
-                             "refused, or buffers of 2 GiB or more")
-        self.staging = torch.empty(self.staging_bytes, dtype=torch.uint8).pin_memory()
-        self.staged = torch.empty(self.staging_bytes, dtype=torch.uint8, device=self.device)
-        self.scratch = torch.empty(self.scratch_bytes, dtype=torch.uint8, device=self.device)
-        self.out = torch.empty(self._shape(self.B), dtype=torch.uint8, device=self.device)
-        self._status = torch.zeros(self.B, dtype=torch.int32, device=self.device)
+        super().__init__(H, W, channels, batch, bgr, max_file_bytes, device)
         self._segmented = torch.zeros(self.B, dtype=torch.int32, device=self.device)
-        self._uploaded = None                     # event behind the last copy out of the staging buffer
-        self._used = self._n = 0
 
-    def _shape(self, n):
-        return (n, self.H, self.W) + ((self.C,) if self.C > 1 else ())
+    def _sizes(self, lib):
+        return (lib.sfh_png_dec_staging_bytes(self.B, self.H, self.W, self.C, self.max_file_bytes),
+                lib.sfh_png_dec_scratch_bytes(self.B, self.H, self.W, self.C))
 
-    def stage(self, files):
-        """host only: parse the files (every chunk CRC verified) and pack them into the pinned staging buffer -> number of files.
-        Waits for the copy of the previous batch out of that buffer; raises for a refused file, with nothing launched."""
-        if isinstance(files, PngBatch):
-            files = files.to_host()
-        files = [_as_bytes_array(f, "PngDecoder") for f in files]
-        n = len(files)
-        if not 1 <= n <= self.B:
-            raise ValueError(f"PngDecoder: {n} files (1 .. {self.B})")
-        if self._uploaded is not None:
-            self._uploaded.synchronize()
-            self._uploaded = None
-        ptrs = (ctypes.c_void_p * n)(*[f.ctypes.data for f in files])
-        sizes = (ctypes.c_int64 * n)(*[f.size for f in files])
-        reason, index = ctypes.c_int32(0), ctypes.c_int32(-1)
-        used = _lib.load().sfh_png_dec_stage(ptrs, sizes, n, self.H, self.W, self.C, self.max_file_bytes,
-                                             ctypes.c_void_p(self.staging.data_ptr()), self.staging_bytes, ctypes.byref(reason),
-                                             ctypes.byref(index))
-        if used < 0:
-            self._n = 0
-            if reason.value:
-                _refuse(reason.value, "PngDecoder", index.value)
-            _lib.check(-1, "png_dec_stage")
-        self._used, self._n = int(used), n
-        return n
+    def _stage(self, lib, ptrs, sizes, n, reason, index):
+        return lib.sfh_png_dec_stage(ptrs, sizes, n, self.H, self.W, self.C, self.max_file_bytes, ptr(self.staging),
+                                     self.staging_bytes, reason, index)
 
-    def upload(self):
-        """the staged batch -> the device, one non-blocking copy on the current stream"""
-        if self._n == 0:
-            raise RuntimeError("PngDecoder.upload: stage() a batch first")
-        self.staged[:self._used].copy_(self.staging[:self._used], non_blocking=True)
-        self._uploaded = torch.cuda.Event()
-        self._uploaded.record(torch.cuda.current_stream(self.device))
+    def _launch(self, lib, n, out, dev):
+        _lib.check(lib.sfh_png_decode(ptr(self.staging), ptr(self.staged), self.staging_bytes, n, self.H, self.W, self.C,
+                                      int(self.bgr), self.max_file_bytes, int(self.serial_only), ptr(self.scratch),
+                                      self.scratch_bytes, ptr(out), ptr(self._status), ptr(self._segmented), stream(dev)),
+                   "png_decode")
 
-    def _checked_out(self, out, n):
-        want = self._shape(n)
-        if not isinstance(out, torch.Tensor):
-            raise ValueError(f"PngDecoder: out: expected a tensor, got {type(out).__name__}")
-        if out.dtype != torch.uint8:
-            raise ValueError(f"PngDecoder: out: dtype {out.dtype} (uint8 only)")
-        if tuple(out.shape[1:]) != want[1:] or out.dim() != len(want) or out.shape[0] < n:
-            raise ValueError(f"PngDecoder: out: expected ({n}+,{','.join(map(str, want[1:]))}), got {tuple(out.shape)}")
-        if not out.is_contiguous():
-            raise ValueError("PngDecoder: out: expected a contiguous tensor")
-        if out.device != self.staged.device:
-            raise RuntimeError(f"PngDecoder: out on {out.device}, the decoder on {self.staged.device}")
-        return out
-
-    def decode_staged(self, out=None):
-        """the uploaded batch -> images (n,H,W[,C]): one small memset and 5 launches on the current stream, 10 when a file of
-        the batch has more than one IDAT chunk"""
-        n = self._n
-        if n == 0:
-            raise RuntimeError("PngDecoder.decode_staged: stage() and upload() a batch first")
-        out = self.out if out is None else self._checked_out(out, n)
-        dev = self.device
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().sfh_png_decode(ctypes.c_void_p(self.staging.data_ptr()), _ptr(self.staged), self.staging_bytes, n,
-                                                  self.H, self.W, self.C, int(self.bgr), self.max_file_bytes, int(self.serial_only),
-                                                  _ptr(self.scratch), self.scratch_bytes, _ptr(out), _ptr(self._status),
-                                                  _ptr(self._segmented), _stream(dev)), "png_decode")
-        return out[:n]
-
-    def decode(self, files, out=None):
-        """files: a list of b <= batch files (bytes or 1-D uint8 arrays) or a PngBatch -> uint8 (b,H,W[,C]) images on the GPU.
-        out: a contiguous uint8 tensor of that shape (or with more images) to decode into.  Everything wrong with the files'
-        chunks or with ``out`` raises before anything is launched."""
-        if out is not None:
-            n = len(files.sizes) if isinstance(files, PngBatch) else len(files)
-            self._checked_out(out, n)
-        self.stage(files)
-        self.upload()
-        return self.decode_staged(out)
-
-    @property
-    def status(self):
-        """int32 (b) of the last call: 0, or the OR of 1 (an over-subscribed or incomplete code-length set, or none for
-        end-of-block), 2 (symbols 286 / 287, distance codes 30 / 31, bits that are no code, block type 3), 4 (a distance beyond
-        the bytes produced), 8 (a stored block with LEN != ~NLEN), 16 (output short of or beyond H (1 + W C)), 32 (the bits end
-        early), 64 (a filter byte above 4), 128 (an Adler-32 mismatch) - such an image came back as zeros.  Synchronises."""
-        return self._status[:self._n].cpu().numpy()
+    @staticmethod
+    def _head(f):
+        head = parse_png(f)
+        return head["height"], head["width"], head["channels"]
 
     def segmented(self):
         """bool (b) of the last call: whether the image's filtered stream came from the segmented leg.  Synchronises."""
         return self._segmented[:self._n].cpu().numpy().astype(bool)
 
 
-def _file_list(file_or_files):
-    single = isinstance(file_or_files, (bytes, bytearray, memoryview, np.ndarray))
-    if single:
-        return [file_or_files], True
-    return (file_or_files.to_host() if isinstance(file_or_files, PngBatch) else list(file_or_files)), False
-
-
 def decode_png_device(file_or_files, bgr=True, device="cuda"):
     """One-off: one file (bytes or a 1-D uint8 array) -> a uint8 GPU tensor (H,W) or (H,W,3|4); a list of files or a PngBatch
     -> (B,H,W[,C]).  The size and the channels are read from the first file.  Raises RuntimeError when an image has a status."""
-    files, single = _file_list(file_or_files)
-    if not files:
-        raise ValueError("decode_png_device: no files")
-    head = parse_png(files[0])
-    dec = PngDecoder(head["height"], head["width"], head["channels"], len(files), bgr=bgr,
-                     max_file_bytes=max(max(len(f) for f in files), 8), device=device)
-    images = dec.decode(files)
-    if dec.status.any():
-        raise RuntimeError(f"decode_png_device: corrupt compressed data, status {dec.status.tolist()}")
-    return images[0] if single else images
+    return PngDecoder.decode_once("decode_png_device", file_or_files, bgr=bgr, device=device)
 
 
 def masks_from_files(files, device):

@@ -18,22 +18,13 @@ others wait for.
 Stated deviation: the files are 1.3-2.2x the size of ``outputs.encode_png``'s (zlib level 1) on label maps and raw-sized
 (+ 0.4-0.8 %) on photographs and noise - dynamic Huffman tables and matches beyond distance 1 are not built.
 """
-import ctypes
-
 import numpy as np
 import torch
 
 from . import _lib
+from ._codec import BatchEncoder, PngBatch, as_image_batch, ptr, split_files, stream  # noqa: F401 (re-exported)
 
 MAX_ROW = 32768
-
-
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
 
 
 def png_capacity(H, W, C):
@@ -49,108 +40,25 @@ def png_capacity(H, W, C):
     return int(cap)
 
 
-def split_files(data, offsets, sizes):
-    """host bytes (1-D uint8 array), offsets (B+1) and sizes (B) -> list of B 1-D uint8 arrays (copies)"""
-    return [np.array(data[int(o):int(o) + int(n)], dtype=np.uint8) for o, n in zip(offsets[:-1], sizes)]
-
-
-class PngBatch:
-    """the encoded files of one batch on the device: ``data`` uint8, file b = data[offsets[b] : offsets[b] + sizes[b]]"""
-
-    def __init__(self, data, offsets, sizes):
-        self.data, self.offsets, self.sizes = data, offsets, sizes
-
-    def to_host(self):
-        """-> list of B 1-D uint8 numpy arrays (the type ``outputs.encode_png`` returns); synchronises"""
-        off = self.offsets.cpu().numpy()
-        sizes = self.sizes.cpu().numpy()
-        data = self.data[:int(off[-1])].cpu().numpy()
-        return split_files(data, off, sizes)
-
-
-class BatchEncoder:
-    """what the device encoders (PngEncoder, sfh_amd.jpegenc.JpegEncoder) share: the output buffers and the refusals of
-    ``encode``'s argument.  A subclass sets H, W, C, B, capacity, device and ``batch_type``."""
-    batch_type = PngBatch
-
-    def new_output(self):
-        return self.batch_type(torch.empty(self.B * self.capacity, dtype=torch.uint8, device=self.device),
-                               torch.empty(self.B + 1, dtype=torch.int64, device=self.device),
-                               torch.empty(self.B, dtype=torch.int32, device=self.device))
-
-    def _checked(self, images):
-        """-> the number of images.  What is wrong with the tensor itself (type, dtype, shape, contiguity) is a ValueError
-        wherever the tensor lies; a well-formed tensor that is not on the GPU is the RuntimeError of every HIP path."""
-        who = type(self).__name__
-        if not isinstance(images, torch.Tensor):
-            raise ValueError(f"{who}: expected a tensor, got {type(images).__name__}")
-        if images.dtype != torch.uint8:
-            raise ValueError(f"{who}: dtype {images.dtype} (uint8 only)")
-        want = (self.H, self.W) if self.C == 1 else (self.H, self.W, 3)
-        shape = tuple(images.shape)
-        if self.C == 1 and len(shape) == 4 and shape[3] == 1:
-            shape = shape[:3]
-        if len(shape) != len(want) + 1 or shape[1:] != want or not 1 <= shape[0] <= self.B:
-            raise ValueError(f"{who}: expected (b,{','.join(map(str, want))}) with b <= {self.B}, got {tuple(images.shape)}")
-        if not images.is_contiguous():
-            raise ValueError(f"{who}: expected a contiguous tensor")
-        if images.device.type != "cuda":
-            raise RuntimeError(f"{who}: device {images.device} - the HIP path has no CPU fallback")
-        return shape[0]
-
-
-def as_image_batch(t, who):
-    """how the one-off entry points read a tensor -> (batch tensor, channels, whether it was ONE image): a 2-D tensor and a 3-D
-    tensor whose last dimension is 3 are one image, any other 3-D tensor a batch of gray images, a 4-D tensor (B,H,W,1|3) a
-    batch"""
-    if not isinstance(t, torch.Tensor):
-        raise ValueError(f"{who}: expected a tensor, got {type(t).__name__}")
-    if t.dtype != torch.uint8:
-        raise ValueError(f"{who}: dtype {t.dtype} (uint8 only)")
-    single = t.dim() == 2 or (t.dim() == 3 and t.shape[2] == 3)
-    batch = t[None] if single else t
-    if batch.dim() == 3:
-        return batch, 1, single
-    if batch.dim() == 4 and batch.shape[3] in (1, 3):
-        return batch, int(batch.shape[3]), single
-    raise ValueError(f"{who}: shape {tuple(t.shape)}")
-
-
 class PngEncoder(BatchEncoder):
     """Encoder of batches of up to ``batch`` H x W images of ``channels`` (1 | 3) channels; owns the scratch, output, sizes and
     offsets buffers (``encode`` reuses them: a PngBatch is valid until the next call without ``out``).  bgr: 3-channel
     tensors are BGR in memory (cv2's convention, like ``outputs.encode_png``); False for RGB tensors."""
 
-    def __init__(self, H, W, channels=1, batch=1, bgr=True, compact=True, device="cuda"):
-        self.H, self.W, self.C, self.B = int(H), int(W), int(channels), int(batch)
-        if self.B < 1:
-            raise ValueError(f"PngEncoder: batch {batch}")
-        self.capacity = png_capacity(self.H, self.W, self.C)
-        self.bgr, self.compact = bool(bgr), bool(compact)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError(f"PngEncoder: device {self.device} - the HIP path has no CPU fallback")
-        self.scratch_bytes = int(_lib.load().sfh_png_scratch_bytes(self.B, self.H, self.W, self.C))
-        if self.scratch_bytes < 0 or self.capacity * self.B >= 2 ** 31:
-            raise ValueError(f"PngEncoder: {self.B} images of {self.W}x{self.H}x{self.C}: encoded batch of 2 GiB or more")
-        self.scratch = torch.empty(self.scratch_bytes, dtype=torch.uint8, device=self.device)
-        self.out = self.new_output()
+    capacity_of = staticmethod(png_capacity)
 
-    def encode(self, images_u8, out=None):
-        """images_u8: uint8 (b,H,W[,3]) on the GPU, b <= batch -> PngBatch (of b files: offsets[:b+1], sizes[:b])"""
-        b = self._checked(images_u8)
-        out = self.out if out is None else out
+    def __init__(self, H, W, channels=1, batch=1, bgr=True, compact=True, device="cuda"):
+        super().__init__(H, W, channels, batch, bgr, compact, device)
+
+    def scratch_bytes_of(self, lib):
+        return lib.sfh_png_scratch_bytes(self.B, self.H, self.W, self.C)
+
+    def _launch(self, images_u8, b, out, dev):
         lib = _lib.load()
-        dev = images_u8.device
-        with torch.cuda.device(dev):
-            _lib.check(lib.sfh_png_encode(_ptr(images_u8), b, self.H, self.W, self.C, int(self.bgr), _ptr(self.scratch),
-                                          self.scratch_bytes, _stream(dev)), "png_encode")
-            _lib.check(lib.sfh_png_pack(_ptr(self.scratch), self.scratch_bytes, b, self.H, self.W, self.C, int(self.compact),
-                                        _ptr(out.data), out.data.numel(), _ptr(out.offsets), _ptr(out.sizes), _stream(dev)),
-                       "png_pack")
-        if b == self.B:
-            return out
-        return PngBatch(out.data, out.offsets[:b + 1], out.sizes[:b])
+        _lib.check(lib.sfh_png_encode(ptr(images_u8), b, self.H, self.W, self.C, int(self.bgr), ptr(self.scratch),
+                                      self.scratch_bytes, stream(dev)), "png_encode")
+        _lib.check(lib.sfh_png_pack(ptr(self.scratch), self.scratch_bytes, b, self.H, self.W, self.C, int(self.compact),
+                                    ptr(out.data), out.data.numel(), ptr(out.offsets), ptr(out.sizes), stream(dev)), "png_pack")
 
 
 def encode_png_device(img_or_batch, bgr=True):

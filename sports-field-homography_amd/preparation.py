@@ -38,7 +38,6 @@ Stated deviations from the reference:
 * the UV label is written as ``<name>.npy`` (uint16 (H,W,3)); a 16-bit TIFF writer is out of scope;
 * frames with fewer than 4 usable points (the reference's ``return None``) get status 0 and are reported, never written.
 """
-import ctypes
 import json
 import os
 
@@ -47,6 +46,7 @@ import torch
 
 from . import _lib
 from . import outputs as O
+from ._codec import ptr as _ptr, stream as _stream
 from .pngenc import files_from_batch
 
 FOOTBALL_PITCH_IGNORE_POINTS = (12, 13, 16, 19, 20)      # dataset_utils/preparation.py:27
@@ -181,9 +181,9 @@ class LabelMaker:
                "reproj_mse": torch.empty((B,), dtype=torch.float64, device=dev),
                "status": torch.empty((B,), dtype=torch.int32, device=dev)}
         lib = _lib.load()
-        p = O._ptr
+        p = _ptr
         with torch.cuda.device(dev):
-            st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            st = _stream(dev)
             _lib.check(lib.sfh_prep_fit(p(d["poi"]), p(m), p(d["ignore"]), B, N, self.norm_size[0], self.norm_size[1],
                                         self.refine if refine is None else int(refine), p(out["theta_c2f"]), p(out["theta"]),
                                         p(out["theta_f32"]), p(out["poi"]), p(out["num_nonzero"]), p(out["reproj_mse"]),
@@ -204,9 +204,9 @@ class LabelMaker:
         if want_uv:
             out["uv"] = torch.empty((B, self.H, self.W, 3), dtype=torch.uint16, device=dev)
         lib = _lib.load()
-        p = O._ptr
+        p = _ptr
         with torch.cuda.device(dev):
-            st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            st = _stream(dev)
             _lib.check(lib.sfh_prep_render(p(theta), p(d["ids"]), int(self.court_ids.shape[0]), int(self.court_ids.shape[1]),
                                            p(d["u"]), p(d["v"]), B, self.H, self.W, 1 if want_uv else 0, p(out["mask"]),
                                            p(out.get("uv")), st), "prep_render")
@@ -231,8 +231,8 @@ def rgb_to_ids(rgb, num_classes):
         raise RuntimeError(f"rgb_to_ids: device {rgb.device} - the HIP path has no CPU fallback")
     out = torch.empty(rgb.shape[:-1], dtype=torch.uint8, device=rgb.device)
     with torch.cuda.device(rgb.device):
-        st = ctypes.c_void_p(torch.cuda.current_stream(rgb.device).cuda_stream)
-        _lib.check(_lib.load().sfh_prep_rgb_to_ids(O._ptr(rgb), out.numel(), int(num_classes), O._ptr(out), st), "prep_rgb_to_ids")
+        st = _stream(rgb.device)
+        _lib.check(_lib.load().sfh_prep_rgb_to_ids(_ptr(rgb), out.numel(), int(num_classes), _ptr(out), st), "prep_rgb_to_ids")
     return out
 
 

@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._codec import ptr as _ptr, stream as _stream
 
 FILTERS = {"box": 4, "bilinear": 2, "bicubic": 3}         # Pillow's numbering
 NEAREST_RULES = {"pil": 0, "cv2": 1}
@@ -32,14 +33,6 @@ MAX_TAPS = 64                                             # SFH_RESAMPLE_MAX_TAP
 
 _TABS = {}
 _NEAREST_TABS = {}
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def _filter_code(name):

@@ -35,10 +35,8 @@ import torch
 
 from . import _lib
 from . import outputs as O
-from .jpegenc import image_files_from_batch
 from . import pngdec
-from .jpegdec import frames_from_files
-from .engine import _ptr
+from ._codec import frames_from_files, image_files_from_batch, ptr as _ptr, stream as _stream
 
 SOURCES = {"auto": 0, "warp": 1, "segm": 2}     # SFH_OVERLAY_AUTO / WARP / SEGM
 LABEL_MAX = 32                                  # SFH_OVERLAY_LABEL_MAX
@@ -201,7 +199,7 @@ class OverlayRenderer:
                 raise ValueError(f"poi: expected a contiguous float32 tensor ({B},N,2) on {dev}")
         lib = _lib.load()
         with torch.cuda.device(dev):
-            stp = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            stp = _stream(dev)
             _lib.check(lib.sfh_overlay_render(_ptr(frames_u8), _ptr(out), B, H, W, _ptr(theta), _ptr(tmpl), bstride, ht, wt,
                                               float(self.mask_classes), _ptr(segm), kind, nc, hs, ws, _ptr(score),
                                               self.score_threshold, src, 0 if self.overlay_threshold is None else 1,
@@ -273,10 +271,8 @@ def visualize(frames, preds_path, dst_dir, court_img, masks_path=None, mask_clas
 
     def flush(chunk, first):
         B = len(chunk)
-        if frames_format == "jpeg":
-            fr = frames_from_files(chunk, device)     # decoded on the GPU (sfh_amd.jpegdec): only the files are uploaded
-        elif frames_format == "png":
-            fr = pngdec.frames_from_files(chunk, device)
+        if frames_format != "array":              # decoded on the GPU (sfh_amd.jpegdec, pngdec): only the files are uploaded
+            fr = frames_from_files(chunk, device, frames_format)
         else:
             fr = torch.from_numpy(np.ascontiguousarray(np.stack(chunk))).to(device)
         keys = pred_names[first:first + B]

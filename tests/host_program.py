@@ -1,0 +1,26 @@
+"""The stand-alone host programs of the decode cores (tests/*_host_main.cpp, which include csrc/*_core.h): found compiler and the
+sanitizer build that tests/test_jpegdec_host.py and tests/test_pngdec_host.py share.  A plain module, imported by both."""
+import os
+import shutil
+import subprocess
+
+from conftest import ROOT
+
+
+def clangxx():
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    near = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(hipcc))), "lib", "llvm", "bin", "clang++")
+    for c in (shutil.which("clang++"), near, "/opt/rocm/lib/llvm/bin/clang++", "/opt/rocm/llvm/bin/clang++"):
+        if c and os.path.exists(c):
+            return c
+    raise AssertionError("no clang++ on this machine (looked on PATH and next to hipcc)")
+
+
+def build_host_program(tmp_path_factory, name):
+    """tests/<name>_host_main.cpp -> a stand-alone executable under AddressSanitizer and UBSan, warnings as errors"""
+    out = str(tmp_path_factory.mktemp(f"{name}_host") / f"{name}_host_main")
+    cmd = [clangxx(), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-Wall",
+           "-Werror", os.path.join(ROOT, "tests", f"{name}_host_main.cpp"), "-o", out]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout + r.stderr
+    return out

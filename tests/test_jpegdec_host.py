@@ -5,8 +5,6 @@ undefined-behaviour sanitizers, gives the restatement's coefficients on well-for
 All comparisons are equality."""
 import functools
 import io
-import os
-import shutil
 import subprocess
 
 import numpy as np
@@ -15,7 +13,7 @@ from PIL import Image
 
 import jpegdec_cases as DC
 import jpegdec_ref as R
-from conftest import ROOT
+from host_program import build_host_program
 
 SMALL = sorted(DC.small_files())
 TEMPLATES = sorted(DC.template_files())
@@ -209,23 +207,9 @@ def test_subsequence_iteration_equals_serial_decode(subseq_bits):
 
 # ------------------------------------------------------------------------------------------------------------ the stand-alone program
 
-def _clangxx():
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    near = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(hipcc))), "lib", "llvm", "bin", "clang++")
-    for c in (shutil.which("clang++"), near, "/opt/rocm/lib/llvm/bin/clang++", "/opt/rocm/llvm/bin/clang++"):
-        if c and os.path.exists(c):
-            return c
-    raise AssertionError("no clang++ on this machine (looked on PATH and next to hipcc)")
-
-
 @pytest.fixture(scope="module")
 def host_program(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("jpegdec_host") / "jpegdec_host_main")
-    cmd = [_clangxx(), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-Wall",
-           "-Werror", os.path.join(ROOT, "tests", "jpegdec_host_main.cpp"), "-o", out]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout + r.stderr
-    return out
+    return build_host_program(tmp_path_factory, "jpegdec")
 
 
 def _run(program, paths, subseq_bits):

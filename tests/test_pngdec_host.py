@@ -3,8 +3,6 @@ the library's host parse equals a restated parse field by field; every refusal f
 (csrc/pngdec_core.h), built as a stand-alone program under the address and undefined-behaviour sanitizers, gives zlib's filtered
 stream, decode_png's pixels and the expected acceptance decision on well-formed files, and a clean run on corrupt ones.
 All comparisons are equality."""
-import os
-import shutil
 import struct
 import subprocess
 import zlib
@@ -15,7 +13,7 @@ import pytest
 from PIL import Image
 
 import pngdec_cases as PC
-from conftest import ROOT
+from host_program import build_host_program
 
 FILES = PC.all_files()
 NAMES = sorted(FILES)
@@ -248,23 +246,9 @@ def test_decoder_refuses_cpu_device():
 
 # ------------------------------------------------------------------------------------------------------------ the stand-alone program
 
-def _clangxx():
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    near = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(hipcc))), "lib", "llvm", "bin", "clang++")
-    for c in (shutil.which("clang++"), near, "/opt/rocm/lib/llvm/bin/clang++", "/opt/rocm/llvm/bin/clang++"):
-        if c and os.path.exists(c):
-            return c
-    raise AssertionError("no clang++ on this machine (looked on PATH and next to hipcc)")
-
-
 @pytest.fixture(scope="module")
 def host_program(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("pngdec_host") / "pngdec_host_main")
-    cmd = [_clangxx(), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-Wall",
-           "-Werror", os.path.join(ROOT, "tests", "pngdec_host_main.cpp"), "-o", out]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout + r.stderr
-    return out
+    return build_host_program(tmp_path_factory, "pngdec")
 
 
 def _run(program, tmp_path, files):
