@@ -31,7 +31,7 @@ for it in range(int(sys.argv[1]) if len(sys.argv) > 1 else 40):
     tape.add_grad(y, dys.clone())
     tape.backward()
     torch.cuda.synchronize()
-    cur = {"y": y.clone(), "dx": tape.pop_grad(xs).clone(), **{k: v.clone() for k, v in tape.param_grads.items()}}
+    cur = {"y": tape.f32(y).clone(), "dx": tape.pop_grad(xs).clone(), **{k: v.clone() for k, v in tape.param_grads.items()}}
     if ref is None:
         ref = cur
         continue

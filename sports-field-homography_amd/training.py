@@ -14,8 +14,9 @@ B*H*W pixels) fit fp16's exponent range, and a step whose activations or gradien
 bf16x6 from the same BatchNorm statistics (TrainStep; under the autograd node a gradient overflow raises
 FP16RangeError); ``bf16x6`` - three bf16 planes, six products; ``fp32`` - fp32 MFMA kernels throughout.  The first
 layer, the stem and the other backward-filter shapes (``sfh_conv_wgrad``) are fp32 MFMA in every mode.  A tape of
-closures records the backward of each layer; gradients of activations are keyed by tensor identity and accumulated
-with ``sfh_slice_add``.  PyTorch provides memory, streams and the autograd hook (``torch.autograd.Function``) only.
+closures records the backward of each layer; an activation's tensors, gradient and BatchNorm bookkeeping are one
+record (``Act``), gradients are accumulated with ``sfh_slice_add``.  PyTorch provides memory, streams and the autograd
+hook (``torch.autograd.Function``) only.
 """
 import ctypes
 import os
@@ -156,37 +157,63 @@ def _warn_range_fallback():
                       "with bf16x6 (set SFH_TRAIN_PRECISION=bf16x6 to avoid the double work)")
 
 
-class Tape:
-    """Backward closures in forward order + gradients of activations by tensor identity."""
+class Act:
+    """One activation of a training pass and everything the backward pass keeps about it.
+    shape (B, H, W, C) | f32: the NHWC fp32 tensor, None when only the split copy was written | split: the S3 / H2 copy,
+    None until something asks for it (Tape.s3) | grad: the gradient accumulated so far | bn: (z, mi, bn) of the
+    BatchNorm + ReLU layer (no residual) that produced it, sole: ONE conv consumes it - that conv's backward-data launch
+    leaves the layer's backward sums in sums_table (sfh_conv_desc.bwd_z), void once a second gradient arrives | sums:
+    fp64 [sum g | sum g * xhat], taken by the pass that completed the gradient (a gradient arriving later is an
+    ordering bug)."""
+    __slots__ = ("shape", "f32", "split", "grad", "bn", "sole", "sums_table", "sums", "__weakref__")
 
-    def __init__(self, fmt="env", options=None):
+    def __init__(self, shape, f32=None, split=None, bn=None, sole=False):
+        self.shape, self.f32, self.split, self.bn, self.sole = tuple(shape), f32, split, bn, sole
+        self.grad = self.sums_table = self.sums = None
+
+    @property
+    def device(self):
+        return (self.f32 if self.f32 is not None else self.split).device
+
+    def need_f32(self, who):
+        """the fp32 tensor, for a kernel of `who` that reads it (the one way to a pointer of an activation's values)"""
+        if self.f32 is None:
+            raise RuntimeError(f"{who}: the activation has no fp32 storage (only its split copy was written) but this "
+                               "kernel reads fp32")
+        return self.f32
+
+    def permute(self, *dims):
+        """the fp32 values as a permuted view (callers that read a layer's output as an NHWC tensor)"""
+        return self.need_f32("Act.permute").permute(*dims)
+
+
+class Tape:
+    """Backward closures in forward order + the activations (Act) that crossed the public boundary as plain tensors."""
+
+    def __init__(self, fmt="env", options=None, gshift=0):
         self.options = options if options is not None else Options()     # (None: the defaults, not the environment)
         self.ops = []
-        self.grads = {}
+        self.resnet_start = None   # index in ops of the first ResNet closure (ResNetTrainer.forward)
+        # tensor identity -> Act, for the tensors handed in or out as plain tensors (input frames, stn_in, the NCHW head
+        # outputs, theta, what tests pass): act.f32 IS that tensor, so its identity cannot be recycled while the entry lives
+        self._acts = {}
         self.param_grads = {}
         self.lib = _lib.load()
         self.fmt = _train_fmt() if fmt == "env" else fmt            # "s3" | "h2" | None
         self.use_s3 = self.fmt is not None
         self.fmt_code = {"s3": _lib.FMT_S3, "h2": _lib.FMT_H2}.get(self.fmt, _lib.FMT_F32)
-        self._s3 = {}
-        self.no_f32 = set()   # ids of activation handles without fp32 storage (conv_bn_act(f32_out=False))
-        # BatchNorm + ReLU layers whose output has ONE consumer (the next conv): id(y) -> {z, mi, bn}; that conv's
-        # backward-data launch leaves the layer's backward sums in entry["table"] (sfh_conv_desc.bwd_z)
-        self.single_consumer = {}
-        # id(y) -> fp64 [sum g | sum g * xhat] of a BatchNorm + ReLU layer whose total gradient is complete and whose sums
-        # were taken by the pass that completed it (pool_backward_fused); a later add_grad to y is an ordering bug
-        self.bwd_sums = {}
-        # id(y) -> {z, mi, bn} of every BatchNorm + ReLU layer without a residual (consumers that complete y's gradient use it to
-        # take the backward sums on the way: out_conv)
-        self.bn_layers = {}
         # f16x3 (H2 copies of activations and gradients): fp16's exponent range has to hold them.
         #   overflow - device word the kernels raise when a value does not fit (checked at the end of the backward pass);
         #   gscale   - power of two all gradients are carried with (the losses are means over B*H*W pixels, their
         #              gradients ~1e-7: far below fp16's range); chosen by run_backward from the largest seed gradient
-        #              (one read-back per step) and divided out of the parameter gradients at its end;
+        #              (one read-back per step, or on the device: gscale_dev = [S, 1 / S]) and divided out of the
+        #              parameter gradients at its end;
+        #   gshift   - power of two that choice is lowered by (TrainStep, after a gradient overflow);
         #   wexp     - per conv weight: exponent of its H2 planes, from ONE batched max over the parameters per step
         self.overflow = None
         self.gscale = 1.0
+        self.gscale_dev = None
+        self.gshift = int(gshift)
         self.wexp = {}
         self.order = E.LaunchOrder()
         self._arena = {}      # dtype -> [zero-filled buffer, next free element]
@@ -208,16 +235,26 @@ class Tape:
         cur[1] += (n + 63) & ~63          # 256- / 512-byte aligned slices
         return out
 
+    def act(self, t):
+        """the Act of t: t itself, or the (memoised) wrapper of a plain tensor"""
+        if isinstance(t, Act):
+            return t
+        a = self._acts.get(id(t))
+        if a is None:
+            a = self._acts[id(t)] = Act(t.shape, f32=t)
+        return a
+
     def s3(self, t):
-        """split copy (S3 or H2, the tape's format) of an NHWC activation (converted once, kept while the tape lives)"""
-        v = self._s3.get(id(t))
-        if v is None:
-            v = self._s3[id(t)] = (t, E.f32_to_split(t, self.fmt, self.overflow))
-        return v[1]
+        """split copy (S3 or H2, the tape's format) of an NHWC activation (converted once, kept while the activation lives)"""
+        a = self.act(t)
+        if a.split is None:
+            a.split = E.f32_to_split(a.need_f32("Tape.s3"), self.fmt, self.overflow)
+        return a.split
 
     def f32(self, t):
-        """fp32 NHWC values of an activation of this pass, also when only its split copy was written (a handle)"""
-        return E.s3_to_f32(self._s3[id(t)][1]) if id(t) in self.no_f32 else t
+        """fp32 NHWC values of an activation of this pass, also when only its split copy was written"""
+        a = self.act(t)
+        return a.f32 if a.f32 is not None else E.s3_to_f32(a.split)
 
     def prepare_h2(self, net, n_pixels):
         """H2 mode: gradient scale for n_pixels = B*H*W and the weight exponents of all conv weights (one sync)."""
@@ -230,7 +267,7 @@ class Tape:
         ws = [p for p in net.parameters() if p.dim() == 4]
         # one launch over all conv weights + one read-back (sfh_multi_absminmax)
         ex = E.weight_exps([w.detach() for w in ws])      # (raises on a non-finite weight)
-        self.wexp.update((id(w), ex[w.data_ptr()]) for w in ws)
+        self.wexp.update(ex)                              # (keyed by the weight's address)
 
     def mark_forward_done(self):
         """H2: remember (on the device, no synchronisation) whether anything overflowed up to here"""
@@ -239,35 +276,52 @@ class Tape:
                                                  _stream()), "copy2d_words")
 
     def wexp_of(self, param):
-        return self.wexp.get(id(param)) if self.fmt == "h2" else None
+        return self.wexp.get(param.data_ptr()) if self.fmt == "h2" else None
 
     def push(self, fn):
         self.ops.append(fn)
 
     def add_grad(self, t, g):
         """grad[t] += g (g has t's shape; ownership of g passes to the tape)."""
-        if id(t) in self.bwd_sums:
+        a = self.act(t)
+        if a.sums is not None:
             raise RuntimeError("Tape.add_grad: a gradient arrived after the layer's BatchNorm sums were taken")
-        cur = self.grads.get(id(t))
-        if cur is None:
-            self.grads[id(t)] = g
+        if tuple(g.shape) != a.shape:
+            raise RuntimeError(f"Tape.add_grad: a gradient of shape {tuple(g.shape)} for an activation of shape {a.shape}")
+        if a.grad is None:
+            a.grad = g
             return
-        ent = self.single_consumer.get(id(t))
-        if ent is not None:
-            ent.pop("table", None)   # a second gradient arrives: the sums of the first are not the layer's
+        a.sums_table = None   # a second gradient arrives: the sums of the first are not the layer's
         B, H, W, C = g.shape
-        _lib.check(self.lib.sfh_slice_add(_ptr(g), H, W, C, 0, 0, 0, _ptr(cur), B, H, W, C, 1, _stream()), "slice_add")
+        _lib.check(self.lib.sfh_slice_add(_ptr(g), H, W, C, 0, 0, 0, _ptr(a.grad), B, H, W, C, 1, _stream()), "slice_add")
 
     def pop_grad(self, t):
-        return self.grads.pop(id(t), None)
+        a = self.act(t)
+        g, a.grad = a.grad, None
+        return g
 
     def peek_grad(self, t):
-        return self.grads.get(id(t))
+        return self.act(t).grad
 
-    def backward(self):
-        for fn in reversed(self.ops):
+    def backward(self, heads=()):
+        """run the closures, last pushed first.  heads [(output tensor, backward fn of its gradient)]: run between the
+        ResNet's closures (whose stem adds its gradient into the heads') and the UNet's"""
+        ops, self.ops = self.ops, []
+        k = self.resnet_start if self.resnet_start is not None else len(ops)
+        for fn in reversed(ops[k:]):
             fn()
-        self.ops = []
+        for t, bwd in heads:
+            bwd(self.pop_grad(t))
+        for fn in reversed(ops[:k]):
+            fn()
+
+    def release(self):
+        """drop the closures and the boundary memo: after it no Act, conv output or split copy is reachable from the tape
+        (the closures reference the tape and the tape the closures - without this the activations would live until the
+        next garbage collection)"""
+        self.ops, self.param_grads = [], {}
+        self.resnet_start = None
+        self._acts.clear()
 
 
 # --------------------------------------------------------------------------------------- layers
@@ -283,11 +337,19 @@ S2D_ROWS = 32
 STATS_ROWS = 2048   # most rows of the table a conv epilogue adds its per-wave BatchNorm sums into (sfh_conv_desc.stats_partial)
 
 
+def stats_rows(npix):
+    """rows of that table for a launch over npix pixels: about a quarter as many as pixel tiles, a power of two"""
+    rows = 64
+    while rows < STATS_ROWS and rows * 1024 < npix:
+        rows *= 2
+    return rows
+
+
 def _bn_forward(lib, z, bn, relu, residual, tape, want_s3=True, want_f32=True, stats=None, pool=False):
     """Batch-statistics BatchNorm (+residual) (+ReLU); updates the running stats in place.  In split-operand mode
     (and want_s3) the split copy the next convolution needs is written by the same kernel.  want_f32=False (with a
-    split copy): nobody reads the fp32 values - the returned tensor is a handle (shape + identity for the tape,
-    no storage behind it) and the kernel writes a third less."""
+    split copy): nobody reads the fp32 values - the returned Act has f32 = None and the kernel writes a third less.
+    -> (y, mi, maxpool2(y) with pool or None); y and the pooled tensor are Acts."""
     B, H, W, C = z.shape
     npix = B * H * W
     mi = _empty((2 * C,), z)
@@ -306,7 +368,7 @@ def _bn_forward(lib, z, bn, relu, residual, tape, want_s3=True, want_f32=True, s
         _lib.check(lib.sfh_bn_finalize(_ptr(acc), npix, C, float(bn.eps), BN_MOMENTUM, _ptr(bn.running_mean),
                                        _ptr(bn.running_var), _ptr(mi), _ptr(nbt), _stream()), "bn_finalize")
     if pool:
-        # y and maxpool2(y) in the split format only, from one pass over z (both come back as handles without fp32 storage)
+        # y and maxpool2(y) in the split format only, from one pass over z (both come back without fp32 storage)
         if not (relu and residual is None and tape.use_s3 and C % 32 == 0 and H >= 2 and W >= 2):
             raise RuntimeError("_bn_forward(pool=True): needs ReLU, no residual, a split format and C % 32 == 0")
         y_s3 = E.split_empty(tape.fmt, B, H, W, C, z.device)
@@ -314,23 +376,13 @@ def _bn_forward(lib, z, bn, relu, residual, tape, want_s3=True, want_f32=True, s
         _lib.check(lib.sfh_bn_apply_pool(_ptr(z), _ptr(mi), _ptr(bn.weight.detach()), _ptr(bn.bias.detach()), B, H, W, C,
                                          _ptr(y_s3), _ptr(p_s3), tape.fmt_code, _ptr(tape.overflow), _stream()),
                    "bn_apply_pool")
-        y = z.new_empty((1,)).expand(z.shape)
-        pl = z.new_empty((1,)).expand(B, H // 2, W // 2, C)
-        for t, ts in ((y, y_s3), (pl, p_s3)):
-            tape.no_f32.add(id(t))
-            tape._s3[id(t)] = (t, ts)
-        return y, mi, pl
+        return Act(z.shape, split=y_s3), mi, Act((B, H // 2, W // 2, C), split=p_s3)
     y_s3 = E.split_empty(tape.fmt, B, H, W, C, z.device) if (want_s3 and tape.use_s3 and C % 32 == 0) else None
-    handle_only = y_s3 is not None and not want_f32
-    y = z.new_empty((1,)).expand(z.shape) if handle_only else _empty(z.shape, z)
+    y = None if (y_s3 is not None and not want_f32) else _empty(z.shape, z)
     _lib.check(lib.sfh_bn_apply(_ptr(z), _ptr(mi), _ptr(bn.weight.detach()), _ptr(bn.bias.detach()),
-                                _ptr(residual), 1 if relu else 0, npix, C, None if handle_only else _ptr(y), _ptr(y_s3),
+                                _ptr(residual), 1 if relu else 0, npix, C, _ptr(y), _ptr(y_s3),
                                 W, tape.fmt_code, _ptr(tape.overflow), _stream()), "bn_apply")
-    if handle_only:
-        tape.no_f32.add(id(y))
-    if y_s3 is not None:
-        tape._s3[id(y)] = (y, y_s3)
-    return y, mi
+    return Act(z.shape, f32=y, split=y_s3), mi, None
 
 
 def _bn_backward(lib, tape, dy, y, z, mi, bn, relu, want_dres, want_s3=False, want_f32=True, sums_table=None, sums=None,
@@ -415,25 +467,46 @@ class _Names:
         return self.by_id[id(p)]
 
 
+def _backward_data(tape, bd, dz_in, B, H, W, src, s3):
+    """dx = the backward-data conv bd over dz_in.  src (an Act or None): the conv's only source - when it is a
+    BatchNorm + ReLU output that nothing else consumed and no gradient has reached yet, that layer's backward sums ride
+    in this launch and are left in src.sums_table."""
+    bd.order = tape.order
+    dx = _empty((B, H, W, bd.cout), dz_in)
+    if src is not None and src.sole and s3 and bd.stats_ok and bd.cout == src.shape[3] and src.grad is None:
+        z, mi, sb = src.bn
+        table = tape.zeros((stats_rows(B * H * W), 2, bd.cout), dz_in, torch.float64)
+        bd.run(dz_in, B, H, W, dx, stats=table, bwd=(z, mi, sb.weight.detach(), sb.bias.detach()))
+        src.sums_table = table
+    else:
+        bd.run(dz_in, B, H, W, dx)
+    return dx
+
+
 def conv_bn_act(tape, names, conv, bn, srcs, B, H, W, relu=True, residual=None, need_dx=True, s3_out=True,
                 f32_out=True, pool=False):
-    """z = conv(cat(srcs)) + bias; y = [relu](bn_train(z) [+ residual]).
+    """z = conv(cat(srcs)) + bias; y = [relu](bn_train(z) [+ residual]) -> y (an Act).
     f32_out=False: the only consumer of y is a split-operand conv (forward and backward-filter read the split
-    copy): y comes back as a handle without fp32 storage (see _bn_forward).
-    pool=True (split formats, ReLU, no residual): returns (y, maxpool2(y)), both as handles with split copies only,
+    copy): y comes back without fp32 storage (see _bn_forward).
+    pool=True (split formats, ReLU, no residual): returns (y, maxpool2(y)), both with split copies only,
     written by one pass; the max-pool's backward (pushed here, so that it runs right before this layer's) completes
     y's gradient and takes the BatchNorm backward sums in the same pass.
 
-    srcs: [(tensor NHWC, channels used, pad_top, pad_left)], one or two (skip first, like torch.cat
+    srcs: [(Act or NHWC tensor, channels used, pad_top, pad_left)], one or two (skip first, like torch.cat
     in unet/unet_parts.py:67).  Stride-1 3x3 / 1x1 convs, and stride-2 ones via zero-stuffing in the
     backward."""
     lib = tape.lib
     ks, stride = conv.kernel_size[0], conv.stride[0]
     w = conv.weight.detach()
     cout = w.shape[0]
-    t0, c0 = srcs[0][0], srcs[0][1]
-    t1, c1 = (srcs[1][0], srcs[1][1]) if len(srcs) > 1 else (None, 0)
+    t0, c0 = tape.act(srcs[0][0]), srcs[0][1]
+    t1, c1 = (tape.act(srcs[1][0]), srcs[1][1]) if len(srcs) > 1 else (None, 0)
+    pad1 = (srcs[1][2], srcs[1][3]) if t1 is not None else (0, 0)
     s3 = tape.use_s3 and c0 % 32 == 0 and c1 % 32 == 0 and c0 == t0.shape[3] and (t1 is None or c1 == t1.shape[3])
+    if not s3:   # the fp32 kernel reads the sources themselves
+        x0, x1 = t0.need_f32("conv_bn_act"), t1.need_f32("conv_bn_act") if t1 is not None else None
+    res = tape.act(residual) if residual is not None else None
+    res_f32 = res.need_f32("conv_bn_act") if res is not None else None
     pc = PackedConv(w, conv.bias, None, ks, c0, c1, relu=False, stride=stride, tag="train_fwd",
                     fmt=tape.fmt if s3 else None, wexp=tape.wexp_of(conv.weight), shared_unit_scale=True)
     pc.order = tape.order
@@ -441,26 +514,14 @@ def conv_bn_act(tape, names, conv, bn, srcs, B, H, W, relu=True, residual=None, 
     ho, wo = (H - 1) // stride + 1, (W - 1) // stride + 1
     z = _empty((B, ho, wo, cout), t0)
     # BatchNorm's batch sums ride in the conv epilogue where the kernel offers it (H2, 3x3, stride 1)
-    stats = None
-    if s3 and pc.stats_ok:
-        rows = 64
-        while rows < STATS_ROWS and rows * 1024 < B * ho * wo:   # about a quarter as many rows as pixel tiles
-            rows *= 2
-        stats = tape.zeros((rows, 2, cout), t0, torch.float64)
-    pc.run(tape.s3(t0) if s3 else t0, B, H, W, z, src1=(tape.s3(t1) if s3 else t1) if t1 is not None else None,
-           pad1=(srcs[1][2], srcs[1][3]) if t1 is not None else (0, 0), stats=stats)
-    if any(id(t) in tape.no_f32 for t in (t0, t1) if t is not None) and not s3:
-        raise RuntimeError("conv_bn_act: a source has no fp32 storage (f32_out=False) but this conv reads fp32")
-    pooled = None
-    if pool:
-        y, mi, pooled = _bn_forward(lib, z, bn, relu, residual, tape, stats=stats, pool=True)
-    else:
-        y, mi = _bn_forward(lib, z, bn, relu, residual, tape, want_s3=s3_out,   # s3_out: a conv consumes y
-                            want_f32=f32_out or residual is not None, stats=stats)
-    if relu and residual is None:
-        tape.bn_layers[id(y)] = {"z": z, "mi": mi, "bn": bn}
-    if not pool and not f32_out and residual is None and relu:
-        tape.single_consumer[id(y)] = {"z": z, "mi": mi, "bn": bn}
+    stats = tape.zeros((stats_rows(B * ho * wo), 2, cout), t0, torch.float64) if s3 and pc.stats_ok else None
+    if s3:
+        x0, x1 = tape.s3(t0), tape.s3(t1) if t1 is not None else None
+    pc.run(x0, B, H, W, z, src1=x1, pad1=pad1, stats=stats)
+    y, mi, pooled = _bn_forward(lib, z, bn, relu, res_f32, tape, want_s3=s3_out,   # s3_out: a conv consumes y
+                                want_f32=f32_out or res is not None, stats=stats, pool=pool)
+    if relu and res is None:
+        y.bn, y.sole = (z, mi, bn), not pool and not f32_out
 
     def backward():
         dy = tape.pop_grad(y)
@@ -468,43 +529,39 @@ def conv_bn_act(tape, names, conv, bn, srcs, B, H, W, relu=True, residual=None, 
             raise RuntimeError("conv_bn_act: no gradient reached this layer")
         wsrc = [(t0, min(c0 + 3 & ~3, t0.shape[3]), 0, 0, 0)]
         if t1 is not None:
-            wsrc.append((t1, c1, c0, srcs[1][2], srcs[1][3]))
+            wsrc.append((t1, c1, c0, *pad1))
         wg_s3 = s3 and wgrad_s3_ok(ks, stride, cout, wsrc)
-        if not wg_s3 and any(id(t) in tape.no_f32 for (t, *_r) in wsrc):
-            raise RuntimeError("conv_bn_act: a source has no fp32 storage (f32_out=False) but its backward-filter reads fp32")
-        # fp32 dz is read by the fp32 backward-filter kernel and by the zero-stuffing of stride-2 layers only
-        ent = tape.single_consumer.pop(id(y), None)
+        if not wg_s3:   # the fp32 backward-filter kernel reads the sources themselves
+            wsrc = [(t.need_f32("conv_bn_act.backward"), *r) for (t, *r) in wsrc]
         # the first layer (three channels stored as four, nothing upstream): its BatchNorm backward rides in the
         # backward-filter kernel's tile load - no dz tensor
-        c4_bn = (tape.options.train_one_pass and not need_dx and not s3 and relu and residual is None and t1 is None
+        c4_bn = (tape.options.train_one_pass and not need_dx and not s3 and relu and res is None and t1 is None
                  and ks == 3 and stride == 1 and c0 <= 4 and t0.shape[3] == 4 and cout % 4 == 0)
-        if c4_bn:
-            _, dgamma, dbeta, _, acc = _bn_backward(lib, tape, dy, y, z, mi, bn, relu, False, apply=False,
-                                                    sums_table=ent.get("table") if ent is not None else None,
-                                                    sums=tape.bwd_sums.pop(id(y), None))
-            g = tape.param_grads
-            g[names(bn.weight)], g[names(bn.bias)] = dgamma, dbeta
-            if conv.bias is not None:
-                g[names(conv.bias)] = tape.zeros((cout,), z)
-            raw = tape.zeros((cout, 9, 4), z)
-            _lib.check(lib.sfh_conv_wgrad_c4_bn(_ptr(dy), _ptr(z), _ptr(mi), _ptr(bn.weight.detach()), _ptr(bn.bias.detach()),
-                                                _ptr(acc), cout, _ptr(t0), c0, B, H, W, _ptr(raw), 4, _stream()),
-                       "conv_wgrad_c4_bn")
-            g[names(conv.weight)] = raw.view(cout, 3, 3, 4)[..., :c0].permute(0, 3, 1, 2)
-            return
-        dz, dgamma, dbeta, dres, dz_s3 = _bn_backward(lib, tape, dy, y, z, mi, bn, relu, residual is not None,
+        ysign = y.need_f32("conv_bn_act.backward") if res is not None else None
+        # take the sums and void the fields: each is a slice of an fp64 arena chunk and would keep it alive to the end of
+        # the pass
+        table, sums, y.sums_table, y.sums = y.sums_table, y.sums, None, None
+        # fp32 dz is read by the fp32 backward-filter kernel and by the zero-stuffing of stride-2 layers only;
+        # c4_bn: the sums only (apply=False) - dz_s3 is then the fp64 sums themselves
+        dz, dgamma, dbeta, dres, dz_s3 = _bn_backward(lib, tape, dy, ysign, z, mi, bn, relu, res is not None,
                                                       want_s3=s3 and stride == 1 and (need_dx or wg_s3),
                                                       want_f32=not (s3 and stride == 1 and wg_s3),
-                                                      sums_table=ent.get("table") if ent is not None else None,
-                                                      sums=tape.bwd_sums.pop(id(y), None))
+                                                      sums_table=table, sums=sums, apply=not c4_bn)
         g = tape.param_grads
         g[names(bn.weight)], g[names(bn.bias)] = dgamma, dbeta
         if conv.bias is not None:
             # a bias in front of a batch-statistics BatchNorm has exactly zero gradient (the batch mean
             # absorbs it); autograd's value is rounding noise around 0
             g[names(conv.bias)] = tape.zeros((cout,), z)
-        if residual is not None:
-            tape.add_grad(residual, dres)
+        if c4_bn:
+            raw = tape.zeros((cout, 9, 4), z)
+            _lib.check(lib.sfh_conv_wgrad_c4_bn(_ptr(dy), _ptr(z), _ptr(mi), _ptr(bn.weight.detach()), _ptr(bn.bias.detach()),
+                                                _ptr(dz_s3), cout, _ptr(wsrc[0][0]), c0, B, H, W, _ptr(raw), 4, _stream()),
+                       "conv_wgrad_c4_bn")
+            g[names(conv.weight)] = raw.view(cout, 3, 3, 4)[..., :c0].permute(0, 3, 1, 2)
+            return
+        if res is not None:
+            tape.add_grad(res, dres)
         if stride == 2:  # zero-stuff dz to the input resolution: stride-1 backward from here on
             u = _empty((B, H, W, cout), dz)
             _lib.check(lib.sfh_zero_stuff2(_ptr(dz), _ptr(u), B, ho, wo, H, W, cout, _stream()), "zero_stuff2")
@@ -519,34 +576,17 @@ def conv_bn_act(tape, names, conv, bn, srcs, B, H, W, relu=True, residual=None, 
         if not need_dx:
             return
         dz_in = ((dz_s3 if dz_s3 is not None else E.f32_to_split(dz, tape.fmt, tape.overflow)) if s3 else dz)
-        if (t1 is not None and c0 % 64 == 0 and c1 % 64 == 0 and (srcs[1][2], srcs[1][3]) == (0, 0)
+        if (t1 is not None and c0 % 64 == 0 and c1 % 64 == 0 and pad1 == (0, 0)
                 and tuple(t1.shape[1:3]) == (H, W) and c0 == t0.shape[3]):
             # two sources of the same size: one backward-data conv per source writes that source's gradient directly
             # (no gradient of the concatenated tensor, no slicing passes)
             for (t, lo, hi) in ((t0, 0, c0), (t1, c0, c0 + c1)):
                 bdh = PackedConv.backward_data(w[:, lo:hi].contiguous(), ks, fmt=tape.fmt if s3 else None,
                                                wexp=tape.wexp_of(conv.weight))
-                bdh.order = tape.order
-                dh = _empty((B, H, W, hi - lo), z)
-                bdh.run(dz_in, B, H, W, dh)
-                tape.add_grad(t, dh)
+                tape.add_grad(t, _backward_data(tape, bdh, dz_in, B, H, W, None, s3))
             return
         bd = PackedConv.backward_data(w, ks, fmt=tape.fmt if s3 else None, wexp=tape.wexp_of(conv.weight))
-        bd.order = tape.order
-        dx = _empty((B, H, W, bd.cout), z)
-        src_ent = tape.single_consumer.get(id(t0)) if t1 is None else None
-        if (src_ent is not None and s3 and bd.stats_ok and bd.cout == t0.shape[3] and tape.peek_grad(t0) is None):
-            # t0 is a BatchNorm + ReLU output that only this conv consumed: its backward sums ride in this launch
-            rows = 64
-            while rows < STATS_ROWS and rows * 1024 < B * H * W:
-                rows *= 2
-            table = tape.zeros((rows, 2, bd.cout), z, torch.float64)
-            sb = src_ent["bn"]
-            bd.run(dz_in, B, H, W, dx, stats=table,
-                   bwd=(src_ent["z"], src_ent["mi"], sb.weight.detach(), sb.bias.detach()))
-            src_ent["table"] = table
-        else:
-            bd.run(dz_in, B, H, W, dx)
+        dx = _backward_data(tape, bd, dz_in, B, H, W, t0 if t1 is None else None, s3)
         if t1 is None:
             tape.add_grad(t0, dx)
             return
@@ -554,7 +594,7 @@ def conv_bn_act(tape, names, conv, bn, srcs, B, H, W, relu=True, residual=None, 
         _lib.check(lib.sfh_slice_add(_ptr(dx), H, W, bd.cout, 0, 0, 0, _ptr(d0), B, H, W, c0, 0, _stream()), "slice_add")
         tape.add_grad(t0, d0)
         d1 = _empty(t1.shape, z)
-        _lib.check(lib.sfh_slice_add(_ptr(dx), H, W, bd.cout, c0, srcs[1][2], srcs[1][3], _ptr(d1), B, t1.shape[1],
+        _lib.check(lib.sfh_slice_add(_ptr(dx), H, W, bd.cout, c0, *pad1, _ptr(d1), B, t1.shape[1],
                                      t1.shape[2], c1, 0, _stream()), "slice_add")
         tape.add_grad(t1, d1)
 
@@ -566,7 +606,7 @@ def conv_bn_act(tape, names, conv, bn, srcs, B, H, W, relu=True, residual=None, 
         dp = tape.pop_grad(pooled)
         if dp is None:
             raise RuntimeError("conv_bn_act(pool=True): no gradient reached the pooled tensor")
-        cur = tape.peek_grad(y)
+        cur = y.grad
         acc = tape.zeros((2 * cout,), z, torch.float64)
         fresh = cur is None
         if fresh:
@@ -576,7 +616,7 @@ def conv_bn_act(tape, names, conv, bn, srcs, B, H, W, relu=True, residual=None, 
                    "pool2_bwd_bn_reduce")
         if fresh:
             tape.add_grad(y, cur)
-        tape.bwd_sums[id(y)] = acc
+        y.sums = acc
 
     tape.push(pool_backward_fused)
     return y, pooled
@@ -585,21 +625,21 @@ def conv_bn_act(tape, names, conv, bn, srcs, B, H, W, relu=True, residual=None, 
 def maxpool2(tape, x):
     """nn.MaxPool2d(2) (unet/unet_parts.py:33)."""
     lib = tape.lib
+    x = tape.act(x)
+    xf = x.need_f32("maxpool2")
     B, H, W, C = x.shape
-    p = _empty((B, H // 2, W // 2, C), x)
-    _lib.check(lib.sfh_maxpool2_fwd(_ptr(x), _ptr(p), B, H, W, C, _stream()), "maxpool2_fwd")
+    p = Act((B, H // 2, W // 2, C), f32=_empty((B, H // 2, W // 2, C), xf))
+    _lib.check(lib.sfh_maxpool2_fwd(_ptr(xf), _ptr(p.f32), B, H, W, C, _stream()), "maxpool2_fwd")
 
     def backward():
         dp = tape.pop_grad(p)
-        cur = tape.peek_grad(x)
-        if cur is None:
-            even = H % 2 == 0 and W % 2 == 0
-            cur = _empty(x.shape, x) if even else _zeros(x.shape, x)
-            _lib.check(lib.sfh_maxpool2_bwd(_ptr(x), _ptr(dp), _ptr(cur), B, H, W, C, 0 if even else 1, _stream()),
-                       "maxpool2_bwd")
+        fresh, even = x.grad is None, H % 2 == 0 and W % 2 == 0
+        # a fresh gradient of an even-sized map is written whole; an odd one keeps zeros in its cropped row / column
+        cur = x.grad if not fresh else _empty(x.shape, xf) if even else _zeros(x.shape, xf)
+        _lib.check(lib.sfh_maxpool2_bwd(_ptr(xf), _ptr(dp), _ptr(cur), B, H, W, C, 0 if fresh and even else 1, _stream()),
+                   "maxpool2_bwd")
+        if fresh:
             tape.add_grad(x, cur)
-        else:
-            _lib.check(lib.sfh_maxpool2_bwd(_ptr(x), _ptr(dp), _ptr(cur), B, H, W, C, 1, _stream()), "maxpool2_bwd")
 
     tape.push(backward)
     return p
@@ -608,31 +648,31 @@ def maxpool2(tape, x):
 def conv_transpose2x2(tape, names, up, x):
     """nn.ConvTranspose2d(cin, cin/2, 2, stride=2) (unet/unet_parts.py:52).  In split-operand mode the result is written
     in the split format only: its consumer is the Up block's conv, whose forward and backward-filter read the split copy
-    (the returned tensor is a handle without fp32 storage, see _bn_forward)."""
+    (the returned Act has no fp32 storage, see _bn_forward)."""
     lib = tape.lib
+    x = tape.act(x)
     B, h, w, cin = x.shape
     wt = up.weight.detach()
     cout = wt.shape[1]
     s3 = tape.use_s3 and cin % 32 == 0
+    wsrc = [(x, cin, 0, 0, 0)]
+    wg_s3 = s3 and wgrad_s3_ok(1, 1, 4 * cout, wsrc)
+    if not wg_s3:   # the fp32 backward-filter kernel (and, without a split format, the forward conv) reads x itself
+        xf = x.need_f32("conv_transpose2x2")
     pc = PackedConv(wt, up.bias, None, 1, cin, relu=False, transposed=True, tag="train_fwd",
                     fmt=tape.fmt if s3 else None, wexp=tape.wexp_of(up.weight), shared_unit_scale=True)
     pc.overflow = tape.overflow
     split_only = s3 and cout % 32 == 0 and CAPTURE is None
     if split_only:
-        u = x.new_empty((1,)).expand(B, 2 * h, 2 * w, cout)
-        u_s3 = E.split_empty(tape.fmt, B, 2 * h, 2 * w, cout, x.device)
-        pc.run(tape.s3(x), B, h, w, u_s3)
-        tape._s3[id(u)] = (u, u_s3)
-        tape.no_f32.add(id(u))
+        u = Act((B, 2 * h, 2 * w, cout), split=E.split_empty(tape.fmt, B, 2 * h, 2 * w, cout, x.device))
+        pc.run(tape.s3(x), B, h, w, u.split)
     else:
-        u = _empty((B, 2 * h, 2 * w, cout), x)
-        pc.run(tape.s3(x) if s3 else x, B, h, w, u)
+        u = Act((B, 2 * h, 2 * w, cout), f32=_empty((B, 2 * h, 2 * w, cout), x))
+        pc.run(tape.s3(x) if s3 else xf, B, h, w, u.f32)
 
     def backward():
         du = tape.pop_grad(u)
         g = tape.param_grads
-        wsrc = [(x, cin, 0, 0, 0)]
-        wg_s3 = s3 and wgrad_s3_ok(1, 1, 4 * cout, wsrc)
         if wg_s3 and cout % 8 == 0 and tape.options.train_one_pass:
             # one pass over du: bias gradient + the split copy of s (nobody reads s itself: backward-filter and
             # backward-data take the split copy)
@@ -651,28 +691,13 @@ def conv_transpose2x2(tape, names, up, x):
             s_split = E.f32_to_split(s, tape.fmt, tape.overflow) if s3 else None
         if wg_s3:   # one split copy of s feeds backward-filter and backward-data
             raw = _wgrad_s3(lib, tape, s_split, 4 * cout, wsrc, B, h, w, cin, 1)
-        elif id(x) in tape.no_f32:
-            raise RuntimeError("conv_transpose2x2: the input has no fp32 storage but its backward-filter reads fp32")
         else:
-            raw = _wgrad(lib, s, wsrc, B, h, w, 1, cin, tape)      # (4*cout, 1, cin)
+            raw = _wgrad(lib, s, [(xf, cin, 0, 0, 0)], B, h, w, 1, cin, tape)      # (4*cout, 1, cin)
         g[names(up.weight)] = raw.view(2, 2, cout, cin).permute(3, 2, 0, 1)
         bd = PackedConv.backward_data(wt, 1, transposed=True, fmt=tape.fmt if s3 else None, wexp=tape.wexp_of(up.weight))
-        bd.order = tape.order
-        dx = _empty((B, h, w, bd.cout), x)
-        src_ent = tape.single_consumer.get(id(x))
-        if src_ent is not None and s3 and bd.stats_ok and bd.cout == cin and tape.peek_grad(x) is None:
-            # x is a BatchNorm + ReLU output that only this transposed conv consumed: the layer's backward sums ride in this
-            # launch (as in conv_bn_act)
-            rows = 64
-            while rows < STATS_ROWS and rows * 1024 < B * h * w:
-                rows *= 2
-            table = tape.zeros((rows, 2, bd.cout), x, torch.float64)
-            sb = src_ent["bn"]
-            bd.run(s_split, B, h, w, dx, stats=table, bwd=(src_ent["z"], src_ent["mi"], sb.weight.detach(), sb.bias.detach()))
-            src_ent["table"] = table
-        else:
-            bd.run(s_split if s3 else s, B, h, w, dx)
-        tape.add_grad(x, dx)
+        # (x as the source: when it is a BatchNorm + ReLU output that only this transposed conv consumed, the layer's
+        # backward sums ride in this launch, as in conv_bn_act)
+        tape.add_grad(x, _backward_data(tape, bd, s_split if s3 else s, B, h, w, x, s3))
 
     tape.push(backward)
     return u
@@ -681,13 +706,15 @@ def conv_transpose2x2(tape, names, up, x):
 def upsample2x(tape, x):
     """nn.Upsample(scale_factor=2, mode='bilinear', align_corners=True) (unet/unet_parts.py:49)."""
     lib = tape.lib
+    x = tape.act(x)
+    xf = x.need_f32("upsample2x")
     B, h, w, C = x.shape
-    u = _empty((B, 2 * h, 2 * w, C), x)
-    _lib.check(lib.sfh_upsample2x_bilinear_nhwc(_ptr(x), _ptr(u), B, h, w, C, _stream()), "upsample2x")
+    u = Act((B, 2 * h, 2 * w, C), f32=_empty((B, 2 * h, 2 * w, C), xf))
+    _lib.check(lib.sfh_upsample2x_bilinear_nhwc(_ptr(xf), _ptr(u.f32), B, h, w, C, _stream()), "upsample2x")
 
     def backward():
         du = tape.pop_grad(u)
-        dx = _empty(x.shape, x)
+        dx = _empty(x.shape, xf)
         _lib.check(lib.sfh_upsample2x_bilinear_nhwc_bwd(_ptr(du), _ptr(dx), B, h, w, C, _stream()), "upsample2x_bwd")
         tape.add_grad(x, dx)
 
@@ -700,36 +727,37 @@ def out_conv(tape, names, oc, y, B, H, W, frame_nhwc=None, stn_cs=0, sole_consum
     sole_consumer: y feeds nothing but this head - when y is a BatchNorm + ReLU output, the backward pass takes that layer's
     backward sums while it writes y's gradient (sfh_outconv_bwd_bn), and reads the layer's conv output instead of y."""
     lib = tape.lib
+    y = tape.act(y)
+    yf = y.need_f32("out_conv")
     wt, bias = oc.conv.weight.detach(), oc.conv.bias.detach()
     nc, cin = wt.shape[0], wt.shape[1]
-    logits = _empty((B, nc, H, W), y)
-    stn_in = _empty((B, H, W, stn_cs), y) if frame_nhwc is not None else None
-    _lib.check(lib.sfh_outconv_fwd(_ptr(y), cin, _ptr(wt), _ptr(bias), nc, B, H, W, _ptr(logits), None, _ptr(stn_in),
+    logits = _empty((B, nc, H, W), yf)
+    stn_in = _empty((B, H, W, stn_cs), yf) if frame_nhwc is not None else None
+    _lib.check(lib.sfh_outconv_fwd(_ptr(yf), cin, _ptr(wt), _ptr(bias), nc, B, H, W, _ptr(logits), None, _ptr(stn_in),
                                    stn_cs, _ptr(frame_nhwc), frame_nhwc.shape[3] if frame_nhwc is not None else 0,
                                    _stream()), "outconv")
 
     def backward(dlogits):
         """dlogits: (B,nc,H,W) contiguous - total gradient wrt the logits."""
-        acc_w = tape.zeros((nc * cin,), y, torch.float64)
-        acc_b = tape.zeros((nc,), y, torch.float64)
-        dy = _empty(y.shape, y)
-        fused = sole_consumer and tape.options.train_one_pass and tape.peek_grad(y) is None
-        ent = tape.bn_layers.get(id(y)) if fused else None
-        if ent is not None:
-            sb = ent["bn"]
-            acc_bn = tape.zeros((2 * cin,), y, torch.float64)
-            _lib.check(lib.sfh_outconv_bwd_bn(_ptr(ent["z"]), _ptr(ent["mi"]), _ptr(sb.weight.detach()), _ptr(sb.bias.detach()),
+        acc_w = tape.zeros((nc * cin,), yf, torch.float64)
+        acc_b = tape.zeros((nc,), yf, torch.float64)
+        dy = _empty(y.shape, yf)
+        fused = sole_consumer and tape.options.train_one_pass and y.grad is None and y.bn is not None
+        if fused:
+            z, mi, sb = y.bn
+            acc_bn = tape.zeros((2 * cin,), yf, torch.float64)
+            _lib.check(lib.sfh_outconv_bwd_bn(_ptr(z), _ptr(mi), _ptr(sb.weight.detach()), _ptr(sb.bias.detach()),
                                               cin, _ptr(wt), _ptr(dlogits), nc, B, H, W, _ptr(dy), _ptr(acc_w), _ptr(acc_b),
                                               _ptr(acc_bn), _stream()), "outconv_bwd_bn")
         else:
-            _lib.check(lib.sfh_outconv_bwd(_ptr(y), cin, _ptr(wt), _ptr(dlogits), nc, B, H, W, _ptr(dy), _ptr(acc_w),
+            _lib.check(lib.sfh_outconv_bwd(_ptr(yf), cin, _ptr(wt), _ptr(dlogits), nc, B, H, W, _ptr(dy), _ptr(acc_w),
                                            _ptr(acc_b), _stream()), "outconv_bwd")
         g = tape.param_grads
         g[names(oc.conv.weight)] = acc_w.to(torch.float32).view(nc, cin, 1, 1)
         g[names(oc.conv.bias)] = acc_b.to(torch.float32)
         tape.add_grad(y, dy)
-        if ent is not None:
-            tape.bwd_sums[id(y)] = acc_bn     # (after add_grad: a later gradient for y would be an ordering bug and raises)
+        if fused:
+            y.sums = acc_bn     # (after add_grad: a later gradient for y would be an ordering bug and raises)
 
     return logits, stn_in, backward
 
@@ -809,6 +837,7 @@ class ResNetTrainer:
         channels; targets: [(NCHW tensor, first channel, channels)] - the pieces of the input that come
         from the UNet heads and whose gradient slots receive the stem's backward-data.  Returns theta (B,9)."""
         lib, rn, names = tape.lib, self.rn, self.names
+        tape.resnet_start = len(tape.ops)
         B, H, W, cs = stn_in.shape
         st = _stream
         H2, W2 = (H + 1) // 2, (W + 1) // 2
@@ -824,11 +853,11 @@ class ResNetTrainer:
         else:
             pc = PackedConv(w0, None, None, 4, 4 * cs, relu=False, stem_cin=cin, tag="train_fwd")
             pc.run(s2d, B, H2, W2, z0)
-        c1, mi0 = _bn_forward(lib, z0, rn.bn1, True, None, tape, want_s3=False)
+        c1, mi0, _ = _bn_forward(lib, z0, rn.bn1, True, None, tape, want_s3=False)
+        c1 = c1.need_f32("ResNetTrainer")
         h, w = (H2 - 1) // 2 + 1, (W2 - 1) // 2 + 1
-        x = _empty((B, h, w, 64), stn_in)
-        _lib.check(lib.sfh_maxpool3x3s2_fwd(_ptr(c1), _ptr(x), B, H2, W2, 64, st()), "maxpool3x3s2")
-        x_pool = x
+        x = x_pool = Act((B, h, w, 64), f32=_empty((B, h, w, 64), stn_in))
+        _lib.check(lib.sfh_maxpool3x3s2_fwd(_ptr(c1), _ptr(x.f32), B, H2, W2, 64, st()), "maxpool3x3s2")
 
         def stem_backward():
             dx = tape.pop_grad(x_pool)
@@ -872,23 +901,23 @@ class ResNetTrainer:
                     t = cba(blk.conv1, blk.bn1, x, h, w, f32_out=mid_f32)
                     x = cba(blk.conv2, blk.bn2, t, ho, wo, residual=idn)
                 if CAPTURE is not None:
-                    CAPTURE[f"layer{li}.{bi}"] = {"in": x_in, "t": t, "out": x}
+                    CAPTURE[f"layer{li}.{bi}"] = {"in": x_in.f32, "t": t.f32, "out": x.f32}
                 h, w = ho, wo
-        feat = x
+        feat, featf = x, x.need_f32("ResNetTrainer")
         C = feat.shape[3]
         wr, br = rn.reg.weight.detach(), rn.reg.bias.detach()
         theta = _empty((B, 9), stn_in)
         pooled = _empty((B, C), stn_in)
-        _lib.check(lib.sfh_avgpool_linear_fwd(_ptr(feat), _ptr(wr), _ptr(br), B, h, w, C, 9, _ptr(pooled), _ptr(theta),
+        _lib.check(lib.sfh_avgpool_linear_fwd(_ptr(featf), _ptr(wr), _ptr(br), B, h, w, C, 9, _ptr(pooled), _ptr(theta),
                                               st()), "avgpool_linear")
         fh, fw = h, w
 
         def head_backward():
             dth = tape.pop_grad(theta)
-            acc_w = tape.zeros((9 * C,), feat, torch.float64)
-            acc_b = tape.zeros((9,), feat, torch.float64)
-            dfeat = _empty(feat.shape, feat)
-            _lib.check(lib.sfh_avgpool_linear_bwd(_ptr(feat), _ptr(wr), _ptr(dth), B, fh, fw, C, 9, _ptr(dfeat),
+            acc_w = tape.zeros((9 * C,), featf, torch.float64)
+            acc_b = tape.zeros((9,), featf, torch.float64)
+            dfeat = _empty(feat.shape, featf)
+            _lib.check(lib.sfh_avgpool_linear_bwd(_ptr(featf), _ptr(wr), _ptr(dth), B, fh, fw, C, 9, _ptr(dfeat),
                                                   _ptr(acc_w), _ptr(acc_b), st()), "avgpool_linear_bwd")
             g = tape.param_grads
             g[names(rn.reg.weight)] = acc_w.to(torch.float32).view(9, C)
@@ -1009,7 +1038,7 @@ def run_backward(net, tape, f, dheads, dtheta, unscale=True, device_scale=False)
             words = E.absminmax_words(seeds)
             sbuf = _empty((2,), seeds[0])
             _lib.check(lib.sfh_grad_scale(_ptr(words), len(heads), 1 if dtheta is not None else 0,
-                                          int(getattr(tape, "gshift", 0)), _ptr(sbuf), _ptr(tape.overflow), _stream()),
+                                          tape.gshift, _ptr(sbuf), _ptr(tape.overflow), _stream()),
                        "grad_scale")
             tape.gscale_dev, tape.gscale = sbuf, None
             one = sbuf[0:1]
@@ -1037,7 +1066,7 @@ def run_backward(net, tape, f, dheads, dtheta, unscale=True, device_scale=False)
             m, target = mt, 13
         if not (math.isfinite(mh) and math.isfinite(mt)):
             raise FP16RangeError("non-finite gradient at the outputs of the model")
-        target += int(getattr(tape, "gshift", 0))        # TrainStep lowers it for good after a gradient overflow (sticky)
+        target += tape.gshift        # TrainStep lowers it for good after a gradient overflow (sticky)
         if m > 0.0:
             S = 2.0 ** (target - math.frexp(m)[1])       # m = f * 2^e, 0.5 <= f < 1  ->  m * S in [2^(target-1), 2^target)
         if heads and 0.0 < mt * S < 2.0 ** -16:
@@ -1057,37 +1086,25 @@ def run_backward(net, tape, f, dheads, dtheta, unscale=True, device_scale=False)
         dtheta = None if dtheta is None else dtheta * S
         dheads = [None if d is None else d.mul_(S) for d in dheads]
     if f["theta"] is not None:
-        tape.grads[id(f["theta"])] = dtheta if dtheta is not None else torch.zeros_like(f["theta"])
+        tape.act(f["theta"]).grad = dtheta if dtheta is not None else torch.zeros_like(f["theta"])
     for (t, _), d in zip(f["heads"], dheads):
-        tape.grads[id(t)] = torch.zeros_like(t) if d is None else d
-    ops, tape.ops = tape.ops, []
-    k = ctx_split(ops)
-    for fn in reversed(ops[k:]):
-        fn()
-    for t, bwd in f["heads"]:
-        bwd(tape.pop_grad(t))
-    for fn in reversed(ops[:k]):
-        fn()
+        tape.act(t).grad = torch.zeros_like(t) if d is None else d
+    tape.backward(f["heads"])
     g = tape.param_grads
     if S != 1.0 and unscale:     # (unscale=False: the caller divides tape.gscale out itself, e.g. once over a flat buffer)
         torch._foreach_mul_([t for t in g.values() if t is not None], 1.0 / S)
     ov = tape.overflow.cpu().tolist() if tape.overflow is not None else [0]
+    # the closures reference the tape and the tape the closures: break the cycle so the activations
+    # are released now rather than at the next garbage collection
+    f["heads"] = []
+    tape.release()
     if ov[0]:
-        tape.ops, tape.param_grads = [], {}
-        tape.grads.clear()
-        tape._s3.clear()
         err = FP16RangeError("training step with SFH_TRAIN_PRECISION=f16x3: an activation or gradient left the range of "
                              "the two-plane fp16 format (or was not finite); use SFH_TRAIN_PRECISION=bf16x6 for this model")
         # the forward pass was clean (its copy of the word is 0): only a GRADIENT overflowed - a lower scale can hold it.
         # Bits 2 / 4 (sfh_grad_scale): a non-finite seed / head and theta gradients that fit no common scale - no scale helps.
         err.phase = "backward" if (len(ov) > 1 and not ov[1] and not (ov[0] & 6)) else "forward"
         raise err
-    # the closures reference the tape and the tape the closures: break the cycle so the activations
-    # are released now rather than at the next garbage collection
-    tape.param_grads = {}
-    tape.grads.clear()
-    tape._s3.clear()
-    f["heads"] = []
     return g
 
 
@@ -1177,14 +1194,6 @@ class _TrainForward(torch.autograd.Function):
         grads = tuple(g.get(names(p)) for p in net.parameters())
         ctx.tape = ctx.f = ctx.x = None
         return (None, None, None) + grads
-
-
-def ctx_split(ops):
-    """index of the first ResNet closure on the tape (the stem's)."""
-    for i, fn in enumerate(ops):
-        if fn.__name__ == "stem_backward":
-            return i
-    return len(ops)
 
 
 def train_forward(net, x):
@@ -1361,8 +1370,7 @@ class TrainStep:
         if not (net.use_unet and net.use_resnet and net.warper) or mode not in ("IMG_AND_MASK", "IMG_AND_MASK_AND_UV"):
             raise NotImplementedError("TrainStep covers the reference's training configurations: UNet + ResNetSTN + warper "
                                       "with resnet_input 'img+mask', or 'img+mask+uv' with the uv head")
-        tape = Tape(fmt=fmt, options=net.options)
-        tape.gshift = self.grad_scale_shift
+        tape = Tape(fmt=fmt, options=net.options, gshift=self.grad_scale_shift)
         B, _, H, W = x.shape
         x = E._f32c(x, "input frames")
         f = run_forward(net, tape, x)
