@@ -5,6 +5,7 @@
 #include <stdio.h>
 
 #include "../../include/sfh_amd.h"
+#include "bn_math.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -30,9 +31,8 @@ static inline int sfh_check_launch(const char* what) {
 
 static inline int sfh_cdiv(int a, int b) { return (a + b - 1) / b; }
 
-// ReLU and max with torch's NaN behaviour (relu(NaN) = NaN, max_pool propagates NaN): v_max_f32 would return the other
-// operand.  A non-finite input frame then produces non-finite outputs, as it does in the reference.
-__device__ __forceinline__ float sfh_relu(float v) { return v < 0.f ? 0.f : v; }
+// ReLU (sfh_relu, bn_math.h) and max with torch's NaN behaviour (relu(NaN) = NaN, max_pool propagates NaN): v_max_f32 would
+// return the other operand.  A non-finite input frame then produces non-finite outputs, as it does in the reference.
 __device__ __forceinline__ float sfh_max_nan(float a, float b) { return (a > b || a != a) ? a : b; }
 
 // Kernels that use more than 64 KB of dynamic LDS need hipFuncAttributeMaxDynamicSharedMemorySize raised once

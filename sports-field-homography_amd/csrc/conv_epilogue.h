@@ -393,9 +393,9 @@ __device__ __forceinline__ void sfh_conv_epilogue(const sfh_conv_desc& d, const 
       double* const row = d.stats_partial + (size_t)(stats_slot & (unsigned)(d.stats_rows - 1)) * (size_t)(2 * d.cout);
       if (d.bwd_z) {
         // backward mode (this launch is the backward-data conv whose output dy is the ONLY gradient of a BatchNorm + ReLU
-        // layer): with z the pre-BatchNorm tensor of that layer (same fp32 NHWC shape as dst), g = dy * (y > 0),
-        // y = (z - mean) * invstd * gamma + beta as bn_apply computes it; the sums of g and of g * xhat (= dbeta, dgamma)
-        // - the separate reduction pass over dy and z (sfh_bn_bwd_reduce) is not needed
+        // layer): with z the pre-BatchNorm tensor of that layer (same fp32 NHWC shape as dst), g = dy * (y > 0), y the
+        // pre-activation recomputed from z (bn_math.h); the sums of g and of g * xhat (= dbeta, dgamma) - the separate
+        // reduction pass over dy and z (sfh_bn_bwd_reduce) is not needed
         const __amdgpu_buffer_rsrc_t rz =
             __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(d.bwd_z), 0, (int)kSfhOOB, 0x00020000);
 #pragma unroll
@@ -415,9 +415,10 @@ __device__ __forceinline__ void sfh_conv_epilogue(const sfh_conv_desc& d, const 
             const bool in_frame = voff[mi] != kSfhOOB;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-              const float xh = (zq[j] - mean[j]) * inv[j];
-              const float y = d.bwd_beta ? xh * gam[j] + bet[j] : 1.f;
-              const float gj = (in_frame && y > 0.f) ? acc[ni][mi][j] : 0.f;
+              const float xh = bn_xhat(zq[j], mean[j], inv[j]);
+              const float y = d.bwd_beta ? bn_y(xh, gam[j], bet[j]) : 1.f;
+              const bool open = bn_relu_open(y);   // (evaluated outside the &&: no branch inside the unrolled loop)
+              const float gj = (in_frame && open) ? acc[ni][mi][j] : 0.f;
               a[j] += (double)gj;
               b[j] += (double)gj * (double)xh;
             }

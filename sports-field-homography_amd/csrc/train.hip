@@ -29,6 +29,26 @@ static inline unsigned red_grid(long npix) {
   return (unsigned)(nb < 1 ? 1 : (nb > RED_BLOCKS ? RED_BLOCKS : nb));
 }
 
+// The end of such a block: thread (pixel lane pl, channel quad q) = threadIdx.x = pl * cq + q holds NV partial sums, NV / 4
+// rows of its quad's four channels (s[4 * r + i]: row r, channel 4 * q + i; `live`: pl < 256 / cq).  One value at a time goes
+// through sh[256], the first cq threads add the lanes up and acc[r * row_stride + 4 * q + i] takes the sum in one atomic.
+template <int NV>
+__device__ __forceinline__ void red_tail(const double (&s)[NV], bool live, int cq, double* sh, double* __restrict__ acc,
+                                         long row_stride) {
+  const int lanes = 256 / cq;
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    __syncthreads();
+    sh[threadIdx.x] = live ? s[j] : 0.0;
+    __syncthreads();
+    if (threadIdx.x < cq) {
+      double t = 0.0;
+      for (int l = 0; l < lanes; ++l) t += sh[l * cq + threadIdx.x];
+      unsafeAtomicAdd(&acc[(long)(j >> 2) * row_stride + 4 * threadIdx.x + (j & 3)], t);
+    }
+  }
+}
+
 // acc[0][c] += sum z, acc[1][c] += sum z^2
 __global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__ z, long npix, int C,
                                                        double* __restrict__ acc) {
@@ -37,7 +57,7 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__
     const int cq = min(1024, C - c0) >> 2;
     const int lanes = 256 / cq;
     const int q = threadIdx.x % cq, pl = threadIdx.x / cq;
-    double s0[4] = {0, 0, 0, 0}, s1[4] = {0, 0, 0, 0};
+    double s[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // [sum z | sum z^2] of the quad's four channels
     if (pl < lanes) {
       // every block streams ONE contiguous range of pixels, four pixels per iteration (64 B per thread in
       // flight; one 16-byte load per thread kept the chip at 2 TB/s).  Measured: 3.4-3.5 TB/s on the 0.94 GB tensors, which is what a read-only stream reaches here
@@ -55,30 +75,20 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__
         for (int u = 0; u < 4; ++u)
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
-            s0[j] += (double)v[u][j];
-            s1[j] += (double)v[u][j] * (double)v[u][j];
+            s[j] += (double)v[u][j];
+            s[4 + j] += (double)v[u][j] * (double)v[u][j];
           }
       }
       for (; p < pend; p += stride) {
         const f32x4 v = *reinterpret_cast<const f32x4*>(zc + p * C);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          s0[j] += (double)v[j];
-          s1[j] += (double)v[j] * (double)v[j];
+          s[j] += (double)v[j];
+          s[4 + j] += (double)v[j] * (double)v[j];
         }
       }
     }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      __syncthreads();
-      sh[threadIdx.x] = (pl < lanes) ? (j < 4 ? s0[j] : s1[j - 4]) : 0.0;
-      __syncthreads();
-      if (threadIdx.x < cq) {
-        double t = 0.0;
-        for (int l = 0; l < lanes; ++l) t += sh[l * cq + threadIdx.x];
-        unsafeAtomicAdd(&acc[(long)(j >> 2) * C + c0 + 4 * threadIdx.x + (j & 3)], t);
-      }
-    }
+    red_tail(s, pl < lanes, cq, sh, acc + c0, C);
   }
 }
 
@@ -101,6 +111,7 @@ __global__ __launch_bounds__(256) void bn_stats_partials_kernel(const double* __
 __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ x, long npix, int C, int cs,
                                                      double* __restrict__ acc) {
   // one channel quad per thread column; supports cs >= C (channel slices)
+  __shared__ double sh[256];
   const int cq = C >> 2;
   for (int q0 = 0; q0 < cq; q0 += 256) {
     const int qn = min(256, cq - q0);
@@ -113,18 +124,7 @@ __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ x
 #pragma unroll
         for (int j = 0; j < 4; ++j) s[j] += (double)v[j];
       }
-    __shared__ double sh[256];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      __syncthreads();
-      sh[threadIdx.x] = (pl < lanes) ? s[j] : 0.0;
-      __syncthreads();
-      if (threadIdx.x < qn) {
-        double t = 0.0;
-        for (int l = 0; l < lanes; ++l) t += sh[l * qn + threadIdx.x];
-        unsafeAtomicAdd(&acc[4 * (q0 + threadIdx.x) + j], t);
-      }
-    }
+    red_tail(s, pl < lanes, qn, sh, acc + 4 * q0, 0);
   }
 }
 
@@ -134,17 +134,7 @@ __global__ void bn_finalize_kernel(const double* __restrict__ acc, long npix, in
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c == 0 && num_batches_tracked) *num_batches_tracked += 1;   // nn.BatchNorm2d's counter (one launch less per layer)
   if (c >= C) return;
-  const double n = (double)npix;
-  const double mean = acc[c] / n;
-  double var = acc[C + c] / n - mean * mean;
-  var = var > 0.0 ? var : 0.0;
-  mean_invstd[c] = (float)mean;
-  mean_invstd[C + c] = (float)(1.0 / sqrt(var + (double)eps));
-  if (running_mean) {
-    const double unbiased = npix > 1 ? var * n / (n - 1.0) : var;
-    running_mean[c] = (float)((1.0 - (double)momentum) * (double)running_mean[c] + (double)momentum * mean);
-    running_var[c] = (float)((1.0 - (double)momentum) * (double)running_var[c] + (double)momentum * unbiased);
-  }
+  bn_finalize_channel(acc[c], acc[C + c], npix, eps, momentum, C, c, mean_invstd, running_mean, running_var);
 }
 
 // bn_stats_partials + bn_finalize in ONE launch (round 6: a training step had 54 such pairs): a workgroup of 16 row lanes x 64
@@ -175,17 +165,7 @@ __global__ __launch_bounds__(1024) void bn_finalize_partials_kernel(const double
     s0 += sh[0][k][cl];
     s1 += sh[1][k][cl];
   }
-  const double n = (double)npix;
-  const double mean = s0 / n;
-  double var = s1 / n - mean * mean;
-  var = var > 0.0 ? var : 0.0;
-  mean_invstd[c] = (float)mean;
-  mean_invstd[C + c] = (float)(1.0 / sqrt(var + (double)eps));
-  if (running_mean) {
-    const double unbiased = npix > 1 ? var * n / (n - 1.0) : var;
-    running_mean[c] = (float)((1.0 - (double)momentum) * (double)running_mean[c] + (double)momentum * mean);
-    running_var[c] = (float)((1.0 - (double)momentum) * (double)running_var[c] + (double)momentum * unbiased);
-  }
+  bn_finalize_channel(s0, s1, npix, eps, momentum, C, c, mean_invstd, running_mean, running_var);
 }
 
 // y = [relu]( (z - mean) * invstd * gamma + beta [+ residual] )
@@ -197,12 +177,10 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
   if (i >= total4) return;
   const int c = (int)((i * 4) % C);
   const f32x4 v = reinterpret_cast<const f32x4*>(z)[i];
+  const BnChannels<4> bn = bn_load<4>(mi, gamma, beta, C, c);
   f32x4 o;
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const float xh = (v[j] - mi[c + j]) * mi[C + c + j];
-    o[j] = xh * gamma[c + j] + beta[c + j];
-  }
+  for (int j = 0; j < 4; ++j) o[j] = bn.y(j, v[j]);
   if (residual) {
     const f32x4 r = reinterpret_cast<const f32x4*>(residual)[i];
 #pragma unroll
@@ -216,9 +194,8 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
 }
 
 // g = dy * (y > 0 if relu); sums: [0] = sum g, [1] = sum g * xhat
-// relu with y == nullptr: the layer has no residual, so the ReLU decision y > 0 is recomputed from z with the
-// arithmetic of bn_apply ((z - mean) * invstd * gamma + beta, same operation order => same bits) instead of
-// reading y: 8 instead of 12 bytes per element.
+// relu with y == nullptr: the layer has no residual, so the ReLU decision y > 0 is recomputed from z (bn_math.h) instead
+// of reading y: 8 instead of 12 bytes per element.
 __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* __restrict__ dy, const float* __restrict__ y,
                                                             const float* __restrict__ z, const float* __restrict__ mi,
                                                             const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -229,28 +206,17 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* __restr
     const int cq = min(1024, C - c0) >> 2;
     const int lanes = 256 / cq;
     const int q = threadIdx.x % cq, pl = threadIdx.x / cq;
-    double s0[4] = {0, 0, 0, 0}, s1[4] = {0, 0, 0, 0};
+    double s[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (pl < lanes) {
       const long stride = (long)gridDim.x * lanes;
       long p = (long)blockIdx.x * lanes + pl;
-      float mean[4], invstd[4], gam[4] = {1.f, 1.f, 1.f, 1.f}, bet[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        mean[j] = mi[c0 + 4 * q + j];
-        invstd[j] = mi[C + c0 + 4 * q + j];
-        if (sign_from_z) {
-          gam[j] = gamma[c0 + 4 * q + j];
-          bet[j] = beta[c0 + 4 * q + j];
-        }
-      }
+      const BnChannels<4> bn = bn_load<4>(mi, gamma, beta, C, c0 + 4 * q, sign_from_z);
       auto add = [&](const f32x4& g, const f32x4& zz, const f32x4& yy) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          const float yv = sign_from_z ? (zz[j] - mean[j]) * invstd[j] * gam[j] + bet[j] : yy[j];
-          const float gj = yv > 0.f ? g[j] : 0.f;
-          const float xh = (zz[j] - mean[j]) * invstd[j];
-          s0[j] += (double)gj;
-          s1[j] += (double)gj * (double)xh;
+          const float gj = bn_gate(sign_from_z ? bn.y(j, zz[j]) : yy[j], g[j]);
+          s[j] += (double)gj;
+          s[4 + j] += (double)gj * (double)bn.xhat(j, zz[j]);
         }
       };
       // two pixels per iteration: six 16-byte loads per thread in flight
@@ -273,50 +239,33 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* __restr
         add(*reinterpret_cast<const f32x4*>(dy + o), *reinterpret_cast<const f32x4*>(z + o), yy);
       }
     }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      __syncthreads();
-      sh[threadIdx.x] = (pl < lanes) ? (j < 4 ? s0[j] : s1[j - 4]) : 0.0;
-      __syncthreads();
-      if (threadIdx.x < cq) {
-        double t = 0.0;
-        for (int l = 0; l < lanes; ++l) t += sh[l * cq + threadIdx.x];
-        unsafeAtomicAdd(&acc[(long)(j >> 2) * C + c0 + 4 * threadIdx.x + (j & 3)], t);
-      }
-    }
+    red_tail(s, pl < lanes, cq, sh, acc + c0, C);
   }
 }
 
 // dz = gamma * invstd * (g - sum_g / N - xhat * sum_gx / N); optionally dres = g
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restrict__ dy, const float* __restrict__ y,
                                                            const float* __restrict__ z, const float* __restrict__ mi,
-                                                           const float* __restrict__ gamma, const double* __restrict__ acc,
-                                                           int relu, long npix, long total4, int C,
-                                                           float* __restrict__ dz, float* __restrict__ dres,
-                                                           const float* __restrict__ beta, float* __restrict__ acc_f32) {
+                                                           const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                           const double* __restrict__ acc, int relu, long npix, long total4,
+                                                           int C, float* __restrict__ dz, float* __restrict__ dres,
+                                                           float* __restrict__ acc_f32) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (acc_f32 && blockIdx.x == 0)   // dbeta | dgamma as float32 for the caller (one conversion launch less per layer)
     for (int k = threadIdx.x; k < 2 * C; k += 256) acc_f32[k] = (float)acc[k];
   if (i >= total4) return;
   const int c = (int)((i * 4) % C);
+  const bool sign_from_z = relu && !y;   // (see bn_bwd_reduce_kernel)
   const f32x4 g4 = reinterpret_cast<const f32x4*>(dy)[i];
   const f32x4 zz = reinterpret_cast<const f32x4*>(z)[i];
   f32x4 yy = {1.f, 1.f, 1.f, 1.f};
   if (relu && y) yy = reinterpret_cast<const f32x4*>(y)[i];
-  if (relu && !y) {   // sign recomputed from z (see bn_bwd_reduce_kernel)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) yy[j] = (zz[j] - mi[c + j]) * mi[C + c + j] * gamma[c + j] + beta[c + j];
-  }
-  const float inv_n = 1.0f / (float)npix;
+  const BnChannels<4> bn = bn_load<4, true>(mi, gamma, beta, C, c, sign_from_z, acc, bn_inv_n(npix));
   f32x4 o, gg;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    const float g = yy[j] > 0.f ? g4[j] : 0.f;
-    const float invstd = mi[C + c + j];
-    const float xh = (zz[j] - mi[c + j]) * invstd;
-    const float mg = (float)acc[c + j] * inv_n, mgx = (float)acc[C + c + j] * inv_n;
-    o[j] = gamma[c + j] * invstd * (g - mg - xh * mgx);
-    gg[j] = g;
+    gg[j] = bn_gate(sign_from_z ? bn.y(j, zz[j]) : yy[j], g4[j]);
+    o[j] = bn.dz(j, zz[j], gg[j]);
   }
   reinterpret_cast<f32x4*>(dz)[i] = o;
   if (dres) reinterpret_cast<f32x4*>(dres)[i] = gg;
@@ -346,7 +295,7 @@ __device__ __forceinline__ void tr_split8(const float (&v)[8], unsigned short* _
   *reinterpret_cast<tr_u16x8*>(dst + e + 2 * ps) = p2;
 }
 
-__device__ __forceinline__ long tr_s3_elem(long row, int x, int c, int W, int C, int np = 3) {
+__device__ __forceinline__ long tr_s3_elem(long row, int x, int c, int W, int C, int np) {
   return ((((row * (C >> 5) + (c >> 5)) * np) * 4 + ((c & 31) >> 3)) * W + x) * 8;
 }
 
@@ -360,6 +309,31 @@ __device__ __forceinline__ void tr_split8_h2(const float (&v)[8], unsigned short
   *reinterpret_cast<tr_u32x4*>(dst + e) = (tr_u32x4){pa[0][0], pa[0][1], pb[0][0], pb[0][1]};
   *reinterpret_cast<tr_u32x4*>(dst + e + ps) = (tr_u32x4){pa[1][0], pa[1][1], pb[1][0], pb[1][1]};
 }
+
+// 8 channels (c0 ..) of pixel (row, x) into the NP planes of a (rows, C/32, NP, 4, W, 8) tensor; a kernel of the H2 format
+// collects `over` across its stores and ends with tr_report
+template <int NP>   // planes of the split copy: 3 = S3 (bf16), 2 = H2 (fp16)
+__device__ __forceinline__ void tr_store_split(const float (&v)[8], unsigned short* __restrict__ dst, long row, int x, int c0,
+                                               int W, int C, unsigned& over) {
+  const long e = tr_s3_elem(row, x, c0, W, C, NP), ps = 4L * W * 8;
+  if constexpr (NP == 3) tr_split8(v, dst, e, ps);
+  else tr_split8_h2(v, dst, e, ps, over);
+}
+
+template <int NP>
+__device__ __forceinline__ void tr_report(unsigned* __restrict__ overflow, unsigned over) {
+  if constexpr (NP == 2)
+    if (overflow && sfh_h2_out_of_range(over)) atomicOr(overflow, 1u);
+}
+
+// the <2> or <3> instance of a split kernel by the launcher's split_fmt (checked to be S3 or H2), 256 threads
+#define SFH_LAUNCH_SPLIT(kernel, split_fmt, grid, stream, ...)                                     \
+  do {                                                                                             \
+    if ((split_fmt) == SFH_FMT_H2)                                                                 \
+      hipLaunchKernelGGL(kernel<2>, grid, dim3(256), 0, (hipStream_t)(stream), __VA_ARGS__);       \
+    else                                                                                           \
+      hipLaunchKernelGGL(kernel<3>, grid, dim3(256), 0, (hipStream_t)(stream), __VA_ARGS__);       \
+  } while (0)
 
 // Thread mapping of the two kernels below: a workgroup = 64 consecutive pixels (of the flattened (rows, W) tensor) x one
 // 32-channel block, wave g of it = channel group g (8 channels): the per-channel terms are wave-uniform (scalar loads, no
@@ -386,14 +360,7 @@ __global__ __launch_bounds__(256) void bn_apply_s3_kernel(const float* __restric
                                                           unsigned short* __restrict__ y_s3, unsigned* __restrict__ overflow) {
   long p, row; int x, c0;
   const bool live = tr_block_thread(npix, W, C, p, row, x, c0);
-  float mean[8], invstd[8], gam[8], bet[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    mean[j] = mi[c0 + j];
-    invstd[j] = mi[C + c0 + j];
-    gam[j] = gamma[c0 + j];
-    bet[j] = beta[c0 + j];
-  }
+  const BnChannels<8> bn = bn_load<8>(mi, gamma, beta, C, c0);
   if (!live) return;
   const long o = p * C + c0;
   float v[8];
@@ -401,7 +368,7 @@ __global__ __launch_bounds__(256) void bn_apply_s3_kernel(const float* __restric
   for (int h = 0; h < 2; ++h) {
     const f32x4 zz = *reinterpret_cast<const f32x4*>(z + o + 4 * h);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) v[4 * h + j] = (zz[j] - mean[4 * h + j]) * invstd[4 * h + j] * gam[4 * h + j] + bet[4 * h + j];
+    for (int j = 0; j < 4; ++j) v[4 * h + j] = bn.y(4 * h + j, zz[j]);
     if (residual) {
       const f32x4 r = *reinterpret_cast<const f32x4*>(residual + o + 4 * h);
 #pragma unroll
@@ -416,39 +383,25 @@ __global__ __launch_bounds__(256) void bn_apply_s3_kernel(const float* __restric
     *reinterpret_cast<f32x4*>(y + o) = (f32x4){v[0], v[1], v[2], v[3]};
     *reinterpret_cast<f32x4*>(y + o + 4) = (f32x4){v[4], v[5], v[6], v[7]};
   }
-  if constexpr (NP == 3) {
-    tr_split8(v, y_s3, tr_s3_elem(row, x, c0, W, C), 4L * W * 8);
-  } else {
-    unsigned over = 0u;
-    tr_split8_h2(v, y_s3, tr_s3_elem(row, x, c0, W, C, 2), 4L * W * 8, over);
-    if (overflow && sfh_h2_out_of_range(over)) atomicOr(overflow, 1u);
-  }
+  unsigned over = 0u;
+  tr_store_split<NP>(v, y_s3, row, x, c0, W, C, over);
+  tr_report<NP>(overflow, over);
 }
 
 template <int NP>
 __global__ __launch_bounds__(256) void bn_bwd_apply_s3_kernel(const float* __restrict__ dy, const float* __restrict__ y,
                                                               const float* __restrict__ z, const float* __restrict__ mi,
-                                                              const float* __restrict__ gamma, const double* __restrict__ acc,
-                                                              int relu, long npix, int W, int C,
-                                                              float* __restrict__ dz, float* __restrict__ dres,
-                                                              unsigned short* __restrict__ dz_s3, unsigned* __restrict__ overflow,
-                                                              const float* __restrict__ beta, float* __restrict__ acc_f32) {
+                                                              const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                              const double* __restrict__ acc, int relu, long npix, int W,
+                                                              int C, float* __restrict__ dz, float* __restrict__ dres,
+                                                              float* __restrict__ acc_f32,
+                                                              unsigned short* __restrict__ dz_s3, unsigned* __restrict__ overflow) {
   if (acc_f32 && blockIdx.x == 0)   // dbeta | dgamma as float32 for the caller (one conversion launch less per layer)
     for (int k = threadIdx.x; k < 2 * C; k += 256) acc_f32[k] = (float)acc[k];
   long p, row; int x, c0;
   const bool live = tr_block_thread(npix, W, C, p, row, x, c0);
-  const float inv_n = 1.0f / (float)npix;
-  const bool sign_from_z = relu && !y;
-  float mean[8], invstd[8], gam[8], bet[8], mg[8], mgx[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    mean[j] = mi[c0 + j];
-    invstd[j] = mi[C + c0 + j];
-    gam[j] = gamma[c0 + j];
-    bet[j] = sign_from_z ? beta[c0 + j] : 0.f;
-    mg[j] = (float)acc[c0 + j] * inv_n;
-    mgx[j] = (float)acc[C + c0 + j] * inv_n;
-  }
+  const bool sign_from_z = relu && !y;   // (see bn_bwd_reduce_kernel)
+  const BnChannels<8> bn = bn_load<8, true>(mi, gamma, beta, C, c0, sign_from_z, acc, bn_inv_n(npix));
   if (!live) return;
   const long o = p * C + c0;
   float v[8], gg[8];
@@ -458,17 +411,10 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_s3_kernel(const float* __res
     const f32x4 zz = *reinterpret_cast<const f32x4*>(z + o + 4 * h);
     f32x4 yy = {1.f, 1.f, 1.f, 1.f};
     if (relu && y) yy = *reinterpret_cast<const f32x4*>(y + o + 4 * h);
-    if (sign_from_z) {   // sign recomputed from z (see bn_bwd_reduce_kernel)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) yy[j] = (zz[j] - mean[4 * h + j]) * invstd[4 * h + j] * gam[4 * h + j] + bet[4 * h + j];
-    }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const int k = 4 * h + j;
-      const float g = yy[j] > 0.f ? g4[j] : 0.f;
-      const float xh = (zz[j] - mean[k]) * invstd[k];
-      v[k] = gam[k] * invstd[k] * (g - mg[k] - xh * mgx[k]);
-      gg[k] = g;
+      gg[4 * h + j] = bn_gate(sign_from_z ? bn.y(4 * h + j, zz[j]) : yy[j], g4[j]);
+      v[4 * h + j] = bn.dz(4 * h + j, zz[j], gg[4 * h + j]);
     }
   }
   if (dz) {
@@ -479,13 +425,9 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_s3_kernel(const float* __res
     *reinterpret_cast<f32x4*>(dres + o) = (f32x4){gg[0], gg[1], gg[2], gg[3]};
     *reinterpret_cast<f32x4*>(dres + o + 4) = (f32x4){gg[4], gg[5], gg[6], gg[7]};
   }
-  if constexpr (NP == 3) {
-    tr_split8(v, dz_s3, tr_s3_elem(row, x, c0, W, C), 4L * W * 8);
-  } else {
-    unsigned over = 0u;
-    tr_split8_h2(v, dz_s3, tr_s3_elem(row, x, c0, W, C, 2), 4L * W * 8, over);
-    if (overflow && sfh_h2_out_of_range(over)) atomicOr(overflow, 1u);
-  }
+  unsigned over = 0u;
+  tr_store_split<NP>(v, dz_s3, row, x, c0, W, C, over);
+  tr_report<NP>(overflow, over);
 }
 
 // ------------------------------------------------------------------ ConvTranspose2d(2, stride 2) backward, first pass
@@ -536,12 +478,10 @@ __global__ __launch_bounds__(256) void s2d_split_colsum_kernel(const float* __re
 #pragma unroll
       for (int j = 0; j < 8; ++j) s[j] += (double)v[j];
 #endif
-      if constexpr (NP == 3) tr_split8(v, s_split, tr_s3_elem((long)rowu[u], xu[u], c0, w, C4), 4L * w * 8);
-      else tr_split8_h2(v, s_split, tr_s3_elem((long)rowu[u], xu[u], c0, w, C4, 2), 4L * w * 8, over);
+      tr_store_split<NP>(v, s_split, (long)rowu[u], xu[u], c0, w, C4, over);
     }
   }
-  if constexpr (NP == 2)
-    if (overflow && sfh_h2_out_of_range(over)) atomicOr(overflow, 1u);
+  tr_report<NP>(overflow, over);
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     double t = s[j];
@@ -639,14 +579,7 @@ __global__ __launch_bounds__(256) void bn_apply_pool_s3_kernel(const float* __re
   const long chunk = (long)(blockIdx.x / (unsigned)nb);
   const int g = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
   const int c0 = cb * 32 + g * 8;
-  float mean[8], invstd[8], gam[8], bet[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    mean[j] = mi[c0 + j];
-    invstd[j] = mi[C + c0 + j];
-    gam[j] = gamma[c0 + j];
-    bet[j] = beta[c0 + j];
-  }
+  const BnChannels<8> bn = bn_load<8>(mi, gamma, beta, C, c0);
   const int qh = (H + 1) >> 1, Wp = (W + 1) & ~1, Ho = H >> 1, Wo = W >> 1;
   const long q = chunk * 64 + (threadIdx.x & 63);
   const unsigned qu = q < ncols ? (unsigned)q : 0u;
@@ -667,11 +600,9 @@ __global__ __launch_bounds__(256) void bn_apply_pool_s3_kernel(const float* __re
     for (int h = 0; h < 2; ++h) {
       const f32x4 zz = *reinterpret_cast<const f32x4*>(z + o + 4 * h);
 #pragma unroll
-      for (int j = 0; j < 4; ++j)
-        vr[k][4 * h + j] = sfh_relu((zz[j] - mean[4 * h + j]) * invstd[4 * h + j] * gam[4 * h + j] + bet[4 * h + j]);
+      for (int j = 0; j < 4; ++j) vr[k][4 * h + j] = sfh_relu(bn.y(4 * h + j, zz[j]));
     }
-    if constexpr (NP == 3) tr_split8(vr[k], y_s3, tr_s3_elem(row, x, c0, W, C), 4L * W * 8);
-    else tr_split8_h2(vr[k], y_s3, tr_s3_elem(row, x, c0, W, C, 2), 4L * W * 8, over);
+    tr_store_split<NP>(vr[k], y_s3, row, x, c0, W, C, over);
   }
   // the window's maximum with maxpool2_fwd's nesting, max(max(a, b), max(c, d)) over (row 0: a b, row 1: c d) - sfh_max_nan
   // picks its second argument on ties, so the nesting decides the sign of a zero; used on the even lane (a, c are its own)
@@ -682,17 +613,14 @@ __global__ __launch_bounds__(256) void bn_apply_pool_s3_kernel(const float* __re
     m[j] = sfh_max_nan(sfh_max_nan(vr[0][j], r0), sfh_max_nan(vr[1][j], r1));
   }
   if (live && !(x & 1) && qy < Ho && (x >> 1) < Wo) {
-    const long pr = (long)b * Ho + qy;
-    if constexpr (NP == 3) tr_split8(m, p_s3, tr_s3_elem(pr, x >> 1, c0, Wo, C), 4L * Wo * 8);
-    else tr_split8_h2(m, p_s3, tr_s3_elem(pr, x >> 1, c0, Wo, C, 2), 4L * Wo * 8, over);
+    tr_store_split<NP>(m, p_s3, (long)b * Ho + qy, x >> 1, c0, Wo, C, over);
   }
-  if constexpr (NP == 2)
-    if (overflow && sfh_h2_out_of_range(over)) atomicOr(overflow, 1u);
+  tr_report<NP>(overflow, over);
 }
 
 // Backward of the same pair, up to the BatchNorm sums: dx (B,H,W,C; the gradient y already has from its other consumer
 // when accumulate != 0) += the max-pool routing of dp (first maximum of each window in scan order, as maxpool2_bwd; the
-// window values y = relu(bn(z)) are recomputed from z with bn_apply's arithmetic instead of read), and, since dx is then
+// window values y = relu(bn(z)) are recomputed from z (bn_math.h) instead of read), and, since dx is then
 // the layer's total gradient, acc[0][c] += sum g, acc[1][c] += sum g * xhat with g = dx * (y > 0): what bn_bwd_reduce would
 // find in a second pass over dx and z.  Mapping of the reductions above; one thread-iteration = a 2x2 window x 4 channels.
 __global__ __launch_bounds__(256) void pool2_bwd_bn_reduce_kernel(const float* __restrict__ z, const float* __restrict__ mi,
@@ -706,17 +634,10 @@ __global__ __launch_bounds__(256) void pool2_bwd_bn_reduce_kernel(const float* _
     const int cq = min(1024, C - c0) >> 2;
     const int lanes = 256 / cq;
     const int cqi = threadIdx.x % cq, pl = threadIdx.x / cq;
-    double s0[4] = {0, 0, 0, 0}, s1[4] = {0, 0, 0, 0};
+    double s[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (pl < lanes) {
       const int cc = c0 + 4 * cqi;
-      float mean[4], invstd[4], gam[4], bet[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        mean[j] = mi[cc + j];
-        invstd[j] = mi[C + cc + j];
-        gam[j] = gamma[cc + j];
-        bet[j] = beta[cc + j];
-      }
+      const BnChannels<4> bn = bn_load<4>(mi, gamma, beta, C, cc);
       for (long q = (long)blockIdx.x * lanes + pl; q < nquads; q += (long)gridDim.x * lanes) {
         const unsigned qrow = (unsigned)q / (unsigned)qw;
         const int qx = (int)((unsigned)q - qrow * (unsigned)qw);
@@ -737,8 +658,8 @@ __global__ __launch_bounds__(256) void pool2_bwd_bn_reduce_kernel(const float* _
           }
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
-            yv[k][j] = (zz[j] - mean[j]) * invstd[j] * gam[j] + bet[j];
-            xh[k][j] = (zz[j] - mean[j]) * invstd[j];
+            yv[k][j] = bn.y(j, zz[j]);
+            xh[k][j] = bn.xhat(j, zz[j]);
           }
         }
         if (window) {
@@ -762,24 +683,14 @@ __global__ __launch_bounds__(256) void pool2_bwd_bn_reduce_kernel(const float* _
           if (window || !accumulate) *reinterpret_cast<f32x4*>(dx + base + off[k]) = t[k];
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
-            const float gj = yv[k][j] > 0.f ? t[k][j] : 0.f;
-            s0[j] += (double)gj;
-            s1[j] += (double)gj * (double)xh[k][j];
+            const float gj = bn_gate(yv[k][j], t[k][j]);
+            s[j] += (double)gj;
+            s[4 + j] += (double)gj * (double)xh[k][j];
           }
         }
       }
     }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      __syncthreads();
-      sh[threadIdx.x] = (pl < lanes) ? (j < 4 ? s0[j] : s1[j - 4]) : 0.0;
-      __syncthreads();
-      if (threadIdx.x < cq) {
-        double tt = 0.0;
-        for (int l = 0; l < lanes; ++l) tt += sh[l * cq + threadIdx.x];
-        unsafeAtomicAdd(&acc[(long)(j >> 2) * C + c0 + 4 * threadIdx.x + (j & 3)], tt);
-      }
-    }
+    red_tail(s, pl < lanes, cq, sh, acc + c0, C);
   }
 }
 
@@ -832,7 +743,7 @@ __global__ __launch_bounds__(256) void zero_stuff2_kernel(const float* __restric
 // logits = w x + b (1x1, cin -> NC): dx[p][ci] = sum_k dl[k][p] w[k][ci];
 // acc_w[k][ci] += sum_p dl[k][p] x[p][ci]; acc_b[k] += sum_p dl[k][p].   dl is NCHW, x / dx NHWC.
 // BN (sfh_outconv_bwd_bn): x is not read - it is the BatchNorm + ReLU output of the layer in front, recomputed from that
-// layer's conv output z with bn_apply's arithmetic (same bits) - and, dx being that layer's whole gradient, the pass also leaves
+// layer's conv output z (bn_math.h) - and, dx being that layer's whole gradient, the pass also leaves
 // its backward sums [sum g | sum g * xhat], g = dx * (x > 0): sfh_bn_bwd_reduce's second pass over dx and z is not needed.
 template <int NC, bool BN>
 __global__ __launch_bounds__(256) void outconv_bwd_kernel(const float* __restrict__ x, int cin,
@@ -849,17 +760,9 @@ __global__ __launch_bounds__(256) void outconv_bwd_kernel(const float* __restric
   f32x4 wk[NC];
 #pragma unroll
   for (int k = 0; k < NC; ++k) wk[k] = *reinterpret_cast<const f32x4*>(w + k * cin + 4 * q);
-  float bmean[4], binv[4], bgam[4], bbet[4];
-  double s0[4] = {0, 0, 0, 0}, s1[4] = {0, 0, 0, 0};
-  if constexpr (BN) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      bmean[j] = bn_mi[4 * q + j];
-      binv[j] = bn_mi[cin + 4 * q + j];
-      bgam[j] = bn_gamma[4 * q + j];
-      bbet[j] = bn_beta[4 * q + j];
-    }
-  }
+  BnChannels<4> bn;
+  double s[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if constexpr (BN) bn = bn_load<4>(bn_mi, bn_gamma, bn_beta, cin, 4 * q);
   // dW / db partial sums: fp32 over at most 64 pixels of a thread, then promoted into fp64 - a workgroup covers npix / 1024
   // pixels, so a thread's chain grows with the image (about 900 terms at 1280x720 x 16) and must not stay in fp32
   float sw[NC][4], sb[NC];
@@ -897,8 +800,8 @@ __global__ __launch_bounds__(256) void outconv_bwd_kernel(const float* __restric
       if constexpr (BN) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          xh[j] = (xv[j] - bmean[j]) * binv[j];
-          xv[j] = sfh_relu((xv[j] - bmean[j]) * binv[j] * bgam[j] + bbet[j]);
+          xh[j] = bn.xhat(j, xv[j]);
+          xv[j] = sfh_relu(bn.y(j, xv[j]));
         }
       }
       f32x4 o = {0.f, 0.f, 0.f, 0.f};
@@ -916,43 +819,26 @@ __global__ __launch_bounds__(256) void outconv_bwd_kernel(const float* __restric
       if constexpr (BN) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          const float gj = xv[j] > 0.f ? o[j] : 0.f;     // (x > 0 exactly where bn_apply's pre-ReLU value is > 0)
-          s0[j] += (double)gj;
-          s1[j] += (double)gj * (double)xh[j];
+          const float gj = bn_gate(xv[j], o[j]);
+          s[j] += (double)gj;
+          s[4 + j] += (double)gj * (double)xh[j];
         }
       }
     }
-  if constexpr (BN) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      __syncthreads();
-      sh[threadIdx.x] = (pl < lanes) ? (j < 4 ? s0[j] : s1[j - 4]) : 0.0;
-      __syncthreads();
-      if (threadIdx.x < cq) {
-        double t = 0.0;
-        for (int l = 0; l < lanes; ++l) t += sh[l * cq + threadIdx.x];
-        unsafeAtomicAdd(&acc_bn[(long)(j >> 2) * cin + 4 * threadIdx.x + (j & 3)], t);
-      }
-    }
-  }
+  if constexpr (BN) red_tail(s, pl < lanes, cq, sh, acc_bn, cin);
 #pragma unroll
   for (int k = 0; k < NC; ++k) {
+    double tw[4];
 #pragma unroll
-    for (int j = 0; j < 5; ++j) {
-      __syncthreads();
-      sh[threadIdx.x] = (pl < lanes) ? (j < 4 ? dsw[k][j] + (double)sw[k][j] : dsb[k] + (double)sb[k]) : 0.0;
-      __syncthreads();
-      if (j < 4) {
-        if (threadIdx.x < cq) {
-          double t = 0.0;
-          for (int l = 0; l < lanes; ++l) t += sh[l * cq + threadIdx.x];
-          unsafeAtomicAdd(&acc_w[k * cin + 4 * threadIdx.x + j], t);
-        }
-      } else if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int l = 0; l < lanes; ++l) t += sh[l * cq];  // q == 0 lanes
-        unsafeAtomicAdd(&acc_b[k], t);
-      }
+    for (int j = 0; j < 4; ++j) tw[j] = dsw[k][j] + (double)sw[k][j];
+    red_tail(tw, pl < lanes, cq, sh, acc_w + k * cin, 0);
+    __syncthreads();
+    sh[threadIdx.x] = (pl < lanes) ? dsb[k] + (double)sb[k] : 0.0;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      double t = 0.0;
+      for (int l = 0; l < lanes; ++l) t += sh[l * cq];  // q == 0 lanes
+      unsafeAtomicAdd(&acc_b[k], t);
     }
   }
 }
@@ -1516,7 +1402,7 @@ int launch_wgrad(WgradArgs a, hipStream_t stream) {
 // blocks of 16 - three MFMAs per four pixels instead of nine - and the halo is 16 bytes per pixel (2 KB instead of 35 KB of
 // LDS: four workgroups per CU).  B fragment: lane (j = n in the block, k = pixel) reads x[pixel + tap(n)][c(n)], one
 // ds_read_b32 at a per-lane constant offset; columns 36 .. 47 read a slot that stays zero.
-// BN: the layer's BatchNorm backward rides in the tile load (bn_bwd_apply_kernel's arithmetic, same operation order): the
+// BN: the layer's BatchNorm backward rides in the tile load (bn_math.h: bn_bwd_apply_kernel's values): the
 // kernel reads dy and z (8 B per element) instead of a dz tensor that a separate pass would first write and this one read
 // back (12 + 4 B per element moved by the pair).
 template <int TH, int TW, bool BN>
@@ -1544,19 +1430,9 @@ __global__ __launch_bounds__(256, 4) void wgrad_c4_kernel(const WgradArgs a) {
   if (tid == 0) xL[HPX] = (f32x4){0.f, 0.f, 0.f, 0.f};
   f32x4 hv, zv[4];
   // (BN) the four channels m0 + 4 * (tid & 15) .. + 3 of every value this thread loads: 256 % 16 == 0
-  float bmean[4], binv[4], bgam[4], bbet[4], bmg[4], bmgx[4];
-  if constexpr (BN) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int m = min(m0 + 4 * (tid & 15) + j, a.M - 1);
-      bmean[j] = a.bn_mi[m];
-      binv[j] = a.bn_mi[a.M + m];
-      bgam[j] = a.bn_gamma[m];
-      bbet[j] = a.bn_beta[m];
-      bmg[j] = (float)a.bn_acc[m] * a.bn_inv_n;
-      bmgx[j] = (float)a.bn_acc[a.M + m] * a.bn_inv_n;
-    }
-  }
+  BnChannels<4> bn;
+  if constexpr (BN)
+    bn = bn_load<4, true>(a.bn_mi, a.bn_gamma, a.bn_beta, a.M, m0 + 4 * (tid & 15), true, a.bn_acc, a.bn_inv_n, a.M - 1);
   auto load_tile = [&](int tile) {
     const int tx = tile % a.ntx;
     const int ty = (tile / a.ntx) % a.nty;
@@ -1582,12 +1458,7 @@ __global__ __launch_bounds__(256, 4) void wgrad_c4_kernel(const WgradArgs a) {
         if constexpr (BN) {
           const f32x4 zz = *reinterpret_cast<const f32x4*>(a.bn_z + o);
 #pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const float yv = (zz[j] - bmean[j]) * binv[j] * bgam[j] + bbet[j];
-            const float g = yv > 0.f ? zv[k][j] : 0.f;
-            const float xh = (zz[j] - bmean[j]) * binv[j];
-            zv[k][j] = bgam[j] * binv[j] * (g - bmg[j] - xh * bmgx[j]);
-          }
+          for (int j = 0; j < 4; ++j) zv[k][j] = bn.dz(j, zz[j], bn_gate(bn.y(j, zz[j]), zv[k][j]));
         }
       }
     }
@@ -1709,13 +1580,8 @@ extern "C" int sfh_bn_apply(const float* z, const float* mean_invstd, const floa
     SFH_REQUIRE(split_fmt == SFH_FMT_S3 || split_fmt == SFH_FMT_H2, "bn_apply: split_fmt=%d (S3 or H2)", split_fmt);
     const long nblk = ((long)npix + 63) / 64 * (C / 32);
     SFH_REQUIRE(nblk < (1L << 31) && npix < (1L << 31) - 64, "bn_apply: tensor too large for one launch");
-    const dim3 grid((unsigned)nblk);
-    if (split_fmt == SFH_FMT_H2)
-      hipLaunchKernelGGL(bn_apply_s3_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, z, mean_invstd, gamma, beta,
-                         residual, relu, (long)npix, W, C, y, (unsigned short*)y_s3, overflow);
-    else
-      hipLaunchKernelGGL(bn_apply_s3_kernel<3>, grid, dim3(256), 0, (hipStream_t)stream, z, mean_invstd, gamma, beta,
-                         residual, relu, (long)npix, W, C, y, (unsigned short*)y_s3, overflow);
+    SFH_LAUNCH_SPLIT(bn_apply_s3_kernel, split_fmt, dim3((unsigned)nblk), stream, z, mean_invstd, gamma, beta, residual, relu,
+                     (long)npix, W, C, y, (unsigned short*)y_s3, overflow);
     return sfh_check_launch("bn_apply_s3_kernel");
   }
   const long total4 = (long)npix * C / 4;
@@ -1747,18 +1613,13 @@ extern "C" int sfh_bn_bwd_apply(const float* dy, const float* y, const float* z,
     SFH_REQUIRE(split_fmt == SFH_FMT_S3 || split_fmt == SFH_FMT_H2, "bn_bwd_apply: split_fmt=%d (S3 or H2)", split_fmt);
     const long nblk = ((long)npix + 63) / 64 * (C / 32);
     SFH_REQUIRE(nblk < (1L << 31) && npix < (1L << 31) - 64, "bn_bwd_apply: tensor too large for one launch");
-    const dim3 grid((unsigned)nblk);
-    if (split_fmt == SFH_FMT_H2)
-      hipLaunchKernelGGL(bn_bwd_apply_s3_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, dy, y, z, mean_invstd, gamma,
-                         acc, relu, (long)npix, W, C, dz, dres, (unsigned short*)dz_s3, overflow, beta, acc_f32);
-    else
-      hipLaunchKernelGGL(bn_bwd_apply_s3_kernel<3>, grid, dim3(256), 0, (hipStream_t)stream, dy, y, z, mean_invstd, gamma,
-                         acc, relu, (long)npix, W, C, dz, dres, (unsigned short*)dz_s3, overflow, beta, acc_f32);
+    SFH_LAUNCH_SPLIT(bn_bwd_apply_s3_kernel, split_fmt, dim3((unsigned)nblk), stream, dy, y, z, mean_invstd, gamma, beta, acc,
+                     relu, (long)npix, W, C, dz, dres, acc_f32, (unsigned short*)dz_s3, overflow);
     return sfh_check_launch("bn_bwd_apply_s3_kernel");
   }
   const long total4 = (long)npix * C / 4;
   hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                     dy, y, z, mean_invstd, gamma, acc, relu, (long)npix, total4, C, dz, dres, beta, acc_f32);
+                     dy, y, z, mean_invstd, gamma, beta, acc, relu, (long)npix, total4, C, dz, dres, acc_f32);
   return sfh_check_launch("bn_bwd_apply_kernel");
 }
 
@@ -1785,13 +1646,8 @@ extern "C" int sfh_s2d_split_colsum(const float* du, int batch, int h, int w, in
 #endif
   if (per < 1) per = 1;
   if (per > nchunks) per = nchunks;
-  const dim3 grid((unsigned)(per * nb));
-  if (split_fmt == SFH_FMT_H2)
-    hipLaunchKernelGGL(s2d_split_colsum_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, du, h, w, cout, npix, nchunks,
-                       (int)per, (unsigned short*)s_split, acc, acc_rows, overflow);
-  else
-    hipLaunchKernelGGL(s2d_split_colsum_kernel<3>, grid, dim3(256), 0, (hipStream_t)stream, du, h, w, cout, npix, nchunks,
-                       (int)per, (unsigned short*)s_split, acc, acc_rows, overflow);
+  SFH_LAUNCH_SPLIT(s2d_split_colsum_kernel, split_fmt, dim3((unsigned)(per * nb)), stream, du, h, w, cout, npix, nchunks,
+                   (int)per, (unsigned short*)s_split, acc, acc_rows, overflow);
   return sfh_check_launch("s2d_split_colsum_kernel");
 }
 
@@ -1805,12 +1661,8 @@ extern "C" int sfh_bn_apply_pool(const float* z, const float* mean_invstd, const
   const long nblk = (nquads + 63) / 64 * (C / 32);
   SFH_REQUIRE(nblk < (1L << 31) && nquads < (1L << 31) - 64 && (long)batch * H * W < (1L << 31),
               "bn_apply_pool: tensor too large for one launch");
-  if (split_fmt == SFH_FMT_H2)
-    hipLaunchKernelGGL(bn_apply_pool_s3_kernel<2>, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, z, mean_invstd,
-                       gamma, beta, H, W, C, nquads, (unsigned short*)y_s3, (unsigned short*)pool_s3, overflow);
-  else
-    hipLaunchKernelGGL(bn_apply_pool_s3_kernel<3>, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, z, mean_invstd,
-                       gamma, beta, H, W, C, nquads, (unsigned short*)y_s3, (unsigned short*)pool_s3, overflow);
+  SFH_LAUNCH_SPLIT(bn_apply_pool_s3_kernel, split_fmt, dim3((unsigned)nblk), stream, z, mean_invstd, gamma, beta, H, W, C,
+                   nquads, (unsigned short*)y_s3, (unsigned short*)pool_s3, overflow);
   return sfh_check_launch("bn_apply_pool_s3_kernel");
 }
 
@@ -1914,7 +1766,7 @@ extern "C" int sfh_conv_wgrad_c4_bn(const float* dy, const float* z, const float
   a.raw = raw; a.raw_n = raw_n; a.n_off = 0;
   a.ntx = a.nty = a.ntiles = a.nsplit = a.mt = a.mn = 0;
   a.bn_z = z; a.bn_mi = mean_invstd; a.bn_gamma = gamma; a.bn_beta = beta; a.bn_acc = acc;
-  a.bn_inv_n = 1.0f / (float)((long)batch * H * W);
+  a.bn_inv_n = bn_inv_n((long)batch * H * W);
   hipStream_t st = (hipStream_t)stream;
   const int t = wgrad_tile(H, W);
   return t == 0 ? launch_wgrad_c4<2, 32, true>(a, st)

@@ -1,5 +1,6 @@
-"""The stand-alone host programs of the decode cores (tests/*_host_main.cpp, which include csrc/*_core.h): found compiler and the
-sanitizer build that tests/test_jpegdec_host.py and tests/test_pngdec_host.py share.  A plain module, imported by both."""
+"""The stand-alone host programs (tests/*_host_main.cpp, which include the plain-C++ headers of csrc/: the decode cores
+*_core.h, bn_math.h): found compiler and the sanitizer build that tests/test_jpegdec_host.py, tests/test_pngdec_host.py and
+tests/test_train_kernel_host.py share.  A plain module, imported by all three."""
 import os
 import shutil
 import subprocess
@@ -17,10 +18,12 @@ def clangxx():
 
 
 def build_host_program(tmp_path_factory, name):
-    """tests/<name>_host_main.cpp -> a stand-alone executable under AddressSanitizer and UBSan, warnings as errors"""
+    """tests/<name>_host_main.cpp -> a stand-alone executable under AddressSanitizer and UBSan, warnings as errors; no
+    multiply-add is contracted, as in the library (build.py FLAGS) - bn_math.h's roundings depend on it, the integer codecs
+    do not care"""
     out = str(tmp_path_factory.mktemp(f"{name}_host") / f"{name}_host_main")
-    cmd = [clangxx(), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-Wall",
-           "-Werror", os.path.join(ROOT, "tests", f"{name}_host_main.cpp"), "-o", out]
+    cmd = [clangxx(), "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined",
+           "-fno-sanitize-recover=undefined", "-Wall", "-Werror", os.path.join(ROOT, "tests", f"{name}_host_main.cpp"), "-o", out]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
     return out

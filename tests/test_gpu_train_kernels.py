@@ -5,6 +5,9 @@ torch autograd), through the raw C entry points:
   sfh_bn_stats, sfh_bn_stats_partials, sfh_bn_finalize, sfh_bn_finalize_partials, sfh_bn_apply, sfh_bn_bwd_reduce,
   sfh_bn_bwd_apply, sfh_colsum, sfh_maxpool2_fwd, sfh_maxpool2_bwd, sfh_outconv_bwd, sfh_outconv_bwd_bn
 
+and two siblings against those: sfh_bn_bwd_apply's launch with a split copy, and sfh_conv_wgrad_c4_bn against
+sfh_bn_bwd_apply + sfh_conv_wgrad.
+
 Every output buffer a test hands to a kernel ends in a guard of 64 sentinel elements that must come back untouched; an
 output the kernel overwrites is pre-filled with NaN, one it accumulates into with non-zero values that the reference adds.
 Every bound is derived (train_kernel_ref.py gives each rounding count) and built from the reference's own absolute sums;
@@ -434,3 +437,100 @@ def test_outconv_bwd_bn(K, shape):
             acc_w=R.ratio(acc_w.result().numpy(), r["acc_w"] + c["acc_w"].numpy(), b["acc_w"]),
             acc_b=R.ratio(acc_b.result().numpy(), r["acc_b"] + c["acc_b"].numpy(), b["acc_b"]),
             acc_bn=R.ratio(acc_bn.result().numpy(), r["acc_bn"] + c["acc_bn"].numpy(), b["acc_bn"]))
+
+
+# ------------------------------------------------------------------------------------------------ siblings of bn_bwd_apply
+def _bwd_acc(c, mode):
+    """the reference's own backward sums as the fp64 accumulator [sum g | sum g xhat] the apply kernels read"""
+    y, relu = cases.bwd_inputs(c, mode)
+    s, _ = R.bn_bwd_reduce_ref(c["dy"], y, c["z"], c["mi"], c["gamma"], c["beta"], relu)
+    return torch.from_numpy(s.astype(np.float64).reshape(-1))
+
+
+@pytest.mark.parametrize("fmt", ["s3", "h2"])
+@pytest.mark.parametrize("mode", cases.BWD_MODES)
+@pytest.mark.parametrize("shape", cases.SPLIT_SHAPES, ids=cases.ident)
+def test_bn_bwd_apply_split_launch(K, shape, mode, fmt):
+    """the launch that also writes the split copy of dz (C % 32 == 0), the mirror of test_bn_apply_split_launch: its fp32 dz
+    and dres have the plain launch's bits (whose bound test_bn_bwd_apply asserts), its planes are engine.f32_to_split of the
+    plain launch's dz bit for bit in both formats, with dz == NULL the planes and dres are the same, acc_f32 is acc.float(),
+    and the overflow word stays 0"""
+    from sfh_amd import engine as E
+    lib, _ptr, _stream = K
+    B, H, W, C = shape
+    c = cases.shape_case(shape)
+    npix = c["npix"]
+    y, relu = cases.bwd_inputs(c, mode)
+    acc = _bwd_acc(c, mode)
+    dev = {k: c[k].cuda() for k in ("dy", "z", "mi", "gamma", "beta")}
+    yg, accg = (y.cuda() if y is not None else None), acc.cuda()
+    args = (_ptr(dev["dy"]), _ptr(yg), _ptr(dev["z"]), _ptr(dev["mi"]), _ptr(dev["gamma"]), _ptr(dev["beta"]), _ptr(accg), relu,
+            npix, C)
+    plain, plain_res = Guarded((B, H, W, C), torch.float32, NAN), Guarded((B, H, W, C), torch.float32, NAN)
+    assert lib.sfh_bn_bwd_apply(*args, _ptr(plain.t), _ptr(plain_res.t), None, 0, 0, None, None, _stream()) == 0
+    want, want_res = plain.result(), plain_res.result()
+    planes_want = E.f32_to_split(plain.t, fmt).cpu()
+    dtype, _, code = E._SPLIT[fmt]
+    for with_dz in (True, False):
+        dz, dres = Guarded((B, H, W, C), torch.float32, NAN), Guarded((B, H, W, C), torch.float32, NAN)
+        planes = Guarded(tuple(planes_want.shape), dtype, NAN)
+        over = Guarded((1,), torch.int32, 0)
+        a32 = Guarded((2 * C,), torch.float32, NAN)
+        assert lib.sfh_bn_bwd_apply(*args, _ptr(dz.t) if with_dz else None, _ptr(dres.t), _ptr(planes.t), W, code, _ptr(over.t),
+                                    _ptr(a32.t), _stream()) == 0
+        assert torch.equal(_bits(planes.result()), _bits(planes_want)), (fmt, with_dz)
+        assert int(over.result()[0]) == 0
+        assert torch.equal(_bits(dres.result()), _bits(want_res))
+        assert torch.equal(_bits(a32.result()), _bits(acc.float()))
+        if with_dz:
+            assert torch.equal(_bits(dz.result()), _bits(want))
+        else:
+            assert bool(torch.isnan(dz.result()).all())
+
+
+WGRAD_C4_ONE_TILE = [(1, 8, 8), (1, 4, 16), (1, 2, 32), (1, 3, 5)]      # one 8x8, 4x16, 2x32 tile; a cropped one
+WGRAD_C4_TILES = [(2, 9, 20), (3, 7, 37)]
+WGRAD_C4_M = [12, 72]                                                    # one partial channel block; two, the second partial
+
+
+@pytest.mark.parametrize("M", WGRAD_C4_M)
+@pytest.mark.parametrize("frame", WGRAD_C4_ONE_TILE + WGRAD_C4_TILES, ids=cases.ident)
+def test_conv_wgrad_c4_bn_vs_two_passes(K, frame, M):
+    """sfh_conv_wgrad_c4_bn (the first layer's BatchNorm backward applied while the gradient tiles are loaded) against the two
+    passes it replaces: sfh_bn_bwd_apply with the ReLU decision recomputed from z and the same acc, then sfh_conv_wgrad on
+    the first-layer shape (x_cs = 4; the three input channels of the fused call are stored as four with a zero, which the
+    plain entry point, N % 4 == 0, takes as N = 4: its fourth column multiplies zeros and the three real ones are compared).
+    raw is zeroed.  A single-tile frame: every address receives exactly one add, the bits are equal.  Several tiles: the order
+    of the fp32 atomics is free, |a - b| <= 2.02 * n * 2^-24 * S per output, n = B * H * W and S the fp64 sum of |dz x| over the
+    pixels of that (m, tap, c) from the two-pass dz - the bound between two fp32 summations of the same n terms."""
+    lib, _ptr, _stream = K
+    B, H, W = frame
+    c = cases.bn_case(B * H * W, M, "randn")
+    npix = c["npix"]
+    acc = _bwd_acc(c, "recompute")
+    g = torch.Generator().manual_seed(1000 * npix + M)
+    x = torch.randn(B, H, W, 4, generator=g)
+    x[..., 3] = 0.0
+    dev = {k: c[k].cuda() for k in ("dy", "z", "mi", "gamma", "beta")}
+    accg, xg = acc.cuda(), x.cuda()
+    fused = Guarded((M, 9, 4), torch.float32, 0.0)
+    assert lib.sfh_conv_wgrad_c4_bn(_ptr(dev["dy"]), _ptr(dev["z"]), _ptr(dev["mi"]), _ptr(dev["gamma"]), _ptr(dev["beta"]),
+                                    _ptr(accg), M, _ptr(xg), 3, B, H, W, _ptr(fused.t), 4, _stream()) == 0
+    dz = Guarded((B, H, W, M), torch.float32, NAN)
+    assert lib.sfh_bn_bwd_apply(_ptr(dev["dy"]), None, _ptr(dev["z"]), _ptr(dev["mi"]), _ptr(dev["gamma"]), _ptr(dev["beta"]),
+                                _ptr(accg), 1, npix, M, _ptr(dz.t), None, None, 0, 0, None, None, _stream()) == 0
+    two = Guarded((M, 9, 4), torch.float32, 0.0)
+    assert lib.sfh_conv_wgrad(_ptr(dz.t), M, M, _ptr(xg), 4, H, W, 4, 0, 0, B, H, W, 3, _ptr(two.t), 4, 0, _stream()) == 0
+    a, b = fused.result(), two.result()
+    assert bool((a[..., 3] == 0).all()) and bool((b[..., 3] == 0).all())
+    assert bool((b[..., :3] != 0).any())
+    if frame in WGRAD_C4_ONE_TILE:
+        assert torch.equal(_bits(a), _bits(b))
+        return
+    dzc = dz.result().double().abs().numpy()
+    xp = np.zeros((B, H + 2, W + 2, 4))
+    xp[:, 1:-1, 1:-1] = x.double().abs().numpy()
+    S = np.stack([np.einsum("bhwm,bhwc->mc", dzc, xp[:, ky:ky + H, kx:kx + W]) for ky in range(3) for kx in range(3)], axis=1)
+    bound = 2.02 * npix * 2.0 ** -24 * S
+    ratio = R.ratio(a.double().numpy(), b.double().numpy(), bound)
+    _report(f"conv_wgrad_c4_bn {cases.ident(frame)} M{M}", fused_vs_two_pass=ratio)

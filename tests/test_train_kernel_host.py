@@ -10,6 +10,7 @@
   * the cancellation case: where the kernels' rule var = E[z^2] - mean^2 leaves a two-pass variance.
 """
 import itertools
+import subprocess
 from fractions import Fraction
 
 import numpy as np
@@ -19,6 +20,7 @@ import torch.nn.functional as F
 
 import train_kernel_cases as cases
 import train_kernel_ref as R
+from host_program import build_host_program
 
 U40 = 2.0 ** -40
 f32 = np.float32
@@ -225,6 +227,25 @@ def test_restated_reductions_inside_bounds():
         assert v <= 1.0, k
 
 
+def _bwd_acc(c, mode):
+    """the reference's own backward sums [sum g | sum g xhat] as the fp64 accumulator bn_bwd_apply reads"""
+    y, relu = cases.bwd_inputs(c, mode)
+    sums, _ = R.bn_bwd_reduce_ref(c["dy"], y, c["z"], c["mi"], c["gamma"], c["beta"], relu)
+    return sums.astype(np.float64).reshape(-1)
+
+
+def _bwd_apply32(c, mode, acc, contract):
+    """bn_bwd_apply_kernel: (g, dz), dz = (gamma * invstd) * ((g - mg) - xhat * mgx) with mg = (float)acc * (1 / (float)n)"""
+    n, C = c["npix"], c["C"]
+    xh, mi, gam = _xhat32(c), _np32(c["mi"]), _np32(c["gamma"])
+    g = _gate32(c, mode, contract)
+    inv_n = f32(1.0) / f32(n)
+    mg, mgx = acc[:C].astype(f32) * inv_n, acc[C:].astype(f32) * inv_n
+    gm = g - mg
+    inner = _fma(-xh, np.broadcast_to(mgx, xh.shape), gm) if contract else gm - xh * mgx
+    return g, (gam * mi[C:]) * inner
+
+
 def test_restated_apply_inside_bounds():
     """bn_apply and bn_bwd_apply on every shape, residual, ReLU and backward mode"""
     worst = {"bn_apply": 0.0, "bn_bwd_apply": 0.0}
@@ -233,18 +254,11 @@ def test_restated_apply_inside_bounds():
         for with_res, relu, contract in itertools.product((False, True), (0, 1), (False, True)):
             r = R.bn_apply_ref(c["z"], c["mi"], c["gamma"], c["beta"], c["residual"] if with_res else None, relu)
             worst["bn_apply"] = max(worst["bn_apply"], R.ratio(_apply32(c, with_res, relu, contract), r["y"], R.bn_apply_bound(r)))
-        xh, mi, gam = _xhat32(c), _np32(c["mi"]), _np32(c["gamma"])
         for mode, contract in itertools.product(cases.BWD_MODES, (False, True)):
             y, relu = cases.bwd_inputs(c, mode)
-            sums, _ = R.bn_bwd_reduce_ref(c["dy"], y, c["z"], c["mi"], c["gamma"], c["beta"], relu)
-            acc = sums.astype(np.float64).reshape(-1)
+            acc = _bwd_acc(c, mode)
             r = R.bn_bwd_apply_ref(c["dy"], y, c["z"], c["mi"], c["gamma"], c["beta"], acc, relu, n)
-            g = _gate32(c, mode, contract)
-            inv_n = f32(1.0) / f32(n)
-            mg, mgx = acc[:C].astype(f32) * inv_n, acc[C:].astype(f32) * inv_n
-            gm = g - mg
-            inner = _fma(-xh, np.broadcast_to(mgx, xh.shape), gm) if contract else gm - xh * mgx
-            got = (gam * mi[C:]) * inner
+            g, got = _bwd_apply32(c, mode, acc, contract)
             worst["bn_bwd_apply"] = max(worst["bn_bwd_apply"], R.ratio(got, r["dz"], R.bn_bwd_apply_bound(r)))
             amb = r["amb"]
             assert np.array_equal(g[~amb].astype(np.float64), r["g"][~amb])                     # dres, bit for bit
@@ -428,3 +442,87 @@ def test_cancellation_case():
               f"(reference: {(dep_ref[live] / inv2[live]).max():.2e}); derived worst case {(worst_case[live] / inv2[live]).max():.2e}")
         assert (dep <= worst_case).all() and (dep_ref <= worst_case).all(), c["id"]
         assert (fin["var"][1] == 0) and fin["invstd"][1] == 1.0 / np.sqrt(float(Fraction(float(f32(cases.EPS))))), c["id"]
+
+
+# ------------------------------------------------------------------------------------------------ the restatement is the code
+# csrc/bn_math.h - the functions every training kernel and the conv epilogue call for this arithmetic - compiled for the host
+# (tests/bn_math_host_main.cpp, a child process under AddressSanitizer and UBSan) against the every-operation-rounded
+# restatements above: IEEE single and double sums, products, one division and one square root on both sides, so the bits are
+# equal and no tolerance is involved.
+@pytest.fixture(scope="module")
+def bn_math_program(tmp_path_factory):
+    return build_host_program(tmp_path_factory, "bn_math")
+
+
+def _run_bn_math(program, tmp_path, mode, dims, inputs, outputs):
+    """arrays -> raw little-endian files -> one run of the program -> the named outputs as flat arrays"""
+    np.asarray(dims, dtype="<i8").tofile(tmp_path / "dims.i64")
+    for name, a in inputs.items():
+        np.ascontiguousarray(a).astype(a.dtype.newbyteorder("<")).tofile(tmp_path / name)
+    r = subprocess.run([program, mode, str(tmp_path)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    return [np.fromfile(tmp_path / name, dtype=dt) for name, dt in outputs]
+
+
+def _same_bits(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    assert a.dtype == b.dtype and a.dtype in (np.float32, np.float64)
+    return a.shape == b.shape and np.array_equal(a.view(np.int32 if a.dtype == np.float32 else np.int64),
+                                                 b.view(np.int32 if a.dtype == np.float32 else np.int64))
+
+
+def _bn_inputs(c, *names):
+    return {f"{k}.f32": _np32(c[k]) for k in names}
+
+
+@pytest.mark.parametrize("relu", [0, 1])
+@pytest.mark.parametrize("with_res", [False, True], ids=["plain", "res"])
+@pytest.mark.parametrize("shape", cases.APPLY_SHAPES + cases.SPLIT_SHAPES, ids=cases.ident)
+def test_bn_math_header_apply_equals_restatement(bn_math_program, tmp_path, shape, with_res, relu):
+    """y of bn_math.h (bn_load, BnChannels::y, sfh_relu) == _apply32(..., contract=False), bit for bit"""
+    c = cases.shape_case(shape)
+    inputs = _bn_inputs(c, "z", "mi", "gamma", "beta", *(["residual"] if with_res else []))
+    y, = _run_bn_math(bn_math_program, tmp_path, "apply", [c["npix"], c["C"], relu, int(with_res)], inputs, [("y.f32", "<f4")])
+    assert _same_bits(y.reshape(c["npix"], c["C"]), _apply32(c, with_res, relu, False))
+
+
+@pytest.mark.parametrize("mode", cases.BWD_MODES)
+@pytest.mark.parametrize("shape", cases.APPLY_SHAPES + cases.SPLIT_SHAPES, ids=cases.ident)
+def test_bn_math_header_backward_equals_restatement(bn_math_program, tmp_path, shape, mode):
+    """g (bn_gate: the strict y > 0, on y given or recomputed; the exact zeros of the constant and the all-zero channel gate to
+    0) == _gate32(..., False) and dz (bn_dz) == _bwd_apply32(..., contract=False), bit for bit.  Without a recomputation beta is
+    not handed over: the header must not read it."""
+    c = cases.shape_case(shape)
+    y, relu = cases.bwd_inputs(c, mode)
+    acc = _bwd_acc(c, mode)
+    inputs = _bn_inputs(c, "dy", "z", "mi", "gamma", *(["beta"] if relu and y is None else []))
+    inputs["acc.f64"] = acc
+    if y is not None:
+        inputs["y.f32"] = _np32(y)
+    g, dz = _run_bn_math(bn_math_program, tmp_path, "bwd", [c["npix"], c["C"], relu, int(y is not None)], inputs,
+                         [("g.f32", "<f4"), ("dz.f32", "<f4")])
+    want_g, want_dz = _bwd_apply32(c, mode, acc, False)
+    assert _same_bits(want_g, _gate32(c, mode, False))
+    if mode == "recompute":
+        assert (want_g[:, 1:3] == 0).all()                  # beta = 0 there: the pre-activation is an exact (signed) zero
+    assert _same_bits(g.reshape(want_g.shape), want_g)
+    assert _same_bits(dz.reshape(want_dz.shape), want_dz)
+
+
+@pytest.mark.parametrize("running", [True, False], ids=["run", "norun"])
+@pytest.mark.parametrize("npix", cases.FINALIZE_NPIX)
+@pytest.mark.parametrize("C", cases.FINALIZE_C)
+def test_bn_math_header_finalize_equals_restatement(bn_math_program, tmp_path, C, npix, running):
+    """mean, invstd and the running pair of bn_finalize_channel == _finalize64(..., contract=False), bit for bit"""
+    c = cases.finalize_case(C, npix)
+    acc, rm, rv = c["acc"].numpy(), _np32(c["running_mean"]), _np32(c["running_var"])
+    inputs = {"acc.f64": acc, "params.f32": np.array([cases.EPS, cases.MOMENTUM], dtype=f32)}
+    outputs = [("mean_invstd.f32", "<f4")]
+    if running:
+        inputs.update({"running_mean.f32": rm, "running_var.f32": rv})
+        outputs += [("running_mean.out", "<f4"), ("running_var.out", "<f4")]
+    got = _run_bn_math(bn_math_program, tmp_path, "finalize", [npix, C, int(running)], inputs, outputs)
+    want = _finalize64(acc, npix, cases.EPS, cases.MOMENTUM, rm if running else None, rv if running else None, False)
+    assert _same_bits(got[0], np.concatenate([want["mean"], want["invstd"]]))
+    if running:
+        assert _same_bits(got[1], want["running_mean"]) and _same_bits(got[2], want["running_var"])
