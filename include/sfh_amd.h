@@ -523,6 +523,28 @@ int sfh_conv_wgrad_s3(const void* dz_s3, int M, const void* x_s3, int x_channels
                       int fmt, void* stream);   /* fmt: SFH_FMT_S3, or SFH_FMT_H2 (both tensors two-plane fp16, three
                                                    fp16 MFMA products per product) */
 
+/* Grouped 3x3 convolution, padding 1, no bias: nn.Conv2d(C, C, 3, stride, 1, groups=G, bias=False) with C = G * cg, the
+ * conv2 of the ResNeXt Bottleneck (models/resnet.py:108-112, groups = 32).  fp32 NHWC in and out, plain fp32 multiply-add
+ * (one rounding per product and per add; csrc/conv_grouped.hip), group g owning channels [g*cg, (g+1)*cg) of both tensors.
+ * Admitted: cg in {4, 8, 16, 32, 64}, stride 1 or 2, any groups >= 1; anything else returns SFH_E_ARG, nothing launched.
+ *
+ * sfh_pack_grouped_weights: w (G*cg, cg, 3, 3) OIHW -> packed (sfh_packed_grouped_weight_floats(G, cg) floats, -1 for a
+ *   refused geometry).  mode 0: the forward layout; mode 1: the backward-data layout (inside each group output and input
+ *   channel swapped, both taps flipped), with which sfh_conv_grouped_fwd at stride 1 maps dz -> dx.
+ * sfh_conv_grouped_fwd: src (B,H,W,C) -> dst (B,Ho,Wo,C), Ho = (H-1)/stride + 1; scale / shift per channel, both NULL
+ *   (dst = the raw accumulator) or both given: dst = [relu](acc * scale + shift), sfh_fold_bn's pair.  The terms of one
+ *   output are added in one fixed order (csrc/conv_grouped_core.h): two calls give the same bits.  wpacked, dst, scale and
+ *   shift 16-byte aligned.  A stride-2 backward-data goes through sfh_zero_stuff2 + the stride-1 call.
+ * sfh_conv_grouped_wgrad: raw (C, 9, cg) fp32, raw[o][tap][c] += sum_p dz[p][o] * src[p*stride + tap - 1][g(o)*cg + c] over
+ *   all B*Ho*Wo output pixels p; dz (B,Ho,Wo,C), src (B,H,W,C) read at its stride directly.  fp32 partial sums per
+ *   workgroup tile, one fp32 atomic add per element and workgroup (their order is free, as in sfh_conv_wgrad).          */
+int64_t sfh_packed_grouped_weight_floats(int groups, int cg);
+int sfh_pack_grouped_weights(const float* w, float* packed, int groups, int cg, int mode, void* stream);
+int sfh_conv_grouped_fwd(const float* src, const float* wpacked, const float* scale, const float* shift, int relu,
+                         float* dst, int batch, int H, int W, int groups, int cg, int stride, void* stream);
+int sfh_conv_grouped_wgrad(const float* dz, const float* src, float* raw, int batch, int H, int W, int groups, int cg,
+                           int stride, void* stream);
+
 /* Backward of OutConv (unet/unet_parts.py:74-77): dlogits NCHW (B,nc,H,W), x NHWC (B,H,W,cin);
  * dx NHWC (optional), acc_w (nc*cin doubles) += dW, acc_b (nc doubles) += db (caller-zeroed).        */
 int sfh_outconv_bwd(const float* x, int cin, const float* w, const float* dlogits_nchw, int nc, int batch,

@@ -119,6 +119,10 @@ SIGNATURES = {
                                  C.c_int, C.c_int, C.c_int, C.c_int, _p, C.c_int, C.c_int, _p]),
     "sfh_conv_wgrad_s3": (C.c_int, [_p, C.c_int, _p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                     C.c_int, C.c_int, C.c_int, _p, C.c_int, C.c_int, C.c_int, _p]),
+    "sfh_packed_grouped_weight_floats": (C.c_int64, [C.c_int, C.c_int]),
+    "sfh_pack_grouped_weights": (C.c_int, [_p, _p, C.c_int, C.c_int, C.c_int, _p]),
+    "sfh_conv_grouped_fwd": (C.c_int, [_p, _p, _p, _p, C.c_int, _p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p]),
+    "sfh_conv_grouped_wgrad": (C.c_int, [_p, _p, _p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p]),
     "sfh_outconv_bwd": (C.c_int, [_p, C.c_int, _p, _p, C.c_int, C.c_int, C.c_int, C.c_int, _p, _p, _p, _p]),
     "sfh_outconv_bwd_bn": (C.c_int, [_p, _p, _p, _p, C.c_int, _p, _p, C.c_int, C.c_int, C.c_int, C.c_int, _p, _p, _p, _p, _p]),
     "sfh_maxpool3x3s2_bwd": (C.c_int, [_p, _p, _p, C.c_int, C.c_int, C.c_int, C.c_int, _p]),

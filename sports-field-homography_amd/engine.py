@@ -1166,8 +1166,52 @@ class StemConv(_H2Layer):
         return dst
 
 
+class GroupedConv(_H2Layer):
+    """One grouped 3x3 conv, nn.Conv2d(C, C, 3, stride, 1, groups=G, bias=False) - the conv2 of a ResNeXt Bottleneck
+    (models/resnet.py:108-112) - on the plain fp32 kernel of csrc/conv_grouped.hip: fp32 NHWC in and out in every precision
+    (one rounding per product and per add is the accuracy the split formats exist to reach).  Like PackedConv it keeps
+    private copies only: the packed weights and the folded BatchNorm epilogue."""
+    fmt = None
+    escale = 1.0
+
+    def __init__(self, weight, bn, groups, stride=1, relu=True, tag="resnet", backward_data=False):
+        """bn None: the raw accumulator (training forward; backward_data=True: the stride-1 conv that maps dz -> dx)"""
+        lib = _lib.load()
+        w = _f32c(weight.detach(), "conv weight")
+        C, cg = w.shape[0], w.shape[1]
+        if C != groups * cg or tuple(w.shape[2:]) != (3, 3):
+            raise ValueError(f"grouped conv weight {tuple(w.shape)} does not match groups={groups}")
+        n = lib.sfh_packed_grouped_weight_floats(groups, cg)
+        if n <= 0 or stride not in (1, 2) or (backward_data and stride != 1):
+            raise ValueError(f"unsupported grouped conv geometry groups={groups} channels per group={cg} stride={stride}")
+        self.tag, self.groups, self.cg, self.cout, self.stride, self.relu = tag, groups, cg, C, stride, bool(relu)
+        self.order = self.overflow = None      # (set by the owning engine like every layer's; this kernel uses neither)
+        self.wpacked = torch.empty(n, dtype=torch.float32, device=w.device)
+        _lib.check(lib.sfh_pack_grouped_weights(_ptr(w), _ptr(self.wpacked), groups, cg, 1 if backward_data else 0, _stream()),
+                   "pack_grouped_weights")
+        self.scale = self.shift = None
+        if bn is not None:
+            self._fold_epilogue(None, bn, C, 1, w.device)
+
+    def run(self, src, batch, H, W, dst):
+        """src (B,H,W,C) -> dst (B,Ho,Wo,C), both contiguous float32 NHWC"""
+        ho, wo = (H - 1) // self.stride + 1, (W - 1) // self.stride + 1
+        for t, shape in ((src, (batch, H, W, self.cout)), (dst, (batch, ho, wo, self.cout))):
+            if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"grouped conv: expected a contiguous float32 tensor {shape}, got {t.dtype} {tuple(t.shape)}")
+        t = _timed(self.tag) if PackedConv.timer is not None else None
+        _lib.check(_lib.load().sfh_conv_grouped_fwd(_ptr(src), _ptr(self.wpacked), _ptr(self.scale), _ptr(self.shift),
+                                                    1 if self.relu else 0, _ptr(dst), batch, H, W, self.groups, self.cg,
+                                                    self.stride, _stream()), "conv_grouped_fwd")
+        if t is not None:
+            t.stop()
+            t.add(2.0 * batch * ho * wo * self.cout * 9 * self.cg, None,
+                  float(4 * (src.numel() + dst.numel() + self.wpacked.numel())))
+        return dst
+
+
 class ResNetEngine(_Engine):
-    """ResNetSTN forward (models/resnet.py:235-254) on the HIP kernels (BasicBlock and Bottleneck depths)."""
+    """ResNetSTN forward (models/resnet.py:235-254) on the HIP kernels (BasicBlock, Bottleneck and ResNeXt depths)."""
 
     def __init__(self, rn, in_channels, device, precision="bf16x6", overflow=None, ranges=None, options=None):
         """precision "bf16x6" / "f16x3": the 3x3 convs (stride 1 and 2) and the 1x1 stride-2 downsample convs run
@@ -1199,8 +1243,12 @@ class ResNetEngine(_Engine):
                 if hasattr(blk, "conv3"):  # Bottleneck (models/resnet.py:120-140): 1x1, 3x3 (stride), 1x1
                     width, cout = blk.conv1.out_channels, blk.conv3.out_channels
                     L[name + ".conv1"] = PC(blk.conv1.weight, None, blk.bn1, 1, cin, tag="resnet", fmt=fmt)
-                    L[name + ".conv2"] = PC(blk.conv2.weight, None, blk.bn2, 3, width, stride=blk.stride,
-                                                    tag="resnet", fmt=fmt)
+                    if blk.conv2.groups > 1:   # ResNeXt: the grouped fp32 kernel in every precision (see _run)
+                        L[name + ".conv2"] = GroupedConv(blk.conv2.weight, blk.bn2, blk.conv2.groups, stride=blk.stride,
+                                                         tag="resnet")
+                    else:
+                        L[name + ".conv2"] = PC(blk.conv2.weight, None, blk.bn2, 3, width, stride=blk.stride,
+                                                tag="resnet", fmt=fmt)
                     L[name + ".conv3"] = PC(blk.conv3.weight, None, blk.bn3, 1, width, tag="resnet",
                                                     fmt=fmt)  # ReLU after the residual add
                 else:  # BasicBlock (models/resnet.py:64-82)
@@ -1291,7 +1339,25 @@ class ResNetEngine(_Engine):
             else:
                 idn, nidn = x, nx
             out, nout = act(name + ".out", ho, wo, cout)
-            if bottleneck:
+            if bottleneck and isinstance(L[name + ".conv2"], GroupedConv):
+                # the grouped conv2 reads and writes fp32: conv1 writes fp32 itself (the split kernels take an fp32
+                # destination); in the split precisions conv2's output goes through one conversion into t2, which keeps
+                # its range word and exponent.  Both steps count as writers of t2, so that a pass resumed for a saturated
+                # t2 starts at conv2 and the fp32 buffer between them can be shared by all blocks of one shape.
+                gc = L[name + ".conv2"]
+                t1 = ws.get(name + ".t1.f32", (B, h, w, width))
+                conv(name + ".conv1", x, nx, h, w, t1, None)
+                if s3:
+                    t2, nt2 = act(name + ".t2", ho, wo, width)
+                    t2f = ws.get(f"grouped.f32.{ho}x{wo}x{width}", (B, ho, wo, width))
+                    do((nt2,), lambda gc=gc, t1=t1, t2f=t2f, h=h, w=w: gc.run(t1, B, h, w, t2f))
+                    do((nt2,), lambda t2f=t2f, t2=t2, nt2=nt2: _f32_to_split_into(t2f, t2, self.overflow, rg.exp(nt2),
+                                                                                  rg.word_ptr(nt2)))
+                else:
+                    t2, nt2 = ws.get(name + ".t2", (B, ho, wo, width)), None
+                    do((), lambda gc=gc, t1=t1, t2=t2, h=h, w=w: gc.run(t1, B, h, w, t2))
+                conv(name + ".conv3", t2, nt2, ho, wo, out, nout, residual=idn, nres=nidn)
+            elif bottleneck:
                 t1, nt1 = act(name + ".t1", h, w, width)
                 conv(name + ".conv1", x, nx, h, w, t1, nt1)
                 t2, nt2 = act(name + ".t2", ho, wo, width)

@@ -100,17 +100,17 @@ class BasicBlock(_NoForward):
 
 
 class Bottleneck(_NoForward):
-    """1x1 -> 3x3 (carries the stride) -> 1x1 (x4 channels) + BN, residual add
+    """1x1 -> 3x3 (carries the stride; grouped in the ResNeXt depths) -> 1x1 (x4 channels) + BN, residual add
     (reference: models/resnet.py:85-140, the "ResNet V1.5" placement of the stride)."""
 
     expansion = 4
 
-    def __init__(self, inplanes, planes, stride=1, downsample=None, base_width=64):
+    def __init__(self, inplanes, planes, stride=1, downsample=None, groups=1, base_width=64):
         super().__init__()
-        width = int(planes * (base_width / 64.0))
+        width = int(planes * (base_width / 64.0)) * groups
         self.conv1 = nn.Conv2d(inplanes, width, 1, bias=False)
         self.bn1 = nn.BatchNorm2d(width)
-        self.conv2 = nn.Conv2d(width, width, 3, stride=stride, padding=1, bias=False)
+        self.conv2 = nn.Conv2d(width, width, 3, stride=stride, padding=1, groups=groups, bias=False)
         self.bn2 = nn.BatchNorm2d(width)
         self.conv3 = nn.Conv2d(width, planes * self.expansion, 1, bias=False)
         self.bn3 = nn.BatchNorm2d(planes * self.expansion)
@@ -119,19 +119,21 @@ class Bottleneck(_NoForward):
         self.stride = stride
 
 
-# name -> (block, blocks per stage, width_per_group); reference table models/resnet.py:361-371
+# name -> (block, blocks per stage, width_per_group, groups); reference table models/resnet.py:361-371
 # ('resnet52' is the reference's key for its ResNet-152 constructor).  Through the reference's
 # factory only resnet18/34/50 are constructible with an explicit in_channels (the deeper and wide
 # constructors do not take that argument, models/resnet.py:297-355); they are accepted here.
 _RESNET_VARIANTS = {
-    "resnet18": (BasicBlock, (2, 2, 2, 2), 64),
-    "resnet34": (BasicBlock, (3, 4, 6, 3), 64),
-    "resnet50": (Bottleneck, (3, 4, 6, 3), 64),
-    "resnet101": (Bottleneck, (3, 4, 23, 3), 64),
-    "resnet52": (Bottleneck, (3, 8, 36, 3), 64),
-    "resnet152": (Bottleneck, (3, 8, 36, 3), 64),
-    "wide_resnet50_2": (Bottleneck, (3, 4, 6, 3), 128),
-    "wide_resnet101_2": (Bottleneck, (3, 4, 23, 3), 128),
+    "resnet18": (BasicBlock, (2, 2, 2, 2), 64, 1),
+    "resnet34": (BasicBlock, (3, 4, 6, 3), 64, 1),
+    "resnet50": (Bottleneck, (3, 4, 6, 3), 64, 1),
+    "resnet101": (Bottleneck, (3, 4, 23, 3), 64, 1),
+    "resnet52": (Bottleneck, (3, 8, 36, 3), 64, 1),
+    "resnet152": (Bottleneck, (3, 8, 36, 3), 64, 1),
+    "wide_resnet50_2": (Bottleneck, (3, 4, 6, 3), 128, 1),
+    "wide_resnet101_2": (Bottleneck, (3, 4, 23, 3), 128, 1),
+    "resnext50_32x4d": (Bottleneck, (3, 4, 6, 3), 4, 32),
+    "resnext101_32x8d": (Bottleneck, (3, 4, 23, 3), 8, 32),
 }
 _RESNET_LAYERS = {k: v[1] for k, v in _RESNET_VARIANTS.items()}
 
@@ -139,18 +141,18 @@ _RESNET_LAYERS = {k: v[1] for k, v in _RESNET_VARIANTS.items()}
 class ResNetSTN(_NoForward):
     """ResNet regressor that emits a 3x3 homography (reference: models/resnet.py:143-257).
 
-    BasicBlock and Bottleneck depths run on the HIP path; the grouped-convolution ResNeXt
-    variants (models/resnet.py:318-337) do not.
+    Every key of the reference's table runs on the HIP path: the BasicBlock and Bottleneck depths, the wide ones, and the
+    ResNeXt depths (models/resnet.py:318-337), whose Bottleneck.conv2 is a 3x3 convolution in 32 groups
+    (csrc/conv_grouped.hip); conv2.weight is then (width, width / 32, 3, 3) as in the reference's checkpoints.
     """
 
     def __init__(self, name="resnet34", in_channels=4):
         super().__init__()
         if name not in _RESNET_VARIANTS:
             raise NotImplementedError(
-                f"resnet_name={name!r}: only {sorted(_RESNET_VARIANTS)} run on the HIP path "
-                "(ResNeXt needs grouped convolutions)"
+                f"resnet_name={name!r}: only {sorted(_RESNET_VARIANTS)} run on the HIP path"
             )
-        self.block, layers, self.base_width = _RESNET_VARIANTS[name]
+        self.block, layers, self.base_width, self.groups = _RESNET_VARIANTS[name]
         self.inplanes = 64
         self.conv0 = nn.Conv2d(in_channels, 64, kernel_size=7, stride=2, padding=3, bias=False)
         self.bn1 = nn.BatchNorm2d(64)
@@ -165,7 +167,8 @@ class ResNetSTN(_NoForward):
         self._init_weights()
 
     def _stage(self, planes, blocks, stride):
-        block, kw = self.block, ({} if self.block is BasicBlock else {"base_width": self.base_width})
+        block = self.block
+        kw = {} if block is BasicBlock else {"groups": self.groups, "base_width": self.base_width}
         down = None
         if stride != 1 or self.inplanes != planes * block.expansion:
             down = nn.Sequential(

@@ -31,7 +31,8 @@ from .options import Options
 BN_MOMENTUM = 0.1  # nn.BatchNorm2d default, unchanged by the reference
 
 # Test hook: set to a dict and the next training pass leaves references to the ResNet blocks' activations
-# ("layer4.1": {"in", "t", "out"} NHWC tensors) and the theta gradient it starts its backward pass from ("dtheta").
+# ("layer4.1": {"in", "t", "out"} NHWC tensors, for a Bottleneck also "t1", the activation between conv1 and conv2; "stem": the
+# stem's activation in front of the max-pool) and the theta gradient it starts its backward pass from ("dtheta").
 # tests/test_gpu_configs.py uses it to re-derive the gradients of the last ResNet stage in fp64 under the ReLU decisions
 # this pass took.  None (the default): nothing is kept.
 CAPTURE = None
@@ -494,8 +495,13 @@ def conv_bn_act(tape, names, conv, bn, srcs, B, H, W, relu=True, residual=None, 
 
     srcs: [(Act or NHWC tensor, channels used, pad_top, pad_left)], one or two (skip first, like torch.cat
     in unet/unet_parts.py:67).  Stride-1 3x3 / 1x1 convs, and stride-2 ones via zero-stuffing in the
-    backward."""
+    backward.  A grouped conv (conv.groups > 1: 3x3, one whole source, no residual, no fused pool) runs on the fp32 leg
+    in every precision (_grouped_conv_bn_act)."""
     lib = tape.lib
+    if conv.groups > 1:
+        if len(srcs) != 1 or srcs[0][1] != conv.in_channels or residual is not None or pool:
+            raise ValueError("conv_bn_act: a grouped conv takes one whole source, no residual and no fused pool")
+        return _grouped_conv_bn_act(tape, names, conv, bn, srcs[0][0], B, H, W, relu, need_dx, s3_out, f32_out)
     ks, stride = conv.kernel_size[0], conv.stride[0]
     w = conv.weight.detach()
     cout = w.shape[0]
@@ -620,6 +626,51 @@ def conv_bn_act(tape, names, conv, bn, srcs, B, H, W, relu=True, residual=None, 
 
     tape.push(pool_backward_fused)
     return y, pooled
+
+
+def _grouped_conv_bn_act(tape, names, conv, bn, src, B, H, W, relu, need_dx, s3_out, f32_out):
+    """conv_bn_act for a grouped 3x3 conv (the conv2 of a ResNeXt Bottleneck; csrc/conv_grouped.hip): forward, backward-filter
+    and backward-data all run on the fp32 leg in every training precision; BatchNorm as for any layer."""
+    lib = tape.lib
+    G, stride = conv.groups, conv.stride[0]
+    w = conv.weight.detach()
+    C, cg = w.shape[0], w.shape[1]
+    if conv.kernel_size != (3, 3) or conv.padding != (1, 1) or conv.bias is not None or conv.in_channels != C:
+        raise ValueError("conv_bn_act: the grouped kernel covers nn.Conv2d(C, C, 3, stride, 1, groups=G, bias=False)")
+    t0 = tape.act(src)
+    x0 = t0.need_f32("conv_bn_act (grouped)")
+    ho, wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    z = _empty((B, ho, wo, C), x0)
+    E.GroupedConv(w, None, G, stride=stride, relu=False, tag="train_fwd").run(x0, B, H, W, z)
+    y, mi, _ = _bn_forward(lib, z, bn, relu, None, tape, want_s3=s3_out, want_f32=f32_out)
+    if relu:
+        y.bn, y.sole = (z, mi, bn), not f32_out
+
+    def backward():
+        dy = tape.pop_grad(y)
+        if dy is None:
+            raise RuntimeError("conv_bn_act: no gradient reached this layer")
+        table, sums, y.sums_table, y.sums = y.sums_table, y.sums, None, None
+        dz, dgamma, dbeta, _, _ = _bn_backward(lib, tape, dy, None, z, mi, bn, relu, False, sums_table=table, sums=sums)
+        g = tape.param_grads
+        g[names(bn.weight)], g[names(bn.bias)] = dgamma, dbeta
+        raw = tape.zeros((C, 9, cg), z)
+        _lib.check(lib.sfh_conv_grouped_wgrad(_ptr(dz), _ptr(x0), _ptr(raw), B, H, W, G, cg, stride, _stream()),
+                   "conv_grouped_wgrad")
+        # a strided view, as for the dense layers: the consumer's copy does the permute
+        g[names(conv.weight)] = raw.view(C, 3, 3, cg).permute(0, 3, 1, 2)
+        if not need_dx:
+            return
+        if stride == 2:  # zero-stuff dz to the input resolution: stride-1 backward from here on
+            u = _empty((B, H, W, C), dz)
+            _lib.check(lib.sfh_zero_stuff2(_ptr(dz), _ptr(u), B, ho, wo, H, W, C, _stream()), "zero_stuff2")
+            dz = u
+        dx = _empty((B, H, W, C), dz)
+        E.GroupedConv(w, None, G, relu=False, tag="bwd_data", backward_data=True).run(dz, B, H, W, dx)
+        tape.add_grad(t0, dx)
+
+    tape.push(backward)
+    return y
 
 
 def maxpool2(tape, x):
@@ -825,7 +876,8 @@ class UNetTrainer:
 
 # --------------------------------------------------------------------------------------- ResNetSTN
 class ResNetTrainer:
-    """ResNetSTN (models/resnet.py:235-254) in training mode; BasicBlock and Bottleneck depths."""
+    """ResNetSTN (models/resnet.py:235-254) in training mode; BasicBlock, Bottleneck and ResNeXt depths (a grouped conv2
+    is conv_bn_act's business)."""
 
     def __init__(self, net):
         self.net = net
@@ -855,6 +907,8 @@ class ResNetTrainer:
             pc.run(s2d, B, H2, W2, z0)
         c1, mi0, _ = _bn_forward(lib, z0, rn.bn1, True, None, tape, want_s3=False)
         c1 = c1.need_f32("ResNetTrainer")
+        if CAPTURE is not None:
+            CAPTURE["stem"] = c1
         h, w = (H2 - 1) // 2 + 1, (W2 - 1) // 2 + 1
         x = x_pool = Act((B, h, w, 64), f32=_empty((B, h, w, 64), stn_in))
         _lib.check(lib.sfh_maxpool3x3s2_fwd(_ptr(c1), _ptr(x.f32), B, H2, W2, 64, st()), "maxpool3x3s2")
@@ -890,9 +944,10 @@ class ResNetTrainer:
                 ho, wo = (h - 1) // s + 1, (w - 1) // s + 1
                 x_in = x
                 idn = cba(blk.downsample[0], blk.downsample[1], x, h, w, relu=False) if blk.downsample is not None else x
+                t1 = None
                 if hasattr(blk, "conv3"):
-                    t = cba(blk.conv1, blk.bn1, x, h, w)
-                    t = cba(blk.conv2, blk.bn2, t, h, w)
+                    t1 = cba(blk.conv1, blk.bn1, x, h, w)
+                    t = cba(blk.conv2, blk.bn2, t1, h, w)
                     x = cba(blk.conv3, blk.bn3, t, ho, wo, residual=idn)
                 else:
                     # t feeds conv2 only (3x3 stride 1): forward, backward-data and backward-filter read its split copy
@@ -902,6 +957,8 @@ class ResNetTrainer:
                     x = cba(blk.conv2, blk.bn2, t, ho, wo, residual=idn)
                 if CAPTURE is not None:
                     CAPTURE[f"layer{li}.{bi}"] = {"in": x_in.f32, "t": t.f32, "out": x.f32}
+                    if t1 is not None:      # Bottleneck: the activation between conv1 and conv2 as well
+                        CAPTURE[f"layer{li}.{bi}"]["t1"] = t1.f32
                 h, w = ho, wo
         feat, featf = x, x.need_f32("ResNetTrainer")
         C = feat.shape[3]
