@@ -115,9 +115,10 @@ typedef struct sfh_conv_desc {
   int32_t reverse_tiles;
   /* OutConv fused behind the last 3x3 conv (sfh_conv_s3_fwd, cout == 64, plain output): with head_w set the
    * launch also computes logits = head_w (head_nc x 64) . y + head_b for its pixels and writes them NCHW to
-   * head_logits (B,head_nc,H,W) and, if head_stn is set, cat((logits, frame)) zero-padded to 8 channels to
-   * head_stn (B,H,W,8) (frame: head_frame, fp32 NHWC with 4 stored channels) - what sfh_outconv_fwd does in
-   * a second pass over y.  head_skip_dst != 0: y itself is not stored. */
+   * head_logits (B,head_nc,H,W) and, if head_stn is set, cat((logits, frame)) zero-padded to cs channels to
+   * head_stn (B,H,W,cs), cs = (head_nc + 3) rounded up to 4: 8 up to 5 classes, 12 for 6..8 (frame: head_frame, fp32
+   * NHWC with 4 stored channels) - what sfh_outconv_fwd does in a second pass over y.  head_skip_dst != 0: y itself
+   * is not stored. */
   const float* head_w;
   const float* head_b;
   int32_t head_nc, head_skip_dst;
@@ -384,7 +385,7 @@ int64_t sfh_ce_workspace_floats(int batch, int H, int W);
 int sfh_consistency_ce_fwd(const float* logits, const int32_t* mask, int batch, int nc, int H,
                            int W, int hm, int wm, float* partial, float* score, void* stream);
 
-/* The two calls above fused for predict()'s usual cases (nearest mode, 4 classes; the logits (B,nc,hl,wl) have the warp's size,
+/* The two calls above fused for predict()'s usual cases (nearest mode, 4, 7 or 8 classes; the logits (B,nc,hl,wl) have the warp's size,
  * or exactly half of it in both directions - predict.py's default geometry, where the reference scores through the nearest-
  * resized mask, i.e. logit pixel (y, x) against mask pixel (2y, 2x); models/reconstructor.py:223-240): out_i32 (B,h,w) = trunc(warp * out_scale) bit-identical to sfh_homography_warp_fwd, and
  * score (B) = mean over the pixels of cross_entropy(logits[:, :, y, x], out_i32[y, x]) - every wave scores the pixels it warps
@@ -675,6 +676,12 @@ int sfh_stem7x7_fwd(const sfh_conv_desc* d, void* stream);
 int64_t sfh_packed_stem_weight_bytes(void);
 int sfh_pack_stem_weights(const float* w, void* packed, int cin, int fmt, int wexp, void* stream);   /* fmt: SFH_FMT_S3, or
     SFH_FMT_H2 (planes of w * 2^wexp; the caller folds 2^-(wexp + h2_exp_src) into the layer's scale) */
+/* 9..16 input channels (6..8 mask classes + frame, img+mask+uv): the same entry with d->cs0 = 12 or 16 stored channels
+ * (d->c0 <= d->cs0, stored channels >= c0 zero) runs the 16-channel instance - 2 taps x 16 channels per MFMA, 25 k-steps - on
+ * weights packed by sfh_pack_stem16_weights (cin <= 16, otherwise as sfh_pack_stem_weights) into
+ * sfh_packed_stem16_weight_bytes() bytes.  Any other cs0, or c0 > cs0, is refused before anything is launched. */
+int64_t sfh_packed_stem16_weight_bytes(void);
+int sfh_pack_stem16_weights(const float* w, void* packed, int cin, int fmt, int wexp, void* stream);
 
 /* Device calibration probe (bench.py `device_calibration`; not on the hot path): `workgroups` x 4 waves each run `iters` x 64
  * register-resident v_mfma_f32_16x16x32_f16 (fp16 operands with random mantissas): executed FLOPs = workgroups * 4 * iters *

@@ -568,7 +568,7 @@ __global__ __launch_bounds__(C::NT, (C::NP == 2 && !DB) ? SFH_H2_WAVES_PER_SIMD 
             lgt[k] = k < nc ? hl[(s * 16 + q) * 8 + k] + hl[((C::NSUBT + s) * 16 + q) * 8 + k] + d.head_b[k] : 0.f;
           const long hw = (long)g.Ho * g.Wo, pix = (long)y * g.Wo + x;
           for (int k = 0; k < nc; ++k) d.head_logits[((long)b * nc + k) * hw + pix] = lgt[k];
-          if (d.head_stn) {
+          if (d.head_stn && nc <= 5) {
             const f32x4 fr = *reinterpret_cast<const f32x4*>(d.head_frame + ((long)b * hw + pix) * 4);
             float v8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
             for (int k = 0; k < nc; ++k) v8[k] = lgt[k];
@@ -576,6 +576,18 @@ __global__ __launch_bounds__(C::NT, (C::NP == 2 && !DB) ? SFH_H2_WAVES_PER_SIMD 
             float* o = d.head_stn + ((long)b * hw + pix) * 8;
             *reinterpret_cast<f32x4*>(o) = (f32x4){v8[0], v8[1], v8[2], v8[3]};
             *reinterpret_cast<f32x4*>(o + 4) = (f32x4){v8[4], v8[5], v8[6], v8[7]};
+          } else if (d.head_stn) {
+            // 6..8 classes: rows of ceil4(nc + 3) = 12 floats, zeros behind the frame (lgt[k >= nc] is 0 already)
+            const f32x4 fr = *reinterpret_cast<const f32x4*>(d.head_frame + ((long)b * hw + pix) * 4);
+            float v4[4] = {0.f, 0.f, 0.f, 0.f};
+            for (int k = 0; k < 3; ++k) {
+              if (nc + k < 8) lgt[nc + k] = fr[k];
+              else v4[nc + k - 8] = fr[k];
+            }
+            float* o = d.head_stn + ((long)b * hw + pix) * 12;
+            *reinterpret_cast<f32x4*>(o) = (f32x4){lgt[0], lgt[1], lgt[2], lgt[3]};
+            *reinterpret_cast<f32x4*>(o + 4) = (f32x4){lgt[4], lgt[5], lgt[6], lgt[7]};
+            *reinterpret_cast<f32x4*>(o + 8) = (f32x4){v4[0], v4[1], v4[2], v4[3]};
           }
         }
       }
@@ -1226,7 +1238,7 @@ extern "C" int sfh_conv_s3_fwd(const sfh_conv_desc* dp, void* stream_) {
   SFH_REQUIRE(!d.shift_border || d.ksize == 2, "conv_s3_fwd: shift_border exists only for the 2x2 up-scatter conv");
   if (d.head_w)
     SFH_REQUIRE(d.ksize == 3 && d.stride == 1 && d.cout == 64 && d.out_mode == SFH_OUT_NHWC && !d.dst_pool && d.head_b &&
-                    d.head_logits && d.head_nc >= 1 && d.head_nc <= 8 && (!d.head_stn || (d.head_frame && d.head_nc <= 5)),
+                    d.head_logits && d.head_nc >= 1 && d.head_nc <= 8 && (!d.head_stn || (d.head_frame && d.head_nc <= 8)),
                 "conv_s3_fwd: the fused OutConv head needs a 3x3 stride-1 conv with 64 output channels and a plain output");
   SFH_REQUIRE(!d.head_skip_dst || d.head_w, "conv_s3_fwd: head_skip_dst without a head");
   SFH_REQUIRE(!d.acc_init || (d.ksize == 3 && d.stride == 1 && d.out_mode == SFH_OUT_NHWC && !(d.ksplit > 1) &&

@@ -617,7 +617,7 @@ extern "C" int sfh_warp_consistency_fwd(const float* theta, const float* tmpl, i
   SFH_REQUIRE(theta && tmpl && logits && out_i32 && partial && score, "warp_consistency: null pointer");
   SFH_REQUIRE(batch > 0 && batch <= 65535 && h > 1 && w > 1 && ht > 0 && wt > 0,
               "warp_consistency: bad geometry b=%d h=%d w=%d ht=%d wt=%d", batch, h, w, ht, wt);
-  SFH_REQUIRE(nc == 4, "warp_consistency: nc=%d (the fused kernel is built for 4 classes; use sfh_homography_warp_fwd + "
+  SFH_REQUIRE(nc == 4 || nc == 7 || nc == 8, "warp_consistency: nc=%d (the fused kernel is built for 4 classes; use sfh_homography_warp_fwd + "
               "sfh_consistency_ce_fwd otherwise)", nc);
   SFH_REQUIRE((hl == h && wl == w) || (2 * hl == h && 2 * wl == w),
               "warp_consistency: logits %dx%d against a warp of %dx%d (the same size, or exactly half of it in both directions)", wl, hl, w, h);
@@ -631,20 +631,28 @@ extern "C" int sfh_warp_consistency_fwd(const float* theta, const float* tmpl, i
   int rpt = 8;
   while (rpt > 2 && segs * sfh_cdiv(h, rpt) < SFH_WARP_MIN_WAVES) rpt >>= 1;
   const dim3 grid((unsigned)sfh_cdiv(w, 64 * J), (unsigned)sfh_cdiv(h, 4 * rpt), (unsigned)batch);
-#define SFH_WCE(JJ, RR)                                                                                             \
+#define SFH_WCE_NC(JJ, RR, NCC)                                                                                    \
   do {                                                                                                              \
     if (ls == 1)                                                                                                    \
-      hipLaunchKernelGGL((warpce_kernel<JJ, RR, 4, 1>), grid, dim3(256), 0, (hipStream_t)stream, theta, tmpl,         \
+      hipLaunchKernelGGL((warpce_kernel<JJ, RR, NCC, 1>), grid, dim3(256), 0, (hipStream_t)stream, theta, tmpl,      \
                          (long)tmpl_bstride, ht, wt, h, w, rdw, rdh, out_scale, logits, out_i32, partial);           \
     else                                                                                                            \
-      hipLaunchKernelGGL((warpce_kernel<JJ, RR, 4, 2>), grid, dim3(256), 0, (hipStream_t)stream, theta, tmpl,         \
+      hipLaunchKernelGGL((warpce_kernel<JJ, RR, NCC, 2>), grid, dim3(256), 0, (hipStream_t)stream, theta, tmpl,      \
                          (long)tmpl_bstride, ht, wt, h, w, rdw, rdh, out_scale, logits, out_i32, partial);           \
+  } while (0)
+  // the class count is a template parameter (the logits of a pixel live in registers): 4, and the 7 / 8 of the wide templates
+#define SFH_WCE(JJ, RR)                                                         \
+  do {                                                                          \
+    if (nc == 4) SFH_WCE_NC(JJ, RR, 4);                                          \
+    else if (nc == 7) SFH_WCE_NC(JJ, RR, 7);                                     \
+    else SFH_WCE_NC(JJ, RR, 8);                                                  \
   } while (0)
   if (J == 5) {
     if (rpt == 8) SFH_WCE(5, 8); else if (rpt == 4) SFH_WCE(5, 4); else SFH_WCE(5, 2);
   } else {
     if (rpt == 8) SFH_WCE(4, 8); else if (rpt == 4) SFH_WCE(4, 4); else SFH_WCE(4, 2);
   }
+#undef SFH_WCE_NC
 #undef SFH_WCE
   int rc = sfh_check_launch("warpce_kernel");
   if (rc) return rc;

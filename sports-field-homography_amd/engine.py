@@ -924,7 +924,7 @@ class UNetEngine(_Engine):
 
     def run(self, x, want_stn_in=False, want_argmax=False, want_uv=False, stn_slot=0):
         """x: (B,3,H,W) float32 NCHW on the GPU.  Returns dict with logits (NCHW, fresh),
-        and optionally stn_in (NHWC8 workspace), argmax (B,H,W uint8), uv, plus the NHWC
+        and optionally stn_in (NHWC workspace of ceil4(nc + 3) stored channels), argmax (B,H,W uint8), uv, plus the NHWC
         workspace tensors x_top / y4 for callers that need them (x_top_exp: exponent of x_top if it is H2)."""
         with _stream_scope():
             return self._run(x, want_stn_in, want_argmax, want_uv, stn_slot)
@@ -1005,9 +1005,11 @@ class UNetEngine(_Engine):
             pooled.append(p)
         y, ny = feats[4]
         logits = torch.empty((B, self.nc, H, W), dtype=torch.float32, device=x.device)
-        if want_stn_in and self.nc + 3 > 8:
-            raise NotImplementedError("mask_classes > 5 with resnet_input='img+mask' needs a wider STN input buffer")
-        stn_in = ws.get("stn_in" if not stn_slot else f"stn_in{stn_slot}", (B, H, W, 8), zero=True) if want_stn_in else None
+        # cat((logits, frame)) zero-padded to a multiple of 4 stored channels - ResNetEngine.cs_in's rule: 8 up to 5 classes,
+        # 12 for 6..8 (the padding channels are zeroed once here and rewritten as zeros by every pass)
+        stn_cs = -(-(self.nc + 3) // 4) * 4
+        stn_in = (ws.get("stn_in" if not stn_slot else f"stn_in{stn_slot}", (B, H, W, stn_cs), zero=True)
+                  if want_stn_in else None)
         head = None
         if self.fuse_head and not want_argmax and not (want_uv and self.outuv is not None):
             head = {"w": self.outc_w, "b": self.outc_b, "nc": self.nc, "logits": logits, "stn": stn_in,
@@ -1083,7 +1085,7 @@ class UNetEngine(_Engine):
         if head is None:
             do((), lambda y=y: _lib.check(
                 lib.sfh_outconv_fwd(_ptr(y), 64, _ptr(self.outc_w), _ptr(self.outc_b), self.nc, B, H, W,
-                                    _ptr(logits), _ptr(amax), _ptr(stn_in), 8 if want_stn_in else 0,
+                                    _ptr(logits), _ptr(amax), _ptr(stn_in), stn_cs if want_stn_in else 0,
                                     _ptr(xin) if want_stn_in else None, 4, _stream()), "outconv"))
         else:
             out.pop("y4")   # not materialised: the fused head consumed it in registers
@@ -1108,29 +1110,35 @@ class UNetEngine(_Engine):
 
 class StemConv(_H2Layer):
     """ResNetSTN stem (7x7 s2 conv + BatchNorm + ReLU) on the tap-packed split-bf16 kernel (csrc/stem.hip):
-    reads the fp32 NHWC STN input (8 stored channels) directly, no space-to-depth copy."""
+    reads the fp32 NHWC STN input (8 stored channels; 12 or 16 for 9..16 input channels) directly, no space-to-depth copy."""
 
-    def __init__(self, conv, bn, cin, tag="resnet", fmt="s3", overflow=None, wexp=None):
-        """fmt: arithmetic of the kernel - "s3": the input is split into three bf16 planes, six products; "h2": two
+    def __init__(self, conv, bn, cin, tag="resnet", fmt="s3", overflow=None, wexp=None, cs=None):
+        """cs: stored channels of the input (default: 8 up to 8 input channels, else cin rounded up to 4); 8 selects the
+        4-taps-by-8-channels instance, 12 / 16 the 2-taps-by-16-channels one.
+        fmt: arithmetic of the kernel - "s3": the input is split into three bf16 planes, six products; "h2": two
         fp16 planes, three products (overflow: the engine's fp16-range word; wexp: the weight exponent, max |w| * 2^wexp
         in [2^13, 2^14), from a caller that has the maximum already - the training tape reads all of them back in one
         batched synchronisation - else one device read-back here)."""
         lib = _lib.load()
         w = _f32c(conv.weight.detach(), "stem weight")
-        if tuple(w.shape) != (64, cin, 7, 7) or cin > 8:
-            raise ValueError(f"stem kernel needs a (64, <=8, 7, 7) weight, got {tuple(w.shape)}")
+        if cs is None:
+            cs = 8 if cin <= 8 else -(-cin // 4) * 4
+        if tuple(w.shape) != (64, cin, 7, 7) or cs not in (8, 12, 16) or not 1 <= cin <= cs:
+            raise ValueError(f"stem kernel needs a (64, <=16, 7, 7) weight and 8, 12 or 16 stored channels, "
+                             f"got {tuple(w.shape)} with {cs} stored")
         if fmt not in ("s3", "h2"):
             raise ValueError(f"fmt={fmt!r}: expected 's3' or 'h2'")
         dev = w.device
-        self.tag, self.cin, self.fmt, self.overflow = tag, cin, fmt, overflow
+        self.tag, self.cin, self.cs, self.fmt, self.overflow = tag, cin, cs, fmt, overflow
         self.exp_src = _lib.H2_ACT_EXP     # h2: the input planes carry x * 2^exp_src (folded into `scale`)
-        self.wpacked = torch.empty(lib.sfh_packed_stem_weight_bytes(), dtype=torch.uint8, device=dev)
+        nbytes, pack = ((lib.sfh_packed_stem_weight_bytes, lib.sfh_pack_stem_weights) if cs == 8 else
+                        (lib.sfh_packed_stem16_weight_bytes, lib.sfh_pack_stem16_weights))
+        self.wpacked = torch.empty(nbytes(), dtype=torch.uint8, device=dev)
         self.escale = 1.0
         wexp = resolve_wexp(w, wexp) if fmt == "h2" else 0
         if fmt == "h2":
             self.escale = 2.0 ** -(wexp + _lib.H2_ACT_EXP)
-        _lib.check(lib.sfh_pack_stem_weights(_ptr(w), _ptr(self.wpacked), cin, _SPLIT[fmt][2], wexp, _stream()),
-                   "pack_stem_weights")
+        _lib.check(pack(_ptr(w), _ptr(self.wpacked), cin, _SPLIT[fmt][2], wexp, _stream()), "pack_stem_weights")
         self.relu = bn is not None
         if bn is None:   # training: the raw conv output z (batch-statistics BatchNorm follows as its own pass)
             self.scale = torch.full((64,), float(self.escale), dtype=torch.float32, device=dev)
@@ -1147,7 +1155,7 @@ class StemConv(_H2Layer):
             self._fold_exp_src(int(exp_src))
         d.h2_exp_src = self.exp_src
         d.h2_range = range_word if (range_word and self.fmt == "h2") else None
-        d.src0, d.c0, d.cs0, d.h0, d.w0 = x_nhwc8.data_ptr(), self.cin, 8, H, W
+        d.src0, d.c0, d.cs0, d.h0, d.w0 = x_nhwc8.data_ptr(), self.cin, self.cs, H, W
         d.batch, d.H, d.W, d.ksize, d.stride = B, H, W, 7, 2
         d.wpacked, d.scale, d.shift = self.wpacked.data_ptr(), self.scale.data_ptr(), self.shift.data_ptr()
         d.cout, d.relu = 64, 1 if self.relu else 0
@@ -1156,7 +1164,7 @@ class StemConv(_H2Layer):
         d.split_arith = _SPLIT[self.fmt][2]
         d.h2_overflow = self.overflow.data_ptr() if (self.overflow is not None and self.fmt == "h2") else None
         ho, wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
-        if tuple(dst.shape) != (B, ho, wo, 64) or tuple(x_nhwc8.shape) != (B, H, W, 8):
+        if tuple(dst.shape) != (B, ho, wo, 64) or tuple(x_nhwc8.shape) != (B, H, W, self.cs):
             raise ValueError(f"stem: shapes {tuple(x_nhwc8.shape)} -> {tuple(dst.shape)} do not match {(B, ho, wo, 64)}")
         t = _timed(self.tag) if PackedConv.timer is not None else None
         _lib.check(_lib.load().sfh_stem7x7_fwd(ctypes.byref(d), _stream()), "stem7x7_fwd")
@@ -1215,8 +1223,9 @@ class ResNetEngine(_Engine):
 
     def __init__(self, rn, in_channels, device, precision="bf16x6", overflow=None, ranges=None, options=None):
         """precision "bf16x6" / "f16x3": the 3x3 convs (stride 1 and 2) and the 1x1 stride-2 downsample convs run
-        on the split-operand kernel with S3 / H2 activations; the stem stays on the fp32 kernel (or, with at most
-        8 input channels, on the tap-packed split-bf16 stem kernel).  ranges / overflow / options: as UNetEngine."""
+        on the split-operand kernel with S3 / H2 activations; the stem runs on the tap-packed split-operand stem kernel
+        (8, 12 or 16 stored input channels and 64 output channels), else on the fp32 kernel.
+        ranges / overflow / options: as UNetEngine."""
         super().__init__(device, precision, overflow, ranges, options)
         fmt, s3 = self.fmt, self.s3
         self.cin = in_channels
@@ -1232,9 +1241,11 @@ class ResNetEngine(_Engine):
         # the stem stays on the fp32 kernel: the 16-tap split-bf16 instance spills registers and
         # measured 1.59 ms against 0.55 ms
         L["stem"] = PC(rn.conv0.weight, None, rn.bn1, 4, 4 * self.cs_in, stem_cin=in_channels, tag="resnet")
-        # bf16x6 mode with <= 8 input channels (every resnet_input mode but img+mask+uv): the tap-packed stem kernel
-        self.stem7 = (StemConv(rn.conv0, rn.bn1, in_channels, fmt=fmt, overflow=self.overflow, wexp=wx.get(rn.conv0.weight.data_ptr()))
-                      if (s3 and self.cs_in == 8 and rn.conv0.out_channels == 64) else None)
+        # the split precisions with at most 16 input channels: the tap-packed stem kernel (its 8-channel instance for every
+        # resnet_input mode up to 5 classes, the 16-channel one for 6..8 classes and for img+mask+uv)
+        self.stem7 = (StemConv(rn.conv0, rn.bn1, in_channels, fmt=fmt, overflow=self.overflow,
+                               wexp=wx.get(rn.conv0.weight.data_ptr()), cs=self.cs_in)
+                      if (s3 and self.cs_in in (8, 12, 16) and rn.conv0.out_channels == 64) else None)
         self.blocks = []
         for li in range(1, 5):
             for bi, blk in enumerate(getattr(rn, f"layer{li}")):
@@ -1412,7 +1423,7 @@ def homography_warp(theta, template, h, w, nearest, scale=None, want_f32=True, w
 
 
 def warp_consistency(theta, template, logits, scale, shared_template=False, warp_hw=None):
-    """predict()'s nearest warp (* mask_classes -> int32) AND the consistency score fused (sfh_warp_consistency_fwd): 4 classes;
+    """predict()'s nearest warp (* mask_classes -> int32) AND the consistency score fused (sfh_warp_consistency_fwd): 4, 7 or 8 classes;
     the warp (warp_hw = (h, w), default the logits' size) has the logits' size or exactly twice it in both directions
     (predict.py's default geometry: the score then goes through the nearest-resized mask, as the reference's).
     -> (warp_mask int32 (B,h,w), score float32 (B,)); the mask is bit-identical to homography_warp()'s."""

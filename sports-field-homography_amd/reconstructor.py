@@ -832,7 +832,8 @@ class Reconstructor(nn.Module):
                     shared = self._template_is_shared(self.court_img, bs)
                     lgt = ret.get('logits')
                     if (consistency and self.use_unet and self.warp_with_nearest and self.fuse_warp_ce
-                            and self.mask_classes == 4 and tuple(lgt.shape[1:]) in ((4, h, w), (4, h // 2, w // 2))
+                            and self.mask_classes in (4, 7, 8)
+                            and tuple(lgt.shape[1:]) in ((self.mask_classes, h, w), (self.mask_classes, h // 2, w // 2))
                             and (h % 2 == 0 and w % 2 == 0 or tuple(lgt.shape[2:]) == (h, w))):
                         # the usual cases - the warp has the logits' size, or twice it (predict.py's default geometry) - warp and
                         # consistency score fused: every wave scores the pixels it warps while their class ids are in registers,
