@@ -199,6 +199,7 @@ __device__ __forceinline__ void sfh_conv_epilogue(const sfh_conv_desc& d, const 
   };
   const unsigned xb = s3 ? 16u : cs * 4u;  // bytes per pixel step along x
   int pb[MT], py[MT], px[MT];
+  bool inframe[MT];   // the lane's pixel is one of the tensor's: only those enter the H2 range / overflow words
   // the fp32 residual beside an S3 destination and the border-class shift table exist only for the
   // 2x2 up-scatter conv (fused Up block); every other instance compiles them out
   unsigned voff[MT], rvoff[UPF ? MT : 1], cls[UPF ? MT : 1];
@@ -231,6 +232,7 @@ __device__ __forceinline__ void sfh_conv_epilogue(const sfh_conv_desc& d, const 
       rowi = (unsigned)(b * g.Ho + y);
       xo = (unsigned)x;
     }
+    inframe[mi] = ok;
     voff[mi] = (ok && !d.head_skip_dst) ? rowi * rowb + xo * xb + lane_co : kSfhOOB;
     if constexpr (UPF) {
       // fp32 NHWC residual beside an S3 destination (same pixel, channel stride cs)
@@ -306,7 +308,12 @@ __device__ __forceinline__ void sfh_conv_epilogue(const sfh_conv_desc& d, const 
       if (h2) {
         if constexpr ((FMTS & 2) != 0) {
           sfh_u32x2 pl[2];
-          sfh_split4_h2(v, h2_dst_scale, pl, over);
+          // lanes past the frame (tile round-up, the shared zero rows) compute a value from the taps that still reach the
+          // frame and store nothing: they must not raise the tensor's words
+          unsigned o = 0u;
+          sfh_split4_h2(v, h2_dst_scale, pl, o);
+          o = inframe[mi] ? o : 0u;
+          over = o > over ? o : over;
 #pragma unroll
           for (int p = 0; p < 2; ++p)
             __builtin_amdgcn_raw_buffer_store_b64(pl[p], rd, (int)voff[mi], (int)(nioff + p * planeb), 0);

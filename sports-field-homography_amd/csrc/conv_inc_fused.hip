@@ -177,7 +177,7 @@ __global__ __launch_bounds__(IFCfg::NT, 2) void conv_inc_fused_kernel(const sfh_
         sfh_u32x2 pl[2];
         unsigned o = 0u;
         sfh_split4_h2(v, mid_scale, pl, o);
-        o = interior ? o : 0u;
+        o = (interior && in_frame) ? o : 0u;   // (as sfh_conv_epilogue: only pixels of the tensor enter the words)
         over_mid = o > over_mid ? o : over_mid;
         // channel 16 ni + 4 lg + j of the half: group 2 ni + (lg >> 1), the (lg & 1) half of its 16 bytes
         const int slot = (2 * ni + (lg >> 1)) * C::HPIXP + pp;

@@ -203,7 +203,10 @@ __global__ __launch_bounds__(256, 2) void conv_upfused_kernel(const sfh_conv_des
       const bool ok = yo < d.H && xo < d.W;
       const unsigned voff = ok ? (unsigned)(b * d.H + yo) * ((cs >> 5) * 8u * run) + (unsigned)xo * 16u + lane_co : kOOB;
       sfh_u32x2 pl[2];
-      sfh_split4_h2(v, dscale, pl, over);
+      unsigned o = 0u;      // (as sfh_conv_epilogue: only pixels of the tensor enter the words)
+      sfh_split4_h2(v, dscale, pl, o);
+      o = ok ? o : 0u;
+      over = o > over ? o : over;
 #pragma unroll
       for (int p = 0; p < 2; ++p) __builtin_amdgcn_raw_buffer_store_b64(pl[p], rd, (int)voff, (int)(p * planeb), 0);
     }

@@ -1729,6 +1729,8 @@ extern "C" int sfh_conv_wgrad(const float* dz, int dz_cs, int M, const float* x,
   SFH_REQUIRE(M > 0 && M % 4 == 0 && dz_cs % 4 == 0 && dz_cs >= M, "conv_wgrad: M=%d dz_cs=%d", M, dz_cs);
   SFH_REQUIRE(N > 0 && N % 4 == 0 && x_cs % 4 == 0 && x_cs >= N, "conv_wgrad: N=%d x_cs=%d", N, x_cs);
   SFH_REQUIRE(n_off >= 0 && n_off + N <= raw_n, "conv_wgrad: n_off=%d N=%d raw_n=%d", n_off, N, raw_n);
+  SFH_REQUIRE(pad_top >= 0 && pad_left >= 0 && pad_top + xh <= H && pad_left + xw <= W,
+              "conv_wgrad: source (%dx%d at %d,%d) does not fit the %dx%d frame", xh, xw, pad_top, pad_left, H, W);
   SFH_REQUIRE(ksize == 1 || ksize == 3 || ksize == 4, "conv_wgrad: ksize %d", ksize);
   SFH_REQUIRE(ksize != 4 || N <= 32, "conv_wgrad: the 4x4 (stem) case supports N <= 32");
   WgradArgs a;
