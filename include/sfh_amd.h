@@ -1155,6 +1155,87 @@ int sfh_resample_u8(const uint8_t* src, uint8_t* dst_u8, float* dst_f32, int bat
 int sfh_resize_gather(const void* src, void* dst, int batch, int C, int elem_bytes, int Hs, int Ws, int Hd, int Wd,
                       const int32_t* yidx, const int32_t* xidx, void* stream);
 
+/* 8- and 16-bit TIFF files (the UV labels) <-> device images, csrc/tiffdec.hip and csrc/tiffenc.hip with the core
+ * csrc/tiff_core.h (the rule: outputs.decode_tiff / outputs.encode_tiff).  Admitted: classic TIFF, the first IFD, II and MM,
+ * strips, chunky, FillOrder 1, unsigned samples of 8 or 16 bits, 1 (BlackIsZero) or 3 (RGB) per pixel, Compression 1 and 5 (TIFF
+ * 6.0 LZW), Predictor 1 and 2, any RowsPerStrip.  Everything else is refused on the host before anything is launched: reasons
+ * below 100 for a malformed or unfit file, from 100 on for a well-formed file that needs something not built.               */
+#define SFH_TIFF_R_OK 0
+#define SFH_TIFF_R_TRUNCATED 1        /* the bytes end inside the 8-byte header                                                */
+#define SFH_TIFF_R_NOT_TIFF 2         /* no II / MM byte-order mark or a magic number other than 42 (43: SFH_TIFF_R_BIGTIFF)     */
+#define SFH_TIFF_R_BAD_IFD 3          /* the first IFD reaches outside the file                                                */
+#define SFH_TIFF_R_BAD_TAG 4          /* a tag whose type is not BYTE, SHORT or LONG, or whose array reaches outside the file    */
+#define SFH_TIFF_R_STRIP 5            /* a strip that reaches outside the file                                                 */
+#define SFH_TIFF_R_STRIP_TABLE 6      /* StripOffsets or StripByteCounts with another length than ceil(H / RowsPerStrip)       */
+#define SFH_TIFF_R_MISSING_TAG 7      /* no ImageWidth, ImageLength, PhotometricInterpretation, StripOffsets or StripByteCounts */
+#define SFH_TIFF_R_BAD_VALUE 8        /* a zero or absurd size, RowsPerStrip 0, a BitsPerSample count other than the samples'   */
+#define SFH_TIFF_R_SIZE 11            /* width, height, channels or bits other than the decoder's                              */
+#define SFH_TIFF_R_TOO_LONG 12        /* more bytes than the decoder's max_file_bytes                                          */
+#define SFH_TIFF_R_BIGTIFF 100
+#define SFH_TIFF_R_TILES 101
+#define SFH_TIFF_R_PLANAR 102         /* PlanarConfiguration 2                                                                 */
+#define SFH_TIFF_R_FILL_ORDER 103     /* FillOrder 2                                                                           */
+#define SFH_TIFF_R_COMPRESSION 104    /* anything but 1 (none) and 5 (LZW)                                                     */
+#define SFH_TIFF_R_PREDICTOR 105      /* anything but 1 and 2                                                                  */
+#define SFH_TIFF_R_BIT_DEPTH 106      /* anything but 8 or 16 bits, or samples of different depths                              */
+#define SFH_TIFF_R_SAMPLE_FORMAT 107  /* signed, float or undefined samples                                                    */
+#define SFH_TIFF_R_SAMPLES 108        /* SamplesPerPixel other than 1 and 3                                                    */
+#define SFH_TIFF_R_PHOTOMETRIC 109    /* palette images; anything but BlackIsZero for one sample and RGB for three              */
+#define SFH_TIFF_R_OLD_LZW 110        /* the bit-reversed LZW of old writers (a strip that starts 00 01, libtiff's test)         */
+
+/* The parse of one file (64 bytes).  file_pos, file_bytes, table_pos: filled by sfh_tiff_dec_stage only - where the file and its
+ * strip table lie in the staging buffer.                                                                                     */
+typedef struct sfh_tiff_info {
+  int32_t width, height, channels, bits, compression, predictor, big_endian, rows_per_strip, nstrips, photometric;
+  int32_t reason;
+  int32_t file_pos, file_bytes, table_pos;
+  int32_t reserved[2];
+} sfh_tiff_info;
+
+/* Host code, no device: the header and the first IFD of host_bytes[0, n) -> host_info, and the strip table as int32 records
+ * {offset, byte count, first row, rows} in host_strips, as many as strip_cap admits (host_strips may be NULL with strip_cap 0);
+ * host_info->nstrips counts all.  Every offset of the file is checked against n.  0, or -1 with host_info->reason =
+ * SFH_TIFF_R_*.                                                                                                              */
+int sfh_tiff_parse(const uint8_t* host_bytes, int64_t n, sfh_tiff_info* host_info, int32_t* host_strips, int64_t strip_cap);
+
+/* bytes of the staging buffer and of the device scratch buffer (the decoded strips of every image, a status word per strip) of
+ * a decoder of `batch` H x W x C files of `bits` bits of at most max_file_bytes; -1 for bad arguments and for buffers of 2 GiB
+ * (staging) / 4 GiB (scratch) or more.                                                                                       */
+int64_t sfh_tiff_dec_staging_bytes(int batch, int H, int W, int C, int bits, int64_t max_file_bytes);
+int64_t sfh_tiff_dec_scratch_bytes(int batch, int H, int W, int C, int bits);
+
+/* Host code, no device: parses `batch` files and packs the batch into host_staging - a 64-byte head {magic, batch, largest strip
+ * count, used bytes}, the sfh_tiff_info of every file, every file's strip table, the files at 16-byte aligned positions - for
+ * ONE copy to the device.  Returns the bytes used, or -1 with *host_reason = SFH_TIFF_R_* and *host_index = the file refused. */
+int64_t sfh_tiff_dec_stage(const uint8_t* const* host_files, const int64_t* host_sizes, int batch, int H, int W, int C, int bits,
+                           int64_t max_file_bytes, uint8_t* host_staging, int64_t staging_bytes, int32_t* host_reason,
+                           int32_t* host_index);
+
+/* `staged`, the device copy of host_staging (which is read here for its head only) -> out (B,H,W) or (B,H,W,3) of uint8 (bits 8)
+ * or uint16 (bits 16); bgr != 0: the file's three samples reversed in memory.  status int32 (B): the OR of the TD_E_* bits of
+ * the image's strips (csrc/tiff_core.h); such an image comes back as zeros.  Three launches: tiff_lzw_kernel, one wave per
+ * (image, strip); tiff_verdict_kernel; tiff_unpredict_kernel (byte order, the predictor's prefix sum per row and channel, the
+ * channel order).  No global atomics, no workgroup waits for another, no host synchronisation.                                */
+int sfh_tiff_decode(const uint8_t* host_staging, const uint8_t* staged, int64_t staged_bytes, int batch, int H, int W, int C,
+                    int bits, int bgr, int64_t max_file_bytes, uint8_t* scratch, int64_t scratch_bytes, void* out, int32_t* status,
+                    void* stream);
+
+/* The encoder.  compression 1 | 5, predictor 1 | 2, rows_per_strip 0 (max(1, 8192 / bytes per row), clamped to H) or 1 .. H.
+ * sfh_tiff_strip_capacity: the most bytes a strip of n bytes encodes to (derived in csrc/tiff_core.h).  sfh_tiff_capacity: the
+ * upper bound of one file, which sizes every buffer; -1 for bad arguments.                                                   */
+int64_t sfh_tiff_strip_capacity(int64_t n, int compression);
+int64_t sfh_tiff_capacity(int H, int W, int C, int bits, int compression, int rows_per_strip);
+int64_t sfh_tiff_scratch_bytes(int batch, int H, int W, int C, int bits, int compression, int rows_per_strip);
+/* ONE launch, one wave per (image, strip): images (B,H,W[,3]) of uint8 / uint16 (bgr != 0: the three samples are written in
+ * reverse order) -> every strip, differenced and LZW-compressed, in its fixed-stride slot of `scratch`, and its byte count.   */
+int sfh_tiff_encode(const void* images, int batch, int H, int W, int C, int bits, int bgr, int compression, int predictor,
+                    int rows_per_strip, uint8_t* scratch, int64_t scratch_bytes, void* stream);
+/* ONE launch, one workgroup per image: the scratch of sfh_tiff_encode (same arguments) -> the files, II: the 8-byte header, the
+ * strips each on an even offset, the tag arrays, the IFD.  compact, out, offsets, sizes: as sfh_png_pack.                     */
+int sfh_tiff_pack(const uint8_t* scratch, int64_t scratch_bytes, int batch, int H, int W, int C, int bits, int compression,
+                  int predictor, int rows_per_strip, int compact, uint8_t* out, int64_t out_bytes, int64_t* offsets, int32_t* sizes,
+                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,8 @@
 Encoder side: ``BatchEncoder`` - images -> fixed-stride slots + a meta record per slot (launch 1) -> the files packed into a
 ``PngBatch`` / ``JpegBatch`` (launch 2).  Decoder side: ``BatchDecoder`` - the host parses the files into ONE pinned staging
 buffer (``stage``), one non-blocking copy takes it to the device (``upload``), the launches read it there (``decode_staged``);
-every image has a status word.  A codec module supplies its names, its refusal reasons and its ctypes calls.
+every image has a status word.  A codec module supplies its names, its refusal reasons and its ctypes calls.  The TIFF codec
+(tiffenc, tiffdec) stands on the same frame; its samples are uint8 or uint16 (``SAMPLE``).
 """
 import ctypes
 
@@ -46,14 +47,23 @@ class JpegBatch(PngBatch):
     ``to_host()`` -> list of B 1-D uint8 numpy arrays (synchronises)"""
 
 
-def as_image_batch(t, who):
+class TiffBatch(PngBatch):
+    """the encoded files of one batch on the device: ``data`` uint8, file b = data[offsets[b] : offsets[b] + sizes[b]];
+    ``to_host()`` -> list of B 1-D uint8 numpy arrays (synchronises)"""
+
+
+def _dtype_name(dtype):
+    return str(dtype).split(".")[-1]
+
+
+def as_image_batch(t, who, dtypes=(torch.uint8,)):
     """how the one-off entry points read a tensor -> (batch tensor, channels, whether it was ONE image): a 2-D tensor and a 3-D
     tensor whose last dimension is 3 are one image, any other 3-D tensor a batch of gray images, a 4-D tensor (B,H,W,1|3) a
     batch"""
     if not isinstance(t, torch.Tensor):
         raise ValueError(f"{who}: expected a tensor, got {type(t).__name__}")
-    if t.dtype != torch.uint8:
-        raise ValueError(f"{who}: dtype {t.dtype} (uint8 only)")
+    if t.dtype not in dtypes:
+        raise ValueError(f"{who}: dtype {t.dtype} ({' or '.join(_dtype_name(d) for d in dtypes)} only)")
     single = t.dim() == 2 or (t.dim() == 3 and t.shape[2] == 3)
     batch = t[None] if single else t
     if batch.dim() == 3:
@@ -73,8 +83,10 @@ def _cuda_device(device, who):
 class BatchEncoder:
     """what the device encoders (PngEncoder, JpegEncoder) share: the constructor, the scratch and output buffers, the refusals
     of ``encode``'s argument and the partial-batch slice.  A subclass sets ``batch_type``, ``capacity_of(H, W, C)`` and
-    ``scratch_bytes_of(lib)``, and launches in ``_launch(images, b, out, dev)``."""
+    ``scratch_bytes_of(lib)``, and launches in ``_launch(images, b, out, dev)``.  ``SAMPLE``: the dtype of the images' samples
+    (TiffEncoder sets it per instance: uint8 or uint16)."""
     batch_type = PngBatch
+    SAMPLE = torch.uint8
 
     def __init__(self, H, W, channels, batch, bgr, compact, device):
         who = type(self).__name__
@@ -102,8 +114,8 @@ class BatchEncoder:
         who = type(self).__name__
         if not isinstance(images, torch.Tensor):
             raise ValueError(f"{who}: expected a tensor, got {type(images).__name__}")
-        if images.dtype != torch.uint8:
-            raise ValueError(f"{who}: dtype {images.dtype} (uint8 only)")
+        if images.dtype != self.SAMPLE:
+            raise ValueError(f"{who}: dtype {images.dtype} ({_dtype_name(self.SAMPLE)} only)")
         want = (self.H, self.W) if self.C == 1 else (self.H, self.W, 3)
         shape = tuple(images.shape)
         if self.C == 1 and len(shape) == 4 and shape[3] == 1:
@@ -155,8 +167,10 @@ class BatchDecoder:
     A subclass sets ``NAME`` (of its C entry points), ``REASONS``, ``CHANNELS``, ``LIMITS`` (the words of the shape refusal),
     ``MAX_SIDE``, ``batch_type`` (the device file batch ``decode`` takes), ``default_max_file_bytes(H, W, C)``, ``_sizes(lib)``
     -> (staging bytes, scratch bytes), ``_stage(lib, ptrs, sizes, n, reason, index)`` -> staged bytes, ``_launch(lib, n, out,
-    dev)``, and for ``decode_once`` ``MIN_FILE_BYTES``, ``CORRUPT`` and ``_head(file)`` -> (H, W, channels)."""
+    dev)``, and for ``decode_once`` ``MIN_FILE_BYTES``, ``CORRUPT`` and ``_head(file)`` -> (H, W, channels).  ``SAMPLE``: the
+    dtype of the images' samples (TiffDecoder sets it per instance: uint8 or uint16)."""
     MAX_SIDE = None
+    SAMPLE = torch.uint8
     _sizes_detail = ""
 
     def __init__(self, H, W, channels, batch, bgr, max_file_bytes, device):
@@ -177,7 +191,7 @@ class BatchDecoder:
         self.staging = torch.empty(self.staging_bytes, dtype=torch.uint8).pin_memory()
         self.staged = torch.empty(self.staging_bytes, dtype=torch.uint8, device=self.device)
         self.scratch = torch.empty(self.scratch_bytes, dtype=torch.uint8, device=self.device)
-        self.out = torch.empty(self._shape(self.B), dtype=torch.uint8, device=self.device)
+        self.out = torch.empty(self._shape(self.B), dtype=self.SAMPLE, device=self.device)
         self._status = torch.zeros(self.B, dtype=torch.int32, device=self.device)
         self._uploaded = None                     # event behind the last copy out of the staging buffer
         self._used = self._n = 0
@@ -223,8 +237,8 @@ class BatchDecoder:
         want = self._shape(n)
         if not isinstance(out, torch.Tensor):
             raise ValueError(f"{who}: out: expected a tensor, got {type(out).__name__}")
-        if out.dtype != torch.uint8:
-            raise ValueError(f"{who}: out: dtype {out.dtype} (uint8 only)")
+        if out.dtype != self.SAMPLE:
+            raise ValueError(f"{who}: out: dtype {out.dtype} ({_dtype_name(self.SAMPLE)} only)")
         if tuple(out.shape[1:]) != want[1:] or out.dim() != len(want) or out.shape[0] < n:
             raise ValueError(f"{who}: out: expected ({n}+,{','.join(map(str, want[1:]))}), got {tuple(out.shape)}")
         if not out.is_contiguous():

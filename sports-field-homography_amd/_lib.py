@@ -208,6 +208,19 @@ SIGNATURES = {
     "sfh_png_dec_stage": (C.c_int64, [_p, _p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, _p, C.c_int64, _p, _p]),
     "sfh_png_decode": (C.c_int, [_p, _p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, _p, C.c_int64,
                                  _p, _p, _p, _p]),
+    "sfh_tiff_parse": (C.c_int, [_p, C.c_int64, _p, _p, C.c_int64]),
+    "sfh_tiff_dec_staging_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64]),
+    "sfh_tiff_dec_scratch_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "sfh_tiff_dec_stage": (C.c_int64, [_p, _p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, _p, C.c_int64, _p, _p]),
+    "sfh_tiff_decode": (C.c_int, [_p, _p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, _p, C.c_int64,
+                                  _p, _p, _p]),
+    "sfh_tiff_strip_capacity": (C.c_int64, [C.c_int64, C.c_int]),
+    "sfh_tiff_capacity": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "sfh_tiff_scratch_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "sfh_tiff_encode": (C.c_int, [_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p, C.c_int64,
+                                  _p]),
+    "sfh_tiff_pack": (C.c_int, [_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p,
+                                C.c_int64, _p, _p, _p]),
     "sfh_resample_max_taps": (C.c_int, []),
     "sfh_resample_tab": (C.c_int, [C.c_int, C.c_int, C.c_int, _p, _p, C.c_int]),
     "sfh_resample_tile_rows": (C.c_int, [C.c_int, C.c_int, C.c_int]),

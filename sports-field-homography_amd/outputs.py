@@ -15,6 +15,8 @@ Mirrors what the reference's ``predict.py`` does with the dict returned by
 The reference encodes PNGs with OpenCV, which is absent here; ``encode_png``/``decode_png`` are a
 small zlib PNG codec for 8-bit gray / 3-channel images.  3-channel arrays are treated as BGR like
 ``cv2.imencode``/``cv2.imdecode`` do (stored RGB in the file), so streams are interchangeable.
+``encode_tiff``/``decode_tiff`` are the same for the 8- and 16-bit TIFF files of the UV labels (LZW, predictor 2): the
+written-down rule that ``sfh_amd.tiffenc`` / ``sfh_amd.tiffdec`` are held to.
 """
 import io
 import json
@@ -228,6 +230,308 @@ def decode_jpeg(buf):
     im = Image.open(io.BytesIO(bytes(np.asarray(buf, dtype=np.uint8).reshape(-1))))
     a = np.array(im)
     return a if a.ndim == 2 else np.ascontiguousarray(a[:, :, ::-1])
+
+
+# ------------------------------------------------------------------------------- TIFF codec
+# The written-down rule of sfh_amd.tiffdec / sfh_amd.tiffenc (csrc/tiff_core.h), in numpy and plain Python: the files libtiff-based
+# writers make of 8- and 16-bit labels.  Refusals: codes from 100 on name a feature that is not built (NotImplementedError), the
+# others a malformed or unfit file (ValueError) - the SFH_TIFF_R_* of include/sfh_amd.h.
+TIFF_REASONS = {1: "the bytes end inside the header", 2: "no byte-order mark or magic 42: not a TIFF file",
+                3: "an IFD that reaches outside the file", 4: "a tag of an unknown type or whose array reaches outside the file",
+                5: "a strip that reaches outside the file", 6: "a strip table whose length is not ceil(H / RowsPerStrip)",
+                7: "a missing required tag", 8: "a zero or absurd size", 11: "size, channels or bits other than the decoder's",
+                12: "a file longer than the decoder's max_file_bytes",
+                100: "BigTIFF", 101: "a tiled image", 102: "PlanarConfiguration 2", 103: "FillOrder 2",
+                104: "a compression other than none and LZW", 105: "a predictor other than 1 and 2",
+                106: "a bit depth other than 8 or 16", 107: "a sample format other than unsigned integer",
+                108: "a sample count other than 1 and 3", 109: "a palette image or a photometric interpretation other than "
+                "BlackIsZero / RGB", 110: "old-style bit-reversed LZW"}
+_TIFF_TAGS = {256: "width", 257: "height", 258: "bits", 259: "compression", 262: "photometric", 266: "fill_order", 273: "offsets",
+              277: "channels", 278: "rows_per_strip", 279: "counts", 284: "planar", 317: "predictor", 339: "sample_format"}
+
+
+def _tiff_refuse(reason, who):
+    what = TIFF_REASONS[reason]
+    if reason >= 100:
+        raise NotImplementedError(f"{who}: {what} is not built")
+    raise ValueError(f"{who}: {what}")
+
+
+def tiff_parse(data, who="decode_tiff"):
+    """header and first IFD of a classic TIFF (bytes) -> dict: width, height, channels, bits, compression, predictor,
+    big_endian, rows_per_strip, photometric and strips = [(offset, byte count, first row, rows)]; raises as ``decode_tiff``"""
+    n = len(data)
+    if n < 2:
+        _tiff_refuse(1, who)
+    if data[:2] not in (b"II", b"MM"):
+        _tiff_refuse(2, who)
+    e = "<" if data[:2] == b"II" else ">"
+    if n < 4:
+        _tiff_refuse(1, who)
+    magic = struct.unpack(e + "H", data[2:4])[0]
+    if magic == 43:
+        _tiff_refuse(100, who)
+    if magic != 42:
+        _tiff_refuse(2, who)
+    if n < 8:
+        _tiff_refuse(1, who)
+    ifd = struct.unpack(e + "I", data[4:8])[0]
+    if ifd < 8 or ifd + 2 > n:
+        _tiff_refuse(3, who)
+    nent = struct.unpack(e + "H", data[ifd:ifd + 2])[0]
+    if ifd + 2 + 12 * nent > n:
+        _tiff_refuse(3, who)
+    tags, tiles = {}, False
+    for i in range(nent):
+        p = ifd + 2 + 12 * i
+        tag, typ, count = struct.unpack(e + "HHI", data[p:p + 8])
+        tiles = tiles or 322 <= tag <= 325
+        if tag not in _TIFF_TAGS:
+            continue
+        size = {1: 1, 3: 2, 4: 4}.get(typ)
+        if size is None or count < 1:
+            _tiff_refuse(4, who)
+        at = p + 8
+        if size * count > 4:
+            at = struct.unpack(e + "I", data[p + 8:p + 12])[0]
+            if at + size * count > n:
+                _tiff_refuse(4, who)
+        tags[_TIFF_TAGS[tag]] = struct.unpack(e + str(count) + " BH I"[size], data[at:at + size * count])
+    if tiles:
+        _tiff_refuse(101, who)
+    if any(k not in tags for k in ("width", "height", "photometric", "offsets", "counts")):
+        _tiff_refuse(7, who)
+    first = lambda k, d: tags[k][0] if k in tags else d
+    W, H = tags["width"][0], tags["height"][0]
+    if not (1 <= W < 1 << 24 and 1 <= H < 1 << 24):
+        _tiff_refuse(8, who)
+    C = first("channels", 1)
+    if C not in (1, 3):
+        _tiff_refuse(108, who)
+    bits = first("bits", 1)
+    if bits not in (8, 16):
+        _tiff_refuse(106, who)
+    if "bits" in tags and len(tags["bits"]) not in (1, C):
+        _tiff_refuse(8, who)
+    if any(b != bits for b in tags.get("bits", ())):
+        _tiff_refuse(106, who)
+    if any(f != 1 for f in tags.get("sample_format", ())):
+        _tiff_refuse(107, who)
+    comp = first("compression", 1)
+    if comp not in (1, 5):
+        _tiff_refuse(104, who)
+    if tags["photometric"][0] != (1 if C == 1 else 2):
+        _tiff_refuse(109, who)
+    if C > 1 and first("planar", 1) != 1:
+        _tiff_refuse(102, who)
+    if first("fill_order", 1) != 1:
+        _tiff_refuse(103, who)
+    pred = first("predictor", 1)
+    if pred not in (1, 2):
+        _tiff_refuse(105, who)
+    rps = first("rows_per_strip", 0xFFFFFFFF)
+    if rps < 1:
+        _tiff_refuse(8, who)
+    rps = min(rps, H)
+    nstrips = -(-H // rps)
+    if len(tags["offsets"]) != nstrips or len(tags["counts"]) != nstrips:
+        _tiff_refuse(6, who)
+    strips = []
+    for s, (off, cnt) in enumerate(zip(tags["offsets"], tags["counts"])):
+        if off + cnt > n:
+            _tiff_refuse(5, who)
+        if comp == 5 and cnt >= 2 and data[off] == 0 and data[off + 1] & 1:
+            _tiff_refuse(110, who)
+        strips.append((off, cnt, s * rps, min(rps, H - s * rps)))
+    pred = pred if comp == 5 else 1              # libtiff applies a predictor inside its LZW codec only
+    return {"width": W, "height": H, "channels": C, "bits": bits, "compression": comp, "predictor": pred,
+            "big_endian": e == ">", "rows_per_strip": rps, "photometric": tags["photometric"][0], "strips": strips}
+
+
+def tiff_lzw_decode(data, total):
+    """one TIFF 6.0 LZW strip (MSB-first codes of 9 .. 12 bits, Clear 256, EOI 257, early change) -> ``total`` bytes; the decode
+    ends when they are complete, so the EOI may be missing and bytes may follow it"""
+    out = bytearray()
+    table = [bytes([i]) for i in range(256)] + [b"", b""]
+    acc = nbits = ip = 0
+    width, prev = 9, None
+    while len(out) < total:
+        while nbits < width:
+            if ip >= len(data):
+                raise ValueError("decode_tiff: the bits of a strip end early")
+            acc = (acc << 8) | data[ip]
+            ip += 1
+            nbits += 8
+        code = (acc >> (nbits - width)) & ((1 << width) - 1)
+        nbits -= width
+        if code == 256:
+            del table[258:]
+            width, prev = 9, None
+            continue
+        if code == 257:
+            break
+        if prev is None:
+            if code > 255:
+                raise ValueError("decode_tiff: a first code after Clear that is not a literal")
+            s = table[code]
+        else:
+            room = len(table) < 4096
+            if code > len(table) or (code == len(table) and not room):
+                raise ValueError("decode_tiff: a code above the next free code")
+            s = table[code] if code < len(table) else prev + prev[:1]
+            if room:
+                table.append(prev + s[:1])
+                if len(table) == (1 << width) - 1 and width < 12:
+                    width += 1
+        out += s
+        prev = s
+    if len(out) != total:
+        raise ValueError("decode_tiff: a strip short of or beyond its rows")
+    return bytes(out)
+
+
+def tiff_lzw_encode(raw):
+    """greedy TIFF 6.0 LZW of one strip, as libtiff writes it: Clear first, the longest match, the width grows when the next free
+    code reaches 1 << width, Clear and restart when it reaches 4094, the last code then EOI at the width the decoder expects
+    there, the final byte zero-padded"""
+    out = bytearray()
+    acc = nb = 0
+
+    def put(code, width):
+        nonlocal acc, nb
+        acc = (acc << width) | code
+        nb += width
+        while nb >= 8:
+            out.append((acc >> (nb - 8)) & 255)
+            nb -= 8
+        acc &= 255
+
+    width, nxt, ent, table = 9, 258, -1, {}
+    put(256, width)
+    for c in raw:
+        if ent < 0:
+            ent = c
+            continue
+        key = (ent << 8) | c
+        found = table.get(key)
+        if found is not None:
+            ent = found
+            continue
+        put(ent, width)
+        table[key] = nxt
+        nxt += 1
+        ent = c
+        if nxt == 4094:
+            put(256, width)
+            table.clear()
+            width, nxt = 9, 258
+        elif nxt > (1 << width) - 1:
+            width += 1
+    if ent >= 0:
+        put(ent, width)
+        nxt += 1
+        if nxt == 4094:
+            put(256, width)
+            width = 9
+        elif nxt > (1 << width) - 1:
+            width += 1
+    put(257, width)
+    if nb:
+        out.append((acc << (8 - nb)) & 255)
+    return bytes(out)
+
+
+def decode_tiff(file, bgr=True):
+    """TIFF file (bytes or a 1-D uint8 array) -> uint8 / uint16 (H,W) or (H,W,3).  bgr: three samples come back reversed, as
+    ``cv2.imread(path, -1)`` returns them.  Classic TIFF, first IFD, II / MM, strips, 8 or 16 bits, 1 or 3 samples, compression 1
+    and 5 (LZW), predictor 1 and 2 (applied to the values read in the file's byte order, per sample at a stride of the sample
+    count; ignored in an uncompressed file, as libtiff does); NotImplementedError / ValueError for everything else (``TIFF_REASONS``)."""
+    data = bytes(np.asarray(file, dtype=np.uint8).reshape(-1)) if not isinstance(file, (bytes, bytearray)) else bytes(file)
+    t = tiff_parse(data)
+    H, W, C, bits = t["height"], t["width"], t["channels"], t["bits"]
+    rowbytes = W * C * bits // 8
+    raw = bytearray()
+    for off, cnt, _, rows in t["strips"]:
+        strip = data[off:off + cnt]
+        if t["compression"] == 5:
+            raw += tiff_lzw_decode(strip, rows * rowbytes)
+        else:
+            if cnt < rows * rowbytes:
+                raise ValueError("decode_tiff: a strip short of or beyond its rows")
+            raw += strip[:rows * rowbytes]
+    dt = np.dtype(np.uint8) if bits == 8 else np.dtype(">u2" if t["big_endian"] else "<u2")
+    a = np.frombuffer(bytes(raw), dtype=dt).reshape(H, W, C).astype(np.uint8 if bits == 8 else np.uint16)
+    if t["predictor"] == 2:
+        a = np.cumsum(a, axis=1, dtype=np.uint64).astype(a.dtype)       # modulo 2^bits
+    if C == 1:
+        return np.ascontiguousarray(a[:, :, 0])
+    return np.ascontiguousarray(a[:, :, ::-1] if bgr else a)
+
+
+def tiff_strip_rows(H, W, C, bits, rows_per_strip=None):
+    """the rows of a strip ``encode_tiff`` writes: about 8 KB by default, libtiff's choice"""
+    if rows_per_strip is None:
+        return min(int(H), max(1, 8192 // (int(W) * int(C) * int(bits) // 8)))
+    if not 1 <= int(rows_per_strip) <= int(H):
+        raise ValueError(f"encode_tiff: rows_per_strip {rows_per_strip!r} (1 .. {H})")
+    return int(rows_per_strip)
+
+
+def encode_tiff(img, compression="lzw", predictor=2, rows_per_strip=None, bgr=True):
+    """uint8 / uint16 (H,W) or (H,W,3) array -> TIFF file bytes as a 1-D uint8 array.  bgr: a 3-channel array is BGR in memory
+    (cv2's convention) and stored reversed - a UV label (id, u, v) is stored (v, u, id), which ``cv2.imread(path, -1)`` returns as
+    (id, u, v).  Little endian; strips of ``rows_per_strip`` rows (default max(1, 8192 // bytes per row)) directly behind the
+    header, each on an even offset; then the BitsPerSample and SampleFormat arrays (3 channels) and the two strip tables (more than
+    one strip); the IFD last: tags 256, 257, 258, 259, 262, 273, 277, 278, 279, 284, 317, 339.  LZW: ``tiff_lzw_encode``.  The
+    predictor belongs to LZW, as in libtiff: an uncompressed file is stored undifferenced with Predictor 1."""
+    a = np.asarray(img)
+    if a.dtype not in (np.uint8, np.uint16):
+        raise ValueError(f"encode_tiff: dtype {a.dtype} (uint8 or uint16)")
+    if a.ndim == 3 and a.shape[2] == 1:
+        a = a[:, :, 0]
+    if a.ndim == 2:
+        a = a[:, :, None]
+    if a.ndim != 3 or a.shape[2] not in (1, 3) or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError(f"encode_tiff: shape {np.asarray(img).shape}")
+    if compression not in ("lzw", "none"):
+        raise ValueError(f'encode_tiff: compression={compression!r} ("lzw" or "none")')
+    if predictor not in (1, 2):
+        raise ValueError(f"encode_tiff: predictor={predictor!r} (1 or 2)")
+    if compression == "none":
+        predictor = 1                            # libtiff applies a predictor inside its LZW codec only
+    H, W, C = a.shape
+    bits = 8 * a.dtype.itemsize
+    R = tiff_strip_rows(H, W, C, bits, rows_per_strip)
+    if C == 3 and bgr:
+        a = a[:, :, ::-1]
+    if predictor == 2:
+        d = a.copy()
+        d[:, 1:] = a[:, 1:] - a[:, :-1]                                   # modulo 2^bits
+        a = d
+    rows = np.ascontiguousarray(a).astype("<u2" if bits == 16 else np.uint8).reshape(H, -1).view(np.uint8)
+    out = bytearray(b"II*\0\0\0\0\0")
+    offsets, counts = [], []
+    for y in range(0, H, R):
+        raw = rows[y:y + R].tobytes()
+        strip = tiff_lzw_encode(raw) if compression == "lzw" else raw
+        offsets.append(len(out))
+        counts.append(len(strip))
+        out += strip + b"\0" * (len(strip) & 1)
+    n = len(offsets)
+    arrays = len(out)
+    if C == 3:
+        out += struct.pack("<6H", bits, bits, bits, 1, 1, 1)
+    tables = len(out)
+    if n > 1:
+        out += struct.pack(f"<{2 * n}I", *offsets, *counts)
+    ifd = len(out)
+    entries = [(256, 4, 1, W), (257, 4, 1, H), (258, 3, C, arrays if C == 3 else bits), (259, 3, 1, 5 if compression == "lzw" else 1),
+               (262, 3, 1, 2 if C == 3 else 1), (273, 4, n, tables if n > 1 else offsets[0]), (277, 3, 1, C), (278, 4, 1, R),
+               (279, 4, n, tables + 4 * n if n > 1 else counts[0]), (284, 3, 1, 1), (317, 3, 1, predictor),
+               (339, 3, C, arrays + 6 if C == 3 else 1)]
+    out += struct.pack("<H", len(entries)) + b"".join(struct.pack("<HHII", *e) for e in entries) + b"\0\0\0\0"
+    out[4:8] = struct.pack("<I", ifd)
+    return np.frombuffer(bytes(out), dtype=np.uint8)
 
 
 # --------------------------------------------------------------------- mask streams on disk

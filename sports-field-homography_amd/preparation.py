@@ -35,7 +35,10 @@ Stated deviations from the reference:
   ``preprocess_uv_mask``'s ``/ 65535`` returns the template value to within 0.5 / 65535;
 * ``generate_uv_template`` zeroes u AND v outside the offset window; with the two separable tables a tap outside the
   window on one axis only keeps the other axis' value (with zero offsets: the last template column and row);
-* the UV label is written as ``<name>.npy`` (uint16 (H,W,3)); a 16-bit TIFF writer is out of scope;
+* the UV label is written as ``<name>.npy`` (uint16 (H,W,3)) by default; ``uv_format="tif"`` / ``"both"`` writes the 16-bit
+  ``<name>.tif`` the reference's ``BasicDataset(use_uv=True)`` looks for (``sfh_amd.tiffenc`` / ``outputs.encode_tiff``: LZW,
+  predictor 2, stored (v, u, id) so that ``cv2.imread(path, -1)`` returns the id in channel 0).  OpenCV is not available here:
+  that its reader swaps the channels of a TIFF is stated from knowledge of its source, not verified;
 * frames with fewer than 4 usable points (the reference's ``return None``) get status 0 and are reported, never written.
 """
 import json
@@ -302,15 +305,22 @@ def to_batch(labels, frames=None, names=None, frame_resize=None):
 
 # ---------------------------------------------------------------------------------------------- dataset on disk
 def prepare_dataset(anno_dir, dst_dir, court_ids=None, court_poi=None, size=(640, 360), num_classes=4, uv=False,
-                    ignore_pts=None, refine=10, norm_size=None, batch=64, maker=None, device="cuda", png="host"):
+                    ignore_pts=None, refine=10, norm_size=None, batch=64, maker=None, device="cuda", png="host",
+                    uv_format="npy", tif="host"):
     """Steps 1-5 and 7 of dataset_utils/preparation.py: reads one ``manual_anno.json`` per game directory of ``anno_dir``
     (``generate_requests``), batches the frames across games and writes per fitted frame, under ``dst_dir/<game>/``,
     ``<frame>.json`` = {theta (frame -> court, 3x3), poi (N,3: x, y, flag), reproj_mse} - the keys ``BasicDataset`` reads -,
-    ``<frame>.png`` = the id mask (``outputs.encode_png``) and, with uv, ``<frame>.npy`` = uint16 (H,W,3) (id, u, v) (where
-    the reference's reader expects a 16-bit TIFF: writing TIFF is out of scope).  maker: any object with ``LabelMaker.make``'s
-    contract (default: a LabelMaker built from the arguments).  png: "host" (outputs.encode_png, the default) or "device"
-    (sfh_amd.pngenc: the masks are encoded on the GPU).  Returns {"written": [game/frame, ..], "skipped": [..]};
+    ``<frame>.png`` = the id mask (``outputs.encode_png``) and, with uv, the UV label uint16 (H,W,3) (id, u, v): uv_format "npy"
+    (the default) writes ``<frame>.npy``, "tif" the 16-bit ``<frame>.tif`` the reference's reader expects, "both" both.  maker:
+    any object with ``LabelMaker.make``'s contract (default: a LabelMaker built from the arguments).  png: "host"
+    (outputs.encode_png, the default) or "device" (sfh_amd.pngenc: the masks are encoded on the GPU).  tif: "host"
+    (outputs.encode_tiff, the default) or "device" (sfh_amd.tiffenc: the UV labels of a batch are encoded in one
+    TiffEncoder.encode and only the files come to the host).  Returns {"written": [game/frame, ..], "skipped": [..]};
     skipped = frames with fewer than 4 usable points (the reference's ``return None``), for which nothing is written."""
+    if uv_format not in ("npy", "tif", "both"):
+        raise ValueError(f'prepare_dataset: uv_format={uv_format!r} ("npy", "tif" or "both")')
+    if tif not in ("host", "device"):
+        raise ValueError(f'prepare_dataset: tif={tif!r} ("host" or "device")')
     if maker is None:
         maker = LabelMaker(court_ids, court_poi, size, num_classes, uv=uv, ignore_pts=ignore_pts, refine=refine,
                            norm_size=norm_size, device=device)
@@ -324,6 +334,10 @@ def prepare_dataset(anno_dir, dst_dir, court_ids=None, court_poi=None, size=(640
             raise ValueError(f"prepare_dataset: manual poi of different shapes in one run: {sorted(shapes)}")
         labels = maker.make(np.stack([p for _, _, p in chunk]))
         files = files_from_batch(labels["mask"], 1, png)
+        tif_files = None
+        if "uv" in labels and uv_format != "npy":
+            from . import tiffenc
+            tif_files = tiffenc.files_from_batch(labels["uv"], tif)
         host = {k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)) for k, v in labels.items()
                 if k != "mask"}
         for k, (game, fid, _) in enumerate(chunk):
@@ -338,13 +352,16 @@ def prepare_dataset(anno_dir, dst_dir, court_ids=None, court_poi=None, size=(640
                            "reproj_mse": float(host["reproj_mse"][k])}, f)
             with open(stem + ".png", "wb") as f:
                 f.write(files[k].tobytes())
-            if "uv" in host:
+            if "uv" in host and uv_format != "tif":
                 np.save(stem + ".npy", host["uv"][k])
+            if tif_files is not None:
+                with open(stem + ".tif", "wb") as f:
+                    f.write(tif_files[k].tobytes())
             written.append(key)
     return {"written": written, "skipped": skipped}
 
 
-def read_dataset(dst_dir, keys, use_uv=False, device="cpu", size=None, decode="host"):
+def read_dataset(dst_dir, keys, use_uv=False, device="cpu", size=None, decode="host", uv_format="npy"):
     """``BasicDataset.__getitem__``'s label side (utils/dataset.py:240-289, anno_keys = theta, poi, reproj_mse; no resize: the
     labels are written at the target size) for the frames ``keys`` (``game/frame``) of a tree written by ``prepare_dataset``,
     collated: the entries ``to_batch`` returns for the same frames (without frames_u8 / image).
@@ -352,7 +369,12 @@ def read_dataset(dst_dir, keys, use_uv=False, device="cpu", size=None, decode="h
     ``Image.NEAREST`` (preprocess_mask), the uint16 UV label with cv2.INTER_NEAREST before it is split (preprocess_uv_mask) - on
     the device (``resample.resize_nearest``): ``device`` must then be a GPU.
     decode: "host" (outputs.decode_png, the default) or "device" - the mask files of all keys in one sfh_amd.pngdec decode, only
-    the files are uploaded: ``device`` must then be a GPU."""
+    the files are uploaded: ``device`` must then be a GPU.
+    uv_format: "npy" (the default) reads the UV label from ``<frame>.npy``, "tif" from the 16-bit ``<frame>.tif`` - with
+    decode="host" through outputs.decode_tiff, with decode="device" the files of all keys in one sfh_amd.tiffdec decode; the
+    batch is the one the ``.npy`` route returns for the same labels."""
+    if uv_format not in ("npy", "tif"):
+        raise ValueError(f'read_dataset: uv_format={uv_format!r} ("npy" or "tif")')
     if decode not in ("host", "device"):
         raise ValueError(f'read_dataset: decode={decode!r} ("host" or "device")')
     if decode == "device" and torch.device(device).type != "cuda":
@@ -363,19 +385,26 @@ def read_dataset(dst_dir, keys, use_uv=False, device="cpu", size=None, decode="h
             raise ValueError(f"read_dataset: size={size} resizes on the device; device={device!r} is not a GPU")
         from . import resample
     masks, uvs, pois, nzs, thetas, ws = [], [], [], [], [], []
-    mask_files = []
+    mask_files, uv_files = [], []
+    if use_uv and uv_format == "tif":
+        load_uv = lambda stem: O.decode_tiff(np.fromfile(stem + ".tif", dtype=np.uint8))
+    else:
+        load_uv = lambda stem: np.load(stem + ".npy")
     for key in keys:
         stem = os.path.join(dst_dir, *str(key).split("/"))
         with open(stem + ".json", "r") as f:
             anno = json.load(f)
-        if use_uv and size is not None:
-            lab = torch.from_numpy(np.ascontiguousarray(np.load(stem + ".npy")).view(np.int16)).to(device).view(torch.uint16)
+        if use_uv and uv_format == "tif" and decode == "device":
+            m = None
+            uv_files.append(np.fromfile(stem + ".tif", dtype=np.uint8))
+        elif use_uv and size is not None:
+            lab = torch.from_numpy(np.ascontiguousarray(load_uv(stem)).view(np.int16)).to(device).view(torch.uint16)
             m, uvp = split_uv(resample.resize_nearest(lab[None], (size[1], size[0]), rule="cv2")[0])
             uvs.append(uvp)
             masks.append(m.contiguous())
             m = None
         elif use_uv:
-            m, uvp = split_uv(np.load(stem + ".npy"))
+            m, uvp = split_uv(load_uv(stem))
             uvs.append(torch.from_numpy(uvp))
         elif decode == "device":
             m = None
@@ -389,7 +418,17 @@ def read_dataset(dst_dir, keys, use_uv=False, device="cpu", size=None, decode="h
         nzs.append(p[:, 2])
         thetas.append(torch.from_numpy(np.asarray(anno["theta"], dtype="float")).type(torch.FloatTensor))
         ws.append(torch.from_numpy(preprocess_weight(np.asarray([anno["reproj_mse"]], dtype="float"))))
-    if mask_files:
+    uv_planes = None
+    if uv_files:
+        from . import tiffdec
+        labs = tiffdec.decode_tiff_device(uv_files, device=device)
+        if labs.dim() != 4 or labs.dtype != torch.uint16:
+            raise ValueError("the UV files must hold 3-channel 16-bit labels of one size")
+        if size is not None:
+            labs = resample.resize_nearest(labs, (size[1], size[0]), rule="cv2")
+        mask_u8, uv_planes = split_uv(labs)
+        mask_u8 = mask_u8.contiguous()
+    elif mask_files:
         from . import pngdec
         mask_u8 = pngdec.masks_from_files(mask_files, device)
     else:
@@ -402,5 +441,5 @@ def read_dataset(dst_dir, keys, use_uv=False, device="cpu", size=None, decode="h
     batch["mask"] = batch["mask_u8"].to(torch.int64)
     batch["num_nonzero"] = torch.count_nonzero(batch["nonzeros"], dim=1).to(torch.float32)
     if use_uv:
-        batch["uv"] = torch.stack(uvs).to(device)
+        batch["uv"] = uv_planes if uv_planes is not None else torch.stack(uvs).to(device)
     return batch
