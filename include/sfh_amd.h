@@ -1236,6 +1236,92 @@ int sfh_tiff_pack(const uint8_t* scratch, int64_t scratch_bytes, int batch, int 
                   int predictor, int rows_per_strip, int compact, uint8_t* out, int64_t out_bytes, int64_t* offsets, int32_t* sizes,
                   void* stream);
 
+/* -------------------------------------------------------------------------------------------------
+ * Deterministic training mode: fixed-order slab sums (csrc/det_core.h states the arithmetic once).
+ *
+ * Every entry above that finishes a sum across workgroups with float atomics (their arrival order is free, so two runs
+ * differ in the last bits) has a sibling NAME_det with the same arguments + (workspace, workspace_bytes) in front of the
+ * stream, and a size query NAME_det_bytes that runs without a device (-1 for a refused geometry).  A sibling computes what
+ * its entry computes, in two launches on the caller's stream:
+ *
+ *   store pass: the entry's kernel stores what it would have added into its own SLAB of the workspace.  Slab r is elements
+ *     [r * E, (r + 1) * E) of the workspace, in the accumulator's type (float for raw, double for the fp64 accumulators);
+ *     every element of every slab is written exactly once with a plain store (an empty share of the work stores zeros),
+ *     so the workspace needs no memset and may be reused by the next call on the same stream.
+ *   sum pass (sfh_det_reduce_f32 / _f64): dst[e] = (...((dst[e] + p_0[e]) + p_1[e]) + ...) + p_{R-1}[e] - the ascending
+ *     chain over the R slabs, starting from what the destination held, in the accumulator's own precision.
+ *
+ *   entry                              slab r = the share of        R                                   E (layout)
+ *   sfh_conv_wgrad_det                 pixel split r                split count of the launch           M * ksize^2 * N  [m][tap][n], n from 0
+ *   sfh_conv_wgrad_s3_det              pixel split r                split count of the launch           M * ksize^2 * N  [m][tap][n], n from 0
+ *   sfh_conv_grouped_wgrad_det         output tile r                tiles of 8 (stride 2: 4) x 16       C * 9 * cg       raw's own layout
+ *   sfh_bn_stats_det, bn_bwd_reduce    reduction block r            min(1024, ceil(npix / 256))         2 * C            [row][c]
+ *   sfh_colsum_det                     reduction block r            min(1024, ceil(npix / 256))         C
+ *   sfh_outconv_bwd_det                block r of ppb pixels        ceil(npix / ppb)                    nc * cin + nc    [k][ci], then [k]
+ *   sfh_avgpool_linear_bwd_det         frame r                      batch                               nout * C + nout  [j][c], then [j]
+ *   sfh_train_losses_det               block r                      min(2048, ceil(npix / 256))         3
+ *   sfh_uv_loss_det                    block r                      min(1024, ceil(B*C*H*W / 256))      1
+ *   sfh_reproj_loss_det                block r of 64 frames         ceil(batch / 64)                    1   (the 64 frames added in frame order)
+ *   sfh_homography_warp_bwd_theta_det  block (x, y): r = y * gx + x ceil(w / 256) * ceil(h / 4)         9 * batch        [b][k]
+ *   (ppb = max(1024, 256 * ceil(floor(npix / 1024) / 256)).  The backward-filter slabs are compact: the sum pass places
+ *   them at columns [n_off, n_off + N) of raw.)
+ *
+ * workspace_bytes >= NAME_det_bytes(...) = R * E * sizeof(element); a workspace that is NULL or smaller returns SFH_E_ARG
+ * with nothing launched.  The library allocates nothing and keeps no pointer.  Same library build, device model, shapes and
+ * operands -> the same bits, whatever else runs on the device; not across batch sizes or devices (the partition depends on
+ * the geometry).  The one-pass forms (sfh_s2d_split_colsum, sfh_pool2_bwd_bn_reduce, sfh_outconv_bwd_bn,
+ * sfh_conv_wgrad_c4_bn, sfh_bn_stats_partials, sfh_conv_desc.stats_partial) have no sibling: the mode takes their plain legs. */
+/* dst[(e / ncol) * dst_row_stride + e % ncol] += sum over r < slabs of partial[r * slab_stride + e], e < elems, in the order
+ * above.  elems % ncol == 0, slab_stride >= elems, dst_row_stride >= ncol.                                                 */
+int sfh_det_reduce_f32(const float* partial, int64_t slabs, int64_t slab_stride, int64_t elems, int ncol, float* dst,
+                       int64_t dst_row_stride, void* stream);
+int sfh_det_reduce_f64(const double* partial, int64_t slabs, int64_t slab_stride, int64_t elems, int ncol, double* dst,
+                       int64_t dst_row_stride, void* stream);
+int64_t sfh_conv_wgrad_det_bytes(int M, int x_cs, int xh, int xw, int N, int pad_top, int pad_left, int batch, int H, int W,
+                                 int ksize);
+int sfh_conv_wgrad_det(const float* dz, int dz_cs, int M, const float* x, int x_cs, int xh, int xw, int N, int pad_top,
+                       int pad_left, int batch, int H, int W, int ksize, float* raw, int raw_n, int n_off, void* workspace,
+                       long long workspace_bytes, void* stream);
+int64_t sfh_conv_wgrad_s3_det_bytes(int M, int N, int batch, int H, int W, int ksize);
+int sfh_conv_wgrad_s3_det(const void* dz_s3, int M, const void* x_s3, int x_channels, int xh, int xw, int N, int pad_top,
+                          int pad_left, int batch, int H, int W, int ksize, float* raw, int raw_n, int n_off, int fmt,
+                          void* workspace, long long workspace_bytes, void* stream);
+int64_t sfh_conv_grouped_wgrad_det_bytes(int batch, int H, int W, int groups, int cg, int stride);
+int sfh_conv_grouped_wgrad_det(const float* dz, const float* src, float* raw, int batch, int H, int W, int groups, int cg,
+                               int stride, void* workspace, long long workspace_bytes, void* stream);
+int64_t sfh_bn_stats_det_bytes(int64_t npix, int C);
+int sfh_bn_stats_det(const float* z, int64_t npix, int C, double* acc, void* workspace, long long workspace_bytes, void* stream);
+int64_t sfh_bn_bwd_reduce_det_bytes(int64_t npix, int C);
+int sfh_bn_bwd_reduce_det(const float* dy, const float* y, const float* z, const float* mean_invstd, const float* gamma,
+                          const float* beta, int relu, int64_t npix, int C, double* acc, void* workspace,
+                          long long workspace_bytes, void* stream);
+int64_t sfh_colsum_det_bytes(int64_t npix, int C);
+int sfh_colsum_det(const float* x, int64_t npix, int C, int cs, double* acc, void* workspace, long long workspace_bytes,
+                   void* stream);
+int64_t sfh_outconv_bwd_det_bytes(int cin, int nc, int batch, int H, int W);
+int sfh_outconv_bwd_det(const float* x, int cin, const float* w, const float* dlogits_nchw, int nc, int batch, int H, int W,
+                        float* dx, double* acc_w, double* acc_b, void* workspace, long long workspace_bytes, void* stream);
+int64_t sfh_avgpool_linear_bwd_det_bytes(int batch, int C, int nout);
+int sfh_avgpool_linear_bwd_det(const float* x, const float* w, const float* dout, int batch, int H, int W, int C, int nout,
+                               float* dx, double* acc_w, double* acc_b, void* workspace, long long workspace_bytes,
+                               void* stream);
+int64_t sfh_train_losses_det_bytes(int batch, int H, int W);
+int sfh_train_losses_det(const float* logits_nchw, const int64_t* gt_mask, const float* weight, const float* warp_mask, int nc,
+                         int batch, int H, int W, float lambda_seg, float lambda_rec, int rec_mse, float lambda_cons,
+                         int focal_flags, float* dlogits_nchw, float* dwarp, double* loss3, void* workspace,
+                         long long workspace_bytes, void* stream);
+int64_t sfh_reproj_loss_det_bytes(int batch);
+int sfh_reproj_loss_det(const float* poi, const float* gt_poi, const float* nonzeros, const float* num_nonzero, int batch,
+                        int npts, float lambda, float* dpoi, double* loss, void* workspace, long long workspace_bytes,
+                        void* stream);
+int64_t sfh_uv_loss_det_bytes(int batch, int C, int H, int W);
+int sfh_uv_loss_det(const float* uv, const float* gt_uv, const float* weight, int nweights, int batch, int C, int H, int W,
+                    float lambda, int mse, float* duv, double* loss, void* workspace, long long workspace_bytes, void* stream);
+int64_t sfh_homography_warp_bwd_theta_det_bytes(int batch, int h, int w);
+int sfh_homography_warp_bwd_theta_det(const float* theta, const float* tmpl, int64_t tmpl_bstride, int ht, int wt, int batch,
+                                      int h, int w, const float* dout, double* acc, void* workspace,
+                                      long long workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -228,7 +228,29 @@ SIGNATURES = {
     "sfh_resample_u8": (C.c_int, [_p, _p, _p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p, _p, C.c_int, C.c_int,
                                   _p, _p, C.c_int, C.c_int, C.c_int, _p]),
     "sfh_resize_gather": (C.c_int, [_p, _p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p, _p, _p]),
+    "sfh_det_reduce_f32": (C.c_int, [_p, C.c_int64, C.c_int64, C.c_int64, C.c_int, _p, C.c_int64, _p]),
+    "sfh_det_reduce_f64": (C.c_int, [_p, C.c_int64, C.c_int64, C.c_int64, C.c_int, _p, C.c_int64, _p]),
 }
+
+
+def _add_det_siblings():
+    """NAME_det: NAME's arguments with (workspace, workspace_bytes) in front of the stream; NAME_det_bytes: the size query
+    (include/sfh_amd.h, deterministic training mode)"""
+    i = C.c_int
+    queries = {
+        "sfh_conv_wgrad": [i] * 11, "sfh_conv_wgrad_s3": [i] * 6, "sfh_conv_grouped_wgrad": [i] * 6,
+        "sfh_bn_stats": [C.c_int64, i], "sfh_bn_bwd_reduce": [C.c_int64, i], "sfh_colsum": [C.c_int64, i],
+        "sfh_outconv_bwd": [i] * 5, "sfh_avgpool_linear_bwd": [i] * 3, "sfh_train_losses": [i] * 3,
+        "sfh_reproj_loss": [i], "sfh_uv_loss": [i] * 4, "sfh_homography_warp_bwd_theta": [i] * 3,
+    }
+    for name, qargs in queries.items():
+        res, args = SIGNATURES[name]
+        SIGNATURES[name + "_det"] = (res, args[:-1] + [_p, C.c_longlong, _p])
+        SIGNATURES[name + "_det_bytes"] = (C.c_int64, qargs)
+
+
+_add_det_siblings()
+DET_ENTRIES = tuple(sorted(n[:-4] for n in SIGNATURES if n.endswith("_det")))
 
 _lib = None
 

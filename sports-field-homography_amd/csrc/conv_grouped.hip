@@ -22,6 +22,7 @@
 //   throughout, one fp32 atomic add per raw element and workgroup, no fp64).
 #include "common.h"
 #include "conv_grouped_core.h"
+#include "det_core.h"   // det_add and the tile count: the deterministic mode's slabs
 
 namespace {
 
@@ -108,7 +109,9 @@ __global__ __launch_bounds__(256) void conv_grouped_kernel(const float* __restri
   }
 }
 
-template <int CG, int S>
+// DET: the store pass of the deterministic mode (det_core.h): raw is the workspace, the tile's workgroups store their sums into
+// slab blockIdx.x (a whole raw); DET = false is the kernel as it was
+template <int CG, int S, bool DET = false>
 __global__ __launch_bounds__(256) void conv_grouped_wgrad_kernel(const float* __restrict__ dz, const float* __restrict__ src,
                                                                  float* __restrict__ raw, int H, int W, int Ho, int Wo, int C,
                                                                  int tiles_x, int tiles_y) {
@@ -177,7 +180,9 @@ __global__ __launch_bounds__(256) void conv_grouped_wgrad_kernel(const float* __
     for (int l = 1; l < NPL; ++l) s += sm[l * NU * 36 + v];
     const int uu = v / 36, k = (v % 36) / 4, j = v % 4;
     const int o = ob * 32 + uu % 32;
-    if (o < C) unsafeAtomicAdd(&raw[gc_raw_index(CG, o, k, chunk * 32 + 4 * (uu / 32) + j)], s);
+    if (o < C)
+      det_add<DET>(&raw[(DET ? det_slab_offset(blockIdx.x, (long)C * 9 * CG) : 0L) + gc_raw_index(CG, o, k, chunk * 32 + 4 * (uu / 32) + j)],
+                   s);
   }
 }
 
@@ -229,13 +234,19 @@ struct FwdLaunch {
 
 template <int CG, int S>
 struct WgradLaunch {
-  static int launch(const float* dz, const float* src, float* raw, int batch, int H, int W, int C, hipStream_t st) {
+  // ws == nullptr: the default mode, atomics onto raw; else the store pass into ws (slab per tile) and the sum pass
+  static int launch(const float* dz, const float* src, float* raw, float* ws, int batch, int H, int W, int C, hipStream_t st) {
     const int Ho = gc_out_size(H, S), Wo = gc_out_size(W, S);
     const int tx = sfh_cdiv(Wo, GC_TW), ty = sfh_cdiv(Ho, gc_tile_h(S));
-    hipLaunchKernelGGL((conv_grouped_wgrad_kernel<CG, S>),
-                       dim3((unsigned)(batch * ty * tx), (unsigned)(sfh_cdiv(C, 32) * (CG / gc_chunk(CG)))), dim3(256), 0, st,
-                       dz, src, raw, H, W, Ho, Wo, C, tx, ty);
-    return sfh_check_launch("conv_grouped_wgrad_kernel");
+    const dim3 grid((unsigned)(batch * ty * tx), (unsigned)(sfh_cdiv(C, 32) * (CG / gc_chunk(CG))));
+    if (!ws) {
+      hipLaunchKernelGGL((conv_grouped_wgrad_kernel<CG, S>), grid, dim3(256), 0, st, dz, src, raw, H, W, Ho, Wo, C, tx, ty);
+      return sfh_check_launch("conv_grouped_wgrad_kernel");
+    }
+    hipLaunchKernelGGL((conv_grouped_wgrad_kernel<CG, S, true>), grid, dim3(256), 0, st, dz, src, ws, H, W, Ho, Wo, C, tx, ty);
+    if (int rc = sfh_check_launch("conv_grouped_wgrad_kernel (deterministic)")) return rc;
+    const long elems = (long)C * 9 * CG;
+    return sfh_det_reduce_f32(ws, (long)batch * ty * tx, elems, elems, CG, raw, CG, st);
   }
 };
 
@@ -284,5 +295,22 @@ extern "C" int sfh_conv_grouped_wgrad(const float* dz, const float* src, float* 
                                       int cg, int stride, void* stream) {
   SFH_REQUIRE(dz && src && raw, "conv_grouped_wgrad: null pointer");
   if (int rc = check_geometry("conv_grouped_wgrad", batch, H, W, groups, cg, stride)) return rc;
-  return dispatch<WgradLaunch>(cg, stride, dz, src, raw, batch, H, W, groups * cg, (hipStream_t)stream);
+  return dispatch<WgradLaunch>(cg, stride, dz, src, raw, (float*)nullptr, batch, H, W, groups * cg, (hipStream_t)stream);
+}
+
+extern "C" int64_t sfh_conv_grouped_wgrad_det_bytes(int batch, int H, int W, int groups, int cg, int stride) {
+  if (!gc_cg_ok(cg) || !(stride == 1 || stride == 2) || batch <= 0 || H <= 0 || W <= 0 || groups <= 0 ||
+      (long)groups * cg > 65536 || (long)batch * H * W >= (1L << 31) / 16)
+    return -1;
+  return det_bytes(det_grouped_tiles(batch, H, W, stride), det_grouped_elems(groups, cg), sizeof(float));
+}
+
+extern "C" int sfh_conv_grouped_wgrad_det(const float* dz, const float* src, float* raw, int batch, int H, int W, int groups,
+                                          int cg, int stride, void* workspace, long long workspace_bytes, void* stream) {
+  SFH_REQUIRE(dz && src && raw, "conv_grouped_wgrad_det: null pointer");
+  if (int rc = check_geometry("conv_grouped_wgrad_det", batch, H, W, groups, cg, stride)) return rc;
+  const long long need = sfh_conv_grouped_wgrad_det_bytes(batch, H, W, groups, cg, stride);
+  SFH_REQUIRE(workspace != nullptr && workspace_bytes >= need, "conv_grouped_wgrad_det: workspace of %lld bytes, %lld needed",
+              workspace ? workspace_bytes : 0LL, need);
+  return dispatch<WgradLaunch>(cg, stride, dz, src, raw, (float*)workspace, batch, H, W, groups * cg, (hipStream_t)stream);
 }

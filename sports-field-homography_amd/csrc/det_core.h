@@ -1,0 +1,194 @@
+// det_core.h - the partition arithmetic of the deterministic training mode, stated once.
+//
+// THE RULE.  In deterministic mode every sum that crosses workgroups is taken in two launches:
+//   store pass: the accumulating kernel stores what it would have added - one value per element and SHARE of the work - into
+//     its own SLAB of a caller-provided workspace.  The slab index is the index that selects the kernel's share: the pixel
+//     split of a backward-filter launch, the block of a pixel reduction, the tile of the grouped backward-filter, the frame
+//     of the pooled head.  Slab r holds elements [r * E, (r + 1) * E) of the workspace, E = elements per slab, in the
+//     accumulator's own type (fp32 for raw, fp64 for the fp64 accumulators).  Every element of every slab is written exactly
+//     once per launch with a plain store (an empty share stores zeros); no float atomic runs, no workgroup waits for another.
+//   sum pass (det_reduce_kernel, csrc/det.hip): dst[e] = (...((dst0[e] + p_0[e]) + p_1[e]) + ...) + p_{R-1}[e] - the ASCENDING
+//     CHAIN over the R slabs, starting from what the destination held (det_sum below), in the accumulator's precision.
+// The result is a function of the operands and the geometry alone; it does not depend on what else runs on the device.
+//
+// Everything below is plain integer arithmetic that host and device evaluate alike.  What the library itself reads here:
+// the launchers and the size queries (sfh_*_det_bytes) the block counts, the split plans and the bytes; the DET kernels the
+// slab offsets (det_slab_offset), the backward-filter element offset (det_wgrad_elem) and det_add; the sum pass det_sum and
+// det_dst_offset.  The share -> slab maps marked RESTATEMENT are not called by any kernel: a kernel's tile or pixel loop is
+// the one its default instantiation has always had (that instruction stream must not move), and the map states beside it
+// which slab that loop's share ends in, for tests/det_host_main.cpp to hold against the same loop written out on the host.
+// Plain C++, no HIP header outside the __HIPCC__ block at the end.
+#pragma once
+
+#if defined(__HIPCC__)
+#define SFH_DET_FN __host__ __device__ __forceinline__
+#else
+#define SFH_DET_FN inline
+#endif
+
+SFH_DET_FN int det_cdiv(int a, int b) { return (a + b - 1) / b; }
+SFH_DET_FN long det_cdivl(long a, long b) { return (a + b - 1) / b; }
+
+// ------------------------------------------------------------------ workspace and sum pass
+SFH_DET_FN long det_slab_offset(long slab, long elems) { return slab * elems; }
+SFH_DET_FN long long det_bytes(long slabs, long elems, int elem_bytes) { return (long long)slabs * elems * elem_bytes; }
+
+// the sum pass of ONE element e: partial = the workspace, `stride` elements from slab to slab
+template <typename T>
+SFH_DET_FN T det_sum(T dst0, const T* partial, long slabs, long stride, long e) {
+  T s = dst0;
+  for (long r = 0; r < slabs; ++r) s += partial[r * stride + e];
+  return s;
+}
+// element e of a slab whose rows are ncol wide -> offset in a destination whose rows are dst_row_stride apart (a
+// backward-filter source that fills columns [n_off, n_off + N) of raw: ncol = N, dst_row_stride = raw_n, dst = raw + n_off)
+SFH_DET_FN long det_dst_offset(long e, int ncol, long dst_row_stride) { return (e / ncol) * dst_row_stride + e % ncol; }
+
+// ------------------------------------------------------------------ pixel reductions (csrc/train.hip)
+// sfh_bn_stats / sfh_colsum / sfh_bn_bwd_reduce: at most DET_RED_BLOCKS blocks of 256 threads, one more per DET_RED_ROWS
+// pixels.  Slab = block.  Elements per slab: 2 * C (bn_stats, bn_bwd_reduce: [row][channel]) or C (colsum).
+#define DET_RED_ROWS 256
+#define DET_RED_BLOCKS 1024
+SFH_DET_FN long det_red_blocks(long npix) {
+  const long nb = (npix + DET_RED_ROWS - 1) / DET_RED_ROWS;
+  return nb < 1 ? 1 : (nb > DET_RED_BLOCKS ? DET_RED_BLOCKS : nb);
+}
+// RESTATEMENT (host walk only) of the kernels' pixel loops:
+// bn_stats: block b streams the contiguous range [b * chunk, min(npix, (b + 1) * chunk)), possibly empty
+SFH_DET_FN long det_red_chunk(long npix, long nblocks) { return (npix + nblocks - 1) / nblocks; }
+SFH_DET_FN long det_red_block_of_pixel_chunked(long p, long npix, long nblocks) { return p / det_red_chunk(npix, nblocks); }
+// colsum / bn_bwd_reduce / train_losses / uv_loss: grid-stride in groups of `lanes` consecutive pixels
+SFH_DET_FN long det_red_block_of_pixel_strided(long p, int lanes, long nblocks) { return (p / lanes) % nblocks; }
+// pixel lanes of a 256-thread block over C channels (channel quads, at most 1024 channels per pass)
+SFH_DET_FN int det_red_lanes(int C) { const int cq = (C < 1024 ? C : 1024) >> 2; return 256 / cq; }
+
+// sfh_outconv_bwd: block b owns pixels [b * ppb, min(npix, (b + 1) * ppb)); slab = block; elements [nc][cin] then [nc]
+SFH_DET_FN long det_outconv_ppb(long npix) {
+  long ppb = (npix / 1024 + 255) / 256 * 256;
+  return ppb < 1024 ? 1024 : ppb;
+}
+SFH_DET_FN long det_outconv_blocks(long npix) { return det_cdivl(npix, det_outconv_ppb(npix)); }
+SFH_DET_FN long det_outconv_elems(int nc, int cin) { return (long)nc * cin + nc; }
+
+// sfh_avgpool_linear_bwd: slab = frame; elements [nout][C] then [nout]
+SFH_DET_FN long det_avgpool_elems(int nout, int C) { return (long)nout * C + nout; }
+
+// sfh_train_losses (3 loss words per slab) and sfh_uv_loss (1): slab = block
+SFH_DET_FN long det_losses_blocks(long npix) { const long nb = (npix + 255) / 256; return nb > 2048 ? 2048 : nb; }
+SFH_DET_FN long det_uv_blocks(long total) { const long nb = (total + 255) / 256; return nb > 1024 ? 1024 : nb; }
+// sfh_reproj_loss: one thread per frame, 64 frames per block; slab = block, one loss word
+SFH_DET_FN long det_reproj_blocks(int batch) { return det_cdiv(batch, 64); }
+
+// warp_bwd_theta_kernel: block (bx, by) covers 256 columns x 4 rows of every frame; slab = by * gx + bx, elements [batch][9]
+SFH_DET_FN int det_warp_gx(int w) { return det_cdiv(w, 256); }
+SFH_DET_FN int det_warp_gy(int h) { return det_cdiv(h, 4); }
+SFH_DET_FN long det_warp_slab(int bx, int by, int gx) { return (long)by * gx + bx; }
+
+// ------------------------------------------------------------------ backward-filter, fp32 MFMA (csrc/train.hip)
+// 64-pixel tiles of th x tw (the shape with the fewest tiles; ties go to the widest), tile index = (b * nty + ty) * ntx + tx.
+// Split s owns the tiles s, s + nsplit, s + 2 * nsplit, ...: slab of a tile = tile % nsplit.  Slab element of raw[m][tap][n]
+// (n counted from the source's first channel): (m * kk + tap) * N + n - the slab is compact, the sum pass places it at
+// column n_off of raw.
+SFH_DET_FN int det_wgrad_tile_shape(int H, int W) {   // 0: 2x32, 1: 4x16, 2: 8x8
+  const int th[3] = {2, 4, 8}, tw[3] = {32, 16, 8};
+  int best = 0;
+  long bc = -1;
+  for (int i = 0; i < 3; ++i) {
+    const long c = (long)det_cdiv(H, th[i]) * det_cdiv(W, tw[i]);
+    if (bc < 0 || c < bc) { bc = c; best = i; }
+  }
+  return best;
+}
+SFH_DET_FN int det_tile_h(int shape) { return shape == 0 ? 2 : (shape == 1 ? 4 : 8); }
+SFH_DET_FN int det_tile_w(int shape) { return shape == 0 ? 32 : (shape == 1 ? 16 : 8); }
+// the first-layer form (wgrad_c4_kernel): 3x3 over at most four channels stored as four, one source of the frame's own size
+SFH_DET_FN bool det_wgrad_is_c4(int ksize, int N, int x_cs, int xh, int xw, int pad_top, int pad_left, int H, int W) {
+  return ksize == 3 && N <= 4 && x_cs == 4 && xh == H && xw == W && pad_top == 0 && pad_left == 0;
+}
+// n columns of a workgroup (16 per sub-block)
+SFH_DET_FN int det_wgrad_nsub(int ksize, int N) { return ksize == 3 ? (N <= 16 ? 1 : 4) : (ksize == 1 ? 4 : 2); }
+
+struct DetWgradPlan {
+  int shape, ntx, nty, ntiles, mt, mn, nsplit, kk;
+  long elems;   // per slab
+};
+SFH_DET_FN DetWgradPlan det_wgrad_plan(int M, int N, int ksize, bool c4, int batch, int H, int W) {
+  DetWgradPlan p;
+  p.shape = det_wgrad_tile_shape(H, W);
+  p.ntx = det_cdiv(W, det_tile_w(p.shape));
+  p.nty = det_cdiv(H, det_tile_h(p.shape));
+  p.ntiles = batch * p.ntx * p.nty;
+  p.mt = det_cdiv(M, 64);
+  p.mn = c4 ? p.mt : p.mt * det_cdiv(N, 16 * det_wgrad_nsub(ksize, N));
+  int ns = det_cdiv(c4 ? 2048 : 1024, p.mn);   // c4: four workgroups per CU, two rounds of 1024
+  if (ns > p.ntiles) ns = p.ntiles;
+  if (ns < 1) ns = 1;
+  if (!c4 && ns > 65535) ns = 65535;
+  if (ns < 8 && p.ntiles >= 8) ns = 8;         // one split per XCD at least
+  p.nsplit = ns;
+  p.kk = ksize * ksize;
+  p.elems = (long)M * p.kk * N;
+  return p;
+}
+SFH_DET_FN int det_wgrad_slab_of_tile(int tile, int nsplit) { return tile % nsplit; }   // RESTATEMENT (host walk only)
+// what the DET instantiations of wgrad_kernel, wgrad_c4_kernel and wgrad_s3_kernel store through
+SFH_DET_FN long det_wgrad_elem(int m, int tap, int n, int kk, int N) { return ((long)m * kk + tap) * N + n; }
+
+// ------------------------------------------------------------------ backward-filter, split operands (csrc/wgrad_s3.hip)
+// Split s owns the contiguous tiles [s * tps, min(ntiles, (s + 1) * tps)): slab of a tile = tile / tps.  Elements as above.
+SFH_DET_FN int det_wgrad_s3_tile_shape(int H, int W) {   // least padded area; ties: the widest
+  const long c0 = (long)det_cdiv(H, 2) * det_cdiv(W, 32), c1 = (long)det_cdiv(H, 4) * det_cdiv(W, 16),
+             c2 = (long)det_cdiv(H, 8) * det_cdiv(W, 8);
+  if (c0 <= c1 && c0 <= c2) return 0;
+  return c1 <= c2 ? 1 : 2;
+}
+struct DetWgradS3Plan {
+  int shape, ntx, nty, ntiles, mn, nsplit, tps, kk;
+  long elems;
+};
+SFH_DET_FN DetWgradS3Plan det_wgrad_s3_plan(int M, int N, int ksize, int batch, int H, int W) {
+  DetWgradS3Plan p;
+  p.shape = det_wgrad_s3_tile_shape(H, W);
+  p.ntx = det_cdiv(W, det_tile_w(p.shape));
+  p.nty = det_cdiv(H, det_tile_h(p.shape));
+  p.ntiles = p.ntx * p.nty * batch;
+  p.mn = (M / 64) * (N / 32);
+  // about three rounds of two workgroups per CU - and a multiple of 8: split s runs on XCD s % 8
+  int nsplit = ((1536 / p.mn + 7) / 8) * 8;
+  // at least 16 tiles per split, as long as one round of workgroups (512) is still launched
+  const int by_tiles = ((p.ntiles / 16 + 7) / 8) * 8, one_round = ((512 / p.mn + 7) / 8) * 8;
+  if (nsplit > by_tiles) nsplit = by_tiles > one_round ? by_tiles : (one_round < nsplit ? one_round : nsplit);
+  if (nsplit < 8) nsplit = 8;
+  if (nsplit > p.ntiles) nsplit = p.ntiles;
+  p.tps = det_cdiv(p.ntiles, nsplit);
+  p.nsplit = det_cdiv(p.ntiles, p.tps);
+  if (p.nsplit > 8 && p.nsplit % 8 != 0 && p.nsplit < 32) {   // e.g. 13 of 16: shave the tail to a multiple of 8
+    const int want = (p.nsplit / 8) * 8;
+    const int tps2 = det_cdiv(p.ntiles, want);
+    if (det_cdiv(p.ntiles, tps2) % 8 == 0) { p.tps = tps2; p.nsplit = det_cdiv(p.ntiles, tps2); }
+  }
+  p.kk = ksize * ksize;
+  p.elems = (long)M * p.kk * N;
+  return p;
+}
+SFH_DET_FN int det_wgrad_s3_slab_of_tile(int tile, int tps) { return tile / tps; }   // RESTATEMENT (host walk only)
+
+// ------------------------------------------------------------------ grouped backward-filter (csrc/conv_grouped.hip)
+// One workgroup row (blockIdx.x) per tile of tile_h x 16 OUTPUT pixels; slab = tile; a slab is a whole raw (C, 9, cg), indexed
+// by gc_raw_index (conv_grouped_core.h); the workgroups of one tile (blockIdx.y: 32 output channels x a 32-channel chunk)
+// write disjoint parts of it.
+SFH_DET_FN long det_grouped_tiles(int batch, int H, int W, int stride) {
+  const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
+  return (long)batch * det_cdiv(Ho, stride == 1 ? 8 : 4) * det_cdiv(Wo, 16);
+}
+SFH_DET_FN long det_grouped_elems(int groups, int cg) { return (long)groups * cg * 9 * cg; }
+
+#if defined(__HIPCC__)
+#include <hip/amd_detail/amd_hip_unsafe_atomics.h>
+// the last add of an accumulating kernel: the default mode's atomic, or the store pass's plain store into the slab
+template <bool DET, typename T>
+__device__ __forceinline__ void det_add(T* p, T v) {
+  if constexpr (DET) *p = v;
+  else unsafeAtomicAdd(p, v);
+}
+#endif

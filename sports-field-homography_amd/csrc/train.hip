@@ -13,6 +13,7 @@
 
 #include "common.h"
 #include "conv_epilogue.h"   // sfh_split4_h2: the two-plane fp16 split of the H2 format
+#include "det_core.h"        // block counts, split plans and det_add: the deterministic mode's slabs
 
 namespace {
 
@@ -21,18 +22,16 @@ namespace {
 // channel quads strides over the pixels (grid-stride, at most RED_BLOCKS blocks so that the fp64
 // atomics on the few accumulator addresses stay cheap) and adds its partials to fp64 accumulators;
 // C > 1024 is processed in chunks of 1024 channels.
-constexpr int RED_ROWS = 256;     // pixels per block below which no further blocks are launched
-constexpr int RED_BLOCKS = 1024;  // 4 per CU
+// (det_core.h: DET_RED_ROWS = 256 pixels per block below which no further blocks are launched, DET_RED_BLOCKS = 1024, 4 per CU)
+static inline unsigned red_grid(long npix) { return (unsigned)det_red_blocks(npix); }
 
-static inline unsigned red_grid(long npix) {
-  long nb = (npix + RED_ROWS - 1) / RED_ROWS;
-  return (unsigned)(nb < 1 ? 1 : (nb > RED_BLOCKS ? RED_BLOCKS : nb));
-}
+// DET (every accumulating kernel below): the store pass of the deterministic mode (det_core.h).  `acc` is then the workspace,
+// the block moves it to its own slab and the last add of every element is a plain store; DET = false is the kernel as it was.
 
 // The end of such a block: thread (pixel lane pl, channel quad q) = threadIdx.x = pl * cq + q holds NV partial sums, NV / 4
 // rows of its quad's four channels (s[4 * r + i]: row r, channel 4 * q + i; `live`: pl < 256 / cq).  One value at a time goes
 // through sh[256], the first cq threads add the lanes up and acc[r * row_stride + 4 * q + i] takes the sum in one atomic.
-template <int NV>
+template <bool DET = false, int NV>
 __device__ __forceinline__ void red_tail(const double (&s)[NV], bool live, int cq, double* sh, double* __restrict__ acc,
                                          long row_stride) {
   const int lanes = 256 / cq;
@@ -44,15 +43,17 @@ __device__ __forceinline__ void red_tail(const double (&s)[NV], bool live, int c
     if (threadIdx.x < cq) {
       double t = 0.0;
       for (int l = 0; l < lanes; ++l) t += sh[l * cq + threadIdx.x];
-      unsafeAtomicAdd(&acc[(long)(j >> 2) * row_stride + 4 * threadIdx.x + (j & 3)], t);
+      det_add<DET>(&acc[(long)(j >> 2) * row_stride + 4 * threadIdx.x + (j & 3)], t);
     }
   }
 }
 
 // acc[0][c] += sum z, acc[1][c] += sum z^2
+template <bool DET = false>
 __global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__ z, long npix, int C,
                                                        double* __restrict__ acc) {
   __shared__ double sh[256];
+  if constexpr (DET) acc += det_slab_offset(blockIdx.x, 2L * C);
   for (int c0 = 0; c0 < C; c0 += 1024) {
     const int cq = min(1024, C - c0) >> 2;
     const int lanes = 256 / cq;
@@ -88,7 +89,7 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__
         }
       }
     }
-    red_tail(s, pl < lanes, cq, sh, acc + c0, C);
+    red_tail<DET>(s, pl < lanes, cq, sh, acc + c0, C);
   }
 }
 
@@ -108,10 +109,12 @@ __global__ __launch_bounds__(256) void bn_stats_partials_kernel(const double* __
 }
 
 // acc[c] += sum x[:, c] over a channel slice (cs >= C)
+template <bool DET = false>
 __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ x, long npix, int C, int cs,
                                                      double* __restrict__ acc) {
   // one channel quad per thread column; supports cs >= C (channel slices)
   __shared__ double sh[256];
+  if constexpr (DET) acc += det_slab_offset(blockIdx.x, C);
   const int cq = C >> 2;
   for (int q0 = 0; q0 < cq; q0 += 256) {
     const int qn = min(256, cq - q0);
@@ -124,7 +127,7 @@ __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ x
 #pragma unroll
         for (int j = 0; j < 4; ++j) s[j] += (double)v[j];
       }
-    red_tail(s, pl < lanes, qn, sh, acc + 4 * q0, 0);
+    red_tail<DET>(s, pl < lanes, qn, sh, acc + 4 * q0, 0);
   }
 }
 
@@ -196,12 +199,14 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
 // g = dy * (y > 0 if relu); sums: [0] = sum g, [1] = sum g * xhat
 // relu with y == nullptr: the layer has no residual, so the ReLU decision y > 0 is recomputed from z (bn_math.h) instead
 // of reading y: 8 instead of 12 bytes per element.
+template <bool DET = false>
 __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* __restrict__ dy, const float* __restrict__ y,
                                                             const float* __restrict__ z, const float* __restrict__ mi,
                                                             const float* __restrict__ gamma, const float* __restrict__ beta,
                                                             int relu, long npix, int C, double* __restrict__ acc) {
   const bool sign_from_z = relu && !y;
   __shared__ double sh[256];
+  if constexpr (DET) acc += det_slab_offset(blockIdx.x, 2L * C);
   for (int c0 = 0; c0 < C; c0 += 1024) {
     const int cq = min(1024, C - c0) >> 2;
     const int lanes = 256 / cq;
@@ -239,7 +244,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* __restr
         add(*reinterpret_cast<const f32x4*>(dy + o), *reinterpret_cast<const f32x4*>(z + o), yy);
       }
     }
-    red_tail(s, pl < lanes, cq, sh, acc + c0, C);
+    red_tail<DET>(s, pl < lanes, cq, sh, acc + c0, C);
   }
 }
 
@@ -745,7 +750,7 @@ __global__ __launch_bounds__(256) void zero_stuff2_kernel(const float* __restric
 // BN (sfh_outconv_bwd_bn): x is not read - it is the BatchNorm + ReLU output of the layer in front, recomputed from that
 // layer's conv output z (bn_math.h) - and, dx being that layer's whole gradient, the pass also leaves
 // its backward sums [sum g | sum g * xhat], g = dx * (x > 0): sfh_bn_bwd_reduce's second pass over dx and z is not needed.
-template <int NC, bool BN>
+template <int NC, bool BN, bool DET = false>
 __global__ __launch_bounds__(256) void outconv_bwd_kernel(const float* __restrict__ x, int cin,
                                                           const float* __restrict__ w, const float* __restrict__ dl,
                                                           long npix, int HW, float* __restrict__ dx,
@@ -754,6 +759,10 @@ __global__ __launch_bounds__(256) void outconv_bwd_kernel(const float* __restric
                                                           const float* __restrict__ bn_gamma, const float* __restrict__ bn_beta,
                                                           double* __restrict__ acc_bn) {
   __shared__ double sh[256];
+  if constexpr (DET) {   // acc_w = the workspace: this block's slab is [NC][cin] weight sums, then [NC] bias sums
+    acc_w += det_slab_offset(blockIdx.x, det_outconv_elems(NC, cin));
+    acc_b = acc_w + (long)NC * cin;
+  }
   const int cq = cin >> 2;  // <= 64
   const int lanes = 256 / cq;
   const int q = threadIdx.x % cq, pl = threadIdx.x / cq;
@@ -831,14 +840,14 @@ __global__ __launch_bounds__(256) void outconv_bwd_kernel(const float* __restric
     double tw[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) tw[j] = dsw[k][j] + (double)sw[k][j];
-    red_tail(tw, pl < lanes, cq, sh, acc_w + k * cin, 0);
+    red_tail<DET>(tw, pl < lanes, cq, sh, acc_w + k * cin, 0);
     __syncthreads();
     sh[threadIdx.x] = (pl < lanes) ? dsb[k] + (double)sb[k] : 0.0;
     __syncthreads();
     if (threadIdx.x == 0) {
       double t = 0.0;
       for (int l = 0; l < lanes; ++l) t += sh[l * cq];  // q == 0 lanes
-      unsafeAtomicAdd(&acc_b[k], t);
+      det_add<DET>(&acc_b[k], t);
     }
   }
 }
@@ -888,11 +897,16 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_bwd_kernel(const float* __re
 
 // AdaptiveAvgPool2d(1) + Linear backward; one block per frame.
 // dx[b,p,c] = (sum_j dout[b][j] w[j][c]) / HW;  acc_w[j][c] += dout[b][j] * mean_p x[b,p,c];  acc_b[j] += dout[b][j]
+template <bool DET = false>
 __global__ __launch_bounds__(256) void avgpool_linear_bwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                                  const float* __restrict__ dout, int HW, int C, int nout,
                                                                  float* __restrict__ dx, double* __restrict__ acc_w,
                                                                  double* __restrict__ acc_b) {
   const int b = blockIdx.x;
+  if constexpr (DET) {   // acc_w = the workspace: frame b's slab is [nout][C] weight terms, then [nout] bias terms
+    acc_w += det_slab_offset(b, det_avgpool_elems(nout, C));
+    acc_b = acc_w + (long)nout * C;
+  }
   const float* xb = x + (long)b * HW * C;
   float* dxb = dx + (long)b * HW * C;
   const float inv = 1.0f / (float)HW;
@@ -904,12 +918,12 @@ __global__ __launch_bounds__(256) void avgpool_linear_bwd_kernel(const float* __
     for (int j = 0; j < nout; ++j) {
       const float d = dout[b * nout + j];
       df += d * w[j * C + c];
-      unsafeAtomicAdd(&acc_w[(long)j * C + c], (double)d * (double)mean);
+      det_add<DET>(&acc_w[(long)j * C + c], (double)d * (double)mean);
     }
     df *= inv;
     for (int i = 0; i < HW; ++i) dxb[(long)i * C + c] = df;
   }
-  if (threadIdx.x < nout) unsafeAtomicAdd(&acc_b[threadIdx.x], (double)dout[b * nout + threadIdx.x]);
+  if (threadIdx.x < nout) det_add<DET>(&acc_b[threadIdx.x], (double)dout[b * nout + threadIdx.x]);
 }
 
 // Backward-data of the 7x7 stride-2 pad-3 stem (models/resnet.py:172) for the first `nc` input channels
@@ -1029,7 +1043,7 @@ __device__ __forceinline__ float cls_loss(const float (&l)[NC], const float (&pr
   return loss;
 }
 
-template <int NC>
+template <int NC, bool DET = false>
 __global__ __launch_bounds__(256) void train_losses_kernel(const LossArgs a) {
   __shared__ double sh[256];
   double s_seg = 0.0, s_rec = 0.0, s_cons = 0.0;
@@ -1075,15 +1089,46 @@ __global__ __launch_bounds__(256) void train_losses_kernel(const LossArgs a) {
       if (threadIdx.x < off) sh[threadIdx.x] += sh[threadIdx.x + off];
       __syncthreads();
     }
-    if (threadIdx.x == 0) unsafeAtomicAdd(&a.loss[k], sh[0] * (double)inv);
+    if (threadIdx.x == 0) det_add<DET>(&a.loss[DET ? det_slab_offset(blockIdx.x, 3) + k : k], sh[0] * (double)inv);
   }
 }
 
 // models/losses.py:6-19 (reduction 'mean') and its gradient wrt the projected points; one thread per frame.
+// DET: the 64 frames of a block (frames past the batch: zeros) are added in frame order and stored into the block's slab (one
+// word).  The frame's body stands twice: shared through a device function, the default instantiation compiled to another
+// instruction stream than the one it was.
+template <bool DET = false>
 __global__ void reproj_loss_kernel(const float* __restrict__ poi, const float* __restrict__ gt,
                                    const float* __restrict__ nonzeros, const float* __restrict__ num_nonzero,
                                    int batch, int npts, float lambda, float* __restrict__ dpoi, double* __restrict__ loss) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if constexpr (DET) {
+    __shared__ double sh[64];
+    double term = 0.0;
+    if (b < batch) {
+      double s = 0.0;
+      const float sc = lambda / (num_nonzero[b] * (float)batch);
+      for (int n = 0; n < npts; ++n) {
+        const long o = ((long)b * npts + n) * 2;
+        const float dx = gt[o] - poi[o], dy = gt[o + 1] - poi[o + 1];
+        const float dist = sqrtf(dx * dx + dy * dy);
+        const float nz = nonzeros[(long)b * npts + n];
+        s += (double)(dist * nz);
+        const float g = dist > 0.f ? nz * sc / dist : 0.f;
+        dpoi[o] = -g * dx;
+        dpoi[o + 1] = -g * dy;
+      }
+      term = s * (double)sc;
+    }
+    sh[threadIdx.x] = term;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      double t = 0.0;
+      for (int l = 0; l < 64; ++l) t += sh[l];
+      loss[blockIdx.x] = t;
+    }
+    return;
+  }
   if (b >= batch) return;
   double s = 0.0;
   const float sc = lambda / (num_nonzero[b] * (float)batch);
@@ -1180,6 +1225,7 @@ __global__ __launch_bounds__(256) void adam_kernel(const OptTensor* __restrict__
 // over CHANNEL and ROW, leaving (B, W) - and multiplies by the (B,) weights, which broadcasts along the LAST axis: the
 // weight of column w is weights[w] (legal only for B == W) or weights[0] (B == 1).  Restated as written: `wcol` = 1 picks
 // weights[w], 0 weights[0].  loss += lambda * mean_{b,w}(weight * mean_{c,h} l); duv = its gradient.
+template <bool DET = false>
 __global__ __launch_bounds__(256) void uv_loss_kernel(const float* __restrict__ uv, const float* __restrict__ gt,
                                                       const float* __restrict__ weight, int wcol, int C, int H, int W,
                                                       long total, float lambda, int mse, float* __restrict__ duv,
@@ -1206,7 +1252,7 @@ __global__ __launch_bounds__(256) void uv_loss_kernel(const float* __restrict__ 
     if (threadIdx.x < off) sh[threadIdx.x] += sh[threadIdx.x + off];
     __syncthreads();
   }
-  if (threadIdx.x == 0) unsafeAtomicAdd(loss, sh[0] * (double)lambda * (double)inv);
+  if (threadIdx.x == 0) det_add<DET>(DET ? loss + blockIdx.x : loss, sh[0] * (double)lambda * (double)inv);
 }
 
 // ------------------------------------------------------------------ multi-tensor copy
@@ -1259,7 +1305,8 @@ struct WgradArgs {
   const float* bn_z; const float* bn_mi; const float* bn_gamma; const float* bn_beta; const double* bn_acc; float bn_inv_n;
 };
 
-template <int KS, int NSUB, int TH, int TW>
+// DET: a.raw is the workspace: split s stores its sums into slab s, element det_wgrad_elem(m, tap, n) (det_core.h)
+template <int KS, int NSUB, int TH, int TW, bool DET = false>
 __global__ __launch_bounds__(256, 2) void wgrad_kernel(const WgradArgs a) {
   static_assert(TH * TW == 64 && TW % 4 == 0, "64-pixel tiles");
   constexpr int PADB = KS == 3 ? 1 : (KS == 4 ? 2 : 0);
@@ -1370,30 +1417,41 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(const WgradArgs a) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int m = m0 + wave * 16 + 4 * kq + r;
-        if (m < a.M) unsafeAtomicAdd(a.raw + ((long)m * KK + t) * a.raw_n + a.n_off + n, acc[t][s][r]);
+        if (m < a.M) {
+          if constexpr (DET) a.raw[det_slab_offset(split, (long)a.M * KK * a.N) + det_wgrad_elem(m, t, n, KK, a.N)] = acc[t][s][r];
+          else unsafeAtomicAdd(a.raw + ((long)m * KK + t) * a.raw_n + a.n_off + n, acc[t][s][r]);
+        }
       }
     }
 }
 
+// The deterministic sibling of a backward-filter launch: the store pass into `ws` (slab per split, compact rows of N columns),
+// then the sum pass onto columns [n_off, n_off + N) of raw.  ws == nullptr: the default mode's launch, atomics onto raw.
+static int wgrad_sum_pass(const float* ws, int nsplit, long elems, int N, float* raw, int raw_n, int n_off, hipStream_t stream) {
+  return sfh_det_reduce_f32(ws, nsplit, elems, elems, N, raw + n_off, raw_n, stream);
+}
+
 template <int KS, int NSUB, int TH, int TW>
-int launch_wgrad(WgradArgs a, hipStream_t stream) {
+int launch_wgrad(WgradArgs a, const DetWgradPlan& p, float* ws, hipStream_t stream) {
   constexpr int HPX = (TH + KS - 1) * (TW + KS - 1);
   const size_t lds = (size_t)(HPX + 64) * 64 * sizeof(float);
-  a.ntx = sfh_cdiv(a.W, TW);
-  a.nty = sfh_cdiv(a.H, TH);
-  a.ntiles = a.batch * a.ntx * a.nty;
-  const int mn = sfh_cdiv(a.M, 64) * sfh_cdiv(a.N, 16 * NSUB);
-  int ns = sfh_cdiv(1024, mn);
-  if (ns > a.ntiles) ns = a.ntiles;
-  if (ns < 1) ns = 1;
-  if (ns > 65535) ns = 65535;
-  if (ns < 8 && a.ntiles >= 8) ns = 8;  // one split per XCD at least
-  a.nsplit = ns;
-  a.mt = sfh_cdiv(a.M, 64);
-  a.mn = mn;
-  const dim3 grid((unsigned)(sfh_cdiv(ns, 8) * 8 * mn));
-  hipLaunchKernelGGL((wgrad_kernel<KS, NSUB, TH, TW>), grid, dim3(256), lds, stream, a);
-  return sfh_check_launch("wgrad_kernel");
+  a.ntx = p.ntx;
+  a.nty = p.nty;
+  a.ntiles = p.ntiles;
+  a.nsplit = p.nsplit;
+  a.mt = p.mt;
+  a.mn = p.mn;
+  const dim3 grid((unsigned)(sfh_cdiv(p.nsplit, 8) * 8 * p.mn));
+  if (!ws) {
+    hipLaunchKernelGGL((wgrad_kernel<KS, NSUB, TH, TW>), grid, dim3(256), lds, stream, a);
+    return sfh_check_launch("wgrad_kernel");
+  }
+  float* raw = a.raw;
+  const int raw_n = a.raw_n, n_off = a.n_off;
+  a.raw = ws;
+  hipLaunchKernelGGL((wgrad_kernel<KS, NSUB, TH, TW, true>), grid, dim3(256), lds, stream, a);
+  if (int rc = sfh_check_launch("wgrad_kernel (deterministic)")) return rc;
+  return wgrad_sum_pass(ws, p.nsplit, p.elems, a.N, raw, raw_n, n_off, stream);
 }
 
 // Backward-filter of a 3x3 conv over at most FOUR input channels (the UNet's first layer: N = 3 stored as 4; round 4).
@@ -1405,7 +1463,7 @@ int launch_wgrad(WgradArgs a, hipStream_t stream) {
 // BN: the layer's BatchNorm backward rides in the tile load (bn_math.h: bn_bwd_apply_kernel's values): the
 // kernel reads dy and z (8 B per element) instead of a dz tensor that a separate pass would first write and this one read
 // back (12 + 4 B per element moved by the pair).
-template <int TH, int TW, bool BN>
+template <int TH, int TW, bool BN, bool DET = false>
 __global__ __launch_bounds__(256, 4) void wgrad_c4_kernel(const WgradArgs a) {
   static_assert(TH * TW == 64 && TW % 4 == 0, "64-pixel tiles");
   constexpr int HR = TH + 2, HW = TW + 2, HPX = HR * HW;
@@ -1498,49 +1556,79 @@ __global__ __launch_bounds__(256, 4) void wgrad_c4_kernel(const WgradArgs a) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int m = m0 + wave * 16 + 4 * kq + r;
-      if (m < a.M) unsafeAtomicAdd(a.raw + ((long)m * 9 + tap) * a.raw_n + a.n_off + c, acc[nb][r]);
+      if (m < a.M) {
+        if constexpr (DET) a.raw[det_slab_offset(split, (long)a.M * 9 * a.N) + det_wgrad_elem(m, tap, c, 9, a.N)] = acc[nb][r];
+        else unsafeAtomicAdd(a.raw + ((long)m * 9 + tap) * a.raw_n + a.n_off + c, acc[nb][r]);
+      }
     }
   }
 }
 
-template <int TH, int TW, bool BN = false>
-int launch_wgrad_c4(WgradArgs a, hipStream_t stream) {
-  a.ntx = sfh_cdiv(a.W, TW);
-  a.nty = sfh_cdiv(a.H, TH);
-  a.ntiles = a.batch * a.ntx * a.nty;
-  const int mn = sfh_cdiv(a.M, 64);
-  int ns = sfh_cdiv(2048, mn);          // four workgroups per CU: two rounds of 1024
-  if (ns > a.ntiles) ns = a.ntiles;
-  if (ns < 1) ns = 1;
-  if (ns < 8 && a.ntiles >= 8) ns = 8;
-  a.nsplit = ns;
-  a.mt = mn;
-  a.mn = mn;
-  const dim3 grid((unsigned)(sfh_cdiv(ns, 8) * 8 * mn));
-  hipLaunchKernelGGL((wgrad_c4_kernel<TH, TW, BN>), grid, dim3(256), 0, stream, a);
-  return sfh_check_launch("wgrad_c4_kernel");
+template <int TH, int TW>
+int launch_wgrad_c4(WgradArgs a, const DetWgradPlan& p, float* ws, hipStream_t stream) {
+  a.ntx = p.ntx;
+  a.nty = p.nty;
+  a.ntiles = p.ntiles;
+  a.nsplit = p.nsplit;
+  a.mt = p.mn;
+  a.mn = p.mn;
+  const dim3 grid((unsigned)(sfh_cdiv(p.nsplit, 8) * 8 * p.mn));
+  if (!ws) {
+    hipLaunchKernelGGL((wgrad_c4_kernel<TH, TW, false>), grid, dim3(256), 0, stream, a);
+    return sfh_check_launch("wgrad_c4_kernel");
+  }
+  float* raw = a.raw;
+  const int raw_n = a.raw_n, n_off = a.n_off;
+  a.raw = ws;
+  hipLaunchKernelGGL((wgrad_c4_kernel<TH, TW, false, true>), grid, dim3(256), 0, stream, a);
+  if (int rc = sfh_check_launch("wgrad_c4_kernel (deterministic)")) return rc;
+  return wgrad_sum_pass(ws, p.nsplit, p.elems, a.N, raw, raw_n, n_off, stream);
 }
 
-// tile shape (rows x cols, 64 pixels) with the fewest padded pixels; ties go to the widest
-static int wgrad_tile(int H, int W) {
-  const int th[3] = {2, 4, 8}, tw[3] = {32, 16, 8};
-  int best = 0;
-  long bc = -1;
-  for (int i = 0; i < 3; ++i) {
-    const long c = (long)sfh_cdiv(H, th[i]) * sfh_cdiv(W, tw[i]);
-    if (bc < 0 || c < bc) { bc = c; best = i; }
-  }
-  return best;
+// the fused BatchNorm form (sfh_conv_wgrad_c4_bn) has no deterministic sibling: the mode takes sfh_bn_bwd_apply + sfh_conv_wgrad
+template <int TH, int TW>
+int launch_wgrad_c4_bn(WgradArgs a, const DetWgradPlan& p, hipStream_t stream) {
+  a.ntx = p.ntx;
+  a.nty = p.nty;
+  a.ntiles = p.ntiles;
+  a.nsplit = p.nsplit;
+  a.mt = p.mn;
+  a.mn = p.mn;
+  const dim3 grid((unsigned)(sfh_cdiv(p.nsplit, 8) * 8 * p.mn));
+  hipLaunchKernelGGL((wgrad_c4_kernel<TH, TW, true>), grid, dim3(256), 0, stream, a);
+  return sfh_check_launch("wgrad_c4_kernel");
 }
 
 }  // namespace
 
 // =============================================================================== C ABI
+// The deterministic siblings (sfh_*_det, include/sfh_amd.h): same arguments + (workspace, workspace_bytes); the store pass into
+// the workspace, then the sum pass (sfh_det_reduce_*) onto the destination.  A workspace that is NULL or smaller than the size
+// query's answer is refused before anything is launched.
+#define SFH_REQUIRE_WS(who, ws, ws_bytes, need)                                                                        \
+  SFH_REQUIRE((ws) != nullptr && (long long)(ws_bytes) >= (long long)(need), "%s: workspace of %lld bytes, %lld needed", \
+              who, (ws) ? (long long)(ws_bytes) : 0LL, (long long)(need))
+
 extern "C" int sfh_bn_stats(const float* z, int64_t npix, int C, double* acc, void* stream) {
   SFH_REQUIRE(z && acc && npix > 0 && C > 0 && C % 4 == 0, "bn_stats: bad argument");
   const unsigned nb = red_grid((long)npix);
-  hipLaunchKernelGGL(bn_stats_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, z, (long)npix, C, acc);
+  hipLaunchKernelGGL(bn_stats_kernel<false>, dim3(nb), dim3(256), 0, (hipStream_t)stream, z, (long)npix, C, acc);
   return sfh_check_launch("bn_stats_kernel");
+}
+
+extern "C" int64_t sfh_bn_stats_det_bytes(int64_t npix, int C) {
+  if (npix <= 0 || C <= 0 || C % 4 != 0) return -1;
+  return det_bytes(det_red_blocks((long)npix), 2L * C, sizeof(double));
+}
+
+extern "C" int sfh_bn_stats_det(const float* z, int64_t npix, int C, double* acc, void* workspace, long long workspace_bytes,
+                                void* stream) {
+  SFH_REQUIRE(z && acc && npix > 0 && C > 0 && C % 4 == 0, "bn_stats_det: bad argument");
+  SFH_REQUIRE_WS("bn_stats_det", workspace, workspace_bytes, sfh_bn_stats_det_bytes(npix, C));
+  const unsigned nb = red_grid((long)npix);
+  hipLaunchKernelGGL(bn_stats_kernel<true>, dim3(nb), dim3(256), 0, (hipStream_t)stream, z, (long)npix, C, (double*)workspace);
+  if (int rc = sfh_check_launch("bn_stats_kernel (deterministic)")) return rc;
+  return sfh_det_reduce_f64((const double*)workspace, nb, 2L * C, 2L * C, 2 * C, acc, 2 * C, stream);
 }
 
 extern "C" int sfh_bn_stats_partials(const double* partial, int rows, int C, double* acc, void* stream) {
@@ -1596,9 +1684,24 @@ extern "C" int sfh_bn_bwd_reduce(const float* dy, const float* y, const float* z
   SFH_REQUIRE(dy && z && mean_invstd && acc && (y || !relu || (gamma && beta)) && npix > 0 && C > 0 && C % 4 == 0,
               "bn_bwd_reduce: bad argument (relu needs y, or gamma and beta to recompute its sign from z)");
   const unsigned nb = red_grid((long)npix);
-  hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, dy, y, z, mean_invstd, gamma,
+  hipLaunchKernelGGL(bn_bwd_reduce_kernel<false>, dim3(nb), dim3(256), 0, (hipStream_t)stream, dy, y, z, mean_invstd, gamma,
                      beta, relu, (long)npix, C, acc);
   return sfh_check_launch("bn_bwd_reduce_kernel");
+}
+
+extern "C" int64_t sfh_bn_bwd_reduce_det_bytes(int64_t npix, int C) { return sfh_bn_stats_det_bytes(npix, C); }
+
+extern "C" int sfh_bn_bwd_reduce_det(const float* dy, const float* y, const float* z, const float* mean_invstd,
+                                     const float* gamma, const float* beta, int relu, int64_t npix, int C, double* acc,
+                                     void* workspace, long long workspace_bytes, void* stream) {
+  SFH_REQUIRE(dy && z && mean_invstd && acc && (y || !relu || (gamma && beta)) && npix > 0 && C > 0 && C % 4 == 0,
+              "bn_bwd_reduce_det: bad argument (relu needs y, or gamma and beta to recompute its sign from z)");
+  SFH_REQUIRE_WS("bn_bwd_reduce_det", workspace, workspace_bytes, sfh_bn_bwd_reduce_det_bytes(npix, C));
+  const unsigned nb = red_grid((long)npix);
+  hipLaunchKernelGGL(bn_bwd_reduce_kernel<true>, dim3(nb), dim3(256), 0, (hipStream_t)stream, dy, y, z, mean_invstd, gamma,
+                     beta, relu, (long)npix, C, (double*)workspace);
+  if (int rc = sfh_check_launch("bn_bwd_reduce_kernel (deterministic)")) return rc;
+  return sfh_det_reduce_f64((const double*)workspace, nb, 2L * C, 2L * C, 2 * C, acc, 2 * C, stream);
 }
 
 extern "C" int sfh_bn_bwd_apply(const float* dy, const float* y, const float* z, const float* mean_invstd,
@@ -1626,8 +1729,23 @@ extern "C" int sfh_bn_bwd_apply(const float* dy, const float* y, const float* z,
 extern "C" int sfh_colsum(const float* x, int64_t npix, int C, int cs, double* acc, void* stream) {
   SFH_REQUIRE(x && acc && npix > 0 && C > 0 && C % 4 == 0 && cs >= C && cs % 4 == 0, "colsum: bad argument");
   const unsigned nb = red_grid((long)npix);
-  hipLaunchKernelGGL(colsum_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, x, (long)npix, C, cs, acc);
+  hipLaunchKernelGGL(colsum_kernel<false>, dim3(nb), dim3(256), 0, (hipStream_t)stream, x, (long)npix, C, cs, acc);
   return sfh_check_launch("colsum_kernel");
+}
+
+extern "C" int64_t sfh_colsum_det_bytes(int64_t npix, int C) {
+  if (npix <= 0 || C <= 0 || C % 4 != 0) return -1;
+  return det_bytes(det_red_blocks((long)npix), C, sizeof(double));
+}
+
+extern "C" int sfh_colsum_det(const float* x, int64_t npix, int C, int cs, double* acc, void* workspace,
+                              long long workspace_bytes, void* stream) {
+  SFH_REQUIRE(x && acc && npix > 0 && C > 0 && C % 4 == 0 && cs >= C && cs % 4 == 0, "colsum_det: bad argument");
+  SFH_REQUIRE_WS("colsum_det", workspace, workspace_bytes, sfh_colsum_det_bytes(npix, C));
+  const unsigned nb = red_grid((long)npix);
+  hipLaunchKernelGGL(colsum_kernel<true>, dim3(nb), dim3(256), 0, (hipStream_t)stream, x, (long)npix, C, cs, (double*)workspace);
+  if (int rc = sfh_check_launch("colsum_kernel (deterministic)")) return rc;
+  return sfh_det_reduce_f64((const double*)workspace, nb, C, C, C, acc, C, stream);
 }
 
 extern "C" int sfh_s2d_split_colsum(const float* du, int batch, int h, int w, int cout, void* s_split, int split_fmt,
@@ -1721,18 +1839,20 @@ extern "C" int sfh_zero_stuff2(const float* src, float* dst, int batch, int ho, 
   return sfh_check_launch("zero_stuff2_kernel");
 }
 
-extern "C" int sfh_conv_wgrad(const float* dz, int dz_cs, int M, const float* x, int x_cs, int xh, int xw, int N,
-                              int pad_top, int pad_left, int batch, int H, int W, int ksize, float* raw, int raw_n,
-                              int n_off, void* stream) {
-  SFH_REQUIRE(dz && x && raw, "conv_wgrad: null pointer");
-  SFH_REQUIRE(batch > 0 && H > 0 && W > 0 && xh > 0 && xw > 0, "conv_wgrad: bad geometry");
-  SFH_REQUIRE(M > 0 && M % 4 == 0 && dz_cs % 4 == 0 && dz_cs >= M, "conv_wgrad: M=%d dz_cs=%d", M, dz_cs);
-  SFH_REQUIRE(N > 0 && N % 4 == 0 && x_cs % 4 == 0 && x_cs >= N, "conv_wgrad: N=%d x_cs=%d", N, x_cs);
-  SFH_REQUIRE(n_off >= 0 && n_off + N <= raw_n, "conv_wgrad: n_off=%d N=%d raw_n=%d", n_off, N, raw_n);
+// ws == nullptr: the default mode; else the deterministic sibling's workspace, already checked against the plan's size
+static int conv_wgrad_impl(const float* dz, int dz_cs, int M, const float* x, int x_cs, int xh, int xw, int N, int pad_top,
+                           int pad_left, int batch, int H, int W, int ksize, float* raw, int raw_n, int n_off, bool det,
+                           void* workspace, long long workspace_bytes, void* stream) {
+  const char* who = det ? "conv_wgrad_det" : "conv_wgrad";
+  SFH_REQUIRE(dz && x && raw, "%s: null pointer", who);
+  SFH_REQUIRE(batch > 0 && H > 0 && W > 0 && xh > 0 && xw > 0, "%s: bad geometry", who);
+  SFH_REQUIRE(M > 0 && M % 4 == 0 && dz_cs % 4 == 0 && dz_cs >= M, "%s: M=%d dz_cs=%d", who, M, dz_cs);
+  SFH_REQUIRE(N > 0 && N % 4 == 0 && x_cs % 4 == 0 && x_cs >= N, "%s: N=%d x_cs=%d", who, N, x_cs);
+  SFH_REQUIRE(n_off >= 0 && n_off + N <= raw_n, "%s: n_off=%d N=%d raw_n=%d", who, n_off, N, raw_n);
   SFH_REQUIRE(pad_top >= 0 && pad_left >= 0 && pad_top + xh <= H && pad_left + xw <= W,
-              "conv_wgrad: source (%dx%d at %d,%d) does not fit the %dx%d frame", xh, xw, pad_top, pad_left, H, W);
-  SFH_REQUIRE(ksize == 1 || ksize == 3 || ksize == 4, "conv_wgrad: ksize %d", ksize);
-  SFH_REQUIRE(ksize != 4 || N <= 32, "conv_wgrad: the 4x4 (stem) case supports N <= 32");
+              "%s: source (%dx%d at %d,%d) does not fit the %dx%d frame", who, xh, xw, pad_top, pad_left, H, W);
+  SFH_REQUIRE(ksize == 1 || ksize == 3 || ksize == 4, "%s: ksize %d", who, ksize);
+  SFH_REQUIRE(ksize != 4 || N <= 32, "%s: the 4x4 (stem) case supports N <= 32", who);
   WgradArgs a;
   a.dz = dz; a.dz_cs = dz_cs; a.M = M;
   a.x = x; a.x_cs = x_cs; a.xh = xh; a.xw = xw; a.N = N; a.pad_top = pad_top; a.pad_left = pad_left;
@@ -1741,18 +1861,49 @@ extern "C" int sfh_conv_wgrad(const float* dz, int dz_cs, int M, const float* x,
   a.ntx = a.nty = a.ntiles = a.nsplit = a.mt = a.mn = 0;
   a.bn_z = a.bn_mi = a.bn_gamma = a.bn_beta = nullptr; a.bn_acc = nullptr; a.bn_inv_n = 0.f;
   hipStream_t st = (hipStream_t)stream;
-  const int t = wgrad_tile(H, W);
-#define SFH_WG(KS_, NS_)                                         \
-  (t == 0 ? launch_wgrad<KS_, NS_, 2, 32>(a, st)                  \
-          : (t == 1 ? launch_wgrad<KS_, NS_, 4, 16>(a, st) : launch_wgrad<KS_, NS_, 8, 8>(a, st)))
   // the network's first layer (3 input channels stored as 4, one source of the frame's own size): n = (tap, channel)
-  if (ksize == 3 && N <= 4 && x_cs == 4 && xh == H && xw == W && pad_top == 0 && pad_left == 0)
-    return t == 0 ? launch_wgrad_c4<2, 32>(a, st) : (t == 1 ? launch_wgrad_c4<4, 16>(a, st) : launch_wgrad_c4<8, 8>(a, st));
+  const bool c4 = det_wgrad_is_c4(ksize, N, x_cs, xh, xw, pad_top, pad_left, H, W);
+  const DetWgradPlan p = det_wgrad_plan(M, N, ksize, c4, batch, H, W);
+  float* ws = nullptr;
+  if (det) {
+    SFH_REQUIRE_WS("conv_wgrad_det", workspace, workspace_bytes, det_bytes(p.nsplit, p.elems, sizeof(float)));
+    ws = (float*)workspace;
+  }
+  const int t = p.shape;
+#define SFH_WG(KS_, NS_)                                         \
+  (t == 0 ? launch_wgrad<KS_, NS_, 2, 32>(a, p, ws, st)           \
+          : (t == 1 ? launch_wgrad<KS_, NS_, 4, 16>(a, p, ws, st) : launch_wgrad<KS_, NS_, 8, 8>(a, p, ws, st)))
+  if (c4)
+    return t == 0 ? launch_wgrad_c4<2, 32>(a, p, ws, st)
+                  : (t == 1 ? launch_wgrad_c4<4, 16>(a, p, ws, st) : launch_wgrad_c4<8, 8>(a, p, ws, st));
   if (ksize == 3 && N <= 16) return SFH_WG(3, 1);
   if (ksize == 3) return SFH_WG(3, 4);
   if (ksize == 1) return SFH_WG(1, 4);
   return SFH_WG(4, 2);
 #undef SFH_WG
+}
+
+extern "C" int sfh_conv_wgrad(const float* dz, int dz_cs, int M, const float* x, int x_cs, int xh, int xw, int N,
+                              int pad_top, int pad_left, int batch, int H, int W, int ksize, float* raw, int raw_n,
+                              int n_off, void* stream) {
+  return conv_wgrad_impl(dz, dz_cs, M, x, x_cs, xh, xw, N, pad_top, pad_left, batch, H, W, ksize, raw, raw_n, n_off, false,
+                         nullptr, 0, stream);
+}
+
+extern "C" int64_t sfh_conv_wgrad_det_bytes(int M, int x_cs, int xh, int xw, int N, int pad_top, int pad_left, int batch, int H,
+                                            int W, int ksize) {
+  if (batch <= 0 || H <= 0 || W <= 0 || M <= 0 || M % 4 != 0 || N <= 0 || N % 4 != 0 ||
+      !(ksize == 1 || ksize == 3 || ksize == 4) || (ksize == 4 && N > 32))
+    return -1;
+  const DetWgradPlan p = det_wgrad_plan(M, N, ksize, det_wgrad_is_c4(ksize, N, x_cs, xh, xw, pad_top, pad_left, H, W), batch, H, W);
+  return det_bytes(p.nsplit, p.elems, sizeof(float));
+}
+
+extern "C" int sfh_conv_wgrad_det(const float* dz, int dz_cs, int M, const float* x, int x_cs, int xh, int xw, int N,
+                                  int pad_top, int pad_left, int batch, int H, int W, int ksize, float* raw, int raw_n,
+                                  int n_off, void* workspace, long long workspace_bytes, void* stream) {
+  return conv_wgrad_impl(dz, dz_cs, M, x, x_cs, xh, xw, N, pad_top, pad_left, batch, H, W, ksize, raw, raw_n, n_off, true,
+                         workspace, workspace_bytes, stream);
 }
 
 extern "C" int sfh_conv_wgrad_c4_bn(const float* dy, const float* z, const float* mean_invstd, const float* gamma,
@@ -1770,9 +1921,9 @@ extern "C" int sfh_conv_wgrad_c4_bn(const float* dy, const float* z, const float
   a.bn_z = z; a.bn_mi = mean_invstd; a.bn_gamma = gamma; a.bn_beta = beta; a.bn_acc = acc;
   a.bn_inv_n = bn_inv_n((long)batch * H * W);
   hipStream_t st = (hipStream_t)stream;
-  const int t = wgrad_tile(H, W);
-  return t == 0 ? launch_wgrad_c4<2, 32, true>(a, st)
-                : (t == 1 ? launch_wgrad_c4<4, 16, true>(a, st) : launch_wgrad_c4<8, 8, true>(a, st));
+  const DetWgradPlan p = det_wgrad_plan(M, N, 3, true, batch, H, W);
+  return p.shape == 0 ? launch_wgrad_c4_bn<2, 32>(a, p, st)
+                      : (p.shape == 1 ? launch_wgrad_c4_bn<4, 16>(a, p, st) : launch_wgrad_c4_bn<8, 8>(a, p, st));
 }
 
 static int launch_outconv_bwd(const float* x, int cin, const float* w, const float* dlogits_nchw, int nc, int batch, int H,
@@ -1784,10 +1935,9 @@ static int launch_outconv_bwd(const float* x, int cin, const float* w, const flo
   const long npix = (long)batch * H * W;
   // every workgroup ends with nc * (cin + 1) fp64 atomics on the same addresses: about 1024 workgroups (at 640x360 x 16:
   // 3840 pixels each, 0.49 ms; 1024 pixels each = 3600 workgroups: 0.56 ms; 8192: 0.63 - profiles/r05_s2d_atomics.txt)
-  long ppb = (npix / 1024 + 255) / 256 * 256;
-  if (ppb < 1024) ppb = 1024;
-  const unsigned grid = (unsigned)((npix + ppb - 1) / ppb);
-#define SFH_OB(N)                                                                                                  \
+  const long ppb = det_outconv_ppb(npix);
+  const unsigned grid = (unsigned)det_outconv_blocks(npix);
+#define SFH_OB(N)                                                                                           \
   case N:                                                                                                          \
     if (acc_bn)                                                                                                    \
       hipLaunchKernelGGL((outconv_bwd_kernel<N, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, x, cin, w,   \
@@ -1804,6 +1954,33 @@ static int launch_outconv_bwd(const float* x, int cin, const float* w, const flo
 extern "C" int sfh_outconv_bwd(const float* x, int cin, const float* w, const float* dlogits_nchw, int nc,
                                int batch, int H, int W, float* dx, double* acc_w, double* acc_b, void* stream) {
   return launch_outconv_bwd(x, cin, w, dlogits_nchw, nc, batch, H, W, dx, acc_w, acc_b, nullptr, nullptr, nullptr, nullptr, stream);
+}
+
+extern "C" int64_t sfh_outconv_bwd_det_bytes(int cin, int nc, int batch, int H, int W) {
+  if (batch <= 0 || H <= 0 || W <= 0 || cin % 4 != 0 || cin < 4 || cin > 256 || nc < 1 || nc > 8) return -1;
+  return det_bytes(det_outconv_blocks((long)batch * H * W), det_outconv_elems(nc, cin), sizeof(double));
+}
+
+extern "C" int sfh_outconv_bwd_det(const float* x, int cin, const float* w, const float* dlogits_nchw, int nc, int batch, int H,
+                                   int W, float* dx, double* acc_w, double* acc_b, void* workspace, long long workspace_bytes,
+                                   void* stream) {
+  SFH_REQUIRE(x && w && dlogits_nchw && acc_w && acc_b && batch > 0 && H > 0 && W > 0, "outconv_bwd_det: bad argument");
+  SFH_REQUIRE(cin % 4 == 0 && cin >= 4 && cin <= 256, "outconv_bwd_det: cin=%d (multiple of 4, <= 256)", cin);
+  SFH_REQUIRE(nc >= 1 && nc <= 8, "outconv_bwd_det: nc=%d unsupported (1..8)", nc);
+  SFH_REQUIRE_WS("outconv_bwd_det", workspace, workspace_bytes, sfh_outconv_bwd_det_bytes(cin, nc, batch, H, W));
+  const long npix = (long)batch * H * W;
+  const long ppb = det_outconv_ppb(npix), nb = det_outconv_blocks(npix), elems = det_outconv_elems(nc, cin);
+  double* ws = (double*)workspace;
+#define SFH_OB(N)                                                                                                          \
+  case N:                                                                                                                  \
+    hipLaunchKernelGGL((outconv_bwd_kernel<N, false, true>), dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, x, cin, \
+                       w, dlogits_nchw, npix, H * W, dx, ws, ws, (int)ppb, nullptr, nullptr, nullptr, nullptr);            \
+    break;
+  switch (nc) { SFH_OB(1) SFH_OB(2) SFH_OB(3) SFH_OB(4) SFH_OB(5) SFH_OB(6) SFH_OB(7) SFH_OB(8) }
+#undef SFH_OB
+  if (int rc = sfh_check_launch("outconv_bwd_kernel (deterministic)")) return rc;
+  if (int rc = sfh_det_reduce_f64(ws, nb, elems, (long)nc * cin, nc * cin, acc_w, nc * cin, stream)) return rc;
+  return sfh_det_reduce_f64(ws + (long)nc * cin, nb, elems, nc, nc, acc_b, nc, stream);
 }
 
 extern "C" int sfh_outconv_bwd_bn(const float* z, const float* mean_invstd, const float* gamma, const float* beta, int cin,
@@ -1827,9 +2004,29 @@ extern "C" int sfh_avgpool_linear_bwd(const float* x, const float* w, const floa
                                       int C, int nout, float* dx, double* acc_w, double* acc_b, void* stream) {
   SFH_REQUIRE(x && w && dout && dx && acc_w && acc_b && batch > 0 && H > 0 && W > 0 && C > 0 && nout > 0 && nout <= 256,
               "avgpool_linear_bwd: bad argument");
-  hipLaunchKernelGGL(avgpool_linear_bwd_kernel, dim3((unsigned)batch), dim3(256), 0, (hipStream_t)stream, x, w, dout,
+  hipLaunchKernelGGL(avgpool_linear_bwd_kernel<false>, dim3((unsigned)batch), dim3(256), 0, (hipStream_t)stream, x, w, dout,
                      H * W, C, nout, dx, acc_w, acc_b);
   return sfh_check_launch("avgpool_linear_bwd_kernel");
+}
+
+extern "C" int64_t sfh_avgpool_linear_bwd_det_bytes(int batch, int C, int nout) {
+  if (batch <= 0 || C <= 0 || nout <= 0 || nout > 256) return -1;
+  return det_bytes(batch, det_avgpool_elems(nout, C), sizeof(double));
+}
+
+extern "C" int sfh_avgpool_linear_bwd_det(const float* x, const float* w, const float* dout, int batch, int H, int W, int C,
+                                          int nout, float* dx, double* acc_w, double* acc_b, void* workspace,
+                                          long long workspace_bytes, void* stream) {
+  SFH_REQUIRE(x && w && dout && dx && acc_w && acc_b && batch > 0 && H > 0 && W > 0 && C > 0 && nout > 0 && nout <= 256,
+              "avgpool_linear_bwd_det: bad argument");
+  SFH_REQUIRE_WS("avgpool_linear_bwd_det", workspace, workspace_bytes, sfh_avgpool_linear_bwd_det_bytes(batch, C, nout));
+  double* ws = (double*)workspace;
+  const long elems = det_avgpool_elems(nout, C);
+  hipLaunchKernelGGL(avgpool_linear_bwd_kernel<true>, dim3((unsigned)batch), dim3(256), 0, (hipStream_t)stream, x, w, dout,
+                     H * W, C, nout, dx, ws, ws);
+  if (int rc = sfh_check_launch("avgpool_linear_bwd_kernel (deterministic)")) return rc;
+  if (int rc = sfh_det_reduce_f64(ws, batch, elems, (long)nout * C, nout * C, acc_w, nout * C, stream)) return rc;
+  return sfh_det_reduce_f64(ws + (long)nout * C, batch, elems, nout, nout, acc_b, nout, stream);
 }
 
 extern "C" int sfh_stem_bwd_data(const float* dz, const float* w, int cin, int c_off, int nc, int batch, int H,
@@ -1852,29 +2049,58 @@ extern "C" int sfh_stem_bwd_data(const float* dz, const float* w, int cin, int c
   return sfh_check_launch("stem_bwd_data_kernel");
 }
 
-extern "C" int sfh_train_losses(const float* logits_nchw, const int64_t* gt_mask, const float* weight,
-                                const float* warp_mask, int nc, int batch, int H, int W, float lambda_seg,
-                                float lambda_rec, int rec_mse, float lambda_cons, int focal_flags,
-                                float* dlogits_nchw, float* dwarp, double* loss3, void* stream) {
+static int train_losses_impl(const float* logits_nchw, const int64_t* gt_mask, const float* weight, const float* warp_mask,
+                             int nc, int batch, int H, int W, float lambda_seg, float lambda_rec, int rec_mse,
+                             float lambda_cons, int focal_flags, float* dlogits_nchw, float* dwarp, double* loss3, bool det,
+                             void* workspace, long long workspace_bytes, void* stream) {
+  const char* who = det ? "train_losses_det" : "train_losses";
   SFH_REQUIRE(logits_nchw && gt_mask && weight && dlogits_nchw && loss3 && batch > 0 && H > 0 && W > 0,
-              "train_losses: bad argument");
-  SFH_REQUIRE(nc >= 2 && nc <= 8, "train_losses: nc=%d unsupported (2..8)", nc);
-  SFH_REQUIRE(warp_mask || (lambda_rec == 0.f && lambda_cons == 0.f), "train_losses: rec/consistency need the warp mask");
+              "%s: bad argument", who);
+  SFH_REQUIRE(nc >= 2 && nc <= 8, "%s: nc=%d unsupported (2..8)", who, nc);
+  SFH_REQUIRE(warp_mask || (lambda_rec == 0.f && lambda_cons == 0.f), "%s: rec/consistency need the warp mask", who);
   LossArgs a;
   a.logits = logits_nchw; a.gt = (const long*)gt_mask; a.weight = weight; a.warp = warp_mask;
   a.nc = nc; a.HW = H * W; a.npix = (long)batch * H * W; a.batch = batch;
   a.l_seg = lambda_seg; a.l_rec = lambda_rec; a.l_cons = lambda_cons; a.rec_mse = rec_mse;
   a.seg_focal = focal_flags & 1; a.cons_focal = (focal_flags >> 1) & 1;
   a.dlogits = dlogits_nchw; a.dwarp = dwarp; a.loss = loss3;
-  long nb = (a.npix + 255) / 256;
-  if (nb > 2048) nb = 2048;
-#define SFH_TL(N)                                                                                         \
-  case N:                                                                                                 \
-    hipLaunchKernelGGL(train_losses_kernel<N>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, a); \
+  const long nb = det_losses_blocks(a.npix);
+  if (det) {
+    SFH_REQUIRE_WS("train_losses_det", workspace, workspace_bytes, det_bytes(nb, 3, sizeof(double)));
+    a.loss = (double*)workspace;
+  }
+#define SFH_TL(N)                                                                                                  \
+  case N:                                                                                                          \
+    if (det)                                                                                                       \
+      hipLaunchKernelGGL((train_losses_kernel<N, true>), dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, a); \
+    else                                                                                                           \
+      hipLaunchKernelGGL((train_losses_kernel<N>), dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, a);       \
     break;
   switch (nc) { SFH_TL(2) SFH_TL(3) SFH_TL(4) SFH_TL(5) SFH_TL(6) SFH_TL(7) SFH_TL(8) }
 #undef SFH_TL
-  return sfh_check_launch("train_losses_kernel");
+  if (int rc = sfh_check_launch(det ? "train_losses_kernel (deterministic)" : "train_losses_kernel")) return rc;
+  return det ? sfh_det_reduce_f64((const double*)workspace, nb, 3, 3, 3, loss3, 3, stream) : SFH_OK;
+}
+
+extern "C" int sfh_train_losses(const float* logits_nchw, const int64_t* gt_mask, const float* weight,
+                                const float* warp_mask, int nc, int batch, int H, int W, float lambda_seg,
+                                float lambda_rec, int rec_mse, float lambda_cons, int focal_flags,
+                                float* dlogits_nchw, float* dwarp, double* loss3, void* stream) {
+  return train_losses_impl(logits_nchw, gt_mask, weight, warp_mask, nc, batch, H, W, lambda_seg, lambda_rec, rec_mse,
+                           lambda_cons, focal_flags, dlogits_nchw, dwarp, loss3, false, nullptr, 0, stream);
+}
+
+extern "C" int64_t sfh_train_losses_det_bytes(int batch, int H, int W) {
+  if (batch <= 0 || H <= 0 || W <= 0) return -1;
+  return det_bytes(det_losses_blocks((long)batch * H * W), 3, sizeof(double));
+}
+
+extern "C" int sfh_train_losses_det(const float* logits_nchw, const int64_t* gt_mask, const float* weight,
+                                    const float* warp_mask, int nc, int batch, int H, int W, float lambda_seg,
+                                    float lambda_rec, int rec_mse, float lambda_cons, int focal_flags, float* dlogits_nchw,
+                                    float* dwarp, double* loss3, void* workspace, long long workspace_bytes, void* stream) {
+  return train_losses_impl(logits_nchw, gt_mask, weight, warp_mask, nc, batch, H, W, lambda_seg, lambda_rec, rec_mse,
+                           lambda_cons, focal_flags, dlogits_nchw, dwarp, loss3, true, workspace, workspace_bytes, stream);
 }
 
 extern "C" int sfh_reproj_loss(const float* poi, const float* gt_poi, const float* nonzeros,
@@ -1882,9 +2108,27 @@ extern "C" int sfh_reproj_loss(const float* poi, const float* gt_poi, const floa
                                double* loss, void* stream) {
   SFH_REQUIRE(poi && gt_poi && nonzeros && num_nonzero && dpoi && loss && batch > 0 && npts > 0,
               "reproj_loss: bad argument");
-  hipLaunchKernelGGL(reproj_loss_kernel, dim3((unsigned)sfh_cdiv(batch, 64)), dim3(64), 0, (hipStream_t)stream, poi,
+  hipLaunchKernelGGL(reproj_loss_kernel<false>, dim3((unsigned)det_reproj_blocks(batch)), dim3(64), 0, (hipStream_t)stream, poi,
                      gt_poi, nonzeros, num_nonzero, batch, npts, lambda, dpoi, loss);
   return sfh_check_launch("reproj_loss_kernel");
+}
+
+extern "C" int64_t sfh_reproj_loss_det_bytes(int batch) {
+  if (batch <= 0) return -1;
+  return det_bytes(det_reproj_blocks(batch), 1, sizeof(double));
+}
+
+extern "C" int sfh_reproj_loss_det(const float* poi, const float* gt_poi, const float* nonzeros, const float* num_nonzero,
+                                   int batch, int npts, float lambda, float* dpoi, double* loss, void* workspace,
+                                   long long workspace_bytes, void* stream) {
+  SFH_REQUIRE(poi && gt_poi && nonzeros && num_nonzero && dpoi && loss && batch > 0 && npts > 0,
+              "reproj_loss_det: bad argument");
+  SFH_REQUIRE_WS("reproj_loss_det", workspace, workspace_bytes, sfh_reproj_loss_det_bytes(batch));
+  const long nb = det_reproj_blocks(batch);
+  hipLaunchKernelGGL(reproj_loss_kernel<true>, dim3((unsigned)nb), dim3(64), 0, (hipStream_t)stream, poi, gt_poi, nonzeros,
+                     num_nonzero, batch, npts, lambda, dpoi, (double*)workspace);
+  if (int rc = sfh_check_launch("reproj_loss_kernel (deterministic)")) return rc;
+  return sfh_det_reduce_f64((const double*)workspace, nb, 1, 1, 1, loss, 1, stream);
 }
 
 extern "C" int sfh_multi_copy(const void* tensor_table, const void* chunk_table, int nchunks, float scale, void* stream) {
@@ -1917,19 +2161,44 @@ extern "C" int sfh_adam_step(const void* tensor_table, const void* chunk_table, 
   return sfh_check_launch("adam_kernel");
 }
 
+static int uv_loss_impl(const float* uv, const float* gt_uv, const float* weight, int nweights, int batch, int C, int H, int W,
+                        float lambda, int mse, float* duv, double* loss, bool det, void* workspace, long long workspace_bytes,
+                        void* stream) {
+  const char* who = det ? "uv_loss_det" : "uv_loss";
+  SFH_REQUIRE(uv && gt_uv && weight && duv && loss && batch > 0 && C > 0 && H > 0 && W > 0, "%s: bad argument", who);
+  SFH_REQUIRE(nweights == 1 || nweights == W,
+              "%s: %d per-sample weights cannot be broadcast along the last axis of the (B, W) = (%d, %d) loss map "
+              "(models/losses.py:38-39 multiplies torch.mean(loss, dim=(1, 2)) of a 4-D map by the weights)", who, nweights, batch, W);
+  const long total = (long)batch * C * H * W;
+  const long nb = det_uv_blocks(total);
+  const int wcol = nweights == W && nweights != 1 ? 1 : 0;
+  const float inv = 1.0f / ((float)batch * (float)C * (float)H * (float)W);
+  if (!det) {
+    hipLaunchKernelGGL(uv_loss_kernel<false>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, uv, gt_uv, weight, wcol, C,
+                       H, W, total, lambda, mse, duv, loss, inv);
+    return sfh_check_launch("uv_loss_kernel");
+  }
+  SFH_REQUIRE_WS("uv_loss_det", workspace, workspace_bytes, det_bytes(nb, 1, sizeof(double)));
+  hipLaunchKernelGGL(uv_loss_kernel<true>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, uv, gt_uv, weight, wcol, C, H,
+                     W, total, lambda, mse, duv, (double*)workspace, inv);
+  if (int rc = sfh_check_launch("uv_loss_kernel (deterministic)")) return rc;
+  return sfh_det_reduce_f64((const double*)workspace, nb, 1, 1, 1, loss, 1, stream);
+}
+
 extern "C" int sfh_uv_loss(const float* uv, const float* gt_uv, const float* weight, int nweights, int batch, int C, int H,
                            int W, float lambda, int mse, float* duv, double* loss, void* stream) {
-  SFH_REQUIRE(uv && gt_uv && weight && duv && loss && batch > 0 && C > 0 && H > 0 && W > 0, "uv_loss: bad argument");
-  SFH_REQUIRE(nweights == 1 || nweights == W,
-              "uv_loss: %d per-sample weights cannot be broadcast along the last axis of the (B, W) = (%d, %d) loss map "
-              "(models/losses.py:38-39 multiplies torch.mean(loss, dim=(1, 2)) of a 4-D map by the weights)", nweights, batch, W);
-  const long total = (long)batch * C * H * W;
-  long nb = (total + 255) / 256;
-  if (nb > 1024) nb = 1024;
-  hipLaunchKernelGGL(uv_loss_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, uv, gt_uv, weight,
-                     nweights == W && nweights != 1 ? 1 : 0, C, H, W, total, lambda, mse, duv, loss,
-                     1.0f / ((float)batch * (float)C * (float)H * (float)W));
-  return sfh_check_launch("uv_loss_kernel");
+  return uv_loss_impl(uv, gt_uv, weight, nweights, batch, C, H, W, lambda, mse, duv, loss, false, nullptr, 0, stream);
+}
+
+extern "C" int64_t sfh_uv_loss_det_bytes(int batch, int C, int H, int W) {
+  if (batch <= 0 || C <= 0 || H <= 0 || W <= 0) return -1;
+  return det_bytes(det_uv_blocks((long)batch * C * H * W), 1, sizeof(double));
+}
+
+extern "C" int sfh_uv_loss_det(const float* uv, const float* gt_uv, const float* weight, int nweights, int batch, int C, int H,
+                               int W, float lambda, int mse, float* duv, double* loss, void* workspace,
+                               long long workspace_bytes, void* stream) {
+  return uv_loss_impl(uv, gt_uv, weight, nweights, batch, C, H, W, lambda, mse, duv, loss, true, workspace, workspace_bytes, stream);
 }
 
 extern "C" int sfh_multi_copy_dscale(const void* tensor_table, const void* chunk_table, int nchunks, const float* scale_dev,

@@ -15,6 +15,7 @@
 
 #include "common.h"
 #include "warp_coords.h"
+#include "det_core.h"   // det_add and the block grid of the theta gradient: the deterministic mode's slabs
 
 // waves a launch should put on the chip before a thread takes more rows (experiment knob of profiles/build_variant.py)
 #ifndef SFH_WARP_MIN_WAVES
@@ -448,6 +449,9 @@ __global__ void poi_kernel(const float* __restrict__ theta, const float* __restr
 // Same chain as autograd through Kornia + F.grid_sample: bilinear-tap differences (out-of-range taps
 // are 0), d px/d u = wt/2, u = X*s with s = 1/(Z+1e-8) (constant 1 when |Z| <= 1e-8).  One thread per
 // 4 output pixels; the 9 sums are reduced per block and added to fp64 accumulators (B,9) with atomics.
+// DET: the store pass of the deterministic mode (det_core.h): acc is the workspace, block (x, y) stores its nine sums of frame
+// b into slab y * gridDim.x + x ([batch][9] doubles; a block outside the frame's rows or columns stores zeros)
+template <bool DET = false>
 __global__ __launch_bounds__(256) void warp_bwd_theta_kernel(const float* __restrict__ theta,
                                                              const float* __restrict__ tmpl, long tmpl_bstride,
                                                              int ht, int wt, int h, int w,
@@ -499,7 +503,11 @@ __global__ __launch_bounds__(256) void warp_bwd_theta_kernel(const float* __rest
       if (threadIdx.x < off) sh[threadIdx.x] += sh[threadIdx.x + off];
       __syncthreads();
     }
-    if (threadIdx.x == 0) unsafeAtomicAdd(&acc[b * 9 + k], sh[0]);
+    if (threadIdx.x == 0) {
+      double* dst = &acc[b * 9 + k];
+      if constexpr (DET) dst += det_slab_offset(det_warp_slab(blockIdx.x, blockIdx.y, gridDim.x), 9L * gridDim.z);
+      det_add<DET>(dst, sh[0]);
+    }
   }
 }
 
@@ -690,10 +698,32 @@ extern "C" int sfh_homography_warp_bwd_theta(const float* theta, const float* tm
   SFH_REQUIRE(theta && tmpl && dout && acc, "homography_warp_bwd: null pointer");
   SFH_REQUIRE(batch > 0 && batch <= 65535 && h > 1 && w > 1 && ht > 0 && wt > 0, "homography_warp_bwd: bad geometry");
   SFH_REQUIRE(tmpl_bstride == 0 || tmpl_bstride >= (int64_t)ht * wt, "homography_warp_bwd: bad template stride");
-  const dim3 grid((unsigned)sfh_cdiv(w, 256), (unsigned)sfh_cdiv(h, 4), (unsigned)batch);
-  hipLaunchKernelGGL(warp_bwd_theta_kernel, grid, dim3(256), 0, (hipStream_t)stream, theta, tmpl,
+  const dim3 grid((unsigned)det_warp_gx(w), (unsigned)det_warp_gy(h), (unsigned)batch);
+  hipLaunchKernelGGL(warp_bwd_theta_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, theta, tmpl,
                      (long)tmpl_bstride, ht, wt, h, w, dout, acc);
   return sfh_check_launch("warp_bwd_theta_kernel");
+}
+
+extern "C" int64_t sfh_homography_warp_bwd_theta_det_bytes(int batch, int h, int w) {
+  if (batch <= 0 || batch > 65535 || h <= 1 || w <= 1) return -1;
+  return det_bytes((long)det_warp_gx(w) * det_warp_gy(h), 9L * batch, sizeof(double));
+}
+
+extern "C" int sfh_homography_warp_bwd_theta_det(const float* theta, const float* tmpl, int64_t tmpl_bstride, int ht, int wt,
+                                                 int batch, int h, int w, const float* dout, double* acc, void* workspace,
+                                                 long long workspace_bytes, void* stream) {
+  SFH_REQUIRE(theta && tmpl && dout && acc, "homography_warp_bwd_det: null pointer");
+  SFH_REQUIRE(batch > 0 && batch <= 65535 && h > 1 && w > 1 && ht > 0 && wt > 0, "homography_warp_bwd_det: bad geometry");
+  SFH_REQUIRE(tmpl_bstride == 0 || tmpl_bstride >= (int64_t)ht * wt, "homography_warp_bwd_det: bad template stride");
+  const long long need = sfh_homography_warp_bwd_theta_det_bytes(batch, h, w);
+  SFH_REQUIRE(workspace != nullptr && workspace_bytes >= need, "homography_warp_bwd_det: workspace of %lld bytes, %lld needed",
+              workspace ? workspace_bytes : 0LL, need);
+  const dim3 grid((unsigned)det_warp_gx(w), (unsigned)det_warp_gy(h), (unsigned)batch);
+  hipLaunchKernelGGL(warp_bwd_theta_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, theta, tmpl, (long)tmpl_bstride, ht, wt,
+                     h, w, dout, (double*)workspace);
+  if (int rc = sfh_check_launch("warp_bwd_theta_kernel (deterministic)")) return rc;
+  return sfh_det_reduce_f64((const double*)workspace, (long)grid.x * grid.y, 9L * batch, 9L * batch, 9 * batch, acc, 9 * batch,
+                            stream);
 }
 
 extern "C" int sfh_poi_project_bwd_theta(const float* theta, const float* poi, int batch, int npts,

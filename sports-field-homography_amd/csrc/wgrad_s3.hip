@@ -23,6 +23,7 @@
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 
 #include "common.h"
+#include "det_core.h"   // the split plan and det_add: the deterministic mode's slabs
 
 namespace {
 
@@ -56,7 +57,9 @@ __device__ __forceinline__ bf16x8 frag(s16x4 lo, s16x4 hi) {
 // KS = 3: nine taps; KS = 1: one tap (ConvTranspose2d as a 1x1 conv over space_to_depth2(dY), Bottleneck 1x1s) - the same
 // tile loop with 12 instead of 108 MFMAs per wave and tile, i.e. bound by the LDS-DMA of the two operands, which is still
 // several times the rate of the fp32 kernel these layers ran on
-template <int TR, int TW, int NP, int KS = 3>
+// DET: the store pass of the deterministic mode (det_core.h): a.raw is the workspace, split s stores its sums (an empty
+// split: zeros) into slab s, element det_wgrad_elem(m, tap, n); DET = false is the kernel as it was
+template <int TR, int TW, int NP, int KS = 3, bool DET = false>
 __global__ __launch_bounds__(256, NP == 2 ? 3 : 2) void wgrad_s3_kernel(const WgS3Args a) {
   static_assert(TR * TW == 64 && (TW == 8 || TW == 16 || TW == 32), "64-pixel tiles, two 32-pixel k-steps");
   static_assert(KS == 3 || KS == 1, "3x3 or 1x1");
@@ -195,60 +198,61 @@ __global__ __launch_bounds__(256, NP == 2 ? 3 : 2) void wgrad_s3_kernel(const Wg
     for (int t9 = 0; t9 < NTAP; ++t9)
 #pragma unroll
       for (int r = 0; r < 4; ++r)
-        unsafeAtomicAdd(a.raw + ((long)(m0 + 16 * mb + r) * NTAP + t9) * a.raw_n + n,
-                        NP == 2 ? acc[mb][t9][r] * (1.f / (float)(1 << (2 * SFH_H2_ACT_EXP))) : acc[mb][t9][r]);
+        if constexpr (DET)
+          a.raw[det_slab_offset(split, (long)a.M * NTAP * a.N) + det_wgrad_elem(m0 + 16 * mb + r, t9, n - a.n_off, NTAP, a.N)] =
+              NP == 2 ? acc[mb][t9][r] * (1.f / (float)(1 << (2 * SFH_H2_ACT_EXP))) : acc[mb][t9][r];
+        else
+          unsafeAtomicAdd(a.raw + ((long)(m0 + 16 * mb + r) * NTAP + t9) * a.raw_n + n,
+                          NP == 2 ? acc[mb][t9][r] * (1.f / (float)(1 << (2 * SFH_H2_ACT_EXP))) : acc[mb][t9][r]);
 }
 
+// p: the split plan (det_core.h, det_wgrad_s3_plan - the split count is a multiple of 8 where it can be, split s runs on XCD
+// s % 8: 22x40 layers with 3 splits ran on 3 of the 8 XCDs, 103 instead of 250 TFLOP/s-equivalent; and at least 16 tiles per
+// split, every split ends with 64 x 32 x 9 fp32 adds per workgroup: ResNet layer1, 90x160, 768 splits of 5 tiles = 28 M atomics
+// for 17 GFLOP, 138 us).  ws == nullptr: the default mode, atomics onto raw; else the store pass into ws and the sum pass.
 template <int TR, int TW, int NP, int KS = 3>
-int launch(WgS3Args a, hipStream_t stream) {
+int launch(WgS3Args a, const DetWgradS3Plan& p, float* ws, hipStream_t stream) {
   constexpr int HP = (TR + KS - 1) * (TW + KS - 1);
   constexpr int PX = ((HP - 4 + 15) / 16) * 16 + 4;
   constexpr int LDS_BYTES = (4 * NP * PX + 8 * NP * 68) * 16;
-  a.ntx = sfh_cdiv(a.W, TW);
-  a.nty = sfh_cdiv(a.H, TR);
-  a.ntiles = a.ntx * a.nty * a.batch;
-  const int mn = a.mblk * a.nblk;
-  // about three rounds of two workgroups per CU - and a multiple of 8: split s runs on XCD s % 8, so that
-  // fewer than 8 (or 12: 8 + 4) splits leave XCDs idle (22x40 layers: 3 splits ran on 3 of the 8 XCDs, 103
-  // instead of 250 TFLOP/s-equivalent)
-  int nsplit = ((1536 / mn + 7) / 8) * 8;
-  // Every split ends with 64 x 32 x 9 fp32 atomics per workgroup: a split of a few tiles spends longer in that tail than
-  // in its MFMAs (ResNet layer1, 90x160: 768 splits of 5 tiles = 28 M atomics for 17 GFLOP, 138 us).  At least 16 tiles
-  // per split, as long as one round of workgroups (512) is still launched.
-  const int by_tiles = ((a.ntiles / 16 + 7) / 8) * 8, one_round = ((512 / mn + 7) / 8) * 8;
-  if (nsplit > by_tiles) nsplit = by_tiles > one_round ? by_tiles : (one_round < nsplit ? one_round : nsplit);
-  if (nsplit < 8) nsplit = 8;
-  if (nsplit > a.ntiles) nsplit = a.ntiles;
-  a.tps = sfh_cdiv(a.ntiles, nsplit);
-  a.nsplit = sfh_cdiv(a.ntiles, a.tps);
-  if (a.nsplit > 8 && a.nsplit % 8 != 0 && a.nsplit < 32) {   // e.g. 13 of 16: shave the tail to a multiple of 8
-    const int want = (a.nsplit / 8) * 8;
-    const int tps2 = sfh_cdiv(a.ntiles, want);
-    if (sfh_cdiv(a.ntiles, tps2) % 8 == 0) { a.tps = tps2; a.nsplit = sfh_cdiv(a.ntiles, tps2); }
-  }
-  const long nblocks = (long)sfh_cdiv(a.nsplit, 8) * 8 * mn;
+  a.ntx = p.ntx;
+  a.nty = p.nty;
+  a.ntiles = p.ntiles;
+  a.tps = p.tps;
+  a.nsplit = p.nsplit;
+  const long nblocks = (long)sfh_cdiv(a.nsplit, 8) * 8 * p.mn;
   SFH_REQUIRE(nblocks < (1L << 31), "conv_wgrad_s3: grid too large");
-  sfh_allow_big_lds(reinterpret_cast<const void*>(&wgrad_s3_kernel<TR, TW, NP, KS>));
-  hipLaunchKernelGGL((wgrad_s3_kernel<TR, TW, NP, KS>), dim3((unsigned)nblocks), dim3(256), LDS_BYTES, stream, a);
-  return sfh_check_launch("wgrad_s3_kernel");
+  if (!ws) {
+    sfh_allow_big_lds(reinterpret_cast<const void*>(&wgrad_s3_kernel<TR, TW, NP, KS>));
+    hipLaunchKernelGGL((wgrad_s3_kernel<TR, TW, NP, KS>), dim3((unsigned)nblocks), dim3(256), LDS_BYTES, stream, a);
+    return sfh_check_launch("wgrad_s3_kernel");
+  }
+  float* raw = a.raw;
+  const int raw_n = a.raw_n, n_off = a.n_off;
+  a.raw = ws;
+  sfh_allow_big_lds(reinterpret_cast<const void*>(&wgrad_s3_kernel<TR, TW, NP, KS, true>));
+  hipLaunchKernelGGL((wgrad_s3_kernel<TR, TW, NP, KS, true>), dim3((unsigned)nblocks), dim3(256), LDS_BYTES, stream, a);
+  if (int rc = sfh_check_launch("wgrad_s3_kernel (deterministic)")) return rc;
+  return sfh_det_reduce_f32(ws, p.nsplit, p.elems, p.elems, a.N, raw + n_off, raw_n, stream);
 }
 
 }  // namespace
 
-extern "C" int sfh_conv_wgrad_s3(const void* dz_s3, int M, const void* x_s3, int x_channels, int xh, int xw, int N,
-                                 int pad_top, int pad_left, int batch, int H, int W, int ksize, float* raw, int raw_n,
-                                 int n_off, int fmt, void* stream) {
-  SFH_REQUIRE(fmt == SFH_FMT_S3 || fmt == SFH_FMT_H2, "conv_wgrad_s3: fmt=%d (S3 or H2)", fmt);
-  SFH_REQUIRE(ksize == 3 || ksize == 1, "conv_wgrad_s3: ksize=%d (3 or 1)", ksize);
+static int conv_wgrad_s3_impl(const void* dz_s3, int M, const void* x_s3, int x_channels, int xh, int xw, int N, int pad_top,
+                              int pad_left, int batch, int H, int W, int ksize, float* raw, int raw_n, int n_off, int fmt,
+                              bool det, void* workspace, long long workspace_bytes, void* stream) {
+  const char* who = det ? "conv_wgrad_s3_det" : "conv_wgrad_s3";
+  SFH_REQUIRE(fmt == SFH_FMT_S3 || fmt == SFH_FMT_H2, "%s: fmt=%d (S3 or H2)", who, fmt);
+  SFH_REQUIRE(ksize == 3 || ksize == 1, "%s: ksize=%d (3 or 1)", who, ksize);
   const unsigned long long bpe = fmt == SFH_FMT_H2 ? 4ULL : 6ULL;
-  SFH_REQUIRE(dz_s3 && x_s3 && raw, "conv_wgrad_s3: null pointer");
-  SFH_REQUIRE(batch > 0 && H > 0 && W > 0 && xh > 0 && xw > 0, "conv_wgrad_s3: bad geometry");
-  SFH_REQUIRE(M > 0 && M % 64 == 0, "conv_wgrad_s3: M=%d must be a multiple of 64", M);
-  SFH_REQUIRE(N > 0 && N % 32 == 0 && x_channels % 32 == 0 && x_channels >= N, "conv_wgrad_s3: N=%d of %d channels", N, x_channels);
-  SFH_REQUIRE(n_off >= 0 && n_off + N <= raw_n, "conv_wgrad_s3: n_off=%d N=%d raw_n=%d", n_off, N, raw_n);
-  SFH_REQUIRE(pad_top >= 0 && pad_left >= 0 && pad_top + xh <= H && pad_left + xw <= W, "conv_wgrad_s3: source does not fit the frame");
+  SFH_REQUIRE(dz_s3 && x_s3 && raw, "%s: null pointer", who);
+  SFH_REQUIRE(batch > 0 && H > 0 && W > 0 && xh > 0 && xw > 0, "%s: bad geometry", who);
+  SFH_REQUIRE(M > 0 && M % 64 == 0, "%s: M=%d must be a multiple of 64", who, M);
+  SFH_REQUIRE(N > 0 && N % 32 == 0 && x_channels % 32 == 0 && x_channels >= N, "%s: N=%d of %d channels", who, N, x_channels);
+  SFH_REQUIRE(n_off >= 0 && n_off + N <= raw_n, "%s: n_off=%d N=%d raw_n=%d", who, n_off, N, raw_n);
+  SFH_REQUIRE(pad_top >= 0 && pad_left >= 0 && pad_top + xh <= H && pad_left + xw <= W, "%s: source does not fit the frame", who);
   const unsigned long long bdz = bpe * batch * H * W * M, bx = bpe * batch * xh * xw * x_channels;
-  SFH_REQUIRE(bdz < kOOB && bx < kOOB, "conv_wgrad_s3: a tensor of %llu bytes exceeds the 4 GiB descriptor range", bdz > bx ? bdz : bx);
+  SFH_REQUIRE(bdz < kOOB && bx < kOOB, "%s: a tensor of %llu bytes exceeds the 4 GiB descriptor range", who, bdz > bx ? bdz : bx);
   WgS3Args a;
   a.dz = dz_s3; a.M = M; a.x = x_s3; a.xc = x_channels; a.xh = xh; a.xw = xw; a.N = N;
   a.pad_top = pad_top; a.pad_left = pad_left; a.batch = batch; a.H = H; a.W = W;
@@ -261,14 +265,21 @@ extern "C" int sfh_conv_wgrad_s3(const void* dz_s3, int M, const void* x_s3, int
   // tile shape with the least padded area (ties: the widest).  Weighting the area by the rate each shape
   // reaches on full tiles (2x32 250, 4x16 190, 8x8 103 TFLOP/s-equivalent) and so moving the 45x80 and 22x40
   // layers to 2x32 tiles was measured slower overall (31.0 vs 27.8 ms per step for all launches).
-  const long c0 = (long)sfh_cdiv(H, 2) * sfh_cdiv(W, 32), c1 = (long)sfh_cdiv(H, 4) * sfh_cdiv(W, 16),
-             c2 = (long)sfh_cdiv(H, 8) * sfh_cdiv(W, 8);
+  const DetWgradS3Plan p = det_wgrad_s3_plan(M, N, ksize, batch, H, W);
+  float* ws = nullptr;
+  if (det) {
+    // (NULL or smaller than sfh_conv_wgrad_s3_det_bytes: refused, nothing launched)
+    SFH_REQUIRE(workspace != nullptr && workspace_bytes >= det_bytes(p.nsplit, p.elems, sizeof(float)),
+                "conv_wgrad_s3_det: workspace of %lld bytes, %lld needed", workspace ? workspace_bytes : 0LL,
+                det_bytes(p.nsplit, p.elems, sizeof(float)));
+    ws = (float*)workspace;
+  }
   hipStream_t st = (hipStream_t)stream;
-#define SFH_WG_PICK(NP_, KS_)                                        \
-  do {                                                               \
-    if (c0 <= c1 && c0 <= c2) return launch<2, 32, NP_, KS_>(a, st); \
-    if (c1 <= c2) return launch<4, 16, NP_, KS_>(a, st);             \
-    return launch<8, 8, NP_, KS_>(a, st);                            \
+#define SFH_WG_PICK(NP_, KS_)                                              \
+  do {                                                                     \
+    if (p.shape == 0) return launch<2, 32, NP_, KS_>(a, p, ws, st);        \
+    if (p.shape == 1) return launch<4, 16, NP_, KS_>(a, p, ws, st);        \
+    return launch<8, 8, NP_, KS_>(a, p, ws, st);                           \
   } while (0)
   if (fmt == SFH_FMT_H2) {
     if (ksize == 1) SFH_WG_PICK(2, 1);
@@ -277,4 +288,24 @@ extern "C" int sfh_conv_wgrad_s3(const void* dz_s3, int M, const void* x_s3, int
   if (ksize == 1) SFH_WG_PICK(3, 1);
   SFH_WG_PICK(3, 3);
 #undef SFH_WG_PICK
+}
+
+extern "C" int sfh_conv_wgrad_s3(const void* dz_s3, int M, const void* x_s3, int x_channels, int xh, int xw, int N,
+                                 int pad_top, int pad_left, int batch, int H, int W, int ksize, float* raw, int raw_n,
+                                 int n_off, int fmt, void* stream) {
+  return conv_wgrad_s3_impl(dz_s3, M, x_s3, x_channels, xh, xw, N, pad_top, pad_left, batch, H, W, ksize, raw, raw_n, n_off, fmt,
+                            false, nullptr, 0, stream);
+}
+
+extern "C" int64_t sfh_conv_wgrad_s3_det_bytes(int M, int N, int batch, int H, int W, int ksize) {
+  if (batch <= 0 || H <= 0 || W <= 0 || M <= 0 || M % 64 != 0 || N <= 0 || N % 32 != 0 || !(ksize == 1 || ksize == 3)) return -1;
+  const DetWgradS3Plan p = det_wgrad_s3_plan(M, N, ksize, batch, H, W);
+  return det_bytes(p.nsplit, p.elems, sizeof(float));
+}
+
+extern "C" int sfh_conv_wgrad_s3_det(const void* dz_s3, int M, const void* x_s3, int x_channels, int xh, int xw, int N,
+                                     int pad_top, int pad_left, int batch, int H, int W, int ksize, float* raw, int raw_n,
+                                     int n_off, int fmt, void* workspace, long long workspace_bytes, void* stream) {
+  return conv_wgrad_s3_impl(dz_s3, M, x_s3, x_channels, xh, xw, N, pad_top, pad_left, batch, H, W, ksize, raw, raw_n, n_off, fmt,
+                            true, workspace, workspace_bytes, stream);
 }

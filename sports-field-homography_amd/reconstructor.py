@@ -186,6 +186,10 @@ class Reconstructor(nn.Module):
         # The launch-plan choices that are still open (options.py; env SFH_OPTIONS, read here and nowhere else).  Part of the
         # engine stamp: assigning another record rebuilds the engines and drops captured graphs.
         self.options = Options.from_env()
+        # Training through the autograd node (training.train_forward): True takes every sum across workgroups through
+        # fixed-order slab sums - the same bits from the same state, inputs and shapes ("Deterministic training").
+        # A plain attribute, like precision; TrainStep has its own keyword.
+        self.train_deterministic = False
         self._engines = None       # (UNetEngine | None, ResNetEngine | None)
         self._engines_by_precision = {}
         self._h2_ranges = None     # engine.H2Ranges: exponents + device range words of the "f16x3" activations

@@ -19,6 +19,7 @@ record (``Act``), gradients are accumulated with ``sfh_slice_add``.  PyTorch pro
 hook (``torch.autograd.Function``) only.
 """
 import ctypes
+import dataclasses
 import os
 
 import torch
@@ -56,6 +57,43 @@ def _zeros(shape, like, dtype=torch.float32):
 
 class FP16RangeError(RuntimeError):
     """an activation or gradient of a training step did not fit the two-plane fp16 (H2) format"""
+
+
+class DetWorkspace:
+    """The slab buffer of the deterministic mode (include/sfh_amd.h, "Deterministic training mode"): ONE buffer, as large as
+    the largest launch so far needed, reused by every accumulating launch of every step.  Legal on one stream - a launch's
+    store pass and sum pass are stream-ordered, and so is the next launch's store pass behind them - and never cleared:
+    every element a sum pass reads was written by the store pass in front of it."""
+
+    def __init__(self, device=None):
+        self.device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self.buf = None
+
+    @property
+    def nbytes(self):
+        return 0 if self.buf is None else self.buf.numel()
+
+    def get(self, nbytes):
+        if self.buf is None or self.buf.numel() < nbytes:
+            self.buf = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
+        return self.buf
+
+
+def _accumulate(det, name, query, *args):
+    """One launch that sums across workgroups: lib.<name>(*args, stream) - float atomics in arrival order - or, with det (a
+    DetWorkspace), its deterministic sibling <name>_det, whose workspace <name>_det_bytes(*query) sizes."""
+    lib = _lib.load()
+    tag = _ACCUMULATE_TAGS.get(name, name[4:])      # the launch tag of _lib.check (the default mode's tags are pinned by a test)
+    if det is None:
+        _lib.check(getattr(lib, name)(*args, _stream()), tag)
+        return
+    need = getattr(lib, name + "_det_bytes")(*query)
+    if need < 0:
+        raise ValueError(f"{name}_det_bytes{tuple(query)}: geometry refused")
+    _lib.check(getattr(lib, name + "_det")(*args, _ptr(det.get(need)), need, _stream()), tag + "_det")
+
+
+_ACCUMULATE_TAGS = {"sfh_homography_warp_bwd_theta": "homography_warp_bwd"}
 
 
 class _MultiCopy:
@@ -191,8 +229,16 @@ class Act:
 class Tape:
     """Backward closures in forward order + the activations (Act) that crossed the public boundary as plain tensors."""
 
-    def __init__(self, fmt="env", options=None, gshift=0):
+    def __init__(self, fmt="env", options=None, gshift=0, deterministic=False, workspace=None):
+        """deterministic: every sum across workgroups of this pass goes through fixed-order slab sums (_accumulate) in
+        `workspace` (a DetWorkspace the caller keeps from step to step; None: one of this tape's own), and every fused form
+        whose sums ride in another kernel's atomics takes its plain leg: Options.train_one_pass off, no conv-epilogue
+        statistics table (conv_bn_act, _backward_data).  self.det is the workspace, None in the default mode."""
         self.options = options if options is not None else Options()     # (None: the defaults, not the environment)
+        self.deterministic = bool(deterministic)
+        self.det = (workspace if workspace is not None else DetWorkspace()) if self.deterministic else None
+        if self.det is not None:
+            self.options = dataclasses.replace(self.options, train_one_pass=False)
         self.ops = []
         self.resnet_start = None   # index in ops of the first ResNet closure (ResNetTrainer.forward)
         # tensor identity -> Act, for the tensors handed in or out as plain tensors (input frames, stn_in, the NCHW head
@@ -365,7 +411,7 @@ def _bn_forward(lib, z, bn, relu, residual, tape, want_s3=True, want_f32=True, s
                    "bn_finalize_partials")
     else:
         acc = tape.zeros((2 * C,), z, torch.float64)
-        _lib.check(lib.sfh_bn_stats(_ptr(z), npix, C, _ptr(acc), _stream()), "bn_stats")
+        _accumulate(tape.det, "sfh_bn_stats", (npix, C), _ptr(z), npix, C, _ptr(acc))
         _lib.check(lib.sfh_bn_finalize(_ptr(acc), npix, C, float(bn.eps), BN_MOMENTUM, _ptr(bn.running_mean),
                                        _ptr(bn.running_var), _ptr(mi), _ptr(nbt), _stream()), "bn_finalize")
     if pool:
@@ -404,8 +450,8 @@ def _bn_backward(lib, tape, dy, y, z, mi, bn, relu, want_dres, want_s3=False, wa
         _lib.check(lib.sfh_bn_stats_partials(_ptr(sums_table), sums_table.shape[0], C, _ptr(acc), _stream()),
                    "bn_stats_partials")
     else:
-        _lib.check(lib.sfh_bn_bwd_reduce(_ptr(dy), _ptr(ysign), _ptr(z), _ptr(mi), _ptr(gam), _ptr(bet), 1 if relu else 0,
-                                         npix, C, _ptr(acc), _stream()), "bn_bwd_reduce")
+        _accumulate(tape.det, "sfh_bn_bwd_reduce", (npix, C), _ptr(dy), _ptr(ysign), _ptr(z), _ptr(mi), _ptr(gam), _ptr(bet),
+                    1 if relu else 0, npix, C, _ptr(acc))
     if not apply:   # the caller's next kernel applies it while loading (sfh_conv_wgrad_c4_bn): sums only
         a = acc.to(torch.float32)
         return None, a[C:], a[:C], None, acc
@@ -419,12 +465,12 @@ def _bn_backward(lib, tape, dy, y, z, mi, bn, relu, want_dres, want_s3=False, wa
     return dz, a[C:], a[:C], dres, dz_s3   # dz, dgamma, dbeta, dresidual, S3 copy of dz
 
 
-def _colsum(lib, t, C=None, cs=None):
+def _colsum(lib, t, C=None, cs=None, det=None):
     C = C or t.shape[-1]
     cs = cs or t.shape[-1]
     npix = t.numel() // cs
     acc = _zeros((C,), t, torch.float64)
-    _lib.check(lib.sfh_colsum(_ptr(t), npix, C, cs, _ptr(acc), _stream()), "colsum")
+    _accumulate(det, "sfh_colsum", (npix, C), _ptr(t), npix, C, cs, _ptr(acc))
     return acc.to(torch.float32)
 
 
@@ -441,20 +487,22 @@ def _wgrad_s3(lib, tape, dz_s3, M, srcs, B, H, W, cin_store, ksize=3):
     raw = tape.zeros((M, ksize * ksize, cin_store), dz_s3)
     for (t, n, n_off, pt, pl) in srcs:
         xs = tape.s3(t)
-        _lib.check(lib.sfh_conv_wgrad_s3(_ptr(dz_s3), M, _ptr(xs), t.shape[3], t.shape[1], t.shape[2], n, pt, pl,
-                                         B, H, W, ksize, _ptr(raw), cin_store, n_off, tape.fmt_code, _stream()),
-                   "conv_wgrad_s3")
+        _accumulate(tape.det, "sfh_conv_wgrad_s3", (M, n, B, H, W, ksize), _ptr(dz_s3), M, _ptr(xs), t.shape[3], t.shape[1],
+                    t.shape[2], n, pt, pl, B, H, W, ksize, _ptr(raw), cin_store, n_off, tape.fmt_code)
     return raw
 
 
-def _wgrad(lib, dz, srcs, B, H, W, ksize, cin_store, tape=None):
-    """raw (M, k*k, cin_store) = sum_p dz[p] (x) xin[p + tap]; srcs = [(tensor, channels, n_off, pad_top, pad_left)]."""
+def _wgrad(lib, dz, srcs, B, H, W, ksize, cin_store, tape=None, det=None):
+    """raw (M, k*k, cin_store) = sum_p dz[p] (x) xin[p + tap]; srcs = [(tensor, channels, n_off, pad_top, pad_left)].
+    det: the deterministic mode's workspace (a caller without a tape names it; with one it is the tape's)."""
+    det = tape.det if tape is not None else det
     M = dz.shape[3]
     raw = (tape.zeros if tape is not None else _zeros)((M, ksize * ksize, cin_store), dz)
     for (t, n, n_off, pt, pl) in srcs:
         # t may be a channel slice of an NHWC tensor: the pixel stride is stride(2), not shape[3]
-        _lib.check(lib.sfh_conv_wgrad(_ptr(dz), dz.shape[3], M, _ptr(t), t.stride(2), t.shape[1], t.shape[2], n,
-                                      pt, pl, B, H, W, ksize, _ptr(raw), cin_store, n_off, _stream()), "conv_wgrad")
+        _accumulate(det, "sfh_conv_wgrad", (M, t.stride(2), t.shape[1], t.shape[2], n, pt, pl, B, H, W, ksize),
+                    _ptr(dz), dz.shape[3], M, _ptr(t), t.stride(2), t.shape[1], t.shape[2], n, pt, pl, B, H, W, ksize, _ptr(raw),
+                    cin_store, n_off)
     return raw
 
 
@@ -474,7 +522,8 @@ def _backward_data(tape, bd, dz_in, B, H, W, src, s3):
     in this launch and are left in src.sums_table."""
     bd.order = tape.order
     dx = _empty((B, H, W, bd.cout), dz_in)
-    if src is not None and src.sole and s3 and bd.stats_ok and bd.cout == src.shape[3] and src.grad is None:
+    if (src is not None and src.sole and s3 and bd.stats_ok and bd.cout == src.shape[3] and src.grad is None
+            and tape.det is None):   # (deterministic mode: the table's sums are atomics - sfh_bn_bwd_reduce takes them)
         z, mi, sb = src.bn
         table = tape.zeros((stats_rows(B * H * W), 2, bd.cout), dz_in, torch.float64)
         bd.run(dz_in, B, H, W, dx, stats=table, bwd=(z, mi, sb.weight.detach(), sb.bias.detach()))
@@ -520,7 +569,9 @@ def conv_bn_act(tape, names, conv, bn, srcs, B, H, W, relu=True, residual=None, 
     ho, wo = (H - 1) // stride + 1, (W - 1) // stride + 1
     z = _empty((B, ho, wo, cout), t0)
     # BatchNorm's batch sums ride in the conv epilogue where the kernel offers it (H2, 3x3, stride 1)
-    stats = tape.zeros((stats_rows(B * ho * wo), 2, cout), t0, torch.float64) if s3 and pc.stats_ok else None
+    # (not in deterministic mode: the table's sums are atomics - sfh_bn_stats takes them there)
+    stats = (tape.zeros((stats_rows(B * ho * wo), 2, cout), t0, torch.float64)
+             if s3 and pc.stats_ok and tape.det is None else None)
     if s3:
         x0, x1 = tape.s3(t0), tape.s3(t1) if t1 is not None else None
     pc.run(x0, B, H, W, z, src1=x1, pad1=pad1, stats=stats)
@@ -655,8 +706,8 @@ def _grouped_conv_bn_act(tape, names, conv, bn, src, B, H, W, relu, need_dx, s3_
         g = tape.param_grads
         g[names(bn.weight)], g[names(bn.bias)] = dgamma, dbeta
         raw = tape.zeros((C, 9, cg), z)
-        _lib.check(lib.sfh_conv_grouped_wgrad(_ptr(dz), _ptr(x0), _ptr(raw), B, H, W, G, cg, stride, _stream()),
-                   "conv_grouped_wgrad")
+        _accumulate(tape.det, "sfh_conv_grouped_wgrad", (B, H, W, G, cg, stride), _ptr(dz), _ptr(x0), _ptr(raw), B, H, W, G,
+                    cg, stride)
         # a strided view, as for the dense layers: the consumer's copy does the permute
         g[names(conv.weight)] = raw.view(C, 3, 3, cg).permute(0, 3, 1, 2)
         if not need_dx:
@@ -736,7 +787,7 @@ def conv_transpose2x2(tape, names, up, x):
             g[names(up.bias)] = acc.to(torch.float32)
             s = None
         else:
-            g[names(up.bias)] = _colsum(lib, du)
+            g[names(up.bias)] = _colsum(lib, du, det=tape.det)
             s = _empty((B, h, w, 4 * cout), x)  # s[(py*2+px)*cout + co] = du[2y+py][2x+px][co]
             _lib.check(lib.sfh_space_to_depth2(_ptr(du), _ptr(s), B, 2 * h, 2 * w, cout, _stream()), "space_to_depth2")
             s_split = E.f32_to_split(s, tape.fmt, tape.overflow) if s3 else None
@@ -801,8 +852,8 @@ def out_conv(tape, names, oc, y, B, H, W, frame_nhwc=None, stn_cs=0, sole_consum
                                               cin, _ptr(wt), _ptr(dlogits), nc, B, H, W, _ptr(dy), _ptr(acc_w), _ptr(acc_b),
                                               _ptr(acc_bn), _stream()), "outconv_bwd_bn")
         else:
-            _lib.check(lib.sfh_outconv_bwd(_ptr(yf), cin, _ptr(wt), _ptr(dlogits), nc, B, H, W, _ptr(dy), _ptr(acc_w),
-                                           _ptr(acc_b), _stream()), "outconv_bwd")
+            _accumulate(tape.det, "sfh_outconv_bwd", (cin, nc, B, H, W), _ptr(yf), cin, _ptr(wt), _ptr(dlogits), nc, B, H, W,
+                        _ptr(dy), _ptr(acc_w), _ptr(acc_b))
         g = tape.param_grads
         g[names(oc.conv.weight)] = acc_w.to(torch.float32).view(nc, cin, 1, 1)
         g[names(oc.conv.bias)] = acc_b.to(torch.float32)
@@ -922,7 +973,7 @@ class ResNetTrainer:
             g[names(rn.bn1.weight)], g[names(rn.bn1.bias)] = dgamma, dbeta
             # the 4x4 backward-filter instance holds 32 input channels: wider inputs go in slices
             raw = _wgrad(lib, dz, [(s2d[..., c:], min(32, 4 * cs - c), c, 0, 0) for c in range(0, 4 * cs, 32)],
-                         B, H2, W2, 4, 4 * cs)                                         # (64, 16, 4*cs)
+                         B, H2, W2, 4, 4 * cs, det=tape.det)                           # (64, 16, 4*cs)
             # 4x4 taps over the space-to-depth input -> 7x7: ky = 2*ty + py - 1 (sfh_pack_conv_weights mode 2)
             r = raw.view(64, 4, 4, 2, 2, cs).permute(0, 5, 1, 3, 2, 4).reshape(64, cs, 8, 8)
             g[names(rn.conv0.weight)] = r[:, :cin, 1:, 1:].contiguous()
@@ -974,8 +1025,8 @@ class ResNetTrainer:
             acc_w = tape.zeros((9 * C,), featf, torch.float64)
             acc_b = tape.zeros((9,), featf, torch.float64)
             dfeat = _empty(feat.shape, featf)
-            _lib.check(lib.sfh_avgpool_linear_bwd(_ptr(featf), _ptr(wr), _ptr(dth), B, fh, fw, C, 9, _ptr(dfeat),
-                                                  _ptr(acc_w), _ptr(acc_b), st()), "avgpool_linear_bwd")
+            _accumulate(tape.det, "sfh_avgpool_linear_bwd", (B, C, 9), _ptr(featf), _ptr(wr), _ptr(dth), B, fh, fw, C, 9,
+                        _ptr(dfeat), _ptr(acc_w), _ptr(acc_b))
             g = tape.param_grads
             g[names(rn.reg.weight)] = acc_w.to(torch.float32).view(9, C)
             g[names(rn.reg.bias)] = acc_b.to(torch.float32)
@@ -986,14 +1037,13 @@ class ResNetTrainer:
 
 
 # ------------------------------------------------------------------------------- whole model
-def warp_backward_theta(theta, court_img, h, w, dout, shared_template):
-    """d loss / d theta of the bilinear warp (models/reconstructor.py:109-118,185-190)."""
-    lib = _lib.load()
+def warp_backward_theta(theta, court_img, h, w, dout, shared_template, det=None):
+    """d loss / d theta of the bilinear warp (models/reconstructor.py:109-118,185-190); det: the deterministic mode's workspace."""
     B = theta.shape[0]
     ht, wt = court_img.shape[2], court_img.shape[3]
     acc = _zeros((B * 9,), theta, torch.float64)
-    _lib.check(lib.sfh_homography_warp_bwd_theta(_ptr(theta), _ptr(court_img), 0 if shared_template else ht * wt, ht, wt,
-                                                 B, h, w, _ptr(dout), _ptr(acc), _stream()), "homography_warp_bwd")
+    _accumulate(det, "sfh_homography_warp_bwd_theta", (B, h, w), _ptr(theta), _ptr(court_img),
+                0 if shared_template else ht * wt, ht, wt, B, h, w, _ptr(dout), _ptr(acc))
     return acc.to(torch.float32).view(B, 9)
 
 
@@ -1165,7 +1215,7 @@ def run_backward(net, tape, f, dheads, dtheta, unscale=True, device_scale=False)
     return g
 
 
-def theta_gradient(net, f, dtheta, dpoi, dwarp):
+def theta_gradient(net, f, dtheta, dpoi, dwarp, det=None):
     """total d loss / d theta (B,9): direct + through transform_poi + through the bilinear warp"""
     theta = f["theta"]
     B = theta.shape[0]
@@ -1175,7 +1225,7 @@ def theta_gradient(net, f, dtheta, dpoi, dwarp):
         dth = _add_small(lib, dth, poi_backward_theta(theta, net.court_poi, dpoi.contiguous()))
     if dwarp is not None and net.warper and not net.warp_with_nearest:
         ww, wh = net.warp_size
-        dth = _add_small(lib, dth, warp_backward_theta(theta, net.court_img, wh, ww, dwarp.contiguous(), f["shared"]))
+        dth = _add_small(lib, dth, warp_backward_theta(theta, net.court_img, wh, ww, dwarp.contiguous(), f["shared"], det))
     return dth
 
 
@@ -1189,7 +1239,16 @@ class _TrainForward(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, net, info, x, *params):
-        tape = Tape(options=net.options)
+        # net.train_deterministic (a plain attribute, like net.precision): fixed-order slab sums; the model keeps the workspace
+        det = None
+        if getattr(net, "train_deterministic", False):
+            det = net.__dict__.get("_det_workspace")
+            if det is None or det.device != x.device:
+                det = net.__dict__["_det_workspace"] = DetWorkspace(x.device)
+        def mk(**kw):
+            return Tape(options=net.options, deterministic=det is not None, workspace=det, **kw)
+        ctx.mk_tape = mk
+        tape = mk()
         x = E._f32c(x.detach(), "input frames")
         ctx.snap_gen = None
         if tape.fmt == "h2":
@@ -1205,7 +1264,7 @@ class _TrainForward(torch.autograd.Function):
                 snap.restore()
                 _warn_range_fallback()
                 net.__dict__["train_range_fallbacks"] = net.__dict__.get("train_range_fallbacks", 0) + 1
-                tape = Tape(fmt="s3", options=net.options)
+                tape = mk(fmt="s3")
                 f = run_forward(net, tape, x)
         else:
             f = run_forward(net, tape, x)
@@ -1226,7 +1285,8 @@ class _TrainForward(torch.autograd.Function):
         d = dict(zip(ctx.keys, douts))
 
         def attempt(tape, f):
-            dth = theta_gradient(net, f, d.get("theta"), d.get("poi"), d.get("warp_mask")) if f["theta"] is not None else None
+            dth = (theta_gradient(net, f, d.get("theta"), d.get("poi"), d.get("warp_mask"), tape.det)
+                   if f["theta"] is not None else None)
             head_keys = ["logits"] + (["uv"] if f["uv"] is not None else []) if f["logits"] is not None else []
             dheads = [None if d.get(k) is None else d[k].contiguous().clone() for k in head_keys]
             return run_backward(net, tape, f, dheads, dth)
@@ -1244,7 +1304,7 @@ class _TrainForward(torch.autograd.Function):
             snap.restore()
             _warn_range_fallback()
             net.__dict__["train_range_fallbacks"] = net.__dict__.get("train_range_fallbacks", 0) + 1
-            tape = Tape(fmt="s3", options=net.options)
+            tape = ctx.mk_tape(fmt="s3")
             g = attempt(tape, run_forward(net, tape, ctx.x))
             net.invalidate_engines()
         names = _Names(net)
@@ -1274,10 +1334,13 @@ class TrainStep:
     def __init__(self, net, lr=1e-4, weight_decay=1e-8, momentum=0.9, alpha=0.99, eps=1e-8, clip_value=0.1,
                  seg_lambda=2.0, rec_lambda=2.0, reproj_lambda=8.0, consist_lambda=1.0, rec_loss="SmoothL1",
                  seg_loss="CE", consist_loss="CE", consist_start_iter=0, optimizer="RMSprop", betas=(0.9, 0.999),
-                 uv_loss="MSE", uv_lambda=2.0):
+                 uv_loss="MSE", uv_lambda=2.0, deterministic=False):
         """optimizer: "RMSprop" (momentum, alpha, eps), "SGD" (momentum) or "Adam" (betas, eps) - train.py:87-95, each behind
         clip_grad_value_(clip_value) with L2 weight_decay; uv_loss / uv_lambda: the UV head's criterion ("MSE" | "SmoothL1" |
-        None) for models built with unet_uv=True (train.py:136-144,203-208; defaults utils/config.py:120,134)."""
+        None) for models built with unet_uv=True (train.py:136-144,203-208; defaults utils/config.py:120,134).
+        deterministic: every sum across workgroups of a step goes through fixed-order slab sums (Tape, DetWorkspace): same
+        library build, device model, shapes, precision, inputs and starting state -> the same bits after every step, whatever
+        else runs on the device.  A property of the run, not of the optimizer state (state_dict() does not carry it)."""
         if optimizer not in ("RMSprop", "SGD", "Adam"):
             print(f"optimizer {optimizer} does not support yet")        # (train.py:94)
             raise NotImplementedError(f"optimizer={optimizer!r}")
@@ -1303,6 +1366,8 @@ class TrainStep:
         self.range_rescales = 0      # steps repeated in f16x3 with a lower gradient scale (kept for the steps that follow)
         self.grad_scale_shift = 0    # power of two the backward pass's scale is lowered by (sticky, <= 0 in normal use)
         self.force_collective = False  # one-rank world: run the gradient all-reduce anyway (sharding.py, RCCL rehearsal)
+        self.deterministic = bool(deterministic)
+        self._det = None             # the mode's DetWorkspace, made at the first deterministic step
         self._init_optimizer([p for p in net.parameters()])
 
     def _init_optimizer(self, params):
@@ -1354,6 +1419,11 @@ class TrainStep:
                                    f"contiguous float32 {tuple(g.shape)} on {g.device}")
         if [p.data_ptr() for p in self.params] != self._pptrs:
             self._build_table()
+
+    @property
+    def det_workspace_bytes(self):
+        """bytes of the deterministic mode's slab workspace: the largest launch so far; 0 while the default mode runs"""
+        return 0 if self._det is None else self._det.nbytes
 
     def state_dict(self):
         """Optimizer state for checkpoint / resume, keyed like ``net.state_dict()`` (train.py:321-322 saves
@@ -1427,7 +1497,10 @@ class TrainStep:
         if not (net.use_unet and net.use_resnet and net.warper) or mode not in ("IMG_AND_MASK", "IMG_AND_MASK_AND_UV"):
             raise NotImplementedError("TrainStep covers the reference's training configurations: UNet + ResNetSTN + warper "
                                       "with resnet_input 'img+mask', or 'img+mask+uv' with the uv head")
-        tape = Tape(fmt=fmt, options=net.options, gshift=self.grad_scale_shift)
+        if self.deterministic and self._det is None:
+            self._det = DetWorkspace(x.device)
+        det = self._det if self.deterministic else None
+        tape = Tape(fmt=fmt, options=net.options, gshift=self.grad_scale_shift, deterministic=self.deterministic, workspace=det)
         B, _, H, W = x.shape
         x = E._f32c(x, "input frames")
         f = run_forward(net, tape, x)
@@ -1437,7 +1510,6 @@ class TrainStep:
         ww, wh = net.warp_size
         if (wh, ww) != (H, W):
             raise NotImplementedError("TrainStep needs warp_size == frame size (the losses compare per pixel)")
-        st = _stream()
         has_uv = bool(net.unet_uv and self.uv_loss is not None)
         losses = _zeros((5 if has_uv else 4,), x, torch.float64)   # seg, rec, consist, reproj[, uv]
         mask = batch["mask"]
@@ -1448,15 +1520,14 @@ class TrainStep:
         # train.py:214 gates on global_step * batch_size with the GLOBAL batch
         from . import sharding
         l_cons = self.lam["consist"] if self.global_step * B * sharding.world_size() >= self.consist_start_iter else 0.0
-        _lib.check(lib.sfh_train_losses(_ptr(logits), _ptr(mask), _ptr(E._f32c(batch["weight"], "weight")), _ptr(warp),
-                                        net.mask_classes, B, H, W, self.lam["seg"], self.lam["rec"], self.rec_mse,
-                                        l_cons, self.focal_flags, _ptr(dlogits), _ptr(dwarp), _ptr(losses), st), "train_losses")
+        _accumulate(det, "sfh_train_losses", (B, H, W), _ptr(logits), _ptr(mask), _ptr(E._f32c(batch["weight"], "weight")),
+                    _ptr(warp), net.mask_classes, B, H, W, self.lam["seg"], self.lam["rec"], self.rec_mse, l_cons,
+                    self.focal_flags, _ptr(dlogits), _ptr(dwarp), _ptr(losses))
         gt_poi = E._f32c(batch["poi"], "gt poi")
         dpoi = _empty(poi.shape, x)
-        _lib.check(lib.sfh_reproj_loss(_ptr(poi), _ptr(gt_poi), _ptr(E._f32c(batch["nonzeros"], "nonzeros")),
-                                       _ptr(E._f32c(batch["num_nonzero"], "num_nonzero")), B, poi.shape[1],
-                                       self.lam["reproj"], _ptr(dpoi), ctypes.c_void_p(losses.data_ptr() + 24), st),
-                   "reproj_loss")
+        _accumulate(det, "sfh_reproj_loss", (B,), _ptr(poi), _ptr(gt_poi), _ptr(E._f32c(batch["nonzeros"], "nonzeros")),
+                    _ptr(E._f32c(batch["num_nonzero"], "num_nonzero")), B, poi.shape[1], self.lam["reproj"], _ptr(dpoi),
+                    ctypes.c_void_p(losses.data_ptr() + 24))
         dheads = [dlogits]
         if net.unet_uv:
             duv = None
@@ -1469,11 +1540,11 @@ class TrainStep:
                 duv = _empty(uv.shape, x)
                 # models/losses.py:38-39 on a 4-D map: mean over (channel, row) -> (B, W), times the (B,) weights along the
                 # LAST axis - the reference's own broadcasting rule (B == 1 or B == W), its shape error otherwise
-                _lib.check(lib.sfh_uv_loss(_ptr(uv), _ptr(gt_uv), _ptr(wgt), wgt.numel(), B, uv.shape[1], H, W, self.uv_lambda,
-                                           1 if self.uv_loss == "MSE" else 0, _ptr(duv),
-                                           ctypes.c_void_p(losses.data_ptr() + 32), st), "uv_loss")
+                _accumulate(det, "sfh_uv_loss", (B, uv.shape[1], H, W), _ptr(uv), _ptr(gt_uv), _ptr(wgt), wgt.numel(), B,
+                            uv.shape[1], H, W, self.uv_lambda, 1 if self.uv_loss == "MSE" else 0, _ptr(duv),
+                            ctypes.c_void_p(losses.data_ptr() + 32))
             dheads.append(duv)
-        g = run_backward(net, tape, f, dheads, theta_gradient(net, f, None, dpoi, dwarp), unscale=False, device_scale=True)
+        g = run_backward(net, tape, f, dheads, theta_gradient(net, f, None, dpoi, dwarp, det), unscale=False, device_scale=True)
         srcs = []
         for p, dst in zip(self.params, self.grads):
             src = g[self.names(p)]
