@@ -1241,7 +1241,11 @@ int sfh_tiff_pack(const uint8_t* scratch, int64_t scratch_bytes, int batch, int 
  *
  * Every entry above that finishes a sum across workgroups with float atomics (their arrival order is free, so two runs
  * differ in the last bits) has a sibling NAME_det with the same arguments + (workspace, workspace_bytes) in front of the
- * stream, and a size query NAME_det_bytes that runs without a device (-1 for a refused geometry).  A sibling computes what
+ * stream, and a size query NAME_det_bytes that runs without a device (-1 for a refused geometry: the rule is the sibling's
+ * own - entry, sibling and query read one plan, csrc/det_core.h - so the query answers -1 exactly where NAME and NAME_det
+ * return SFH_E_ARG for the arguments the query sees.  For sfh_conv_wgrad_det_bytes that includes a source that does not
+ * fit the frame (pad_top + xh > H, pad_left + xw > W, a negative pad), xh or xw <= 0, x_cs < N and x_cs % 4 != 0; for
+ * sfh_conv_wgrad_s3_det_bytes a launch of 2^31 workgroups or more).  A sibling computes what
  * its entry computes, in two launches on the caller's stream:
  *
  *   store pass: the entry's kernel stores what it would have added into its own SLAB of the workspace.  Slab r is elements

@@ -6,6 +6,7 @@ Legs, run alternately `reps` times, each in a child process of its own (a fresh 
 clock around `steps` steps, ending in a device synchronise):
   parent         the parent commit's library and package: DIR is a checkout of that commit with its library built
                  (git worktree add DIR HEAD~1 && python DIR/__graft_entry__.py); skipped without --parent-tree
+  parent_deterministic  the same tree, TrainStep(deterministic=True): the parent beside the deterministic leg as well
   default        this commit, TrainStep(deterministic=False)
   two_pass       this commit, default mode with Options(train_one_pass=False): the plain legs the deterministic mode takes,
                  still on atomics - the part of the cost that is the lost fusions
@@ -21,7 +22,7 @@ import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LEGS = ("parent", "default", "two_pass", "deterministic")
+LEGS = ("parent", "parent_deterministic", "default", "two_pass", "deterministic")
 B, H, W = 16, 360, 640
 
 
@@ -41,7 +42,7 @@ def child(leg, tree, steps):
     net.to(dev).train()
     if leg == "two_pass":
         net.options = dataclasses.replace(net.options, train_one_pass=False)
-    ts = TrainStep(net, **({"deterministic": True} if leg == "deterministic" else {}))
+    ts = TrainStep(net, **({"deterministic": True} if leg.endswith("deterministic") else {}))
     g = torch.Generator().manual_seed(7)
     npoi = poi.shape[1]
     batch = {"mask": torch.randint(0, 4, (B, H, W), generator=g).to(dev), "weight": torch.ones(B, device=dev),
@@ -74,12 +75,12 @@ def main():
         return child(a.child, a.tree, a.steps)
     env = dict(os.environ, SFH_TRAIN_PRECISION="f16x3")
     env.pop("SFH_AMD_LIB", None)
-    legs = [leg for leg in LEGS if leg != "parent" or a.parent_tree]
+    legs = [leg for leg in LEGS if not leg.startswith("parent") or a.parent_tree]
     rows = []
     with open(a.out, "w") as out:    # one run, one record: an earlier file is replaced
         for rep in range(a.reps):
             for leg in legs:
-                tree = os.path.abspath(a.parent_tree) if leg == "parent" else ROOT
+                tree = os.path.abspath(a.parent_tree) if leg.startswith("parent") else ROOT
                 r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", leg, "--tree", tree, "--steps", str(a.steps)],
                                    env=env, cwd=tree, capture_output=True, text=True, timeout=900)
                 line = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")]
@@ -95,12 +96,14 @@ def main():
                    "det_workspace_bytes": max(r["det_workspace_bytes"] for r in rows),
                    "deterministic_over_default": round(med["deterministic"] / med["default"], 3),
                    "two_pass_over_default": round(med["two_pass"] / med["default"], 3)}
-        if "parent" in med:
-            par = [r["ms_per_step"] for r in rows if r["leg"] == "parent"]
-            summary["parent_spread_ms"] = round(max(par) - min(par), 3)
-            summary["default_minus_parent_ms_per_rep"] = [
-                round(d["ms_per_step"] - p["ms_per_step"], 3)
-                for d, p in zip((r for r in rows if r["leg"] == "default"), (r for r in rows if r["leg"] == "parent"))]
+        # "no slower": per mode, this commit's median minus the parent's, beside the spread of the parent's own repetitions
+        for ours, theirs in (("default", "parent"), ("deterministic", "parent_deterministic")):
+            if theirs in med:
+                par = [r["ms_per_step"] for r in rows if r["leg"] == theirs]
+                summary[f"{theirs}_spread_ms"] = round(max(par) - min(par), 3)
+                summary[f"{ours}_minus_{theirs}_median_ms"] = round(med[ours] - med[theirs], 3)
+                summary[f"{ours}_minus_{theirs}_ms_per_rep"] = [
+                    round(d["ms_per_step"] - p, 3) for d, p in zip((r for r in rows if r["leg"] == ours), par)]
         out.write(json.dumps(summary) + "\n")
         print(summary)
 

@@ -22,7 +22,7 @@
 //   throughout, one fp32 atomic add per raw element and workgroup, no fp64).
 #include "common.h"
 #include "conv_grouped_core.h"
-#include "det_core.h"   // det_add and the tile count: the deterministic mode's slabs
+#include "det_core.h"   // det_add and det_grouped_plan: the admitted geometries and the deterministic mode's slabs
 
 namespace {
 
@@ -250,14 +250,13 @@ struct WgradLaunch {
   }
 };
 
-// what the three entries refuse alike; nothing is launched after a refusal
-int check_geometry(const char* who, int batch, int H, int W, int groups, int cg, int stride) {
-  SFH_REQUIRE(gc_cg_ok(cg), "%s: %d channels per group (4, 8, 16, 32 or 64)", who, cg);
-  SFH_REQUIRE(stride == 1 || stride == 2, "%s: stride %d (1 or 2)", who, stride);
-  SFH_REQUIRE(batch > 0 && H > 0 && W > 0 && groups > 0, "%s: bad geometry batch=%d H=%d W=%d groups=%d", who, batch, H, W,
-              groups);
-  SFH_REQUIRE((long)groups * cg <= 65536 && (long)batch * H * W < (1L << 31) / 16, "%s: %d x %d x %d x %d groups too large", who,
-              batch, H, W, groups);
+// the words for what det_grouped_plan (det_core.h) refuses: forward, backward-filter, its sibling and the size query refuse
+// alike; nothing is launched after a refusal
+int check_geometry(const char* who, const DetPlan& p, int batch, int H, int W, int groups, int cg, int stride) {
+  SFH_REQUIRE(p.why != DET_BAD_CG, "%s: %d channels per group (4, 8, 16, 32 or 64)", who, cg);
+  SFH_REQUIRE(p.why != DET_BAD_STRIDE, "%s: stride %d (1 or 2)", who, stride);
+  SFH_REQUIRE(p.why != DET_BAD_FRAME, "%s: bad geometry batch=%d H=%d W=%d groups=%d", who, batch, H, W, groups);
+  SFH_REQUIRE(p.ok, "%s: %d x %d x %d x %d groups too large", who, batch, H, W, groups);
   return SFH_OK;
 }
 
@@ -284,33 +283,35 @@ extern "C" int sfh_conv_grouped_fwd(const float* src, const float* wpacked, cons
                                     float* dst, int batch, int H, int W, int groups, int cg, int stride, void* stream) {
   SFH_REQUIRE(src && wpacked && dst, "conv_grouped_fwd: null pointer");
   SFH_REQUIRE((scale == nullptr) == (shift == nullptr), "conv_grouped_fwd: scale and shift come together");
-  if (int rc = check_geometry("conv_grouped_fwd", batch, H, W, groups, cg, stride)) return rc;
+  const DetPlan p = det_grouped_plan(batch, H, W, groups, cg, stride);   // the forward admits what the backward-filter admits
+  if (int rc = check_geometry("conv_grouped_fwd", p, batch, H, W, groups, cg, stride)) return rc;
   SFH_REQUIRE(aligned16(wpacked) && aligned16(dst) && aligned16(scale) && aligned16(shift),
               "conv_grouped_fwd: wpacked, dst, scale and shift must be 16-byte aligned");
   return dispatch<FwdLaunch>(cg, stride, src, wpacked, scale, shift, relu ? 1 : 0, dst, batch, H, W, groups * cg,
                              (hipStream_t)stream);
 }
 
+static int conv_grouped_wgrad_impl(const float* dz, const float* src, float* raw, int batch, int H, int W, int groups, int cg,
+                                   int stride, bool det, void* workspace, long long workspace_bytes, void* stream) {
+  const char* who = det ? "conv_grouped_wgrad_det" : "conv_grouped_wgrad";
+  const DetPlan p = det_grouped_plan(batch, H, W, groups, cg, stride);
+  SFH_REQUIRE(dz && src && raw, "%s: null pointer", who);
+  if (int rc = check_geometry(who, p, batch, H, W, groups, cg, stride)) return rc;
+  if (det) SFH_REQUIRE_WS(who, workspace, workspace_bytes, p);
+  return dispatch<WgradLaunch>(cg, stride, dz, src, raw, det ? (float*)workspace : (float*)nullptr, batch, H, W, groups * cg,
+                               (hipStream_t)stream);
+}
+
 extern "C" int sfh_conv_grouped_wgrad(const float* dz, const float* src, float* raw, int batch, int H, int W, int groups,
                                       int cg, int stride, void* stream) {
-  SFH_REQUIRE(dz && src && raw, "conv_grouped_wgrad: null pointer");
-  if (int rc = check_geometry("conv_grouped_wgrad", batch, H, W, groups, cg, stride)) return rc;
-  return dispatch<WgradLaunch>(cg, stride, dz, src, raw, (float*)nullptr, batch, H, W, groups * cg, (hipStream_t)stream);
+  return conv_grouped_wgrad_impl(dz, src, raw, batch, H, W, groups, cg, stride, false, nullptr, 0, stream);
 }
 
 extern "C" int64_t sfh_conv_grouped_wgrad_det_bytes(int batch, int H, int W, int groups, int cg, int stride) {
-  if (!gc_cg_ok(cg) || !(stride == 1 || stride == 2) || batch <= 0 || H <= 0 || W <= 0 || groups <= 0 ||
-      (long)groups * cg > 65536 || (long)batch * H * W >= (1L << 31) / 16)
-    return -1;
-  return det_bytes(det_grouped_tiles(batch, H, W, stride), det_grouped_elems(groups, cg), sizeof(float));
+  return det_bytes(det_grouped_plan(batch, H, W, groups, cg, stride));
 }
 
 extern "C" int sfh_conv_grouped_wgrad_det(const float* dz, const float* src, float* raw, int batch, int H, int W, int groups,
                                           int cg, int stride, void* workspace, long long workspace_bytes, void* stream) {
-  SFH_REQUIRE(dz && src && raw, "conv_grouped_wgrad_det: null pointer");
-  if (int rc = check_geometry("conv_grouped_wgrad_det", batch, H, W, groups, cg, stride)) return rc;
-  const long long need = sfh_conv_grouped_wgrad_det_bytes(batch, H, W, groups, cg, stride);
-  SFH_REQUIRE(workspace != nullptr && workspace_bytes >= need, "conv_grouped_wgrad_det: workspace of %lld bytes, %lld needed",
-              workspace ? workspace_bytes : 0LL, need);
-  return dispatch<WgradLaunch>(cg, stride, dz, src, raw, (float*)workspace, batch, H, W, groups * cg, (hipStream_t)stream);
+  return conv_grouped_wgrad_impl(dz, src, raw, batch, H, W, groups, cg, stride, true, workspace, workspace_bytes, stream);
 }

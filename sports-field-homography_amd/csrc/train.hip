@@ -22,8 +22,8 @@ namespace {
 // channel quads strides over the pixels (grid-stride, at most RED_BLOCKS blocks so that the fp64
 // atomics on the few accumulator addresses stay cheap) and adds its partials to fp64 accumulators;
 // C > 1024 is processed in chunks of 1024 channels.
-// (det_core.h: DET_RED_ROWS = 256 pixels per block below which no further blocks are launched, DET_RED_BLOCKS = 1024, 4 per CU)
-static inline unsigned red_grid(long npix) { return (unsigned)det_red_blocks(npix); }
+// (det_core.h, det_red_blocks: DET_RED_ROWS = 256 pixels per block below which no further blocks are launched,
+// DET_RED_BLOCKS = 1024, 4 per CU)
 
 // DET (every accumulating kernel below): the store pass of the deterministic mode (det_core.h).  `acc` is then the workspace,
 // the block moves it to its own slab and the last add of every element is a plain store; DET = false is the kernel as it was.
@@ -1425,33 +1425,30 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(const WgradArgs a) {
     }
 }
 
-// The deterministic sibling of a backward-filter launch: the store pass into `ws` (slab per split, compact rows of N columns),
-// then the sum pass onto columns [n_off, n_off + N) of raw.  ws == nullptr: the default mode's launch, atomics onto raw.
-static int wgrad_sum_pass(const float* ws, int nsplit, long elems, int N, float* raw, int raw_n, int n_off, hipStream_t stream) {
-  return sfh_det_reduce_f32(ws, nsplit, elems, elems, N, raw + n_off, raw_n, stream);
-}
-
-template <int KS, int NSUB, int TH, int TW>
-int launch_wgrad(WgradArgs a, const DetWgradPlan& p, float* ws, hipStream_t stream) {
-  constexpr int HPX = (TH + KS - 1) * (TW + KS - 1);
-  const size_t lds = (size_t)(HPX + 64) * 64 * sizeof(float);
+// the plan's grid numbers into the kernel's arguments; returns the grid: whole rounds of 8 splits (one per XCD)
+static dim3 wgrad_grid(WgradArgs& a, const DetWgradPlan& p) {
   a.ntx = p.ntx;
   a.nty = p.nty;
   a.ntiles = p.ntiles;
   a.nsplit = p.nsplit;
-  a.mt = p.mt;
+  a.mt = p.mt;   // (the first-layer form: mn == mt)
   a.mn = p.mn;
-  const dim3 grid((unsigned)(sfh_cdiv(p.nsplit, 8) * 8 * p.mn));
-  if (!ws) {
-    hipLaunchKernelGGL((wgrad_kernel<KS, NSUB, TH, TW>), grid, dim3(256), lds, stream, a);
-    return sfh_check_launch("wgrad_kernel");
-  }
+  return dim3((unsigned)(sfh_cdiv(p.nsplit, 8) * 8 * p.mn));
+}
+
+// A backward-filter launch.  ws == nullptr: the default mode, atomics onto raw.  Else the deterministic sibling: the store pass
+// into `ws` (slab per split, compact rows of N columns), then the sum pass onto columns [n_off, n_off + N) of raw.
+template <int KS, int NSUB, int TH, int TW>
+int launch_wgrad(WgradArgs a, const DetWgradPlan& p, float* ws, hipStream_t stream) {
+  constexpr int HPX = (TH + KS - 1) * (TW + KS - 1);
+  const size_t lds = (size_t)(HPX + 64) * 64 * sizeof(float);
+  const dim3 grid = wgrad_grid(a, p);
   float* raw = a.raw;
-  const int raw_n = a.raw_n, n_off = a.n_off;
-  a.raw = ws;
-  hipLaunchKernelGGL((wgrad_kernel<KS, NSUB, TH, TW, true>), grid, dim3(256), lds, stream, a);
-  if (int rc = sfh_check_launch("wgrad_kernel (deterministic)")) return rc;
-  return wgrad_sum_pass(ws, p.nsplit, p.elems, a.N, raw, raw_n, n_off, stream);
+  if (ws) a.raw = ws;
+  if (!ws) hipLaunchKernelGGL((wgrad_kernel<KS, NSUB, TH, TW>), grid, dim3(256), lds, stream, a);
+  else hipLaunchKernelGGL((wgrad_kernel<KS, NSUB, TH, TW, true>), grid, dim3(256), lds, stream, a);
+  if (int rc = sfh_check_launch(ws ? "wgrad_kernel (deterministic)" : "wgrad_kernel")) return rc;
+  return ws ? sfh_det_reduce_f32(ws, p.slabs, p.elems, p.elems, a.N, raw + a.n_off, a.raw_n, stream) : SFH_OK;
 }
 
 // Backward-filter of a 3x3 conv over at most FOUR input channels (the UNet's first layer: N = 3 stored as 4; round 4).
@@ -1566,35 +1563,19 @@ __global__ __launch_bounds__(256, 4) void wgrad_c4_kernel(const WgradArgs a) {
 
 template <int TH, int TW>
 int launch_wgrad_c4(WgradArgs a, const DetWgradPlan& p, float* ws, hipStream_t stream) {
-  a.ntx = p.ntx;
-  a.nty = p.nty;
-  a.ntiles = p.ntiles;
-  a.nsplit = p.nsplit;
-  a.mt = p.mn;
-  a.mn = p.mn;
-  const dim3 grid((unsigned)(sfh_cdiv(p.nsplit, 8) * 8 * p.mn));
-  if (!ws) {
-    hipLaunchKernelGGL((wgrad_c4_kernel<TH, TW, false>), grid, dim3(256), 0, stream, a);
-    return sfh_check_launch("wgrad_c4_kernel");
-  }
+  const dim3 grid = wgrad_grid(a, p);
   float* raw = a.raw;
-  const int raw_n = a.raw_n, n_off = a.n_off;
-  a.raw = ws;
-  hipLaunchKernelGGL((wgrad_c4_kernel<TH, TW, false, true>), grid, dim3(256), 0, stream, a);
-  if (int rc = sfh_check_launch("wgrad_c4_kernel (deterministic)")) return rc;
-  return wgrad_sum_pass(ws, p.nsplit, p.elems, a.N, raw, raw_n, n_off, stream);
+  if (ws) a.raw = ws;
+  if (!ws) hipLaunchKernelGGL((wgrad_c4_kernel<TH, TW, false>), grid, dim3(256), 0, stream, a);
+  else hipLaunchKernelGGL((wgrad_c4_kernel<TH, TW, false, true>), grid, dim3(256), 0, stream, a);
+  if (int rc = sfh_check_launch(ws ? "wgrad_c4_kernel (deterministic)" : "wgrad_c4_kernel")) return rc;
+  return ws ? sfh_det_reduce_f32(ws, p.slabs, p.elems, p.elems, a.N, raw + a.n_off, a.raw_n, stream) : SFH_OK;
 }
 
 // the fused BatchNorm form (sfh_conv_wgrad_c4_bn) has no deterministic sibling: the mode takes sfh_bn_bwd_apply + sfh_conv_wgrad
 template <int TH, int TW>
 int launch_wgrad_c4_bn(WgradArgs a, const DetWgradPlan& p, hipStream_t stream) {
-  a.ntx = p.ntx;
-  a.nty = p.nty;
-  a.ntiles = p.ntiles;
-  a.nsplit = p.nsplit;
-  a.mt = p.mn;
-  a.mn = p.mn;
-  const dim3 grid((unsigned)(sfh_cdiv(p.nsplit, 8) * 8 * p.mn));
+  const dim3 grid = wgrad_grid(a, p);
   hipLaunchKernelGGL((wgrad_c4_kernel<TH, TW, true>), grid, dim3(256), 0, stream, a);
   return sfh_check_launch("wgrad_c4_kernel");
 }
@@ -1602,33 +1583,30 @@ int launch_wgrad_c4_bn(WgradArgs a, const DetWgradPlan& p, hipStream_t stream) {
 }  // namespace
 
 // =============================================================================== C ABI
-// The deterministic siblings (sfh_*_det, include/sfh_amd.h): same arguments + (workspace, workspace_bytes); the store pass into
-// the workspace, then the sum pass (sfh_det_reduce_*) onto the destination.  A workspace that is NULL or smaller than the size
-// query's answer is refused before anything is launched.
-#define SFH_REQUIRE_WS(who, ws, ws_bytes, need)                                                                        \
-  SFH_REQUIRE((ws) != nullptr && (long long)(ws_bytes) >= (long long)(need), "%s: workspace of %lld bytes, %lld needed", \
-              who, (ws) ? (long long)(ws_bytes) : 0LL, (long long)(need))
+// An accumulating entry, its deterministic sibling (sfh_*_det, include/sfh_amd.h: same arguments + (workspace,
+// workspace_bytes)) and its size query (sfh_*_det_bytes) share one plan (det_core.h): the two entries forward into one static
+// function (ws == nullptr, 0 bytes for the plain entry), which checks what the query does not see, refuses what the plan
+// refuses, in deterministic mode checks the workspace (SFH_REQUIRE_WS), launches the DET = det instantiation and then runs the
+// sum pass (sfh_det_reduce_*) onto the destination; the query answers det_bytes(plan).
+static int bn_stats_impl(const float* z, int64_t npix, int C, double* acc, bool det, void* ws, long long ws_bytes, void* stream) {
+  const char* who = det ? "bn_stats_det" : "bn_stats";
+  const DetPlan p = det_red_plan((long)npix, C, 2);
+  SFH_REQUIRE(z && acc && p.ok, "%s: bad argument", who);
+  if (det) SFH_REQUIRE_WS(who, ws, ws_bytes, p);
+  SFH_LAUNCH_DET(bn_stats_kernel, det, dim3((unsigned)p.slabs), dim3(256), stream, z, (long)npix, C, det ? (double*)ws : acc);
+  if (int rc = sfh_check_launch(det ? "bn_stats_kernel (deterministic)" : "bn_stats_kernel")) return rc;
+  return det ? sfh_det_reduce_f64((const double*)ws, p.slabs, p.elems, p.elems, 2 * C, acc, 2 * C, stream) : SFH_OK;
+}
 
 extern "C" int sfh_bn_stats(const float* z, int64_t npix, int C, double* acc, void* stream) {
-  SFH_REQUIRE(z && acc && npix > 0 && C > 0 && C % 4 == 0, "bn_stats: bad argument");
-  const unsigned nb = red_grid((long)npix);
-  hipLaunchKernelGGL(bn_stats_kernel<false>, dim3(nb), dim3(256), 0, (hipStream_t)stream, z, (long)npix, C, acc);
-  return sfh_check_launch("bn_stats_kernel");
+  return bn_stats_impl(z, npix, C, acc, false, nullptr, 0, stream);
 }
 
-extern "C" int64_t sfh_bn_stats_det_bytes(int64_t npix, int C) {
-  if (npix <= 0 || C <= 0 || C % 4 != 0) return -1;
-  return det_bytes(det_red_blocks((long)npix), 2L * C, sizeof(double));
-}
+extern "C" int64_t sfh_bn_stats_det_bytes(int64_t npix, int C) { return det_bytes(det_red_plan((long)npix, C, 2)); }
 
 extern "C" int sfh_bn_stats_det(const float* z, int64_t npix, int C, double* acc, void* workspace, long long workspace_bytes,
                                 void* stream) {
-  SFH_REQUIRE(z && acc && npix > 0 && C > 0 && C % 4 == 0, "bn_stats_det: bad argument");
-  SFH_REQUIRE_WS("bn_stats_det", workspace, workspace_bytes, sfh_bn_stats_det_bytes(npix, C));
-  const unsigned nb = red_grid((long)npix);
-  hipLaunchKernelGGL(bn_stats_kernel<true>, dim3(nb), dim3(256), 0, (hipStream_t)stream, z, (long)npix, C, (double*)workspace);
-  if (int rc = sfh_check_launch("bn_stats_kernel (deterministic)")) return rc;
-  return sfh_det_reduce_f64((const double*)workspace, nb, 2L * C, 2L * C, 2 * C, acc, 2 * C, stream);
+  return bn_stats_impl(z, npix, C, acc, true, workspace, workspace_bytes, stream);
 }
 
 extern "C" int sfh_bn_stats_partials(const double* partial, int rows, int C, double* acc, void* stream) {
@@ -1678,15 +1656,24 @@ extern "C" int sfh_bn_apply(const float* z, const float* mean_invstd, const floa
   return sfh_check_launch("bn_apply_kernel");
 }
 
+static int bn_bwd_reduce_impl(const float* dy, const float* y, const float* z, const float* mean_invstd, const float* gamma,
+                              const float* beta, int relu, int64_t npix, int C, double* acc, bool det, void* ws,
+                              long long ws_bytes, void* stream) {
+  const char* who = det ? "bn_bwd_reduce_det" : "bn_bwd_reduce";
+  const DetPlan p = det_red_plan((long)npix, C, 2);
+  SFH_REQUIRE(dy && z && mean_invstd && acc && (y || !relu || (gamma && beta)) && p.ok,
+              "%s: bad argument (relu needs y, or gamma and beta to recompute its sign from z)", who);
+  if (det) SFH_REQUIRE_WS(who, ws, ws_bytes, p);
+  SFH_LAUNCH_DET(bn_bwd_reduce_kernel, det, dim3((unsigned)p.slabs), dim3(256), stream, dy, y, z, mean_invstd, gamma, beta, relu,
+                 (long)npix, C, det ? (double*)ws : acc);
+  if (int rc = sfh_check_launch(det ? "bn_bwd_reduce_kernel (deterministic)" : "bn_bwd_reduce_kernel")) return rc;
+  return det ? sfh_det_reduce_f64((const double*)ws, p.slabs, p.elems, p.elems, 2 * C, acc, 2 * C, stream) : SFH_OK;
+}
+
 extern "C" int sfh_bn_bwd_reduce(const float* dy, const float* y, const float* z, const float* mean_invstd,
                                  const float* gamma, const float* beta, int relu, int64_t npix, int C, double* acc,
                                  void* stream) {
-  SFH_REQUIRE(dy && z && mean_invstd && acc && (y || !relu || (gamma && beta)) && npix > 0 && C > 0 && C % 4 == 0,
-              "bn_bwd_reduce: bad argument (relu needs y, or gamma and beta to recompute its sign from z)");
-  const unsigned nb = red_grid((long)npix);
-  hipLaunchKernelGGL(bn_bwd_reduce_kernel<false>, dim3(nb), dim3(256), 0, (hipStream_t)stream, dy, y, z, mean_invstd, gamma,
-                     beta, relu, (long)npix, C, acc);
-  return sfh_check_launch("bn_bwd_reduce_kernel");
+  return bn_bwd_reduce_impl(dy, y, z, mean_invstd, gamma, beta, relu, npix, C, acc, false, nullptr, 0, stream);
 }
 
 extern "C" int64_t sfh_bn_bwd_reduce_det_bytes(int64_t npix, int C) { return sfh_bn_stats_det_bytes(npix, C); }
@@ -1694,14 +1681,7 @@ extern "C" int64_t sfh_bn_bwd_reduce_det_bytes(int64_t npix, int C) { return sfh
 extern "C" int sfh_bn_bwd_reduce_det(const float* dy, const float* y, const float* z, const float* mean_invstd,
                                      const float* gamma, const float* beta, int relu, int64_t npix, int C, double* acc,
                                      void* workspace, long long workspace_bytes, void* stream) {
-  SFH_REQUIRE(dy && z && mean_invstd && acc && (y || !relu || (gamma && beta)) && npix > 0 && C > 0 && C % 4 == 0,
-              "bn_bwd_reduce_det: bad argument (relu needs y, or gamma and beta to recompute its sign from z)");
-  SFH_REQUIRE_WS("bn_bwd_reduce_det", workspace, workspace_bytes, sfh_bn_bwd_reduce_det_bytes(npix, C));
-  const unsigned nb = red_grid((long)npix);
-  hipLaunchKernelGGL(bn_bwd_reduce_kernel<true>, dim3(nb), dim3(256), 0, (hipStream_t)stream, dy, y, z, mean_invstd, gamma,
-                     beta, relu, (long)npix, C, (double*)workspace);
-  if (int rc = sfh_check_launch("bn_bwd_reduce_kernel (deterministic)")) return rc;
-  return sfh_det_reduce_f64((const double*)workspace, nb, 2L * C, 2L * C, 2 * C, acc, 2 * C, stream);
+  return bn_bwd_reduce_impl(dy, y, z, mean_invstd, gamma, beta, relu, npix, C, acc, true, workspace, workspace_bytes, stream);
 }
 
 extern "C" int sfh_bn_bwd_apply(const float* dy, const float* y, const float* z, const float* mean_invstd,
@@ -1726,26 +1706,26 @@ extern "C" int sfh_bn_bwd_apply(const float* dy, const float* y, const float* z,
   return sfh_check_launch("bn_bwd_apply_kernel");
 }
 
-extern "C" int sfh_colsum(const float* x, int64_t npix, int C, int cs, double* acc, void* stream) {
-  SFH_REQUIRE(x && acc && npix > 0 && C > 0 && C % 4 == 0 && cs >= C && cs % 4 == 0, "colsum: bad argument");
-  const unsigned nb = red_grid((long)npix);
-  hipLaunchKernelGGL(colsum_kernel<false>, dim3(nb), dim3(256), 0, (hipStream_t)stream, x, (long)npix, C, cs, acc);
-  return sfh_check_launch("colsum_kernel");
+static int colsum_impl(const float* x, int64_t npix, int C, int cs, double* acc, bool det, void* ws, long long ws_bytes,
+                       void* stream) {
+  const char* who = det ? "colsum_det" : "colsum";
+  const DetPlan p = det_red_plan((long)npix, C, 1);
+  SFH_REQUIRE(x && acc && p.ok && cs >= C && cs % 4 == 0, "%s: bad argument", who);
+  if (det) SFH_REQUIRE_WS(who, ws, ws_bytes, p);
+  SFH_LAUNCH_DET(colsum_kernel, det, dim3((unsigned)p.slabs), dim3(256), stream, x, (long)npix, C, cs, det ? (double*)ws : acc);
+  if (int rc = sfh_check_launch(det ? "colsum_kernel (deterministic)" : "colsum_kernel")) return rc;
+  return det ? sfh_det_reduce_f64((const double*)ws, p.slabs, p.elems, p.elems, C, acc, C, stream) : SFH_OK;
 }
 
-extern "C" int64_t sfh_colsum_det_bytes(int64_t npix, int C) {
-  if (npix <= 0 || C <= 0 || C % 4 != 0) return -1;
-  return det_bytes(det_red_blocks((long)npix), C, sizeof(double));
+extern "C" int sfh_colsum(const float* x, int64_t npix, int C, int cs, double* acc, void* stream) {
+  return colsum_impl(x, npix, C, cs, acc, false, nullptr, 0, stream);
 }
+
+extern "C" int64_t sfh_colsum_det_bytes(int64_t npix, int C) { return det_bytes(det_red_plan((long)npix, C, 1)); }
 
 extern "C" int sfh_colsum_det(const float* x, int64_t npix, int C, int cs, double* acc, void* workspace,
                               long long workspace_bytes, void* stream) {
-  SFH_REQUIRE(x && acc && npix > 0 && C > 0 && C % 4 == 0 && cs >= C && cs % 4 == 0, "colsum_det: bad argument");
-  SFH_REQUIRE_WS("colsum_det", workspace, workspace_bytes, sfh_colsum_det_bytes(npix, C));
-  const unsigned nb = red_grid((long)npix);
-  hipLaunchKernelGGL(colsum_kernel<true>, dim3(nb), dim3(256), 0, (hipStream_t)stream, x, (long)npix, C, cs, (double*)workspace);
-  if (int rc = sfh_check_launch("colsum_kernel (deterministic)")) return rc;
-  return sfh_det_reduce_f64((const double*)workspace, nb, C, C, C, acc, C, stream);
+  return colsum_impl(x, npix, C, cs, acc, true, workspace, workspace_bytes, stream);
 }
 
 extern "C" int sfh_s2d_split_colsum(const float* du, int batch, int h, int w, int cout, void* s_split, int split_fmt,
@@ -1791,7 +1771,7 @@ extern "C" int sfh_pool2_bwd_bn_reduce(const float* z, const float* mean_invstd,
               "pool2_bwd_bn_reduce: bad argument");
   const long nquads = (long)batch * ((H + 1) / 2) * ((W + 1) / 2);
   SFH_REQUIRE(nquads < (1L << 31) && (long)batch * H * W < (1L << 31), "pool2_bwd_bn_reduce: tensor too large for one launch");
-  const unsigned nb = red_grid(nquads);
+  const unsigned nb = (unsigned)det_red_blocks(nquads);
   hipLaunchKernelGGL(pool2_bwd_bn_reduce_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, z, mean_invstd, gamma, beta,
                      dpool, H, W, C, nquads, accumulate, dx, acc);
   return sfh_check_launch("pool2_bwd_bn_reduce_kernel");
@@ -1839,20 +1819,20 @@ extern "C" int sfh_zero_stuff2(const float* src, float* dst, int batch, int ho, 
   return sfh_check_launch("zero_stuff2_kernel");
 }
 
-// ws == nullptr: the default mode; else the deterministic sibling's workspace, already checked against the plan's size
 static int conv_wgrad_impl(const float* dz, int dz_cs, int M, const float* x, int x_cs, int xh, int xw, int N, int pad_top,
                            int pad_left, int batch, int H, int W, int ksize, float* raw, int raw_n, int n_off, bool det,
                            void* workspace, long long workspace_bytes, void* stream) {
   const char* who = det ? "conv_wgrad_det" : "conv_wgrad";
+  // the network's first layer (3 input channels stored as 4, one source of the frame's own size): p.c4, n = (tap, channel)
+  const DetWgradPlan p = det_wgrad_plan(M, x_cs, xh, xw, N, pad_top, pad_left, batch, H, W, ksize);
   SFH_REQUIRE(dz && x && raw, "%s: null pointer", who);
-  SFH_REQUIRE(batch > 0 && H > 0 && W > 0 && xh > 0 && xw > 0, "%s: bad geometry", who);
-  SFH_REQUIRE(M > 0 && M % 4 == 0 && dz_cs % 4 == 0 && dz_cs >= M, "%s: M=%d dz_cs=%d", who, M, dz_cs);
-  SFH_REQUIRE(N > 0 && N % 4 == 0 && x_cs % 4 == 0 && x_cs >= N, "%s: N=%d x_cs=%d", who, N, x_cs);
+  SFH_REQUIRE(p.why != DET_BAD_FRAME, "%s: bad geometry", who);
+  SFH_REQUIRE(p.why != DET_BAD_M && dz_cs % 4 == 0 && dz_cs >= M, "%s: M=%d dz_cs=%d", who, M, dz_cs);
+  SFH_REQUIRE(p.why != DET_BAD_N, "%s: N=%d x_cs=%d", who, N, x_cs);
   SFH_REQUIRE(n_off >= 0 && n_off + N <= raw_n, "%s: n_off=%d N=%d raw_n=%d", who, n_off, N, raw_n);
-  SFH_REQUIRE(pad_top >= 0 && pad_left >= 0 && pad_top + xh <= H && pad_left + xw <= W,
-              "%s: source (%dx%d at %d,%d) does not fit the %dx%d frame", who, xh, xw, pad_top, pad_left, H, W);
-  SFH_REQUIRE(ksize == 1 || ksize == 3 || ksize == 4, "%s: ksize %d", who, ksize);
-  SFH_REQUIRE(ksize != 4 || N <= 32, "%s: the 4x4 (stem) case supports N <= 32", who);
+  SFH_REQUIRE(p.why != DET_BAD_FIT, "%s: source (%dx%d at %d,%d) does not fit the %dx%d frame", who, xh, xw, pad_top, pad_left, H, W);
+  SFH_REQUIRE(p.why != DET_BAD_KSIZE, "%s: ksize %d", who, ksize);
+  SFH_REQUIRE(p.ok, "%s: the 4x4 (stem) case supports N <= 32", who);
   WgradArgs a;
   a.dz = dz; a.dz_cs = dz_cs; a.M = M;
   a.x = x; a.x_cs = x_cs; a.xh = xh; a.xw = xw; a.N = N; a.pad_top = pad_top; a.pad_left = pad_left;
@@ -1861,19 +1841,13 @@ static int conv_wgrad_impl(const float* dz, int dz_cs, int M, const float* x, in
   a.ntx = a.nty = a.ntiles = a.nsplit = a.mt = a.mn = 0;
   a.bn_z = a.bn_mi = a.bn_gamma = a.bn_beta = nullptr; a.bn_acc = nullptr; a.bn_inv_n = 0.f;
   hipStream_t st = (hipStream_t)stream;
-  // the network's first layer (3 input channels stored as 4, one source of the frame's own size): n = (tap, channel)
-  const bool c4 = det_wgrad_is_c4(ksize, N, x_cs, xh, xw, pad_top, pad_left, H, W);
-  const DetWgradPlan p = det_wgrad_plan(M, N, ksize, c4, batch, H, W);
-  float* ws = nullptr;
-  if (det) {
-    SFH_REQUIRE_WS("conv_wgrad_det", workspace, workspace_bytes, det_bytes(p.nsplit, p.elems, sizeof(float)));
-    ws = (float*)workspace;
-  }
+  if (det) SFH_REQUIRE_WS(who, workspace, workspace_bytes, p);
+  float* ws = det ? (float*)workspace : nullptr;   // the launchers: nullptr is the default mode
   const int t = p.shape;
 #define SFH_WG(KS_, NS_)                                         \
   (t == 0 ? launch_wgrad<KS_, NS_, 2, 32>(a, p, ws, st)           \
           : (t == 1 ? launch_wgrad<KS_, NS_, 4, 16>(a, p, ws, st) : launch_wgrad<KS_, NS_, 8, 8>(a, p, ws, st)))
-  if (c4)
+  if (p.c4)
     return t == 0 ? launch_wgrad_c4<2, 32>(a, p, ws, st)
                   : (t == 1 ? launch_wgrad_c4<4, 16>(a, p, ws, st) : launch_wgrad_c4<8, 8>(a, p, ws, st));
   if (ksize == 3 && N <= 16) return SFH_WG(3, 1);
@@ -1892,11 +1866,7 @@ extern "C" int sfh_conv_wgrad(const float* dz, int dz_cs, int M, const float* x,
 
 extern "C" int64_t sfh_conv_wgrad_det_bytes(int M, int x_cs, int xh, int xw, int N, int pad_top, int pad_left, int batch, int H,
                                             int W, int ksize) {
-  if (batch <= 0 || H <= 0 || W <= 0 || M <= 0 || M % 4 != 0 || N <= 0 || N % 4 != 0 ||
-      !(ksize == 1 || ksize == 3 || ksize == 4) || (ksize == 4 && N > 32))
-    return -1;
-  const DetWgradPlan p = det_wgrad_plan(M, N, ksize, det_wgrad_is_c4(ksize, N, x_cs, xh, xw, pad_top, pad_left, H, W), batch, H, W);
-  return det_bytes(p.nsplit, p.elems, sizeof(float));
+  return det_bytes(det_wgrad_plan(M, x_cs, xh, xw, N, pad_top, pad_left, batch, H, W, ksize));
 }
 
 extern "C" int sfh_conv_wgrad_det(const float* dz, int dz_cs, int M, const float* x, int x_cs, int xh, int xw, int N,
@@ -1921,73 +1891,70 @@ extern "C" int sfh_conv_wgrad_c4_bn(const float* dy, const float* z, const float
   a.bn_z = z; a.bn_mi = mean_invstd; a.bn_gamma = gamma; a.bn_beta = beta; a.bn_acc = acc;
   a.bn_inv_n = bn_inv_n((long)batch * H * W);
   hipStream_t st = (hipStream_t)stream;
-  const DetWgradPlan p = det_wgrad_plan(M, N, 3, true, batch, H, W);
+  const DetWgradPlan p = det_wgrad_plan(M, 4, H, W, 4, 0, 0, batch, H, W, 3);   // the first-layer form: channels as stored, four
   return p.shape == 0 ? launch_wgrad_c4_bn<2, 32>(a, p, st)
                       : (p.shape == 1 ? launch_wgrad_c4_bn<4, 16>(a, p, st) : launch_wgrad_c4_bn<8, 8>(a, p, st));
 }
 
+// acc_bn != nullptr: the BatchNorm-fused form (sfh_outconv_bwd_bn), which has no deterministic sibling
 static int launch_outconv_bwd(const float* x, int cin, const float* w, const float* dlogits_nchw, int nc, int batch, int H,
                               int W, float* dx, double* acc_w, double* acc_b, const float* bn_mi, const float* bn_gamma,
-                              const float* bn_beta, double* acc_bn, void* stream) {
-  SFH_REQUIRE(x && w && dlogits_nchw && acc_w && acc_b && batch > 0 && H > 0 && W > 0, "outconv_bwd: bad argument");
-  SFH_REQUIRE(cin % 4 == 0 && cin >= 4 && cin <= 256, "outconv_bwd: cin=%d (multiple of 4, <= 256)", cin);
-  SFH_REQUIRE(nc >= 1 && nc <= 8, "outconv_bwd: nc=%d unsupported (1..8)", nc);
+                              const float* bn_beta, double* acc_bn, bool det, void* workspace, long long workspace_bytes,
+                              void* stream) {
+  const char* who = det ? "outconv_bwd_det" : "outconv_bwd";
+  const DetPlan p = det_outconv_plan(cin, nc, batch, H, W);
+  SFH_REQUIRE(x && w && dlogits_nchw && acc_w && acc_b && p.why != DET_BAD_FRAME, "%s: bad argument", who);
+  SFH_REQUIRE(p.why != DET_BAD_CIN, "%s: cin=%d (multiple of 4, <= 256)", who, cin);
+  SFH_REQUIRE(p.ok, "%s: nc=%d unsupported (1..8)", who, nc);
+  SFH_REQUIRE(!(det && acc_bn), "%s: the BatchNorm-fused form has no deterministic mode", who);
+  if (det) SFH_REQUIRE_WS(who, workspace, workspace_bytes, p);
   const long npix = (long)batch * H * W;
   // every workgroup ends with nc * (cin + 1) fp64 atomics on the same addresses: about 1024 workgroups (at 640x360 x 16:
   // 3840 pixels each, 0.49 ms; 1024 pixels each = 3600 workgroups: 0.56 ms; 8192: 0.63 - profiles/r05_s2d_atomics.txt)
   const long ppb = det_outconv_ppb(npix);
-  const unsigned grid = (unsigned)det_outconv_blocks(npix);
-#define SFH_OB(N)                                                                                           \
-  case N:                                                                                                          \
-    if (acc_bn)                                                                                                    \
-      hipLaunchKernelGGL((outconv_bwd_kernel<N, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, x, cin, w,   \
-                         dlogits_nchw, npix, H * W, dx, acc_w, acc_b, (int)ppb, bn_mi, bn_gamma, bn_beta, acc_bn); \
-    else                                                                                                           \
-      hipLaunchKernelGGL((outconv_bwd_kernel<N, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, x, cin, w,  \
-                         dlogits_nchw, npix, H * W, dx, acc_w, acc_b, (int)ppb, bn_mi, bn_gamma, bn_beta, acc_bn); \
+  double* ws = (double*)workspace;   // the store pass finds both parts of its slab from the workspace's base
+#define SFH_OB_LAUNCH(...)                                                                                              \
+  hipLaunchKernelGGL((outconv_bwd_kernel<__VA_ARGS__>), dim3((unsigned)p.slabs), dim3(256), 0, (hipStream_t)stream, x, cin, \
+                     w, dlogits_nchw, npix, H * W, dx, det ? ws : acc_w, det ? ws : acc_b, (int)ppb, bn_mi, bn_gamma,     \
+                     bn_beta, acc_bn)
+#define SFH_OB(N)                                 \
+  case N:                                         \
+    if (acc_bn) SFH_OB_LAUNCH(N, true);           \
+    else if (!det) SFH_OB_LAUNCH(N, false);       \
+    else SFH_OB_LAUNCH(N, false, true);           \
     break;
   switch (nc) { SFH_OB(1) SFH_OB(2) SFH_OB(3) SFH_OB(4) SFH_OB(5) SFH_OB(6) SFH_OB(7) SFH_OB(8) }
 #undef SFH_OB
-  return sfh_check_launch("outconv_bwd_kernel");
+#undef SFH_OB_LAUNCH
+  if (int rc = sfh_check_launch(det ? "outconv_bwd_kernel (deterministic)" : "outconv_bwd_kernel")) return rc;
+  if (!det) return SFH_OK;
+  if (int rc = sfh_det_reduce_f64(ws, p.slabs, p.elems, (long)nc * cin, nc * cin, acc_w, nc * cin, stream)) return rc;
+  return sfh_det_reduce_f64(ws + (long)nc * cin, p.slabs, p.elems, nc, nc, acc_b, nc, stream);
 }
 
 extern "C" int sfh_outconv_bwd(const float* x, int cin, const float* w, const float* dlogits_nchw, int nc,
                                int batch, int H, int W, float* dx, double* acc_w, double* acc_b, void* stream) {
-  return launch_outconv_bwd(x, cin, w, dlogits_nchw, nc, batch, H, W, dx, acc_w, acc_b, nullptr, nullptr, nullptr, nullptr, stream);
+  return launch_outconv_bwd(x, cin, w, dlogits_nchw, nc, batch, H, W, dx, acc_w, acc_b, nullptr, nullptr, nullptr, nullptr, false,
+                            nullptr, 0, stream);
 }
 
 extern "C" int64_t sfh_outconv_bwd_det_bytes(int cin, int nc, int batch, int H, int W) {
-  if (batch <= 0 || H <= 0 || W <= 0 || cin % 4 != 0 || cin < 4 || cin > 256 || nc < 1 || nc > 8) return -1;
-  return det_bytes(det_outconv_blocks((long)batch * H * W), det_outconv_elems(nc, cin), sizeof(double));
+  return det_bytes(det_outconv_plan(cin, nc, batch, H, W));
 }
 
 extern "C" int sfh_outconv_bwd_det(const float* x, int cin, const float* w, const float* dlogits_nchw, int nc, int batch, int H,
                                    int W, float* dx, double* acc_w, double* acc_b, void* workspace, long long workspace_bytes,
                                    void* stream) {
-  SFH_REQUIRE(x && w && dlogits_nchw && acc_w && acc_b && batch > 0 && H > 0 && W > 0, "outconv_bwd_det: bad argument");
-  SFH_REQUIRE(cin % 4 == 0 && cin >= 4 && cin <= 256, "outconv_bwd_det: cin=%d (multiple of 4, <= 256)", cin);
-  SFH_REQUIRE(nc >= 1 && nc <= 8, "outconv_bwd_det: nc=%d unsupported (1..8)", nc);
-  SFH_REQUIRE_WS("outconv_bwd_det", workspace, workspace_bytes, sfh_outconv_bwd_det_bytes(cin, nc, batch, H, W));
-  const long npix = (long)batch * H * W;
-  const long ppb = det_outconv_ppb(npix), nb = det_outconv_blocks(npix), elems = det_outconv_elems(nc, cin);
-  double* ws = (double*)workspace;
-#define SFH_OB(N)                                                                                                          \
-  case N:                                                                                                                  \
-    hipLaunchKernelGGL((outconv_bwd_kernel<N, false, true>), dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, x, cin, \
-                       w, dlogits_nchw, npix, H * W, dx, ws, ws, (int)ppb, nullptr, nullptr, nullptr, nullptr);            \
-    break;
-  switch (nc) { SFH_OB(1) SFH_OB(2) SFH_OB(3) SFH_OB(4) SFH_OB(5) SFH_OB(6) SFH_OB(7) SFH_OB(8) }
-#undef SFH_OB
-  if (int rc = sfh_check_launch("outconv_bwd_kernel (deterministic)")) return rc;
-  if (int rc = sfh_det_reduce_f64(ws, nb, elems, (long)nc * cin, nc * cin, acc_w, nc * cin, stream)) return rc;
-  return sfh_det_reduce_f64(ws + (long)nc * cin, nb, elems, nc, nc, acc_b, nc, stream);
+  return launch_outconv_bwd(x, cin, w, dlogits_nchw, nc, batch, H, W, dx, acc_w, acc_b, nullptr, nullptr, nullptr, nullptr, true,
+                            workspace, workspace_bytes, stream);
 }
 
 extern "C" int sfh_outconv_bwd_bn(const float* z, const float* mean_invstd, const float* gamma, const float* beta, int cin,
                                   const float* w, const float* dlogits_nchw, int nc, int batch, int H, int W, float* dx,
                                   double* acc_w, double* acc_b, double* acc_bn, void* stream) {
   SFH_REQUIRE(mean_invstd && gamma && beta && acc_bn && dx, "outconv_bwd_bn: null pointer");
-  return launch_outconv_bwd(z, cin, w, dlogits_nchw, nc, batch, H, W, dx, acc_w, acc_b, mean_invstd, gamma, beta, acc_bn, stream);
+  return launch_outconv_bwd(z, cin, w, dlogits_nchw, nc, batch, H, W, dx, acc_w, acc_b, mean_invstd, gamma, beta, acc_bn, false,
+                            nullptr, 0, stream);
 }
 
 extern "C" int sfh_maxpool3x3s2_bwd(const float* x, const float* dy, float* dx, int batch, int H, int W, int C,
@@ -2000,33 +1967,35 @@ extern "C" int sfh_maxpool3x3s2_bwd(const float* x, const float* dy, float* dx, 
   return sfh_check_launch("maxpool3x3s2_bwd_kernel");
 }
 
+static int avgpool_linear_bwd_impl(const float* x, const float* w, const float* dout, int batch, int H, int W, int C, int nout,
+                                   float* dx, double* acc_w, double* acc_b, bool det, void* workspace, long long workspace_bytes,
+                                   void* stream) {
+  const char* who = det ? "avgpool_linear_bwd_det" : "avgpool_linear_bwd";
+  const DetPlan p = det_avgpool_plan(batch, C, nout);
+  SFH_REQUIRE(x && w && dout && dx && acc_w && acc_b && p.ok && H > 0 && W > 0, "%s: bad argument", who);
+  if (det) SFH_REQUIRE_WS(who, workspace, workspace_bytes, p);
+  double* ws = (double*)workspace;   // the store pass finds both parts of its slab from the workspace's base
+  SFH_LAUNCH_DET(avgpool_linear_bwd_kernel, det, dim3((unsigned)p.slabs), dim3(256), stream, x, w, dout, H * W, C, nout, dx,
+                 det ? ws : acc_w, det ? ws : acc_b);
+  if (int rc = sfh_check_launch(det ? "avgpool_linear_bwd_kernel (deterministic)" : "avgpool_linear_bwd_kernel")) return rc;
+  if (!det) return SFH_OK;
+  if (int rc = sfh_det_reduce_f64(ws, p.slabs, p.elems, (long)nout * C, nout * C, acc_w, nout * C, stream)) return rc;
+  return sfh_det_reduce_f64(ws + (long)nout * C, p.slabs, p.elems, nout, nout, acc_b, nout, stream);
+}
+
 extern "C" int sfh_avgpool_linear_bwd(const float* x, const float* w, const float* dout, int batch, int H, int W,
                                       int C, int nout, float* dx, double* acc_w, double* acc_b, void* stream) {
-  SFH_REQUIRE(x && w && dout && dx && acc_w && acc_b && batch > 0 && H > 0 && W > 0 && C > 0 && nout > 0 && nout <= 256,
-              "avgpool_linear_bwd: bad argument");
-  hipLaunchKernelGGL(avgpool_linear_bwd_kernel<false>, dim3((unsigned)batch), dim3(256), 0, (hipStream_t)stream, x, w, dout,
-                     H * W, C, nout, dx, acc_w, acc_b);
-  return sfh_check_launch("avgpool_linear_bwd_kernel");
+  return avgpool_linear_bwd_impl(x, w, dout, batch, H, W, C, nout, dx, acc_w, acc_b, false, nullptr, 0, stream);
 }
 
 extern "C" int64_t sfh_avgpool_linear_bwd_det_bytes(int batch, int C, int nout) {
-  if (batch <= 0 || C <= 0 || nout <= 0 || nout > 256) return -1;
-  return det_bytes(batch, det_avgpool_elems(nout, C), sizeof(double));
+  return det_bytes(det_avgpool_plan(batch, C, nout));
 }
 
 extern "C" int sfh_avgpool_linear_bwd_det(const float* x, const float* w, const float* dout, int batch, int H, int W, int C,
                                           int nout, float* dx, double* acc_w, double* acc_b, void* workspace,
                                           long long workspace_bytes, void* stream) {
-  SFH_REQUIRE(x && w && dout && dx && acc_w && acc_b && batch > 0 && H > 0 && W > 0 && C > 0 && nout > 0 && nout <= 256,
-              "avgpool_linear_bwd_det: bad argument");
-  SFH_REQUIRE_WS("avgpool_linear_bwd_det", workspace, workspace_bytes, sfh_avgpool_linear_bwd_det_bytes(batch, C, nout));
-  double* ws = (double*)workspace;
-  const long elems = det_avgpool_elems(nout, C);
-  hipLaunchKernelGGL(avgpool_linear_bwd_kernel<true>, dim3((unsigned)batch), dim3(256), 0, (hipStream_t)stream, x, w, dout,
-                     H * W, C, nout, dx, ws, ws);
-  if (int rc = sfh_check_launch("avgpool_linear_bwd_kernel (deterministic)")) return rc;
-  if (int rc = sfh_det_reduce_f64(ws, batch, elems, (long)nout * C, nout * C, acc_w, nout * C, stream)) return rc;
-  return sfh_det_reduce_f64(ws + (long)nout * C, batch, elems, nout, nout, acc_b, nout, stream);
+  return avgpool_linear_bwd_impl(x, w, dout, batch, H, W, C, nout, dx, acc_w, acc_b, true, workspace, workspace_bytes, stream);
 }
 
 extern "C" int sfh_stem_bwd_data(const float* dz, const float* w, int cin, int c_off, int nc, int batch, int H,
@@ -2054,8 +2023,8 @@ static int train_losses_impl(const float* logits_nchw, const int64_t* gt_mask, c
                              float lambda_cons, int focal_flags, float* dlogits_nchw, float* dwarp, double* loss3, bool det,
                              void* workspace, long long workspace_bytes, void* stream) {
   const char* who = det ? "train_losses_det" : "train_losses";
-  SFH_REQUIRE(logits_nchw && gt_mask && weight && dlogits_nchw && loss3 && batch > 0 && H > 0 && W > 0,
-              "%s: bad argument", who);
+  const DetPlan p = det_losses_plan(batch, H, W);
+  SFH_REQUIRE(logits_nchw && gt_mask && weight && dlogits_nchw && loss3 && p.ok, "%s: bad argument", who);
   SFH_REQUIRE(nc >= 2 && nc <= 8, "%s: nc=%d unsupported (2..8)", who, nc);
   SFH_REQUIRE(warp_mask || (lambda_rec == 0.f && lambda_cons == 0.f), "%s: rec/consistency need the warp mask", who);
   LossArgs a;
@@ -2064,9 +2033,9 @@ static int train_losses_impl(const float* logits_nchw, const int64_t* gt_mask, c
   a.l_seg = lambda_seg; a.l_rec = lambda_rec; a.l_cons = lambda_cons; a.rec_mse = rec_mse;
   a.seg_focal = focal_flags & 1; a.cons_focal = (focal_flags >> 1) & 1;
   a.dlogits = dlogits_nchw; a.dwarp = dwarp; a.loss = loss3;
-  const long nb = det_losses_blocks(a.npix);
+  const long nb = p.slabs;   // blocks
   if (det) {
-    SFH_REQUIRE_WS("train_losses_det", workspace, workspace_bytes, det_bytes(nb, 3, sizeof(double)));
+    SFH_REQUIRE_WS(who, workspace, workspace_bytes, p);
     a.loss = (double*)workspace;
   }
 #define SFH_TL(N)                                                                                                  \
@@ -2091,8 +2060,7 @@ extern "C" int sfh_train_losses(const float* logits_nchw, const int64_t* gt_mask
 }
 
 extern "C" int64_t sfh_train_losses_det_bytes(int batch, int H, int W) {
-  if (batch <= 0 || H <= 0 || W <= 0) return -1;
-  return det_bytes(det_losses_blocks((long)batch * H * W), 3, sizeof(double));
+  return det_bytes(det_losses_plan(batch, H, W));
 }
 
 extern "C" int sfh_train_losses_det(const float* logits_nchw, const int64_t* gt_mask, const float* weight,
@@ -2103,32 +2071,32 @@ extern "C" int sfh_train_losses_det(const float* logits_nchw, const int64_t* gt_
                            lambda_cons, focal_flags, dlogits_nchw, dwarp, loss3, true, workspace, workspace_bytes, stream);
 }
 
+static int reproj_loss_impl(const float* poi, const float* gt_poi, const float* nonzeros, const float* num_nonzero, int batch,
+                            int npts, float lambda, float* dpoi, double* loss, bool det, void* ws, long long ws_bytes,
+                            void* stream) {
+  const char* who = det ? "reproj_loss_det" : "reproj_loss";
+  const DetPlan p = det_reproj_plan(batch);
+  SFH_REQUIRE(poi && gt_poi && nonzeros && num_nonzero && dpoi && loss && p.ok && npts > 0, "%s: bad argument", who);
+  if (det) SFH_REQUIRE_WS(who, ws, ws_bytes, p);
+  SFH_LAUNCH_DET(reproj_loss_kernel, det, dim3((unsigned)p.slabs), dim3(64), stream, poi, gt_poi, nonzeros, num_nonzero, batch,
+                 npts, lambda, dpoi, det ? (double*)ws : loss);
+  if (int rc = sfh_check_launch(det ? "reproj_loss_kernel (deterministic)" : "reproj_loss_kernel")) return rc;
+  return det ? sfh_det_reduce_f64((const double*)ws, p.slabs, 1, 1, 1, loss, 1, stream) : SFH_OK;
+}
+
 extern "C" int sfh_reproj_loss(const float* poi, const float* gt_poi, const float* nonzeros,
                                const float* num_nonzero, int batch, int npts, float lambda, float* dpoi,
                                double* loss, void* stream) {
-  SFH_REQUIRE(poi && gt_poi && nonzeros && num_nonzero && dpoi && loss && batch > 0 && npts > 0,
-              "reproj_loss: bad argument");
-  hipLaunchKernelGGL(reproj_loss_kernel<false>, dim3((unsigned)det_reproj_blocks(batch)), dim3(64), 0, (hipStream_t)stream, poi,
-                     gt_poi, nonzeros, num_nonzero, batch, npts, lambda, dpoi, loss);
-  return sfh_check_launch("reproj_loss_kernel");
+  return reproj_loss_impl(poi, gt_poi, nonzeros, num_nonzero, batch, npts, lambda, dpoi, loss, false, nullptr, 0, stream);
 }
 
-extern "C" int64_t sfh_reproj_loss_det_bytes(int batch) {
-  if (batch <= 0) return -1;
-  return det_bytes(det_reproj_blocks(batch), 1, sizeof(double));
-}
+extern "C" int64_t sfh_reproj_loss_det_bytes(int batch) { return det_bytes(det_reproj_plan(batch)); }
 
 extern "C" int sfh_reproj_loss_det(const float* poi, const float* gt_poi, const float* nonzeros, const float* num_nonzero,
                                    int batch, int npts, float lambda, float* dpoi, double* loss, void* workspace,
                                    long long workspace_bytes, void* stream) {
-  SFH_REQUIRE(poi && gt_poi && nonzeros && num_nonzero && dpoi && loss && batch > 0 && npts > 0,
-              "reproj_loss_det: bad argument");
-  SFH_REQUIRE_WS("reproj_loss_det", workspace, workspace_bytes, sfh_reproj_loss_det_bytes(batch));
-  const long nb = det_reproj_blocks(batch);
-  hipLaunchKernelGGL(reproj_loss_kernel<true>, dim3((unsigned)nb), dim3(64), 0, (hipStream_t)stream, poi, gt_poi, nonzeros,
-                     num_nonzero, batch, npts, lambda, dpoi, (double*)workspace);
-  if (int rc = sfh_check_launch("reproj_loss_kernel (deterministic)")) return rc;
-  return sfh_det_reduce_f64((const double*)workspace, nb, 1, 1, 1, loss, 1, stream);
+  return reproj_loss_impl(poi, gt_poi, nonzeros, num_nonzero, batch, npts, lambda, dpoi, loss, true, workspace, workspace_bytes,
+                          stream);
 }
 
 extern "C" int sfh_multi_copy(const void* tensor_table, const void* chunk_table, int nchunks, float scale, void* stream) {
@@ -2165,24 +2133,19 @@ static int uv_loss_impl(const float* uv, const float* gt_uv, const float* weight
                         float lambda, int mse, float* duv, double* loss, bool det, void* workspace, long long workspace_bytes,
                         void* stream) {
   const char* who = det ? "uv_loss_det" : "uv_loss";
-  SFH_REQUIRE(uv && gt_uv && weight && duv && loss && batch > 0 && C > 0 && H > 0 && W > 0, "%s: bad argument", who);
+  const DetPlan p = det_uv_plan(batch, C, H, W);
+  SFH_REQUIRE(uv && gt_uv && weight && duv && loss && p.ok, "%s: bad argument", who);
   SFH_REQUIRE(nweights == 1 || nweights == W,
               "%s: %d per-sample weights cannot be broadcast along the last axis of the (B, W) = (%d, %d) loss map "
               "(models/losses.py:38-39 multiplies torch.mean(loss, dim=(1, 2)) of a 4-D map by the weights)", who, nweights, batch, W);
   const long total = (long)batch * C * H * W;
-  const long nb = det_uv_blocks(total);
   const int wcol = nweights == W && nweights != 1 ? 1 : 0;
   const float inv = 1.0f / ((float)batch * (float)C * (float)H * (float)W);
-  if (!det) {
-    hipLaunchKernelGGL(uv_loss_kernel<false>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, uv, gt_uv, weight, wcol, C,
-                       H, W, total, lambda, mse, duv, loss, inv);
-    return sfh_check_launch("uv_loss_kernel");
-  }
-  SFH_REQUIRE_WS("uv_loss_det", workspace, workspace_bytes, det_bytes(nb, 1, sizeof(double)));
-  hipLaunchKernelGGL(uv_loss_kernel<true>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, uv, gt_uv, weight, wcol, C, H,
-                     W, total, lambda, mse, duv, (double*)workspace, inv);
-  if (int rc = sfh_check_launch("uv_loss_kernel (deterministic)")) return rc;
-  return sfh_det_reduce_f64((const double*)workspace, nb, 1, 1, 1, loss, 1, stream);
+  if (det) SFH_REQUIRE_WS(who, workspace, workspace_bytes, p);
+  SFH_LAUNCH_DET(uv_loss_kernel, det, dim3((unsigned)p.slabs), dim3(256), stream, uv, gt_uv, weight, wcol, C, H, W, total, lambda,
+                 mse, duv, det ? (double*)workspace : loss, inv);
+  if (int rc = sfh_check_launch(det ? "uv_loss_kernel (deterministic)" : "uv_loss_kernel")) return rc;
+  return det ? sfh_det_reduce_f64((const double*)workspace, p.slabs, 1, 1, 1, loss, 1, stream) : SFH_OK;
 }
 
 extern "C" int sfh_uv_loss(const float* uv, const float* gt_uv, const float* weight, int nweights, int batch, int C, int H,
@@ -2191,8 +2154,7 @@ extern "C" int sfh_uv_loss(const float* uv, const float* gt_uv, const float* wei
 }
 
 extern "C" int64_t sfh_uv_loss_det_bytes(int batch, int C, int H, int W) {
-  if (batch <= 0 || C <= 0 || H <= 0 || W <= 0) return -1;
-  return det_bytes(det_uv_blocks((long)batch * C * H * W), 1, sizeof(double));
+  return det_bytes(det_uv_plan(batch, C, H, W));
 }
 
 extern "C" int sfh_uv_loss_det(const float* uv, const float* gt_uv, const float* weight, int nweights, int batch, int C, int H,

@@ -692,38 +692,33 @@ extern "C" int sfh_poi_project_fwd(const float* theta, const float* poi, int bat
   return sfh_check_launch("poi_kernel");
 }
 
+static int warp_bwd_theta_impl(const float* theta, const float* tmpl, int64_t tmpl_bstride, int ht, int wt, int batch, int h,
+                               int w, const float* dout, double* acc, bool det, void* ws, long long ws_bytes, void* stream) {
+  const char* who = det ? "homography_warp_bwd_det" : "homography_warp_bwd";
+  const DetPlan p = det_warp_plan(batch, h, w);
+  SFH_REQUIRE(theta && tmpl && dout && acc, "%s: null pointer", who);
+  SFH_REQUIRE(p.ok && ht > 0 && wt > 0, "%s: bad geometry", who);
+  SFH_REQUIRE(tmpl_bstride == 0 || tmpl_bstride >= (int64_t)ht * wt, "%s: bad template stride", who);
+  if (det) SFH_REQUIRE_WS(who, ws, ws_bytes, p);
+  const dim3 grid((unsigned)det_warp_gx(w), (unsigned)det_warp_gy(h), (unsigned)batch);
+  SFH_LAUNCH_DET(warp_bwd_theta_kernel, det, grid, dim3(256), stream, theta, tmpl, (long)tmpl_bstride, ht, wt, h, w, dout,
+                 det ? (double*)ws : acc);
+  if (int rc = sfh_check_launch(det ? "warp_bwd_theta_kernel (deterministic)" : "warp_bwd_theta_kernel")) return rc;
+  return det ? sfh_det_reduce_f64((const double*)ws, p.slabs, p.elems, p.elems, 9 * batch, acc, 9 * batch, stream) : SFH_OK;
+}
+
 extern "C" int sfh_homography_warp_bwd_theta(const float* theta, const float* tmpl, int64_t tmpl_bstride,
                                              int ht, int wt, int batch, int h, int w, const float* dout,
                                              double* acc, void* stream) {
-  SFH_REQUIRE(theta && tmpl && dout && acc, "homography_warp_bwd: null pointer");
-  SFH_REQUIRE(batch > 0 && batch <= 65535 && h > 1 && w > 1 && ht > 0 && wt > 0, "homography_warp_bwd: bad geometry");
-  SFH_REQUIRE(tmpl_bstride == 0 || tmpl_bstride >= (int64_t)ht * wt, "homography_warp_bwd: bad template stride");
-  const dim3 grid((unsigned)det_warp_gx(w), (unsigned)det_warp_gy(h), (unsigned)batch);
-  hipLaunchKernelGGL(warp_bwd_theta_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, theta, tmpl,
-                     (long)tmpl_bstride, ht, wt, h, w, dout, acc);
-  return sfh_check_launch("warp_bwd_theta_kernel");
+  return warp_bwd_theta_impl(theta, tmpl, tmpl_bstride, ht, wt, batch, h, w, dout, acc, false, nullptr, 0, stream);
 }
 
-extern "C" int64_t sfh_homography_warp_bwd_theta_det_bytes(int batch, int h, int w) {
-  if (batch <= 0 || batch > 65535 || h <= 1 || w <= 1) return -1;
-  return det_bytes((long)det_warp_gx(w) * det_warp_gy(h), 9L * batch, sizeof(double));
-}
+extern "C" int64_t sfh_homography_warp_bwd_theta_det_bytes(int batch, int h, int w) { return det_bytes(det_warp_plan(batch, h, w)); }
 
 extern "C" int sfh_homography_warp_bwd_theta_det(const float* theta, const float* tmpl, int64_t tmpl_bstride, int ht, int wt,
                                                  int batch, int h, int w, const float* dout, double* acc, void* workspace,
                                                  long long workspace_bytes, void* stream) {
-  SFH_REQUIRE(theta && tmpl && dout && acc, "homography_warp_bwd_det: null pointer");
-  SFH_REQUIRE(batch > 0 && batch <= 65535 && h > 1 && w > 1 && ht > 0 && wt > 0, "homography_warp_bwd_det: bad geometry");
-  SFH_REQUIRE(tmpl_bstride == 0 || tmpl_bstride >= (int64_t)ht * wt, "homography_warp_bwd_det: bad template stride");
-  const long long need = sfh_homography_warp_bwd_theta_det_bytes(batch, h, w);
-  SFH_REQUIRE(workspace != nullptr && workspace_bytes >= need, "homography_warp_bwd_det: workspace of %lld bytes, %lld needed",
-              workspace ? workspace_bytes : 0LL, need);
-  const dim3 grid((unsigned)det_warp_gx(w), (unsigned)det_warp_gy(h), (unsigned)batch);
-  hipLaunchKernelGGL(warp_bwd_theta_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, theta, tmpl, (long)tmpl_bstride, ht, wt,
-                     h, w, dout, (double*)workspace);
-  if (int rc = sfh_check_launch("warp_bwd_theta_kernel (deterministic)")) return rc;
-  return sfh_det_reduce_f64((const double*)workspace, (long)grid.x * grid.y, 9L * batch, 9L * batch, 9 * batch, acc, 9 * batch,
-                            stream);
+  return warp_bwd_theta_impl(theta, tmpl, tmpl_bstride, ht, wt, batch, h, w, dout, acc, true, workspace, workspace_bytes, stream);
 }
 
 extern "C" int sfh_poi_project_bwd_theta(const float* theta, const float* poi, int batch, int npts,

@@ -220,20 +220,17 @@ int launch(WgS3Args a, const DetWgradS3Plan& p, float* ws, hipStream_t stream) {
   a.ntiles = p.ntiles;
   a.tps = p.tps;
   a.nsplit = p.nsplit;
-  const long nblocks = (long)sfh_cdiv(a.nsplit, 8) * 8 * p.mn;
-  SFH_REQUIRE(nblocks < (1L << 31), "conv_wgrad_s3: grid too large");
+  float* raw = a.raw;
   if (!ws) {
     sfh_allow_big_lds(reinterpret_cast<const void*>(&wgrad_s3_kernel<TR, TW, NP, KS>));
-    hipLaunchKernelGGL((wgrad_s3_kernel<TR, TW, NP, KS>), dim3((unsigned)nblocks), dim3(256), LDS_BYTES, stream, a);
-    return sfh_check_launch("wgrad_s3_kernel");
+    hipLaunchKernelGGL((wgrad_s3_kernel<TR, TW, NP, KS>), dim3((unsigned)p.nblocks), dim3(256), LDS_BYTES, stream, a);
+  } else {
+    a.raw = ws;
+    sfh_allow_big_lds(reinterpret_cast<const void*>(&wgrad_s3_kernel<TR, TW, NP, KS, true>));
+    hipLaunchKernelGGL((wgrad_s3_kernel<TR, TW, NP, KS, true>), dim3((unsigned)p.nblocks), dim3(256), LDS_BYTES, stream, a);
   }
-  float* raw = a.raw;
-  const int raw_n = a.raw_n, n_off = a.n_off;
-  a.raw = ws;
-  sfh_allow_big_lds(reinterpret_cast<const void*>(&wgrad_s3_kernel<TR, TW, NP, KS, true>));
-  hipLaunchKernelGGL((wgrad_s3_kernel<TR, TW, NP, KS, true>), dim3((unsigned)nblocks), dim3(256), LDS_BYTES, stream, a);
-  if (int rc = sfh_check_launch("wgrad_s3_kernel (deterministic)")) return rc;
-  return sfh_det_reduce_f32(ws, p.nsplit, p.elems, p.elems, a.N, raw + n_off, raw_n, stream);
+  if (int rc = sfh_check_launch(ws ? "wgrad_s3_kernel (deterministic)" : "wgrad_s3_kernel")) return rc;
+  return ws ? sfh_det_reduce_f32(ws, p.slabs, p.elems, p.elems, a.N, raw + a.n_off, a.raw_n, stream) : SFH_OK;
 }
 
 }  // namespace
@@ -242,17 +239,25 @@ static int conv_wgrad_s3_impl(const void* dz_s3, int M, const void* x_s3, int x_
                               int pad_left, int batch, int H, int W, int ksize, float* raw, int raw_n, int n_off, int fmt,
                               bool det, void* workspace, long long workspace_bytes, void* stream) {
   const char* who = det ? "conv_wgrad_s3_det" : "conv_wgrad_s3";
+  // 96-pixel tiles (3x32 / 6x16 / 12x8: three k-steps per LDS fill, so that the MFMAs of one workgroup outlast
+  // the DMA wait of its co-resident partner) were measured no faster: 25.7 vs 24.0 ms per step for all launches.
+  // tile shape with the least padded area (ties: the widest).  Weighting the area by the rate each shape
+  // reaches on full tiles (2x32 250, 4x16 190, 8x8 103 TFLOP/s-equivalent) and so moving the 45x80 and 22x40
+  // layers to 2x32 tiles was measured slower overall (31.0 vs 27.8 ms per step for all launches).
+  // the split plan covers what the size query sees (M, N, batch, H, W, ksize); the source's own size and place it does not
+  const DetWgradS3Plan p = det_wgrad_s3_plan(M, N, batch, H, W, ksize);
   SFH_REQUIRE(fmt == SFH_FMT_S3 || fmt == SFH_FMT_H2, "%s: fmt=%d (S3 or H2)", who, fmt);
-  SFH_REQUIRE(ksize == 3 || ksize == 1, "%s: ksize=%d (3 or 1)", who, ksize);
+  SFH_REQUIRE(p.why != DET_BAD_KSIZE, "%s: ksize=%d (3 or 1)", who, ksize);
   const unsigned long long bpe = fmt == SFH_FMT_H2 ? 4ULL : 6ULL;
   SFH_REQUIRE(dz_s3 && x_s3 && raw, "%s: null pointer", who);
-  SFH_REQUIRE(batch > 0 && H > 0 && W > 0 && xh > 0 && xw > 0, "%s: bad geometry", who);
-  SFH_REQUIRE(M > 0 && M % 64 == 0, "%s: M=%d must be a multiple of 64", who, M);
-  SFH_REQUIRE(N > 0 && N % 32 == 0 && x_channels % 32 == 0 && x_channels >= N, "%s: N=%d of %d channels", who, N, x_channels);
+  SFH_REQUIRE(p.why != DET_BAD_FRAME && xh > 0 && xw > 0, "%s: bad geometry", who);
+  SFH_REQUIRE(p.why != DET_BAD_M, "%s: M=%d must be a multiple of 64", who, M);
+  SFH_REQUIRE(p.why != DET_BAD_N && x_channels % 32 == 0 && x_channels >= N, "%s: N=%d of %d channels", who, N, x_channels);
   SFH_REQUIRE(n_off >= 0 && n_off + N <= raw_n, "%s: n_off=%d N=%d raw_n=%d", who, n_off, N, raw_n);
   SFH_REQUIRE(pad_top >= 0 && pad_left >= 0 && pad_top + xh <= H && pad_left + xw <= W, "%s: source does not fit the frame", who);
   const unsigned long long bdz = bpe * batch * H * W * M, bx = bpe * batch * xh * xw * x_channels;
   SFH_REQUIRE(bdz < kOOB && bx < kOOB, "%s: a tensor of %llu bytes exceeds the 4 GiB descriptor range", who, bdz > bx ? bdz : bx);
+  SFH_REQUIRE(p.ok, "%s: grid too large", who);
   WgS3Args a;
   a.dz = dz_s3; a.M = M; a.x = x_s3; a.xc = x_channels; a.xh = xh; a.xw = xw; a.N = N;
   a.pad_top = pad_top; a.pad_left = pad_left; a.batch = batch; a.H = H; a.W = W;
@@ -260,20 +265,8 @@ static int conv_wgrad_s3_impl(const void* dz_s3, int M, const void* x_s3, int x_
   a.mblk = M / 64; a.nblk = N / 32;
   a.bytes_dz = (unsigned)bdz; a.bytes_x = (unsigned)bx;
   a.ntx = a.nty = a.ntiles = a.nsplit = a.tps = 0;
-  // 96-pixel tiles (3x32 / 6x16 / 12x8: three k-steps per LDS fill, so that the MFMAs of one workgroup outlast
-  // the DMA wait of its co-resident partner) were measured no faster: 25.7 vs 24.0 ms per step for all launches.
-  // tile shape with the least padded area (ties: the widest).  Weighting the area by the rate each shape
-  // reaches on full tiles (2x32 250, 4x16 190, 8x8 103 TFLOP/s-equivalent) and so moving the 45x80 and 22x40
-  // layers to 2x32 tiles was measured slower overall (31.0 vs 27.8 ms per step for all launches).
-  const DetWgradS3Plan p = det_wgrad_s3_plan(M, N, ksize, batch, H, W);
-  float* ws = nullptr;
-  if (det) {
-    // (NULL or smaller than sfh_conv_wgrad_s3_det_bytes: refused, nothing launched)
-    SFH_REQUIRE(workspace != nullptr && workspace_bytes >= det_bytes(p.nsplit, p.elems, sizeof(float)),
-                "conv_wgrad_s3_det: workspace of %lld bytes, %lld needed", workspace ? workspace_bytes : 0LL,
-                det_bytes(p.nsplit, p.elems, sizeof(float)));
-    ws = (float*)workspace;
-  }
+  if (det) SFH_REQUIRE_WS(who, workspace, workspace_bytes, p);
+  float* ws = det ? (float*)workspace : nullptr;   // launch(): nullptr is the default mode
   hipStream_t st = (hipStream_t)stream;
 #define SFH_WG_PICK(NP_, KS_)                                              \
   do {                                                                     \
@@ -298,9 +291,7 @@ extern "C" int sfh_conv_wgrad_s3(const void* dz_s3, int M, const void* x_s3, int
 }
 
 extern "C" int64_t sfh_conv_wgrad_s3_det_bytes(int M, int N, int batch, int H, int W, int ksize) {
-  if (batch <= 0 || H <= 0 || W <= 0 || M <= 0 || M % 64 != 0 || N <= 0 || N % 32 != 0 || !(ksize == 1 || ksize == 3)) return -1;
-  const DetWgradS3Plan p = det_wgrad_s3_plan(M, N, ksize, batch, H, W);
-  return det_bytes(p.nsplit, p.elems, sizeof(float));
+  return det_bytes(det_wgrad_s3_plan(M, N, batch, H, W, ksize));
 }
 
 extern "C" int sfh_conv_wgrad_s3_det(const void* dz_s3, int M, const void* x_s3, int x_channels, int xh, int xw, int N,

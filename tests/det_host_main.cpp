@@ -1,6 +1,8 @@
 // det_host_main.cpp - the partition arithmetic of the deterministic training mode (csrc/det_core.h) walked on the host, for
 // every kernel family, with the kernels' own loops and lane maps RESTATED beside it (the kernels do not call the share -> slab
-// maps of det_core.h; they and this program share the plans, counts, bytes, slab and element offsets and the sum pass).  Built and run by tests/test_det_host.py
+// maps of det_core.h).  Slabs, elements per slab and bytes of every line come from the family's plan (det_*_plan, det_bytes):
+// the function the launcher and the size query call; the slab and element offsets and the sum pass are the kernels' own too.
+// Built and run by tests/test_det_host.py
 // with -fsanitize=address,undefined and -ffp-contract=off; it links nothing of the library.
 //
 //   det_host_main walk CASES      CASES: one geometry per line,
@@ -49,6 +51,14 @@ struct Ws {
   }
 };
 
+// what every walk starts from: the family's plan (the function the launcher and the size query call), and what it prints
+static bool admitted(const DetPlan& p, const char* who) {
+  CHECK(p.ok && p.why == DET_OK && p.slabs >= 1 && p.elems >= 1, "%s: a case geometry is refused (rule %d)", who, (int)p.why);
+  if (!p.ok) printf("0 0 -1\n");
+  return p.ok;
+}
+static void print_plan(const DetPlan& p) { printf("%ld %ld %lld\n", p.slabs, p.elems, det_bytes(p)); }
+
 static void once(const std::vector<int>& seen, const char* who) {
   long bad = 0;
   for (int c : seen) bad += c != 1;
@@ -56,9 +66,10 @@ static void once(const std::vector<int>& seen, const char* who) {
 }
 
 static void walk_wgrad(int M, int N, int ks, int x_cs, int xh, int xw, int pt, int pl, int B, int H, int W) {
-  const bool c4 = det_wgrad_is_c4(ks, N, x_cs, xh, xw, pt, pl, H, W);
-  const DetWgradPlan p = det_wgrad_plan(M, N, ks, c4, B, H, W);
-  CHECK(p.ntiles == B * det_cdiv(H, det_tile_h(p.shape)) * det_cdiv(W, det_tile_w(p.shape)) && p.nsplit >= 1 && p.nsplit <= p.ntiles,
+  const DetWgradPlan p = det_wgrad_plan(M, x_cs, xh, xw, N, pt, pl, B, H, W, ks);
+  if (!admitted(p, "wgrad")) return;
+  const bool c4 = p.c4;
+  CHECK(p.slabs == p.nsplit && p.ntiles == B * det_cdiv(H, det_tile_h(p.shape)) * det_cdiv(W, det_tile_w(p.shape)) && p.nsplit >= 1 && p.nsplit <= p.ntiles,
         "wgrad plan: %d tiles, %d splits", p.ntiles, p.nsplit);
   std::vector<int> seen((size_t)p.ntiles, 0);
   for (int s = 0; s < p.nsplit; ++s)
@@ -67,7 +78,7 @@ static void walk_wgrad(int M, int N, int ks, int x_cs, int xh, int xw, int pt, i
       ++seen[(size_t)tile];
     }
   once(seen, "wgrad tiles");
-  Ws ws(p.nsplit, p.elems);
+  Ws ws(p.slabs, p.elems);
   const int nsub = det_wgrad_nsub(ks, N);
   for (int split = 0; split < p.nsplit; ++split)
     for (int mni = 0; mni < p.mn; ++mni)
@@ -97,12 +108,13 @@ static void walk_wgrad(int M, int N, int ks, int x_cs, int xh, int xw, int pt, i
           }
       }
   ws.finish("wgrad");
-  printf("%d %ld %lld\n", p.nsplit, p.elems, det_bytes(p.nsplit, p.elems, 4));
+  print_plan(p);
 }
 
 static void walk_wgrad_s3(int M, int N, int ks, int B, int H, int W) {
-  const DetWgradS3Plan p = det_wgrad_s3_plan(M, N, ks, B, H, W);
-  CHECK(p.nsplit >= 1 && p.tps >= 1 && (long)p.nsplit * p.tps >= p.ntiles && (long)(p.nsplit - 1) * p.tps < p.ntiles,
+  const DetWgradS3Plan p = det_wgrad_s3_plan(M, N, B, H, W, ks);
+  if (!admitted(p, "wgrad_s3")) return;
+  CHECK(p.slabs == p.nsplit && p.nsplit >= 1 && p.tps >= 1 && (long)p.nsplit * p.tps >= p.ntiles && (long)(p.nsplit - 1) * p.tps < p.ntiles,
         "wgrad_s3 plan: %d tiles, %d splits of %d", p.ntiles, p.nsplit, p.tps);
   std::vector<int> seen((size_t)p.ntiles, 0);
   for (int s = 0; s < p.nsplit; ++s) {
@@ -113,7 +125,7 @@ static void walk_wgrad_s3(int M, int N, int ks, int B, int H, int W) {
     }
   }
   once(seen, "wgrad_s3 tiles");
-  Ws ws(p.nsplit, p.elems);
+  Ws ws(p.slabs, p.elems);
   const int nblk = N / 32;
   for (int split = 0; split < p.nsplit; ++split)
     for (int mni = 0; mni < p.mn; ++mni)
@@ -126,14 +138,16 @@ static void walk_wgrad_s3(int M, int N, int ks, int B, int H, int W) {
             for (int r = 0; r < 4; ++r) ws.store(split, det_wgrad_elem(m0 + 16 * mb + r, t9, n, p.kk, N));
       }
   ws.finish("wgrad_s3");
-  printf("%d %ld %lld\n", p.nsplit, p.elems, det_bytes(p.nsplit, p.elems, 4));
+  print_plan(p);
 }
 
 static void walk_grouped(int B, int H, int W, int G, int cg, int s) {
   const int C = G * cg, KC = gc_chunk(cg), NCH = cg / KC, NU = 32 * (KC / 4);
-  const long tiles = det_grouped_tiles(B, H, W, s), E = det_grouped_elems(G, cg);
+  const DetPlan p = det_grouped_plan(B, H, W, G, cg, s);
+  if (!admitted(p, "grouped")) return;
+  const long tiles = p.slabs;
   CHECK(tiles == (long)B * det_cdiv(gc_out_size(H, s), gc_tile_h(s)) * det_cdiv(gc_out_size(W, s), GC_TW), "grouped tiles");
-  Ws ws(tiles, E);
+  Ws ws(tiles, p.elems);
   for (long tile = 0; tile < tiles; ++tile)                       // blockIdx.x = the tile = the slab
     for (int by = 0; by < det_cdiv(C, 32) * NCH; ++by) {
       const int ob = by / NCH, chunk = by % NCH;
@@ -143,7 +157,7 @@ static void walk_grouped(int B, int H, int W, int G, int cg, int s) {
       }
     }
   ws.finish("grouped");
-  printf("%ld %ld %lld\n", tiles, E, det_bytes(tiles, E, 4));
+  print_plan(p);
 }
 
 // red_tail of a block: NV / 4 rows of the quad's four channels, for every channel chunk
@@ -156,7 +170,9 @@ static void red_tail_store(Ws& ws, long block, int C, int rows, long row_stride)
 }
 
 static void walk_red(long npix, int C, bool colsum) {
-  const long nb = det_red_blocks(npix);
+  const DetPlan plan = det_red_plan(npix, C, colsum ? 1 : 2);
+  if (!admitted(plan, colsum ? "colsum" : "red")) return;
+  const long nb = plan.slabs;
   CHECK(nb >= 1 && nb <= DET_RED_BLOCKS, "red blocks %ld", nb);
   std::vector<int> chunked((size_t)npix, 0), strided((size_t)npix, 0);
   const long chunk = det_red_chunk(npix, nb);
@@ -175,8 +191,7 @@ static void walk_red(long npix, int C, bool colsum) {
   }
   once(chunked, "red pixels (chunked)");
   if (C <= 1024) once(strided, "red pixels (strided)");   // (wider tensors: the lane count changes per channel chunk)
-  const long E = colsum ? C : 2L * C;
-  Ws ws(nb, E);
+  Ws ws(nb, plan.elems);
   for (long b = 0; b < nb; ++b) {
     if (!colsum) { red_tail_store(ws, b, C, 2, C); continue; }
     for (int q0 = 0; q0 < C / 4; q0 += 256) {                                // colsum_kernel: 256 quads per pass, one row
@@ -186,16 +201,18 @@ static void walk_red(long npix, int C, bool colsum) {
     }
   }
   ws.finish(colsum ? "colsum" : "red");
-  printf("%ld %ld %lld\n", nb, E, det_bytes(nb, E, 8));
+  print_plan(plan);
 }
 
 static void walk_outconv(long npix, int nc, int cin) {
-  const long ppb = det_outconv_ppb(npix), nb = det_outconv_blocks(npix), E = det_outconv_elems(nc, cin);
+  const DetPlan plan = det_outconv_plan(cin, nc, 1, 1, (int)npix);   // the plan reads batch * H * W
+  if (!admitted(plan, "outconv")) return;
+  const long ppb = det_outconv_ppb(npix), nb = plan.slabs;
   std::vector<int> seen((size_t)npix, 0);
   for (long b = 0; b < nb; ++b)
     for (long p = b * ppb; p < (npix < (b + 1) * ppb ? npix : (b + 1) * ppb); ++p) ++seen[(size_t)p];
   once(seen, "outconv pixels");
-  Ws ws(nb, E);
+  Ws ws(nb, plan.elems);
   for (long b = 0; b < nb; ++b)
     for (int k = 0; k < nc; ++k) {
       for (int tid = 0; tid < cin / 4; ++tid)
@@ -203,16 +220,17 @@ static void walk_outconv(long npix, int nc, int cin) {
       ws.store(b, (long)nc * cin + k);
     }
   ws.finish("outconv");
-  printf("%ld %ld %lld\n", nb, E, det_bytes(nb, E, 8));
+  print_plan(plan);
 }
 
-static void walk_flat(const char* who, long slabs, long E, int per_slab_rows, int row) {
-  Ws ws(slabs, E);
-  for (long b = 0; b < slabs; ++b)
+static void walk_flat(const char* who, const DetPlan& p, int per_slab_rows, int row) {
+  if (!admitted(p, who)) return;
+  Ws ws(p.slabs, p.elems);
+  for (long b = 0; b < p.slabs; ++b)
     for (int r = 0; r < per_slab_rows; ++r)
       for (int k = 0; k < row; ++k) ws.store(b, (long)r * row + k);
   ws.finish(who);
-  printf("%ld %ld %lld\n", slabs, E, det_bytes(slabs, E, 8));
+  print_plan(p);
 }
 
 static int walk(const char* path) {
@@ -235,17 +253,17 @@ static int walk(const char* path) {
     else if (k == "red") walk_red(a[0], (int)a[1], false);
     else if (k == "colsum") walk_red(a[0], (int)a[1], true);
     else if (k == "outconv") walk_outconv(a[0], (int)a[1], (int)a[2]);
-    else if (k == "avgpool") walk_flat("avgpool", a[0], det_avgpool_elems((int)a[2], (int)a[1]), 1, (int)det_avgpool_elems((int)a[2], (int)a[1]));
-    else if (k == "losses") walk_flat("losses", det_losses_blocks(a[0]), 3, 1, 3);
-    else if (k == "uv") walk_flat("uv", det_uv_blocks(a[0]), 1, 1, 1);
-    else if (k == "reproj") walk_flat("reproj", det_reproj_blocks((int)a[0]), 1, 1, 1);
+    else if (k == "avgpool") walk_flat("avgpool", det_avgpool_plan((int)a[0], (int)a[1], (int)a[2]), 1, (int)a[2] * (int)a[1] + (int)a[2]);
+    else if (k == "losses") walk_flat("losses", det_losses_plan(1, 1, (int)a[0]), 1, 3);   // the plan reads batch * H * W
+    else if (k == "uv") walk_flat("uv", det_uv_plan(1, 1, 1, (int)a[0]), 1, 1);           // batch * C * H * W
+    else if (k == "reproj") walk_flat("reproj", det_reproj_plan((int)a[0]), 1, 1);
     else if (k == "warp") {
       const int gx = det_warp_gx((int)a[2]), gy = det_warp_gy((int)a[1]);
       std::vector<int> seen((size_t)gx * gy, 0);
       for (int by = 0; by < gy; ++by)
         for (int bx = 0; bx < gx; ++bx) ++seen.at((size_t)det_warp_slab(bx, by, gx));
       once(seen, "warp blocks");
-      walk_flat("warp", (long)gx * gy, 9L * a[0], (int)a[0], 9);
+      walk_flat("warp", det_warp_plan((int)a[0], (int)a[1], (int)a[2]), (int)a[0], 9);
     } else { fprintf(stderr, "unknown family %s\n", fam); fclose(f); return 2; }
   }
   fclose(f);

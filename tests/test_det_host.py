@@ -10,7 +10,8 @@
   are restated in the program (the kernels keep the loops their default instantiation always had), so the "exactly one
   slab" and "written exactly once" walks check the plans against a restatement, not against what the device evaluates: that
   is the GPU suite's part (NaN-filled workspaces, slabs read back);
-- the size queries and the refusals of a missing or short workspace through ctypes, without a device.
+- the size queries and the refusals of a missing or short workspace through ctypes, without a device;
+- for every rule of every family's plan, a geometry that the size query, the plain entry and the sibling refuse alike.
 No sanitizer runs on code loaded into Python."""
 import ctypes
 import os
@@ -161,6 +162,36 @@ def test_every_accumulating_entry_has_its_sibling_and_query():
         assert _lib.SIGNATURES[n + "_det_bytes"][0] is ctypes.c_int64
 
 
+_HOST_BUFFER = (ctypes.c_double * 4096)()
+
+
+def _host_pointer():
+    """host memory for every pointer argument: nothing below may reach a launch"""
+    return ctypes.cast(_HOST_BUFFER, ctypes.c_void_p)
+
+
+def _entry_calls(p):
+    """entry -> function of the geometry the size query sees -> (the query's arguments, the plain entry's arguments).  The
+    defaults are an admitted geometry; what the query does not see (channel strides, raw_n, npts, ...) is always valid."""
+    return {
+        "sfh_bn_stats": lambda npix=10, C=4: ((npix, C), (p, npix, C, p)),
+        "sfh_bn_bwd_reduce": lambda npix=10, C=4: ((npix, C), (p, None, p, p, p, p, 1, npix, C, p)),
+        "sfh_colsum": lambda npix=10, C=4: ((npix, C), (p, npix, C, 1024, p)),
+        "sfh_conv_wgrad": lambda M=64, x_cs=32, xh=5, xw=6, N=32, pad_top=0, pad_left=0, B=1, H=5, W=6, ks=3: (
+            (M, x_cs, xh, xw, N, pad_top, pad_left, B, H, W, ks),
+            (p, 1024, M, p, x_cs, xh, xw, N, pad_top, pad_left, B, H, W, ks, p, 1024, 0)),
+        "sfh_conv_wgrad_s3": lambda M=64, N=32, B=1, H=5, W=6, ks=3: (
+            (M, N, B, H, W, ks), (p, M, p, 1 << 20, H, W, N, 0, 0, B, H, W, ks, p, 1 << 20, 0, 2)),
+        "sfh_conv_grouped_wgrad": lambda B=1, H=5, W=6, G=2, cg=4, stride=1: ((B, H, W, G, cg, stride), (p, p, p, B, H, W, G, cg, stride)),
+        "sfh_outconv_bwd": lambda cin=8, nc=3, B=1, H=5, W=6: ((cin, nc, B, H, W), (p, cin, p, p, nc, B, H, W, p, p, p)),
+        "sfh_avgpool_linear_bwd": lambda B=2, C=8, nout=9: ((B, C, nout), (p, p, p, B, 3, 3, C, nout, p, p, p)),
+        "sfh_train_losses": lambda B=1, H=5, W=6: ((B, H, W), (p, p, p, p, 4, B, H, W, 2.0, 2.0, 0, 1.0, 0, p, p, p)),
+        "sfh_reproj_loss": lambda batch=3: ((batch,), (p, p, p, p, batch, 5, 8.0, p, p)),
+        "sfh_uv_loss": lambda B=1, C=2, H=5, W=6: ((B, C, H, W), (p, p, p, 1, B, C, H, W, 2.0, 1, p, p)),
+        "sfh_homography_warp_bwd_theta": lambda B=2, h=5, w=6: ((B, h, w), (p, p, 0, 9, 16, B, h, w, p, p)),
+    }
+
+
 def test_size_queries_and_refusals_without_a_device():
     """closed forms of the queries; refused geometries answer -1; a NULL or short workspace returns -1 before anything could be
     launched (the pointers below are host memory: a launch would be an error of its own, not -1)"""
@@ -181,22 +212,8 @@ def test_size_queries_and_refusals_without_a_device():
     assert lib.sfh_reproj_loss_det_bytes(65) == 16 and lib.sfh_reproj_loss_det_bytes(0) == -1
     assert lib.sfh_homography_warp_bwd_theta_det_bytes(3, 5, 257) == 2 * 2 * 27 * 8
     assert lib.sfh_homography_warp_bwd_theta_det_bytes(3, 1, 257) == -1
-    buf = (ctypes.c_double * 4096)()
-    p = ctypes.cast(buf, ctypes.c_void_p)
-    calls = {
-        "sfh_bn_stats": ((10, 4), (p, 10, 4, p)),
-        "sfh_bn_bwd_reduce": ((10, 4), (p, None, p, p, p, p, 1, 10, 4, p)),
-        "sfh_colsum": ((10, 4), (p, 10, 4, 4, p)),
-        "sfh_conv_wgrad": ((64, 32, 5, 6, 32, 0, 0, 1, 5, 6, 3), (p, 64, 64, p, 32, 5, 6, 32, 0, 0, 1, 5, 6, 3, p, 32, 0)),
-        "sfh_conv_wgrad_s3": ((64, 32, 1, 5, 6, 3), (p, 64, p, 32, 5, 6, 32, 0, 0, 1, 5, 6, 3, p, 32, 0, 2)),
-        "sfh_conv_grouped_wgrad": ((1, 5, 6, 2, 4, 1), (p, p, p, 1, 5, 6, 2, 4, 1)),
-        "sfh_outconv_bwd": ((8, 3, 1, 5, 6), (p, 8, p, p, 3, 1, 5, 6, p, p, p)),
-        "sfh_avgpool_linear_bwd": ((2, 8, 9), (p, p, p, 2, 3, 3, 8, 9, p, p, p)),
-        "sfh_train_losses": ((1, 5, 6), (p, p, p, p, 4, 1, 5, 6, 2.0, 2.0, 0, 1.0, 0, p, p, p)),
-        "sfh_reproj_loss": ((3,), (p, p, p, p, 3, 5, 8.0, p, p)),
-        "sfh_uv_loss": ((1, 2, 5, 6), (p, p, p, 1, 1, 2, 5, 6, 2.0, 1, p, p)),
-        "sfh_homography_warp_bwd_theta": ((2, 5, 6), (p, p, 0, 9, 16, 2, 5, 6, p, p)),
-    }
+    p = _host_pointer()
+    calls = {name: make() for name, make in _entry_calls(p).items()}
     assert sorted(calls) == list(_lib.DET_ENTRIES)
     for name, (query, args) in calls.items():
         need = getattr(lib, name + "_det_bytes")(*query)
@@ -206,3 +223,50 @@ def test_size_queries_and_refusals_without_a_device():
         assert fn(*args, p, need - 1, None) == -1 and b"workspace" in lib.sfh_last_error(), name
     assert lib.sfh_det_reduce_f32(None, 1, 1, 1, 1, None, 1, None) == -1
     assert lib.sfh_det_reduce_f64(p, 2, 3, 4, 1, p, 1, None) == -1        # slab_stride < elems
+
+
+# (entry, the geometry it must refuse): every rule of the family's plan (csrc/det_core.h) at least once
+_PIXELS = [dict(npix=0), dict(C=0), dict(C=6)]
+_FRAME = [dict(B=0), dict(H=0), dict(W=0)]
+REFUSED = (
+    [(n, g) for n in ("sfh_bn_stats", "sfh_bn_bwd_reduce", "sfh_colsum") for g in _PIXELS]
+    + [("sfh_conv_wgrad", g) for g in _FRAME + [
+        dict(xh=0), dict(xw=0), dict(M=0), dict(M=6), dict(N=0, x_cs=8), dict(N=6, x_cs=8),
+        dict(x_cs=16),                                   # x_cs < N
+        dict(x_cs=34),                                   # x_cs % 4 != 0
+        dict(pad_top=1),                                 # a source of the frame's height, one row down: one row too tall
+        dict(pad_left=1), dict(pad_top=-1, xh=4), dict(pad_left=-1, xw=5),
+        dict(ks=5), dict(ks=2), dict(ks=4, N=64, x_cs=64)]]
+    + [("sfh_conv_wgrad_s3", g) for g in _FRAME + [
+        dict(ks=4), dict(ks=5), dict(M=0), dict(M=48), dict(N=0), dict(N=16),
+        dict(M=1 << 20, N=1 << 20, H=1, W=1)]]           # 2^29 workgroups per split round: the grid does not fit
+    + [("sfh_conv_grouped_wgrad", g) for g in _FRAME + [
+        dict(cg=5), dict(cg=128), dict(stride=3), dict(stride=0), dict(G=0), dict(G=16385),   # G * cg > 65536
+        dict(B=2, H=8192, W=8192)]]                      # 2^27 pixels
+    + [("sfh_outconv_bwd", g) for g in _FRAME + [dict(cin=0), dict(cin=6), dict(cin=260), dict(nc=0), dict(nc=9)]]
+    + [("sfh_avgpool_linear_bwd", g) for g in [dict(B=0), dict(C=0), dict(nout=0), dict(nout=257)]]
+    + [("sfh_train_losses", g) for g in _FRAME]
+    + [("sfh_uv_loss", g) for g in _FRAME + [dict(C=0)]]
+    + [("sfh_reproj_loss", dict(batch=0))]
+    + [("sfh_homography_warp_bwd_theta", g) for g in [dict(B=0), dict(B=65536), dict(h=1), dict(w=1)]]
+)
+
+
+def test_every_entry_has_refused_geometries():
+    from sfh_amd import _lib
+    assert sorted({n for n, _ in REFUSED}) == list(_lib.DET_ENTRIES)
+
+
+@pytest.mark.parametrize("name,geometry", REFUSED, ids=[f"{n[4:]}-{'-'.join(f'{k}={v}' for k, v in g.items())}" for n, g in REFUSED])
+def test_query_entry_and_sibling_refuse_alike(name, geometry):
+    """one plan per family: what the size query answers -1 for, the plain entry and the sibling refuse, and the sibling's
+    refusal is the geometry's - it comes before the workspace (here a usable pointer and 2^40 bytes) is looked at.  All three
+    return before any device call (the pointers are host memory, and this machine may have no device)."""
+    from sfh_amd import _lib
+    lib = _lib.load()
+    p = _host_pointer()
+    query, args = _entry_calls(p)[name](**geometry)
+    assert getattr(lib, name + "_det_bytes")(*query) == -1
+    assert getattr(lib, name)(*args, None) == -1
+    assert getattr(lib, name + "_det")(*args, p, 1 << 40, None) == -1
+    assert b"workspace" not in lib.sfh_last_error(), lib.sfh_last_error()
