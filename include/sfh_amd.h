@@ -584,19 +584,30 @@ int sfh_poi_project_bwd_theta(const float* theta, const float* poi, int batch, i
  * lambda (0 disables).  focal_flags bit 0 / bit 1: the segmentation / consistency term is
  * kornia.losses.FocalLoss(alpha=1, gamma=2) instead of CE (train.py:101,126; Kornia 0.5/0.6 formula:
  * sum_k (onehot_k + 1e-6) * -(1 - q_k)^2 log q_k with q = softmax + 1e-8).  gt_mask int64 (B,H,W); outputs d/dlogits (NCHW), d/dwarp (B,H,W, optional) and
- * loss3[0..2] += seg, rec, consistency (fp64, caller-zeroed).                                           */
+ * loss3[0..2] += seg, rec, consistency (fp64, caller-zeroed).
+ * The consistency target is clamp(trunc(fl32(warp * fl32(nc))), 0, nc - 1): the fp32 product is the reference's own
+ * (warp_mask * nc).to(long); the clamp is this project's addition - torch raises at warp = 1 (and below 0), here such a pixel
+ * takes class nc - 1 (0).  The reconstruction target is fl32(fl32(gt) / fl32(nc)); SmoothL1 branches on |d| < 1.           */
 int sfh_train_losses(const float* logits_nchw, const int64_t* gt_mask, const float* weight,
                      const float* warp_mask, int nc, int batch, int H, int W, float lambda_seg,
                      float lambda_rec, int rec_mse, float lambda_cons, int focal_flags, float* dlogits_nchw,
                      float* dwarp, double* loss3, void* stream);
-/* ReprojectionLoss (models/losses.py:6-31), reduction 'mean', times lambda: *loss += value; dpoi (B,N,2). */
+/* ReprojectionLoss (models/losses.py:6-31), reduction 'mean', times lambda: *loss += value; dpoi (B,N,2).
+ * A point with dist == 0 gets the gradient 0, where torch propagates NaN (0 / 0 in the square root's backward). */
 int sfh_reproj_loss(const float* poi, const float* gt_poi, const float* nonzeros, const float* num_nonzero,
                     int batch, int npts, float lambda, float* dpoi, double* loss, void* stream);
 /* nn.utils.clip_grad_value_(clip) + torch.optim.RMSprop step (train.py:88,234-237) over many tensors in
  * one launch.  tensor_table: device array of {float* param; const float* grad; float* square_avg;
  * float* momentum_buf;}; chunk_table: device array of {int32 tensor; int32 count; int64 offset;}, one
  * workgroup per chunk.  clip_value <= 0 disables clipping, momentum == 0 skips the buffer; the gradient
- * is multiplied by grad_scale first (1/world after a data-parallel all-reduce sum, else 1).            */
+ * is multiplied by grad_scale first (1/world after a data-parallel all-reduce sum, else 1).
+ * The clip is clamp_ as clip_grad_value_ applies it, in all three optimizers: a NaN gradient stays NaN and poisons the weight
+ * and the states it touches, as in torch; +-inf go to +-clip_value.
+ * alpha (and Adam's beta1, beta2) as received; the complement 1 - alpha is formed in fp32 from that float and is exact; torch
+ * rounds 1 - alpha_double to fp32 separately, a relative difference of the gain of at most 2^-24 / (1 - alpha) (the roundings of
+ * alpha and of torch's complement, 2^-24 in all, seen from the complement): 10 ulps (9.3e-7) at alpha 0.99, 3 ulps (2.2e-7) at beta1 0.9, 111 ulps (1.29e-5) at
+ * beta2 0.999.  tests/test_step_tail_host.py carries that difference through the recursion and states the distance to
+ * torch.optim per element and state tensor.                                                             */
 int sfh_rmsprop_step(const void* tensor_table, const void* chunk_table, int nchunks, float lr, float alpha,
                      float eps, float weight_decay, float momentum, float clip_value, float grad_scale,
                      void* stream);

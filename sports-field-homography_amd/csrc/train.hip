@@ -1153,6 +1153,10 @@ __global__ void reproj_loss_kernel(const float* __restrict__ poi, const float* _
 struct OptTensor { float* p; const float* g; float* sq; float* buf; };
 struct OptChunk { int tensor; int count; long offset; };
 
+// clamp_ as clip_grad_value_ applies it: a NaN gradient stays NaN (both compares are false) and poisons the weight as it does
+// in torch - fminf(fmaxf(g, -clip), clip) turned it into -clip; every other input, +-inf and -0 included, gives the same bits
+__device__ __forceinline__ float opt_clip(float g, float clip) { return g < -clip ? -clip : (g > clip ? clip : g); }
+
 __global__ __launch_bounds__(256) void rmsprop_kernel(const OptTensor* __restrict__ table, const OptChunk* __restrict__ chunks,
                                                       float lr, float alpha, float eps, float wd, float mu, float clip,
                                                       float gscale) {
@@ -1161,7 +1165,7 @@ __global__ __launch_bounds__(256) void rmsprop_kernel(const OptTensor* __restric
   for (int i = threadIdx.x; i < c.count; i += 256) {
     const long o = c.offset + i;
     float g = t.g[o] * gscale;   // 1/world: data-parallel mean of the all-reduced sum
-    if (clip > 0.f) g = fminf(fmaxf(g, -clip), clip);
+    if (clip > 0.f) g = opt_clip(g, clip);
     const float p = t.p[o];
     g = g + wd * p;
     const float sq = alpha * t.sq[o] + (1.0f - alpha) * g * g;
@@ -1185,7 +1189,7 @@ __global__ __launch_bounds__(256) void sgd_kernel(const OptTensor* __restrict__ 
   for (int i = threadIdx.x; i < c.count; i += 256) {
     const long o = c.offset + i;
     float g = t.g[o] * gscale;
-    if (clip > 0.f) g = fminf(fmaxf(g, -clip), clip);
+    if (clip > 0.f) g = opt_clip(g, clip);
     const float p = t.p[o];
     g = g + wd * p;
     if (mu > 0.f) {
@@ -1207,7 +1211,7 @@ __global__ __launch_bounds__(256) void adam_kernel(const OptTensor* __restrict__
   for (int i = threadIdx.x; i < c.count; i += 256) {
     const long o = c.offset + i;
     float g = t.g[o] * gscale;
-    if (clip > 0.f) g = fminf(fmaxf(g, -clip), clip);
+    if (clip > 0.f) g = opt_clip(g, clip);
     const float p = t.p[o];
     g = g + wd * p;
     float m = t.buf[o];

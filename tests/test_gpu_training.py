@@ -470,23 +470,35 @@ def test_loss_kernels_vs_torch(T, rec, cls):
     assert _relerr(dp, poi.grad) < 1e-5
 
 
-def test_rmsprop_kernel_vs_torch(T):
-    """clip_grad_value_(0.1) + RMSprop(lr, weight_decay, momentum 0.9) over three steps, odd tensor sizes."""
-    g = torch.Generator().manual_seed(5)
+def _optimizer_kernel_vs_torch(T, kind, make_opt, hp, seed):
+    """clip_grad_value_(0.1) + a torch.optim optimizer in fp32 against the multi-tensor kernel over three steps on odd tensor
+    sizes: the weights AND both state tensors, after every step, element by element.  The bound (tests/step_tail_ref.py,
+    opt_step) is the distance between the kernel's rule (gain 1 - fl32(beta), exact) and torch's (fl32(1 - beta_double))
+    carried through the recursion, plus the rounding bound of the rule once for the kernel and once for torch's own fp32
+    arithmetic - below the 2e-6 this test used to allow on the weights alone, on every element."""
+    import step_tail_ref as R
+    from sfh_amd import _lib
+    from sfh_amd.engine import _ptr, _stream
+    g = torch.Generator().manual_seed(seed)
     shapes = [(64, 3, 3, 3), (64,), (9, 512), (70001,), (1,)]
     net = torch.nn.ParameterList([torch.nn.Parameter(torch.randn(s, generator=g)) for s in shapes])
     ref = [p.detach().clone().requires_grad_(True) for p in net]
-    opt = torch.optim.RMSprop(ref, lr=1e-3, weight_decay=1e-4, momentum=0.9)
+    opt = make_opt(ref)
+    start = [p.detach().double().numpy().reshape(-1).copy() for p in net]
     net.cuda()
     holder = torch.nn.Module()
     holder.ps = net
     ts = T.TrainStep.__new__(T.TrainStep)
     # only the optimizer part of TrainStep, on a bare parameter list
-    ts.net, ts.hp = holder, dict(lr=1e-3, wd=1e-4, mu=0.9, alpha=0.99, eps=1e-8, clip=0.1)
+    ts.net, ts.hp = holder, {k: hp[k] for k in ("lr", "wd", "mu", "alpha", "eps", "clip")}
     T.TrainStep._init_optimizer(ts, list(net))
-    from sfh_amd import _lib
-    from sfh_amd.engine import _ptr, _stream
     lib = _lib.load()
+    ck, ct = R.complements(kind, hp), R.complements(kind, hp, torch_like=True)
+    dc = tuple(abs(a - b) for a, b in zip(ck, ct))
+    state = [dict(p=p0, sq=np.zeros_like(p0), buf=np.zeros_like(p0)) for p0 in start]
+    e_far, e_near = [None] * len(shapes), [None] * len(shapes)
+    keys = {"rmsprop": ("square_avg", "momentum_buffer"), "sgd": (None, "momentum_buffer"), "adam": ("exp_avg_sq", "exp_avg")}[kind]
+    worst = {"p": 0.0, "sq": 0.0, "buf": 0.0}
     for it in range(3):
         grads = [torch.randn(s, generator=g) * (0.3 if it else 0.05) for s in shapes]
         for p, gr in zip(ref, grads):
@@ -495,12 +507,38 @@ def test_rmsprop_kernel_vs_torch(T):
         opt.step()
         for dst, gr in zip(ts.grads, grads):
             dst.copy_(gr)
-        hp = ts.hp
-        _lib.check(lib.sfh_rmsprop_step(_ptr(ts.table), _ptr(ts.chunks), ts.nchunks, hp["lr"], hp["alpha"], hp["eps"],
-                                        hp["wd"], hp["mu"], hp["clip"], 1.0, _stream()), "rmsprop")
-    torch.cuda.synchronize()
-    for p, r in zip(net, ref):
-        assert (p.detach().cpu() - r.detach()).abs().max().item() < 2e-6
+        if kind == "rmsprop":
+            rc = lib.sfh_rmsprop_step(_ptr(ts.table), _ptr(ts.chunks), ts.nchunks, hp["lr"], hp["alpha"], hp["eps"], hp["wd"],
+                                      hp["mu"], hp["clip"], 1.0, _stream())
+        elif kind == "sgd":
+            rc = lib.sfh_sgd_step(_ptr(ts.table), _ptr(ts.chunks), ts.nchunks, hp["lr"], hp["wd"], hp["mu"], hp["clip"], 1.0, _stream())
+        else:
+            rc = lib.sfh_adam_step(_ptr(ts.table), _ptr(ts.chunks), ts.nchunks, hp["lr"], hp["b1"], hp["b2"], hp["eps"], hp["wd"],
+                                   hp["clip"], 1.0, it + 1, _stream())
+        _lib.check(rc, kind)
+        torch.cuda.synchronize()
+        for i, (p, r) in enumerate(zip(net, ref)):
+            gi = grads[i].numpy().reshape(-1)
+            _, e_far[i] = R.opt_step(kind, state[i], gi, hp, step=it + 1, err_in=e_far[i], dcomp=dc)       # kernel -> rule -> torch's rule
+            state[i], e_near[i] = R.opt_step(kind, state[i], gi, hp, step=it + 1, err_in=e_near[i])        # torch's fp32 -> torch's rule
+            st = opt.state[r]
+            got = {"p": p.detach(), "sq": ts.sq[i], "buf": ts.buf[i]}
+            want = {"p": r.detach(), "sq": st[keys[0]] if keys[0] else torch.zeros_like(r), "buf": st[keys[1]]}
+            for k in got:
+                bound = e_far[i][k] + e_near[i][k]
+                assert k != "p" or bound.max() < 2e-6       # never wider than the tolerance the weights had
+                worst[k] = max(worst[k], R.ratio(got[k].cpu().numpy().reshape(-1), want[k].numpy().reshape(-1).astype(np.float64), bound))
+    print(f"RATIO {kind} kernel / torch.optim fp32: " + " ".join(f"{k} {v:.3f}" for k, v in worst.items()))
+    assert all(v <= 1.0 for v in worst.values()), worst
+    return ts
+
+
+_OPT_HP = dict(lr=1e-3, wd=1e-4, mu=0.9, alpha=0.99, eps=1e-8, clip=0.1, gscale=1.0, b1=0.9, b2=0.999)
+
+
+def test_rmsprop_kernel_vs_torch(T):
+    """clip_grad_value_(0.1) + RMSprop(lr, weight_decay, momentum 0.9) over three steps, odd tensor sizes."""
+    _optimizer_kernel_vs_torch(T, "rmsprop", lambda ref: torch.optim.RMSprop(ref, lr=1e-3, weight_decay=1e-4, momentum=0.9), _OPT_HP, 5)
 
 
 @pytest.mark.parametrize("prec", ["bf16x6", "f16x3"])
@@ -1167,42 +1205,16 @@ def test_fused_training_passes_give_the_gradients_of_the_separate_ones(T, prec, 
 def test_sgd_and_adam_kernels_vs_torch(T, name):
     """train.py:89-92: clip_grad_value_(0.1) + torch.optim.SGD(lr, momentum 0.9, weight_decay) / torch.optim.Adam(lr,
     betas (0.9, 0.999), weight_decay) over three steps on odd tensor sizes, like test_rmsprop_kernel_vs_torch."""
-    g = torch.Generator().manual_seed(6)
-    shapes = [(64, 3, 3, 3), (64,), (9, 512), (70001,), (1,)]
-    net = torch.nn.ParameterList([torch.nn.Parameter(torch.randn(s, generator=g)) for s in shapes])
-    ref = [p.detach().clone().requires_grad_(True) for p in net]
-    if name == "SGD":
-        opt = torch.optim.SGD(ref, lr=1e-2, weight_decay=1e-4, momentum=0.9)
-    else:
-        opt = torch.optim.Adam(ref, lr=1e-3, betas=(0.9, 0.999), weight_decay=1e-4)
-    net.cuda()
-    holder = torch.nn.Module()
-    holder.ps = net
-    ts = T.TrainStep.__new__(T.TrainStep)
-    ts.net, ts.hp = holder, dict(lr=1e-2 if name == "SGD" else 1e-3, wd=1e-4, mu=0.9, alpha=0.99, eps=1e-8, clip=0.1)
-    T.TrainStep._init_optimizer(ts, list(net))
     from sfh_amd import _lib
     from sfh_amd.engine import _ptr, _stream
-    lib = _lib.load()
-    for it in range(3):
-        grads = [torch.randn(s, generator=g) * (0.3 if it else 0.05) for s in shapes]
-        for p, gr in zip(ref, grads):
-            p.grad = gr.clone()
-        torch.nn.utils.clip_grad_value_(ref, 0.1)
-        opt.step()
-        for dst, gr in zip(ts.grads, grads):
-            dst.copy_(gr)
-        hp = ts.hp
-        if name == "SGD":
-            _lib.check(lib.sfh_sgd_step(_ptr(ts.table), _ptr(ts.chunks), ts.nchunks, hp["lr"], hp["wd"], hp["mu"], hp["clip"],
-                                        1.0, _stream()), "sgd")
-        else:
-            _lib.check(lib.sfh_adam_step(_ptr(ts.table), _ptr(ts.chunks), ts.nchunks, hp["lr"], 0.9, 0.999, hp["eps"],
-                                         hp["wd"], hp["clip"], 1.0, it + 1, _stream()), "adam")
-    torch.cuda.synchronize()
-    for p, r in zip(net, ref):
-        assert (p.detach().cpu() - r.detach()).abs().max().item() < 2e-6
+    if name == "SGD":
+        ts = _optimizer_kernel_vs_torch(T, "sgd", lambda ref: torch.optim.SGD(ref, lr=1e-2, weight_decay=1e-4, momentum=0.9),
+                                        dict(_OPT_HP, lr=1e-2), 6)
+    else:
+        ts = _optimizer_kernel_vs_torch(T, "adam", lambda ref: torch.optim.Adam(ref, lr=1e-3, betas=(0.9, 0.999), weight_decay=1e-4),
+                                        _OPT_HP, 6)
     # Adam's step counter starts at 1
+    lib = _lib.load()
     assert lib.sfh_adam_step(_ptr(ts.table), _ptr(ts.chunks), ts.nchunks, 1e-3, 0.9, 0.999, 1e-8, 0.0, 0.1, 1.0, 0, _stream()) != 0
 
 
