@@ -1,4 +1,5 @@
-"""One SHA-256 per (kernel, case) of every order-fixed output of the BatchNorm family of csrc/train.hip, on the shapes of
+"""One SHA-256 per (kernel, case) of every order-fixed output of the BatchNorm family of csrc/train_bn.hip (with the
+fused OutConv and first-layer backward-filter of train_heads.hip and train_wgrad.hip), on the shapes of
 tests/train_kernel_cases.py and of the two sibling tests of tests/test_gpu_train_kernels.py.  Two builds of the library
 compute the same bits exactly when the two listings are equal line for line:
 
@@ -6,7 +7,8 @@ compute the same bits exactly when the two listings are equal line for line:
     SFH_AMD_LIB=<other libsfh_amd.so> python profiles/train_kernel_digest.py > other.txt       (a fresh process each)
 
 Atomically summed outputs (the fp64 accumulators, multi-tile weight gradients) have a free order and are not listed; the
-bound tests hold them.  profiles/ab_bn_math.txt keeps the listing of the commit that introduced csrc/bn_math.h."""
+bound tests hold them.  profiles/ab_bn_math.txt keeps the listing of the commit that introduced csrc/bn_math.h,
+profiles/ab_train_split.txt that of the commit that split csrc/train.hip into those files."""
 import hashlib
 import itertools
 import os

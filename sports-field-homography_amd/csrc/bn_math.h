@@ -5,9 +5,10 @@
 // beta, xhat = (z - mean) * invstd, exactly as the forward did - one fp32 rounding per operation, in this grouping, no
 // contraction (build.py compiles every translation unit with -ffp-contract=off) - and gates with the strict y > 0.  So no
 // kernel writes these expressions out; all of them call the functions below:
-//   train.hip        bn_apply_kernel, bn_bwd_reduce_kernel, bn_bwd_apply_kernel, bn_apply_s3_kernel, bn_bwd_apply_s3_kernel,
-//                    bn_apply_pool_s3_kernel, pool2_bwd_bn_reduce_kernel, outconv_bwd_kernel<NC, true>,
-//                    wgrad_c4_kernel<TH, TW, true>
+//   train_bn.hip     bn_apply_kernel, bn_bwd_reduce_kernel, bn_bwd_apply_kernel, bn_apply_s3_kernel, bn_bwd_apply_s3_kernel,
+//                    bn_apply_pool_s3_kernel, pool2_bwd_bn_reduce_kernel
+//   train_heads.hip  outconv_bwd_kernel<NC, true>
+//   train_wgrad.hip  wgrad_c4_kernel<TH, TW, true>
 //   conv_epilogue.h  the backward-sums branch of the conv epilogue
 // tests/bn_math_host_main.cpp runs this file on the CPU against the fp32 / fp64 restatements of
 // tests/test_train_kernel_host.py, bit for bit.

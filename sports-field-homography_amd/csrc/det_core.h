@@ -62,7 +62,7 @@ SFH_DET_FN T det_sum(T dst0, const T* partial, long slabs, long stride, long e) 
 // backward-filter source that fills columns [n_off, n_off + N) of raw: ncol = N, dst_row_stride = raw_n, dst = raw + n_off)
 SFH_DET_FN long det_dst_offset(long e, int ncol, long dst_row_stride) { return (e / ncol) * dst_row_stride + e % ncol; }
 
-// ------------------------------------------------------------------ pixel reductions (csrc/train.hip)
+// ------------------------------------------------------------------ pixel reductions (csrc/train_bn.hip)
 // sfh_bn_stats / sfh_colsum / sfh_bn_bwd_reduce: at most DET_RED_BLOCKS blocks of 256 threads, one more per DET_RED_ROWS
 // pixels.  Slab = block.  Elements per slab: 2 * C (bn_stats, bn_bwd_reduce: [row][channel]) or C (colsum).
 #define DET_RED_ROWS 256
@@ -131,7 +131,7 @@ SFH_DET_FN DetPlan det_warp_plan(int batch, int h, int w) {   // batch is gridDi
   return det_admit((long)det_warp_gx(w) * det_warp_gy(h), 9L * batch, sizeof(double));
 }
 
-// ------------------------------------------------------------------ backward-filter, fp32 MFMA (csrc/train.hip)
+// ------------------------------------------------------------------ backward-filter, fp32 MFMA (csrc/train_wgrad.hip)
 // 64-pixel tiles of th x tw (the shape with the fewest tiles; ties go to the widest), tile index = (b * nty + ty) * ntx + tx.
 // Split s owns the tiles s, s + nsplit, s + 2 * nsplit, ...: slab of a tile = tile % nsplit.  Slab element of raw[m][tap][n]
 // (n counted from the source's first channel): (m * kk + tap) * N + n - the slab is compact, the sum pass places it at

@@ -1,5 +1,6 @@
 // bn_math_host_main.cpp - the training-mode BatchNorm arithmetic of csrc/bn_math.h run on the host, element by element through
-// the same functions the kernels of csrc/train.hip and the conv epilogue call.  Built and run by
+// the same functions the kernels of csrc/train_bn.hip, train_heads.hip and train_wgrad.hip and the conv epilogue call.
+// Built and run by
 // tests/test_train_kernel_host.py with -fsanitize=address,undefined and -ffp-contract=off (the library's own setting); it links
 // nothing of the library.
 //

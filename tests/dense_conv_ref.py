@@ -1,6 +1,6 @@
 """fp64 CPU references (test infrastructure only) for the dense convolution launches: sfh_conv_fwd (csrc/conv_mfma.hip),
 sfh_conv_s3_fwd in its S3 and H2 source formats (csrc/conv_s3.hip), sfh_conv_small_fwd (csrc/conv_small.hip), the same
-kernels as backward-data through pack modes 1, 3 and 4, and the backward-filter pair sfh_conv_wgrad (csrc/train.hip) and
+kernels as backward-data through pack modes 1, 3 and 4, and the backward-filter pair sfh_conv_wgrad (csrc/train_wgrad.hip) and
 sfh_conv_wgrad_s3 (csrc/wgrad_s3.hip).  Plain numpy / torch-CPU; nothing here imports the library.
 
 Tensors are NHWC numpy arrays as the kernels see them.  Every reference returns its value and the absolute sum

@@ -1,4 +1,4 @@
-"""fp64 CPU references (test infrastructure only) for the kernels that open and close a training step (csrc/train.hip):
+"""fp64 CPU references (test infrastructure only) for the kernels that open and close a training step (csrc/train_step.hip):
 
   sfh_train_losses, sfh_reproj_loss, sfh_uv_loss (and their _det siblings), sfh_rmsprop_step, sfh_sgd_step, sfh_adam_step,
   sfh_multi_copy, sfh_multi_copy_dscale, sfh_grad_scale

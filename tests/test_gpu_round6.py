@@ -57,8 +57,8 @@ def test_new_weights_with_two_batches_in_flight_finish_on_the_old_engines():
 
 
 def test_outconv_backward_filter_at_1280x720_against_fp64():
-    """ADVICE r05 (csrc/train.hip outconv_bwd_kernel): a workgroup covers npix / 1024 pixels, so a thread's dW / db chain
-    grows with the image (about 900 terms at 1280x720 x 16); the partial sums are promoted to fp64 every 64 pixels.  dW
+    """ADVICE r05 (csrc/train_heads.hip outconv_bwd_kernel): a workgroup covers npix / 1024 pixels, so a thread's dW / db
+    chain grows with the image (about 900 terms at 1280x720 x 16); the partial sums are promoted to fp64 every 64 pixels.  dW
     and db of sfh_outconv_bwd at 1280x720 against an fp64 contraction of the same tensors (unet/unet_parts.py:71-77)."""
     import ctypes
     from sfh_amd import _lib

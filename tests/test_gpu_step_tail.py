@@ -1,4 +1,4 @@
-"""The kernels that open and close a training step (csrc/train.hip) one by one against the fp64 CPU references of
+"""The kernels that open and close a training step (csrc/train_step.hip) one by one against the fp64 CPU references of
 tests/step_tail_ref.py (which tests/test_step_tail_host.py holds against torch), through the raw C entry points:
 
   sfh_train_losses, sfh_reproj_loss, sfh_uv_loss and their _det siblings, sfh_rmsprop_step, sfh_sgd_step, sfh_adam_step,

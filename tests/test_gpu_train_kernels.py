@@ -1,6 +1,6 @@
-"""The plain training kernels of csrc/train.hip - the anchor the fused kernels and the conv epilogue sums are held to - one
-by one against the fp64 CPU references of tests/train_kernel_ref.py (which tests/test_train_kernel_host.py holds against
-torch autograd), through the raw C entry points:
+"""The plain training kernels of csrc/train_bn.hip and csrc/train_heads.hip - the anchor the fused kernels and the conv
+epilogue sums are held to - one by one against the fp64 CPU references of tests/train_kernel_ref.py (which
+tests/test_train_kernel_host.py holds against torch autograd), through the raw C entry points:
 
   sfh_bn_stats, sfh_bn_stats_partials, sfh_bn_finalize, sfh_bn_finalize_partials, sfh_bn_apply, sfh_bn_bwd_reduce,
   sfh_bn_bwd_apply, sfh_colsum, sfh_maxpool2_fwd, sfh_maxpool2_bwd, sfh_outconv_bwd, sfh_outconv_bwd_bn

@@ -1,6 +1,6 @@
 """Inputs shared by tests/test_train_kernel_host.py (CPU) and tests/test_gpu_train_kernels.py (GPU): the smallest shapes at
-which each plain training kernel of csrc/train.hip can still go wrong.  Everything is drawn from seeded generators, so both
-files see the same numbers; the cases are cached, and nobody writes into them."""
+which each plain training kernel of csrc/train_bn.hip and csrc/train_heads.hip can still go wrong.  Everything is drawn
+from seeded generators, so both files see the same numbers; the cases are cached, and nobody writes into them."""
 import functools
 import zlib
 

@@ -1,4 +1,5 @@
-"""fp64 CPU references (test infrastructure only) for the plain training kernels of csrc/train.hip, one per entry point:
+"""fp64 CPU references (test infrastructure only) for the plain training kernels of csrc/train_bn.hip and
+csrc/train_heads.hip (the OutConv pair), one per entry point:
 
   sfh_bn_stats, sfh_bn_stats_partials, sfh_bn_finalize, sfh_bn_finalize_partials, sfh_bn_apply, sfh_bn_bwd_reduce,
   sfh_bn_bwd_apply, sfh_colsum, sfh_maxpool2_fwd, sfh_maxpool2_bwd, sfh_outconv_bwd, sfh_outconv_bwd_bn
