@@ -22,8 +22,9 @@ from . import sharding
 from .engine import _ptr, _stream
 
 # slots of the accumulator vector (include/sfh_amd.h, SFH_EVAL_*)
-SEG, REC, UV, REPROJ, REPROJ_PX, CONSIST, NBATCH, FRAMES, BAD = range(9)
-SLOTS = 9
+SEG, REC, UV, REPROJ, REPROJ_PX, CONSIST, NBATCH, FRAMES, BAD = (_lib.ABI.defines["SFH_EVAL_" + s] for s in (
+    "SEG", "REC", "UV", "REPROJ", "REPROJ_PX", "CONSIST", "NBATCH", "FRAMES", "BAD"))
+SLOTS = _lib.ABI.defines["SFH_EVAL_SLOTS"]
 
 
 def scores_from_accumulator(acc):

@@ -41,20 +41,8 @@ REASONS = {1: "the bytes end inside the header", 2: "no SOI marker: not a JPEG f
            107: "a non-interleaved file (several scans)", 108: "DNL / height 0", 109: "extended sequential, lossless or hierarchical frames"}
 
 
-class HuffTab(ctypes.Structure):
-    _fields_ = [("look", ctypes.c_uint16 * 256), ("maxcode", ctypes.c_int32 * 18), ("valoff", ctypes.c_int32 * 18),
-                ("vals", ctypes.c_uint8 * 256)]
-
-
-class JpegInfo(ctypes.Structure):
-    """mirror of sfh_jpeg_info (include/sfh_amd.h)"""
-    _fields_ = [(n, ctypes.c_int32) for n in ("width", "height", "ncomp", "hsamp", "vsamp", "mcus_x", "mcus_y", "blocks_per_mcu",
-                                              "restart_interval", "nsegments", "scan_begin", "scan_end", "reason")] + [
-        ("qsel", ctypes.c_int32 * 3), ("dcsel", ctypes.c_int32 * 3), ("acsel", ctypes.c_int32 * 3),
-        ("file_pos", ctypes.c_int32), ("file_bytes", ctypes.c_int32), ("seg_pos", ctypes.c_int32), ("nsub", ctypes.c_int32),
-        ("reserved", ctypes.c_int32 * 2), ("quant", (ctypes.c_uint16 * 64) * 4), ("dc", HuffTab * 4), ("ac", HuffTab * 4)]
-
-
+HuffTab = _lib.ABI.structs["sfh_jpeg_hufftab"]
+JpegInfo = _lib.ABI.structs["sfh_jpeg_info"]
 assert ctypes.sizeof(JpegInfo) == 7920
 
 

@@ -26,7 +26,7 @@ import torch
 from . import _lib
 from ._codec import BatchEncoder, JpegBatch, as_image_batch, image_files_from_batch, ptr, stream  # noqa: F401 (re-exported)
 
-MAX_WIDTH = 2048
+MAX_WIDTH = _lib.ABI.defines["SFH_JPEG_MAX_WIDTH"]
 
 
 def jpeg_capacity(H, W, C):

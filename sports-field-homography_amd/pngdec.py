@@ -48,13 +48,7 @@ STATUS_BITS = {1: "an over-subscribed or incomplete code-length set", 2: "an inv
                128: "an Adler-32 mismatch"}
 
 
-class PngInfo(ctypes.Structure):
-    """mirror of sfh_png_info (include/sfh_amd.h)"""
-    _fields_ = [(n, ctypes.c_int32) for n in ("width", "height", "channels", "bit_depth", "color_type", "interlace", "nidat",
-                                              "idat_bytes", "cmf", "flg")] + [("adler", ctypes.c_uint32)] + [
-        (n, ctypes.c_int32) for n in ("reason", "file_pos", "file_bytes", "range_pos", "joined_pos")]
-
-
+PngInfo = _lib.ABI.structs["sfh_png_info"]
 assert ctypes.sizeof(PngInfo) == 64
 
 

@@ -24,7 +24,7 @@ import torch
 from . import _lib
 from ._codec import BatchEncoder, PngBatch, as_image_batch, ptr, split_files, stream  # noqa: F401 (re-exported)
 
-MAX_ROW = 32768
+MAX_ROW = _lib.ABI.defines["SFH_PNG_MAX_ROW"]
 
 
 def png_capacity(H, W, C):

@@ -54,7 +54,7 @@ from .pngenc import files_from_batch
 
 FOOTBALL_PITCH_IGNORE_POINTS = (12, 13, 16, 19, 20)      # dataset_utils/preparation.py:27
 MAX_VALUE_UINT16 = 65535
-MAX_POINTS = 256                                         # SFH_PREP_MAX_POINTS
+MAX_POINTS = _lib.ABI.defines["SFH_PREP_MAX_POINTS"]
 
 
 # ---------------------------------------------------------------------------------------------- host helpers

@@ -27,9 +27,9 @@ import torch
 from . import _lib
 from ._codec import ptr as _ptr, stream as _stream
 
-FILTERS = {"box": 4, "bilinear": 2, "bicubic": 3}         # Pillow's numbering
-NEAREST_RULES = {"pil": 0, "cv2": 1}
-MAX_TAPS = 64                                             # SFH_RESAMPLE_MAX_TAPS (include/sfh_amd.h)
+FILTERS = {f: _lib.ABI.defines["SFH_FILTER_" + f.upper()] for f in ("box", "bilinear", "bicubic")}     # Pillow's numbering
+NEAREST_RULES = {r: _lib.ABI.defines["SFH_NEAREST_" + r.upper()] for r in ("pil", "cv2")}
+MAX_TAPS = _lib.ABI.defines["SFH_RESAMPLE_MAX_TAPS"]
 
 _TABS = {}
 _NEAREST_TABS = {}

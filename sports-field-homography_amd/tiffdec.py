@@ -34,13 +34,7 @@ STATUS_BITS = {1: "a code above the next free code", 2: "a first code after Clea
                4: "output short of or beyond the strip's rows", 8: "the bits end early"}
 
 
-class TiffInfo(ctypes.Structure):
-    """mirror of sfh_tiff_info (include/sfh_amd.h)"""
-    _fields_ = [(n, ctypes.c_int32) for n in ("width", "height", "channels", "bits", "compression", "predictor", "big_endian",
-                                              "rows_per_strip", "nstrips", "photometric", "reason", "file_pos", "file_bytes",
-                                              "table_pos", "reserved0", "reserved1")]
-
-
+TiffInfo = _lib.ABI.structs["sfh_tiff_info"]
 assert ctypes.sizeof(TiffInfo) == 64
 
 

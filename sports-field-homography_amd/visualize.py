@@ -38,8 +38,8 @@ from . import outputs as O
 from . import pngdec
 from ._codec import frames_from_files, image_files_from_batch, ptr as _ptr, stream as _stream
 
-SOURCES = {"auto": 0, "warp": 1, "segm": 2}     # SFH_OVERLAY_AUTO / WARP / SEGM
-LABEL_MAX = 32                                  # SFH_OVERLAY_LABEL_MAX
+SOURCES = {s: _lib.ABI.defines["SFH_OVERLAY_" + s.upper()] for s in ("auto", "warp", "segm")}
+LABEL_MAX = _lib.ABI.defines["SFH_OVERLAY_LABEL_MAX"]
 LABEL_COLORS = ((0, 255, 0), (0, 0, 255))       # score < score_threshold, otherwise (viz_preds.py:125,127)
 GLYPH_W, GLYPH_H, GLYPH_ADVANCE = 5, 7, 6
 CHARSET = "0123456789.-+e naif"                 # glyph code = index
