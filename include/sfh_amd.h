@@ -1337,6 +1337,69 @@ int sfh_homography_warp_bwd_theta_det(const float* theta, const float* tmpl, int
                                       int h, int w, const float* dout, double* acc, void* workspace,
                                       long long workspace_bytes, void* stream);
 
+/* -------------------------------------------------------------------------------------------------
+ * Homography refinement against the segmentation (csrc/refine.hip): direct alignment of the court template to the UNet's
+ * class probabilities, a few damped Gauss-Newton steps per frame, coarse to fine.  THE RULE, stated here once; the kernels
+ * and the numpy restatement tests/refine_ref.py follow it.
+ *
+ * Planes.  For a class count nc in 2..8 the foreground planes are c = 1 .. nc-1; plane c is channel c-1 of a channel-last
+ *   tensor of CP channels, CP = 4 for nc <= 5 and 8 otherwise; the pad channels are 0.
+ *   Template plane at level f:  Tf[c] = (count over the f x f block of (id == c)) / f^2 in fp32, id = rint(fl32(v * nc)) of the
+ *     template (N,1,ht,wt) valued k/nc.
+ *   Evidence plane at level f:  Ef[c] = (sum over the f x f block, row by row, of softmax(logits)[c]) / f^2, all fp32;
+ *     softmax(l)[c] = e_c / (e_0 + e_1 + ... + e_{nc-1}) in that order, e_k = expf(l_k - max l), one IEEE division.
+ *   f must divide ht, wt, hl and wl; otherwise the call is refused and nothing is launched.
+ *   Background is not a plane: a tap outside the template reads 0 in every plane, and 0 is what background is.
+ * Coordinates.  theta addresses the model's warp grid (H, W) (Reconstructor.warp's).  Evidence column j of level f over
+ *   logits of width wl has xn = fmaf(ax, j, cx), ax = 2 f W / (wl (W-1)), cx = (f W / wl - 1) / (W-1) - 1, both evaluated in
+ *   fp64 on the host and rounded once to fp32 (sfh_refine_axis): the centre of the averaged pixel in create_meshgrid's
+ *   convention.  Rows alike with H and hl.  With f = 1 and wl = W this grid is the warp's own up to rounding; it is NOT
+ *   required to be bit-equal to the warp kernels' (i / (W-1) - 0.5) * 2.
+ *   Then X, Y, Z, s, u = s X, v = s Y exactly as the warp (s = 1 / (Z + 1e-8) where |Z| > 1e-8, else 1), px = fma(u + 1,
+ *   (wt/f) / 2, -0.5), py alike with ht/f; bilinear taps with zero padding at (floor px, floor py).  The weights wx1 = px -
+ *   floor px, wx0 = 1 - wx1 (wy alike), the value ((t00 wy0 wx0 + t01 wy0 wx1) + t10 wy1 wx0) + t11 wy1 wx1 and the tap
+ *   differences duf = wy0 (t01 - t00) + wy1 (t11 - t10), dvf = wx0 (t10 - t00) + wx1 (t11 - t01) are fp32, every operation
+ *   rounded; everything behind them is fp64 (the staging of sfh_homography_warp_bwd_theta).
+ * Cost and normal equations.  r_c(p) = value_c(p) - Ef[c](p), cost = sum_p sum_c r_c^2.  theta[8] is held fixed; per pixel
+ *   J_c = du_c a + dv_c b with du_c = duf_c (wt/f) / 2, dv_c = dvf_c (ht/f) / 2, a = du/dtheta = (s xn, s yn, s, 0, 0, 0, gu xn,
+ *   gu yn), b = dv/dtheta = (0, 0, 0, s xn, s yn, s, gv xn, gv yn), gu = -X s^2, gv = -Y s^2 (0 where |Z| <= 1e-8).
+ *   SFH_REFINE_SUMS = 45 sums per frame, the layout of sfh_prep_fit's step: the upper triangle of J^T J row by row
+ *   (36), J^T r (8), the cost (1).
+ * Step (Levenberg-Marquardt, the rule of sfh_prep_fit).  Solve (J^T J + lambda diag(J^T J)) delta = -J^T r by Cholesky in
+ *   fp64; the candidate is fl32(theta_k + delta_k), k < 8 (the accepted theta itself when a pivot is not > 0).  It is accepted
+ *   iff every pivot was > 0 and cost(candidate) < cost(accepted) - a NaN cost rejects.  Accepted: lambda / 10; rejected:
+ *   lambda * 10; lambda = 1e-3 at the start of every level.  Schedule: the levels from coarse to fine, `iters` steps each.
+ *
+ * One level = sfh_refine_accumulate(theta) + sfh_refine_step(first = 1), then `iters` times sfh_refine_accumulate(candidate)
+ * + sfh_refine_step(first = 0), the last of them with last = 1.  The library allocates nothing and keeps no pointer. */
+#define SFH_REFINE_SUMS 45
+/* a[0] = ax, a[1] = cx of an axis of n warp-grid points seen through nl logits at level f (HOST pointer; no device call) */
+int sfh_refine_axis(int f, int n, int nl, float* a);
+/* tmpl (n,1,ht,wt) float -> planes (n, ht/f, wt/f, CP) float */
+int sfh_refine_template_planes(const float* tmpl, int n, int ht, int wt, int nc, int f, float* planes, void* stream);
+/* logits (batch,nc,hl,wl) float NCHW -> planes (batch, hl/f, wl/f, CP) float */
+int sfh_refine_evidence_planes(const float* logits, int batch, int nc, int hl, int wl, int f, float* planes, void* stream);
+/* bytes of the partial sums of sfh_refine_accumulate for an evidence grid of h x w (the finest level's serves every coarser
+ * one): ceil(w / 64) * ceil(h / 64) * batch * 45 doubles; -1 for batch outside 1..65535 or h, w < 1 */
+int64_t sfh_refine_workspace_bytes(int batch, int h, int w);
+/* The 45 sums of theta (batch,9) per workgroup: tplanes (n, ht/f, wt/f, CP) with tplanes_bstride floats from frame to frame (0:
+ * one template for every frame; else a multiple of 4), eplanes (batch, hl/f, wl/f, CP), both 16-byte aligned (they are read with
+ * 16-byte loads; anything else returns SFH_E_ARG); H, W the warp grid.  Workgroup (x, y) covers 64 columns x
+ * 64 rows of the evidence grid and stores its sums of frame b at workspace[((y * gx + x) * batch + b) * 45 + e], one plain
+ * store per sum (wave shuffle, then LDS; no atomics).  A workspace that is NULL or short returns SFH_E_ARG, nothing launched. */
+int sfh_refine_accumulate(const float* theta, const float* tplanes, int64_t tplanes_bstride, int ht, int wt,
+                          const float* eplanes, int batch, int nc, int hl, int wl, int H, int W, int f, void* workspace,
+                          long long workspace_bytes, void* stream);
+/* One wave per frame: sums the `slabs` partials [slab][batch][45] of theta_eval (batch,9) in ascending slab order from 0 and
+ * applies the step rule against the per-frame state: theta_acc (batch,9) float, sums_acc (batch,45) double, lambda (batch)
+ * double, pivots_ok (batch) int32.  first != 0: theta_eval is adopted as the level's start, lambda = 1e-3,
+ * accepted[b * nlevels + level] = 0 and cost[(b * nlevels + level) * 2] = its cost.  Otherwise accept / reject as above
+ * (accepted is incremented).  Every call writes cost[(b * nlevels + level) * 2 + 1] = the accepted cost and theta_next
+ * (batch,9): the next candidate, or the accepted theta when last != 0.  theta_next may be theta_eval. */
+int sfh_refine_step(const double* partial, int64_t slabs, int batch, int first, int last, const float* theta_eval,
+                    float* theta_acc, double* sums_acc, double* lambda, int32_t* pivots_ok, float* theta_next, double* cost,
+                    int32_t* accepted, int level, int nlevels, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,7 +14,7 @@ LIB = os.path.join(_HERE, "libsfh_amd.so")
 SOURCES = ["capi.hip", "conv_mfma.hip", "conv_s3.hip", "conv_c4h2.hip", "pointwise.hip", "warp.hip", "train_bn.hip", "train_heads.hip",
            "train_wgrad.hip", "train_step.hip", "stem.hip", "wgrad_s3.hip", "probe.hip", "conv_small.hip", "conv_upfused.hip", "conv_inc_fused.hip", "hostprep.hip",
            "eval.hip", "augment.hip", "overlay.hip", "prepare.hip", "mapping.hip", "pngenc.hip", "jpegenc.hip", "resample.hip",
-           "jpegdec.hip", "pngdec.hip", "conv_grouped.hip", "tiffdec.hip", "tiffenc.hip", "det.hip"]
+           "jpegdec.hip", "pngdec.hip", "conv_grouped.hip", "tiffdec.hip", "tiffenc.hip", "det.hip", "refine.hip"]
 # warp.hip's coordinate arithmetic must not be contracted into FMAs (bit-exact nearest
 # sampling against oracle/warp_ref.py); the flag is harmless elsewhere.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off",
@@ -35,7 +35,10 @@ EXTRA_FLAGS = {"warp.hip": _NO_SLP, "conv_s3.hip": _NO_SLP, "conv_mfma.hip": _NO
                # prepare.hip's render kernel is warp.hip's coordinate arithmetic again (csrc/warp_coords.h)
                "prepare.hip": _NO_SLP,
                # mapping.hip's top-view kernels are that coordinate arithmetic once more, sampling the frame instead
-               "mapping.hip": _NO_SLP}
+               "mapping.hip": _NO_SLP,
+               # refine.hip's accumulate kernel is that coordinate arithmetic plus per-class fp32 bilinear values and tap
+               # differences in front of an fp64 chain: VALU-issue-bound by the same reasoning, not by measurement
+               "refine.hip": _NO_SLP}
 
 
 def _stale(target, deps):

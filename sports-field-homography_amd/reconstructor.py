@@ -213,6 +213,9 @@ class Reconstructor(nn.Module):
         # 4 frames 3.83 -> 3.72 ms, 1 and >= 8 frames +-0) - at the price of theta differing from predict()'s in the last
         # bits (another fp32 summation order); batches of 16 never split, so the headline is untouched either way
         self.pipeline_splitk = True
+        # predict() / predict_async(): a refine.ThetaRefiner aligns the STN's theta to the segmentation before warp, consistency
+        # score and POI are computed; the STN's own theta is returned as 'theta_stn'.  None: every path and output as before
+        self.refiner = None
         self._engine_stamp = None
         self._weights_generation = 0
         self._tmpl_shared = None   # (data_ptr, shape) -> bool cache
@@ -665,7 +668,8 @@ class Reconstructor(nn.Module):
         self._require_eval("predict_replay")
         simple = (self.use_unet and self.use_resnet and x.is_cuda and x.shape[0] > 0 and x.shape[0] <= self._max_frames(x)
                   and not self._needs_resize(x) and self.resnet_input == Input.IMG_AND_MASK
-                  and x.dtype == torch.float32 and x.is_contiguous() and E.PackedConv.timer is None)
+                  and x.dtype == torch.float32 and x.is_contiguous() and E.PackedConv.timer is None
+                  and self.__dict__.get("refiner") is None)
         if not simple:
             return self.predict(x, consistency=consistency, project_poi=project_poi)
         cache = self.__dict__.setdefault("_replay", {})
@@ -797,6 +801,8 @@ class Reconstructor(nn.Module):
                 ret["uv"] = torch.empty((0, 2, th, tw), dtype=f32, device=dev)
         if self.use_resnet:
             ret["theta"] = torch.empty((0, 1, 3, 3), dtype=f32, device=dev)
+            if predict and self.__dict__.get("refiner") is not None:
+                ret["theta_stn"] = torch.empty((0, 1, 3, 3), dtype=f32, device=dev)
             if self.warper:
                 ret["warp_mask"] = torch.empty((0, h, w), dtype=torch.int32 if predict else f32, device=dev)
                 if predict and consistency and self.use_unet:
@@ -826,6 +832,12 @@ class Reconstructor(nn.Module):
             if r is not None:
                 ret['logits'] = r["logits"]
             if theta is not None:
+                refiner = self.__dict__.get("refiner")
+                if refiner is not None:
+                    if r is None:
+                        raise ValueError("a refiner needs the UNet's logits as evidence: this model has use_unet=False")
+                    ret['theta_stn'] = theta
+                    theta = refiner(theta, r["logits"], offset=off)['theta']
                 ret['theta'] = theta
                 if self.warper:
                     bs = theta.shape[0]
