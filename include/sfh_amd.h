@@ -287,14 +287,16 @@ int64_t sfh_packed_weight_floats(int ksize, int c0, int c1, int cout_virtual);
 int sfh_pack_conv_weights(const float* w, float* packed, int ksize, int c0, int c1,
                           int cout_virtual, int mode, int aux, void* stream);
 
-/* (B,H,W,cs) -> (B,ceil(H/2),ceil(W/2),4*cs): out[Y][X][(py*2+px)*cs + c] = in[2Y+py][2X+px][c]
- * (zero where 2Y+py >= H or 2X+px >= W). */
+/* (B,H,W,cs) -> (B,ceil(H/2),ceil(W/2),4*cs): out[Y][X][(py*2+px)*cs + c] = in[2Y+py][2X+px][c], bit for bit
+ * (+0.0 where 2Y+py >= H or 2X+px >= W: the odd row / column).  cs a multiple of 4. */
 int sfh_space_to_depth2(const float* src, float* dst, int batch, int H, int W, int cs, void* stream);
 
 /* scale = gamma / sqrt(var + eps); shift = (conv_bias - mean) * scale + beta
  * (eval-mode BatchNorm2d folded behind the conv; conv_bias may be NULL).
  * With gamma == NULL: scale = 1, shift = conv_bias (plain bias epilogue).
- * `repeat` replicates the n-vector (transposed conv: 4 sub-positions).                    */
+ * `repeat` replicates the n-vector (transposed conv: 4 sub-positions): element i < n * repeat holds channel i % n.
+ * Evaluated as gamma * (1 / sqrtf(var + eps)) in fp32; with gamma == NULL scale is exactly 1 and shift exactly the bias
+ * (+0.0 without one).                                                                       */
 int sfh_fold_bn(const float* conv_bias, const float* gamma, const float* beta,
                 const float* mean, const float* var, float eps, int n, int repeat,
                 float* scale, float* shift, void* stream);
@@ -329,16 +331,25 @@ int sfh_u8hwc_area_to_f32nchw(const uint8_t* src, float* dst, int batch, int C, 
                               const int32_t* xofs, const int32_t* xsi, const float* xalpha, const int32_t* yofs,
                               const int32_t* ysi, const float* ybeta, void* stream);
 
-/* (B, C, H, W) fp32 -> (B, H, W, cs) fp32, channels >= C zero-filled. */
+/* (B, C, H, W) fp32 -> (B, H, W, cs) fp32; cs >= C, a multiple of 4.  Every value is moved bit for bit; the padding lanes
+ * C .. cs-1 of every pixel are written as +0.0. */
 int sfh_nchw_to_nhwc(const float* src, float* dst, int batch, int C, int H, int W, int cs,
                      void* stream);
-/* (B, H, W, cs) -> (B, C, H, W) */
+/* (B, H, W, cs) -> (B, C, H, W), bit for bit; what the padding lanes C .. cs-1 hold does not enter the result. */
 int sfh_nhwc_to_nchw(const float* src, float* dst, int batch, int C, int H, int W, int cs,
                      void* stream);
 
 /* F.interpolate on NCHW planes (planes = B*C): mode 1 = 'bilinear' (align_corners as given; the input
  * resize of forward_unet, models/reconstructor.py:136, uses False), mode 0 = 'nearest' (the logits / uv
- * resize, models/reconstructor.py:153,156). */
+ * resize, models/reconstructor.py:153,156).
+ * Index rules, decided in fp32 as ATen decides them:
+ *   nearest:  source index min(floor(fl32(o * fl32(fl32(in) / fl32(out)))), in - 1) per axis - not floor(o * in / out): 26 -> 22
+ *             reads source 12 at o = 11 where the exact quotient is 13.  A gather, bit for bit; align_corners is ignored.
+ *   bilinear: src = o * fl32((in - 1) / (out - 1)) with align_corners (0 for out = 1), otherwise
+ *             max(0, fl32(in / out) * (o + 0.5) - 0.5); i0 = min(trunc(src), in - 1), i1 = i0 + (i0 < in - 1), l = src - i0;
+ *             value = (1 - ly) * ((1 - lx) * v00 + lx * v01) + ly * ((1 - lx) * v10 + lx * v11), every operation rounded
+ *             (no multiply-add contraction).  The fp32 src carries a few u * src, and the weights with it.
+ * sfh_upsample2x_bilinear_nhwc is the bilinear rule with align_corners and out = 2 * in on NHWC; C a multiple of 4. */
 int sfh_resize_nchw(const float* src, float* dst, int64_t planes, int hs, int ws, int hd, int wd, int mode,
                     int align_corners, void* stream);
 /* nn.Upsample(scale_factor=2, mode='bilinear', align_corners=True) of the bilinear Up variant
@@ -351,7 +362,14 @@ int sfh_upsample2x_bilinear_nhwc(const float* src, float* dst, int batch, int H,
  *   argmax_u8 (B,H,W): argmax over classes == preds_to_masks (utils/postprocess.py:7-18);
  *   stn_in  (B,H,W,stn_cs): [logits(nc), frame channels (3, read from frame_nhwc with
  *   stride frame_cs), zero padding] == torch.cat((logits, x), 1) of
- *   models/reconstructor.py:179,214 in NHWC.                                               */
+ *   models/reconstructor.py:179,214 in NHWC.
+ * cin a multiple of 8 (<= 1024); stn_cs a multiple of 4 with nc + 3 <= stn_cs <= 16, frame_cs >= 3.
+ * stn_in lanes: the logits' own bits, then the frame's first three channels' bits, then +0.0 up to stn_cs; nothing beyond.
+ * argmax rule: best = 0; for k = 1 .. nc-1: if logit[k] > logit[best] then best = k - on the fp32 logits the kernel stores.
+ * A tie goes to the FIRST index.  Non-finite logits: a NaN never compares greater, so a NaN at class 0 stays the answer and
+ * a NaN elsewhere is skipped; +inf wins like any large value.  This differs from the reference's argmax(softmax(.)), which
+ * answers 0 for every pixel that holds a NaN or a +inf ([1, nan, 3, .5] and [1, 2, inf, 0]: 2 here, 0 there) and from it
+ * only there and inside a top-2 margin of 1.2e-7.  The fused head epilogue and sfh_mask_format_fwd share this rule.      */
 int sfh_outconv_fwd(const float* x, int cin, const float* w, const float* bias, int nc,
                     int batch, int H, int W, float* logits_nchw, uint8_t* argmax_u8,
                     float* stn_in, int stn_cs, const float* frame_nhwc, int frame_cs,
@@ -380,7 +398,10 @@ int sfh_poi_project_fwd(const float* theta, const float* poi, int batch, int npt
 /* Consistency score (models/reconstructor.py:226-238): mean over pixels of
  * cross_entropy(logits[:, :, y, x], mask[y, x]).  logits NCHW (B,nc,H,W), mask int32
  * (B,hm,wm) (nearest-resized to HxW when sizes differ), partial: workspace of
- * sfh_ce_workspace_floats(batch, H, W) floats, score: (B).                                */
+ * sfh_ce_workspace_floats(batch, H, W) floats, score: (B).
+ * Mask resize rule: F.interpolate(mode='nearest') in fp32 per axis, source row min(floor(fl32(y * fl32(hm / H))), hm - 1) and
+ * the same with wm / W for the column (the nearest rule of sfh_resize_nchw).  One partial per 2048 pixels of a frame, summed
+ * in a fixed order: a second launch gives the same bits.                                  */
 int64_t sfh_ce_workspace_floats(int batch, int H, int W);
 int sfh_consistency_ce_fwd(const float* logits, const int32_t* mask, int batch, int nc, int H,
                            int W, int hm, int wm, float* partial, float* score, void* stream);
@@ -407,7 +428,8 @@ int sfh_mask_format_fwd(const void* src, int src_kind, int nc, int batch, int hs
                         int wd, int mode, const uint8_t* palette, uint8_t* out, void* stream);
 
 /* ResNetSTN pieces (models/resnet.py:235-254). */
-/* MaxPool2d(kernel 3, stride 2, padding 1) on NHWC (B,H,W,C) -> (B,Ho,Wo,C). */
+/* MaxPool2d(kernel 3, stride 2, padding 1) on NHWC (B,H,W,C) -> (B,Ho,Wo,C), C a multiple of 4.  A selection, bit for bit;
+ * a NaN anywhere in the window is the result (torch's rule), the padding never wins (a window of -inf gives -inf). */
 int sfh_maxpool3x3s2_fwd(const float* x, float* y, int batch, int H, int W, int C, void* stream);
 /* The same pooling written straight into a split tensor (dst_fmt SFH_FMT_H2 with exponent act_exp + the optional overflow /
  * range words of the format, or SFH_FMT_S3): what sfh_maxpool3x3s2_fwd followed by sfh_f32_to_h2 / sfh_f32_to_s3 gives, in
