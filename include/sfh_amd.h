@@ -1422,6 +1422,71 @@ int sfh_refine_step(const double* partial, int64_t slabs, int batch, int first, 
                     float* theta_acc, double* sums_acc, double* lambda, int32_t* pivots_ok, float* theta_next, double* cost,
                     int32_t* accepted, int level, int nlevels, void* stream);
 
+/* -------------------------------------------------------------------------------------------------
+ * Registration metrics (csrc/metrics.hip): how good a homography is against a labelled one, per frame, in the terms the
+ * sports-field registration literature reports - per-class segmentation IoU, IoU_part, IoU_whole, the projection error on the
+ * court and the reprojection error in the frame.  THE RULES, stated here once; the kernels and the numpy restatement
+ * tests/metrics_ref.py follow them.  The reference project has no counterpart.  theta maps the normalised frame to the
+ * normalised court (Reconstructor.warp's matrix); every entry launches on `stream`, synchronises nothing, reads nothing back,
+ * allocates nothing and OVERWRITES its outputs (the caller zero-fills the sticky flag only).
+ *
+ * Matrix of a theta.  m = the nine fp32 entries converted to fp64.  adj(theta) is the fp64 adjugate, the nine expressions of
+ *   inverse_h33 (csrc/warp_coords.h) WITHOUT the multiplication by 1 / det:
+ *     a0 = m4 m8 - m5 m7   a1 = m2 m7 - m1 m8   a2 = m1 m5 - m2 m4
+ *     a3 = m5 m6 - m3 m8   a4 = m0 m8 - m2 m6   a5 = m2 m3 - m0 m5
+ *     a6 = m3 m7 - m4 m6   a7 = m1 m6 - m0 m7   a8 = m0 m4 - m1 m3          det = (m0 a0 + m1 a3) + m2 a6
+ *   every product and difference individually rounded.  A theta is USABLE iff det is finite and != 0 (a non-finite entry
+ *   makes det non-finite).  Where a theta is not usable, theta and adj(theta) both read as the zero matrix in everything below.
+ * Predicate.  in(M, q) for a 3 x 3 fp64 matrix M (row-major) and q = (a, b, c):  X = (M0 a + M1 b) + M2 c, Y and W likewise
+ *   with rows 1 and 2, every operation individually rounded;  in  iff  |W| > 0  and  |X| <= |W|  and  |Y| <= |W|.  A NaN
+ *   anywhere makes it false; the zero matrix makes it false.  The predicate is BLIND TO THE SIGN OF W, on purpose: the warp
+ *   kernel divides by Z whatever its sign, so the predicate selects exactly the points that the model's own warp would draw
+ *   into the square, the ones behind the horizon included.
+ *
+ * sfh_metrics_confusion.  out int64 (B,nc,nc): out[b][g][p] = the number of pixels of frame b with ground-truth class g and
+ *   predicted class p; nc 2 .. 8, H * W < 2^31.  gt int64 (B,H,W); a pixel whose gt is -100 is counted nowhere.  pred by
+ *   pred_kind: 0 int32 ids (B,H,W); 1 uint8 ids (B,H,W); 2 fp32 logits NCHW (B,nc,H,W), the class by the argmax rule stated
+ *   above sfh_outconv_fwd (ties, NaN and +inf as stated there); 3 fp32 (B,H,W) warp mask valued k / nc, class =
+ *   trunc(fl32(v * fl32(nc))), the rule of sfh_eval_batch, valid iff -1 < fl32(v * fl32(nc)) < nc.  *flag (caller-zeroed,
+ *   sticky): bit 1 is ORed for a gt id outside [0, nc) other than -100, bit 2 for a predicted class outside [0, nc) (a
+ *   non-finite kind-3 value included; at a pixel whose gt is -100 too); a pixel with either defect is counted nowhere.
+ *   Two launches: a clear of out, then the count - per wave one step per DISTINCT (g, p) key present (ballot, popcount; lane k
+ *   of a wave keeps the count of key k in a register), per workgroup one LDS word per key, across workgroups 64-bit integer
+ *   atomic adds onto the cleared output (integer addition: the same bits in any order).
+ *
+ * sfh_metrics_region.  out int64 (B,3) = [nA, nB, nAB]: the canvas pixels where in(A, q), in(B, q), and both hold.  The
+ *   canvas is the court raster wc x hc (both >= 2) extended by mx, my >= 0 pixels on each side: x = -mx .. wc-1+mx, y = -my ..
+ *   hc-1+my, fewer than 2^31 pixels, wc, hc, mx, my <= 2^20.  Pixel (x, y) is the homogeneous court point
+ *     q = ((2x - (wc-1)) (hc-1),  (2y - (hc-1)) (wc-1),  (wc-1) (hc-1)),   exact integers (below 2^53) converted to fp64:
+ *   create_meshgrid's (i / (n-1) - 0.5) * 2 raster of sfh_topview_render without its division.
+ *     mode 0 (part):  A = adj(theta_pred), B = adj(theta_gt) - the court pixels from which the frame is visible under each
+ *       theta (use mx = my = 0);  IoU_part = nAB / (nA + nB - nAB).
+ *     mode 1 (whole): A = theta_gt * adj(theta_pred), entry (i, j) = (g[i][0] a[0][j] + g[i][1] a[1][j]) + g[i][2] a[2][j] in
+ *       fp64, and the zero matrix unless both thetas are usable; B = the identity - the image of the court rectangle under
+ *       theta_pred * theta_gt^-1 against the rectangle itself;  IoU_whole by the same formula.  The margin bounds what is
+ *       counted of the image outside the court: that is part of the rule.
+ *   A theta that is not usable gives 0 for the counts that depend on it.  The matrices are formed once per workgroup.
+ *
+ * sfh_metrics_points.  out double (B,4) = [reproj_mean, n_pts, proj_mean, n_lattice], all fp64, one wave per frame.
+ *   Reprojection (frame): court point n = (u, v) of court_pts double (N,2), normalised court coordinates shared by the
+ *     batch, is counted iff in(adj(theta_gt), (u, v, 1)) - it is visible in the ground truth.  With (Xg, Yg, Wg) and (Xp, Yp,
+ *     Wp) its images under adj(theta_gt) and adj(theta_pred) by the predicate's expressions, dx = (Xp / Wp - Xg / Wg)
+ *     frame_sx, dy alike with frame_sy, error = sqrt(dx dx + dy dy).  frame_sx, frame_sy: pixels per normalised frame unit
+ *     (target_w / 2, target_h / 2).
+ *   Projection (court): the frame lattice x_k = -1 + (2k + 1) / gx, k = 0 .. gx-1, y_l alike with gy (1 <= gx, gy <= 4096).
+ *     A lattice point is counted iff in(theta_gt, (x, y, 1)) - it lies on the court.  Its error is the same expression with
+ *     theta_gt and theta_pred in place of the adjugates and court_sx, court_sy (court units per normalised court unit, e.g.
+ *     metres / 2) in place of the frame's.
+ *   Lane l sums the errors of its points l, l + 64, ... in that order, the lanes are added by the fixed shuffle tree of
+ *   sfh_eval_batch; mean = sum / n, so 0 / 0 is written as NaN (no counted point).  A theta_pred that is not usable, or whose
+ *   Wp is 0 at a counted point, yields a non-finite mean: the caller counts such frames instead of hiding them.           */
+int sfh_metrics_confusion(const void* pred, int pred_kind, const int64_t* gt, int nc, int batch, int H, int W, int64_t* out,
+                          uint32_t* flag, void* stream);
+int sfh_metrics_region(const float* theta_pred, const float* theta_gt, int batch, int mode, int wc, int hc, int mx, int my,
+                       int64_t* out, void* stream);
+int sfh_metrics_points(const float* theta_pred, const float* theta_gt, int batch, const double* court_pts, int npts, int gx,
+                       int gy, double frame_sx, double frame_sy, double court_sx, double court_sy, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
