@@ -1487,6 +1487,70 @@ int sfh_metrics_region(const float* theta_pred, const float* theta_gt, int batch
 int sfh_metrics_points(const float* theta_pred, const float* theta_gt, int batch, const double* court_pts, int npts, int gx,
                        int gy, double frame_sx, double frame_sy, double court_sx, double court_sy, double* out, void* stream);
 
+/* -------------------------------------------------------------------------------------------------
+ * Homography fit from the UV head (csrc/uvfit.hip).  The UV map is a dense set of frame -> court correspondences, one per
+ * court pixel in view; a homography fitted to them is an estimate of theta that owes nothing to the STN's nine regressed
+ * numbers, with a quality figure in court pixels.  Iteratively reweighted least squares: every pass is one linear 8 x 8 solve.
+ * THE RULE, stated here once; the kernels and the numpy restatement tests/uvfit_ref.py follow it.  The reference project has
+ * no counterpart.
+ *
+ * Inputs per frame.  uv (2,h,w) fp32 NCHW (the head's output, or a label through preparation.split_uv); optionally logits
+ *   (nc,h,w) and a start theta0 (9) fp32.  (wt, ht): the court raster the UV labels were rendered from (LabelMaker's court_ids
+ *   size; it need not be the court template's).  (W, H): the warp grid theta addresses.
+ * Gate.  Pixel (i, j) counts iff u > u_min and v > v_min, u_min = 0.5 / wt and v_min = 0.5 / ht evaluated in fp64 on the host
+ *   and rounded once to fp32 (a NaN fails; in the labels 0 means "no court here") and, with logits, its class is not 0 by the
+ *   argmax rule stated above sfh_outconv_fwd (strict > scan, first maximum).
+ * Coordinates.  Frame: x = fmaf(ax, j, cx0), y = fmaf(ay, i, cy0) in fp32 with (ax, cx0) = sfh_refine_axis(1, W, w) and (ay,
+ *   cy0) = sfh_refine_axis(1, H, h): the pixel centres on the grid theta addresses; then widened to fp64.  Court: cx = 2 u - kx,
+ *   cy = 2 v - ky in fp64 (u, v widened; 2 u is exact), kx = 1 + 1 / wt, ky = 1 + 1 / ht evaluated in fp64 on the host:
+ *   generate_uv_template gives court column c the value (c + 1) / wt, and the warp's tap rule is px = (cx + 1) wt / 2 - 0.5.
+ * Residual under a theta (its nine fp32 entries widened; theta[8] is used as read):  X = (t0 x + t1 y) + t2, Y and Wd alike
+ *   with rows 1 and 2;  ex = (X / Wd - cx) (wt / 2), ey = (Y / Wd - cy) (ht / 2), r2 = ex ex + ey ey, all fp64, every operation
+ *   individually rounded (no contraction).
+ * Weight.  c = 1 + r2 / d2 with d2 = delta delta (delta in court pixels), omega = (1 / c) / (Wd Wd): the Cauchy weight times the
+ *   factor that turns the algebraic residual into the geometric one to first order.  omega = 0 where |Wd| <= 1e-8 or r2 is not
+ *   finite.  Without a theta (first pass, no theta0): omega = 1.  A pixel with omega == 0 adds nothing to the moments.
+ * Sums.  SFH_UVFIT_SUMS = 27 per frame, fp64, over the gated pixels; with wx = omega x, wy = omega y, m = {wx x, wx y, wy y,
+ *   wx, wy, omega} (the weighted {x^2, xy, y^2, x, y, 1}) and q = cx cx + cy cy:
+ *     0..5    m[0..5]                    6..10   cx m[0..4]              11..15  cy m[0..4]
+ *     16..18  q m[0..2]                  19, 20  omega cx, omega cy      21, 22  q wx, q wy          23  omega q
+ *     24      n: the gated pixels        25      the gated pixels with r2 <= d2
+ *     26      sum of r2 / c over the gated pixels with omega != 0         (25 and 26 are 0 without a theta)
+ * Assembly.  With theta[8] fixed at 1 a pixel gives the rows r1 = [x, y, 1, 0, 0, 0, -cx x, -cx y | cx] and r2 = [0, 0, 0, x,
+ *   y, 1, -cy x, -cy y | cy];  A = sum omega (r1^T r1 + r2^T r2) and g = sum omega (r1^T cx + r2^T cy) are, by sum index,
+ *     A[0..2][0..2] = A[3..5][3..5] = [[0, 1, 3], [1, 2, 4], [3, 4, 5]]      A[0..2][3..5] = 0
+ *     A[0..2][6] = -[6, 7, 9]     A[0..2][7] = -[7, 8, 10]     A[3..5][6] = -[11, 12, 14]     A[3..5][7] = -[12, 13, 15]
+ *     A[6][6] = 16   A[6][7] = 17   A[7][7] = 18   (symmetric)              g = [9, 10, 19, 14, 15, 20, -21, -22]
+ *   and the algebraic cost of an h is  (h^T A h - 2 h^T g) + S23,  h^T A h = sum_i h_i (sum_k A[i][k] h_k), both sums ascending.
+ * Step.  A h = g by Cholesky in fp64, the operation order of sfh_refine_step; no damping, no accept / reject: each pass is a
+ *   linear solve.  theta_next = (fl32(h_0) .. fl32(h_7), 1).  The solve FAILS when a pivot is not > 0, when n < 4 or when one of
+ *   the 27 sums is not finite; a frame whose solve failed is DEAD from then on (status < pass says so).  A frame that fails or
+ *   is dead gets theta_next = theta_eval: the last solved theta, else theta0, else nine NaNs (no theta_eval).  status = the
+ *   number of solves that succeeded.
+ * Schedule.  sfh_uvfit_accumulate(theta0 or NULL) + sfh_uvfit_step(pass 0), then `iters` times accumulate(candidate) + step
+ *   (pass 1 ..), then one accumulate + step with last = 1, which solves nothing, passes theta_eval through and writes the
+ *   statistics of that final theta: 2 (iters + 2) launches on the caller's stream, no synchronisation, no read-back.  Every
+ *   output is overwritten; the library allocates nothing and keeps no pointer. */
+#define SFH_UVFIT_SUMS 27
+/* bytes of the partial sums of sfh_uvfit_accumulate: ceil(w / 64) * ceil(h / 64) * batch * 27 doubles; -1 for batch outside
+ * 1..65535 or h, w < 2 */
+int64_t sfh_uvfit_workspace_bytes(int batch, int h, int w);
+/* The 27 sums per workgroup: uv (batch,2,h,w), logits (batch,nc,h,w) or NULL (then nc is not read; else 2..8), theta (batch,9)
+ * or NULL.  Workgroup (x, y) covers 64 columns x 64 rows of the grid (any h, w >= 2; a tile may be partly outside) and stores
+ * its sums of frame b at workspace[((y * gx + x) * batch + b) * 27 + e], one plain store per sum (wave shuffle, then LDS; no
+ * atomics: the same bits every run).  H, W, wt, ht >= 2, delta > 0; a workspace that is NULL or short returns SFH_E_ARG, as
+ * every refusal does, with nothing launched. */
+int sfh_uvfit_accumulate(const float* uv, const float* logits, int nc, const float* theta, int batch, int h, int w, int H, int W,
+                         int wt, int ht, float u_min, float v_min, double kx, double ky, double delta, void* workspace,
+                         long long workspace_bytes, void* stream);
+/* One wave per frame: sums the `slabs` partials [slab][batch][27] in ascending slab order from 0, assembles, solves and applies
+ * the dead-frame rule.  pass: the number of step calls of this schedule before this one (0: status is not read); last != 0:
+ * nothing is solved.  theta_eval (batch,9): the theta the partials were accumulated under, NULL only on pass 0 without a
+ * theta0; theta_next (batch,9) may be theta_eval.  status (batch) int32.  stats (batch,4) double = [n, inliers (S25),
+ * sqrt(S26 / n), the algebraic cost of theta_next's first eight entries], written on every call. */
+int sfh_uvfit_step(const double* partial, int64_t slabs, int batch, int pass, int last, const float* theta_eval,
+                   float* theta_next, int32_t* status, double* stats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

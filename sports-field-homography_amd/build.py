@@ -14,7 +14,8 @@ LIB = os.path.join(_HERE, "libsfh_amd.so")
 SOURCES = ["capi.hip", "conv_mfma.hip", "conv_s3.hip", "conv_c4h2.hip", "pointwise.hip", "warp.hip", "train_bn.hip", "train_heads.hip",
            "train_wgrad.hip", "train_step.hip", "stem.hip", "wgrad_s3.hip", "probe.hip", "conv_small.hip", "conv_upfused.hip", "conv_inc_fused.hip", "hostprep.hip",
            "eval.hip", "augment.hip", "overlay.hip", "prepare.hip", "mapping.hip", "pngenc.hip", "jpegenc.hip", "resample.hip",
-           "jpegdec.hip", "pngdec.hip", "conv_grouped.hip", "tiffdec.hip", "tiffenc.hip", "det.hip", "refine.hip", "metrics.hip"]
+           "jpegdec.hip", "pngdec.hip", "conv_grouped.hip", "tiffdec.hip", "tiffenc.hip", "det.hip", "refine.hip", "metrics.hip",
+           "uvfit.hip"]
 # warp.hip's coordinate arithmetic must not be contracted into FMAs (bit-exact nearest
 # sampling against oracle/warp_ref.py); the flag is harmless elsewhere.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off",

@@ -131,6 +131,15 @@ SFH_DET_FN DetPlan det_warp_plan(int batch, int h, int w) {   // batch is gridDi
   return det_admit((long)det_warp_gx(w) * det_warp_gy(h), 9L * batch, sizeof(double));
 }
 
+// uvfit_accumulate_kernel (csrc/uvfit.hip): block (bx, by) covers 64 columns x 64 rows of every frame; slab = by * gx + bx,
+// elements [batch][27] (SFH_UVFIT_SUMS).  by is gridDim.y and batch gridDim.z: both at most 65535.
+#define DET_UVFIT_TILE 64
+#define DET_UVFIT_SUMS 27
+SFH_DET_FN DetPlan det_uvfit_plan(int batch, int h, int w) {
+  if (batch <= 0 || batch > 65535 || h < 2 || w < 2 || det_cdiv(h, DET_UVFIT_TILE) > 65535) return det_refuse(DET_BAD_ARG);
+  return det_admit((long)det_cdiv(w, DET_UVFIT_TILE) * det_cdiv(h, DET_UVFIT_TILE), (long)DET_UVFIT_SUMS * batch, sizeof(double));
+}
+
 // ------------------------------------------------------------------ backward-filter, fp32 MFMA (csrc/train_wgrad.hip)
 // 64-pixel tiles of th x tw (the shape with the fewest tiles; ties go to the widest), tile index = (b * nty + ty) * ntx + tx.
 // Split s owns the tiles s, s + nsplit, s + 2 * nsplit, ...: slab of a tile = tile % nsplit.  Slab element of raw[m][tap][n]

@@ -922,14 +922,16 @@ class UNetEngine(_Engine):
         if net.outuv is not None:
             self.outuv = (snapshot(net.outuv.conv.weight), snapshot(net.outuv.conv.bias))
 
-    def run(self, x, want_stn_in=False, want_argmax=False, want_uv=False, stn_slot=0):
+    def run(self, x, want_stn_in=False, want_argmax=False, want_uv=False, stn_slot=0, uv_beside_head=False):
         """x: (B,3,H,W) float32 NCHW on the GPU.  Returns dict with logits (NCHW, fresh),
         and optionally stn_in (NHWC workspace of ceil4(nc + 3) stored channels), argmax (B,H,W uint8), uv, plus the NHWC
-        workspace tensors x_top / y4 for callers that need them (x_top_exp: exponent of x_top if it is H2)."""
+        workspace tensors x_top / y4 for callers that need them (x_top_exp: exponent of x_top if it is H2).
+        uv_beside_head: with want_uv, the logits and stn_in still come from the fused head - the bits a run without want_uv
+        gives - and the last conv also stores y (sfh_conv_desc.head_skip_dst = 0), from which sfh_outconv_fwd takes uv."""
         with _stream_scope():
-            return self._run(x, want_stn_in, want_argmax, want_uv, stn_slot)
+            return self._run(x, want_stn_in, want_argmax, want_uv, stn_slot, uv_beside_head)
 
-    def _run(self, x, want_stn_in, want_argmax, want_uv, stn_slot=0):
+    def _run(self, x, want_stn_in, want_argmax, want_uv, stn_slot=0, uv_beside_head=False):
         """stn_slot: which of the STN-input buffers this pass writes (Reconstructor.predict_async alternates two, so that
         the ResNet of batch k can still read its input while the UNet of batch k + 1 writes the other)"""
         lib = _lib.load()
@@ -1011,9 +1013,10 @@ class UNetEngine(_Engine):
         stn_in = (ws.get("stn_in" if not stn_slot else f"stn_in{stn_slot}", (B, H, W, stn_cs), zero=True)
                   if want_stn_in else None)
         head = None
-        if self.fuse_head and not want_argmax and not (want_uv and self.outuv is not None):
+        uv_here = want_uv and self.outuv is not None
+        if self.fuse_head and not want_argmax and (not uv_here or uv_beside_head):
             head = {"w": self.outc_w, "b": self.outc_b, "nc": self.nc, "logits": logits, "stn": stn_in,
-                    "frame": xin if want_stn_in else None, "skip_dst": True}
+                    "frame": xin if want_stn_in else None, "skip_dst": not uv_here}
         for i in range(1, 5):
             skip, nskip = feats[4 - i]
             hs, ws_ = _hw(skip)
@@ -1087,7 +1090,7 @@ class UNetEngine(_Engine):
                 lib.sfh_outconv_fwd(_ptr(y), 64, _ptr(self.outc_w), _ptr(self.outc_b), self.nc, B, H, W,
                                     _ptr(logits), _ptr(amax), _ptr(stn_in), stn_cs if want_stn_in else 0,
                                     _ptr(xin) if want_stn_in else None, 4, _stream()), "outconv"))
-        else:
+        elif head["skip_dst"]:
             out.pop("y4")   # not materialised: the fused head consumed it in registers
         out["logits"] = logits
         if want_argmax:

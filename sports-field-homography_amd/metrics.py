@@ -348,6 +348,7 @@ def evaluate_registration(net, loader, device, court_pts=None, court_size=None, 
     """Registration metrics of ``net.predict`` over a labelled loader (batches of ``preparation.to_batch``: image, mask, theta)
     -> {"theta": summary, "frames": table} of the theta predict() returns - the refined one where ``net.refiner`` is set - and
     then also {"theta_stn": summary, "frames_stn": table} of the STN's own theta: the pair says whether refinement helps.
+    Where ``net.uv_fitter`` is set, {"theta_uv": summary, "frames_uv": table} score the UV fit on the same frames.
     The segmentation is scored where the logits have the mask's size, the warp mask (of the returned theta) likewise.
     court_pts (N,2) normalised: default the model's ``court_poi``; court_size (wc, hc): default the court template's.  Eval
     mode under no_grad; the net is left in train mode, as eval_reconstructor leaves it."""
@@ -376,7 +377,7 @@ def evaluate_registration(net, loader, device, court_pts=None, court_size=None, 
                     raise ValueError("evaluate_registration: the model predicts no theta (use_resnet=False)")
                 if not acc:
                     fs = (int(gt_mask.shape[-1]), int(gt_mask.shape[-2])) if gt_mask is not None else tuple(net.target_size)
-                    for key in ('theta', 'theta_stn'):
+                    for key in ('theta', 'theta_stn', 'theta_uv'):
                         if key in preds:
                             acc[key] = RegistrationMetrics(nc, court_size, fs, court_pts, units=units, lattice=lattice)
                 fits = lambda t: t is not None and gt_mask is not None and tuple(t.shape[-2:]) == tuple(gt_mask.shape[-2:])  # noqa: E731
@@ -386,6 +387,8 @@ def evaluate_registration(net, loader, device, court_pts=None, court_size=None, 
                 acc['theta'].add(preds['theta'].contiguous(), theta_gt, gt_mask, logits=logits, warp_mask=warp, names=names)
                 if 'theta_stn' in acc:
                     acc['theta_stn'].add(preds['theta_stn'].contiguous(), theta_gt, gt_mask, logits=logits, names=names)
+                if 'theta_uv' in acc:
+                    acc['theta_uv'].add(preds['theta_uv'].contiguous(), theta_gt, gt_mask, logits=logits, names=names)
     finally:
         net.train()
     if not acc:
@@ -395,4 +398,7 @@ def evaluate_registration(net, loader, device, court_pts=None, court_size=None, 
     if 'theta_stn' in acc:
         stn = acc['theta_stn'].table()
         result["theta_stn"], result["frames_stn"] = summarize(stn), stn
+    if 'theta_uv' in acc:
+        fit = acc['theta_uv'].table()
+        result["theta_uv"], result["frames_uv"] = summarize(fit), fit
     return result

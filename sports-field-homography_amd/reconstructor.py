@@ -216,9 +216,26 @@ class Reconstructor(nn.Module):
         # predict() / predict_async(): a refine.ThetaRefiner aligns the STN's theta to the segmentation before warp, consistency
         # score and POI are computed; the STN's own theta is returned as 'theta_stn'.  None: every path and output as before
         self.refiner = None
+        # predict(): a uvfit.UVFit fits a homography to the UV head's output, gated by the logits and started from the STN's
+        # theta where the model has one; it is returned as 'theta_uv' with its statistics 'uv_fit' (B,4) and changes no other
+        # output.  Needs use_unet and unet_uv.  None: every path, key and bit as before
+        self.uv_fitter = None
         self._engine_stamp = None
         self._weights_generation = 0
         self._tmpl_shared = None   # (data_ptr, shape) -> bool cache
+
+    @property
+    def uv_fitter(self):
+        return self.__dict__.get("_uv_fitter")
+
+    @uv_fitter.setter
+    def uv_fitter(self, fitter):
+        if fitter is not None:
+            if not (self.use_unet and self.unet_uv):
+                raise ValueError("uv_fitter needs the UV head: this model has use_unet=%r, unet_uv=%r" % (self.use_unet, self.unet_uv))
+            if not callable(fitter):
+                raise ValueError("uv_fitter must be a uvfit.UVFit (or None)")
+        self.__dict__["_uv_fitter"] = fitter
 
     # ------------------------------------------------------------------ engine plumbing
     def _param_stamp(self):
@@ -663,13 +680,13 @@ class Reconstructor(nn.Module):
         returned from a replay that saturated.  What it buys is bounded by the GPU, not the host: at one frame the launches
         already run back to back (94.6 % busy, profiles/r06_batch1_launch_table.txt), so the wall time drops by the idle 5 % and
         the enqueue latency, 2.19 -> ~2.0 ms; at 8 frames nothing.  For a caller whose own thread is busy (decoding, writing) it
-        returns that thread.  Configurations outside the pipeline's (resize paths, other input modes, sub-batching) fall through to
-        predict()."""
+        returns that thread.  Configurations outside the pipeline's (resize paths, other input modes - 'img+mask+uv' among them -,
+        sub-batching, a refiner or a uv_fitter) fall through to predict()."""
         self._require_eval("predict_replay")
         simple = (self.use_unet and self.use_resnet and x.is_cuda and x.shape[0] > 0 and x.shape[0] <= self._max_frames(x)
                   and not self._needs_resize(x) and self.resnet_input == Input.IMG_AND_MASK
                   and x.dtype == torch.float32 and x.is_contiguous() and E.PackedConv.timer is None
-                  and self.__dict__.get("refiner") is None)
+                  and self.__dict__.get("refiner") is None and self.uv_fitter is None)
         if not simple:
             return self.predict(x, consistency=consistency, project_poi=project_poi)
         cache = self.__dict__.setdefault("_replay", {})
@@ -722,8 +739,8 @@ class Reconstructor(nn.Module):
         recomputed with predict()."""
         self._require_eval("predict_async")
         simple = (self.use_unet and self.use_resnet and x.shape[0] > 0 and x.shape[0] <= self._max_frames(x)
-                  and not self._needs_resize(x) and self.resnet_input == Input.IMG_AND_MASK)
-        if not simple:      # configurations the pipeline does not cover run synchronously
+                  and not self._needs_resize(x) and self.resnet_input == Input.IMG_AND_MASK and self.uv_fitter is None)
+        if not simple:      # configurations the pipeline does not cover ('img+mask+uv' models, a uv_fitter) run synchronously
             return _Done(self.predict(x, consistency=consistency, project_poi=project_poi))
         p = self.__dict__.get("_pipe")
         dev = x.device
@@ -809,28 +826,41 @@ class Reconstructor(nn.Module):
                     ret["consist_score"] = torch.empty((0,), dtype=f32, device=dev)
             if project_poi or not predict:
                 ret["poi"] = torch.empty((0,) + tuple(self.court_poi.shape[1:]), dtype=f32, device=dev)
+        if predict and self.uv_fitter is not None:
+            ret["theta_uv"] = torch.empty((0, 1, 3, 3), dtype=f32, device=dev)
+            ret["uv_fit"] = torch.empty((0, 4), dtype=torch.float64, device=dev)
         return ret
 
     def _predict_one(self, x, off, consistency, project_poi):
         return self._guarded(lambda xi, o: self._predict_phases(xi, o, consistency, project_poi), x, off)
 
     def _predict_phases(self, x, off, consistency, project_poi, stn_slot=0, pipelined=False):
+        fitter = self.uv_fitter
+
         def run_unet(resume=None):
             if not self.use_unet:
                 return None
-            return self._run_unet(x, resume=resume, want_stn_in=self.resnet_input == Input.IMG_AND_MASK, stn_slot=stn_slot)
+            kw = {}
+            if self.use_resnet and self.resnet_input == Input.IMG_AND_MASK_AND_UV:
+                kw["want_uv"] = True      # the unfused head path: logits and uv by sfh_outconv_fwd, as forward() runs it
+            elif fitter is not None:
+                # the logits (and stn_in) stay the fused head's - a uv_fitter changes no bit of them - and the last conv also
+                # stores its output, from which sfh_outconv_fwd takes uv
+                kw["want_uv"] = kw["uv_beside_head"] = True
+            return self._run_unet(x, resume=resume, want_stn_in=self.resnet_input == Input.IMG_AND_MASK, stn_slot=stn_slot, **kw)
 
         def run_stn(r, resume=None):
             if not self.use_resnet:
                 return None
-            if self.resnet_input == Input.IMG_AND_MASK_AND_UV:
-                raise NotImplementedError  # the reference's predict() has no uv branch either (:216)
+            # 'img+mask+uv': cat(logits, x, uv) as forward() assembles it (the reference's predict() has no uv branch, :216)
             return self._stn(x, r, resume=resume, splitk=False if (pipelined and not self.pipeline_splitk) else None)
 
         def tail(r, theta):
             ret = {}
             if r is not None:
                 ret['logits'] = r["logits"]
+            if fitter is not None:
+                ret['theta_uv'], ret['uv_fit'], _ = fitter(r["uv"], r["logits"], theta)
             if theta is not None:
                 refiner = self.__dict__.get("refiner")
                 if refiner is not None:
