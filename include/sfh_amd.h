@@ -1388,7 +1388,8 @@ int sfh_homography_warp_bwd_theta_det(const float* theta, const float* tmpl, int
  *   SFH_REFINE_SUMS = 45 sums per frame, the layout of sfh_prep_fit's step: the upper triangle of J^T J row by row
  *   (36), J^T r (8), the cost (1).
  * Step (Levenberg-Marquardt, the rule of sfh_prep_fit).  Solve (J^T J + lambda diag(J^T J)) delta = -J^T r by Cholesky in
- *   fp64; the candidate is fl32(theta_k + delta_k), k < 8 (the accepted theta itself when a pivot is not > 0).  It is accepted
+ *   fp64 - the operation order is stated once, in csrc/chol8.h, for this step, sfh_prep_fit's and sfh_uvfit_step's.  The
+ *   candidate is fl32(theta_k + delta_k), k < 8 (the accepted theta itself when a pivot is not > 0).  It is accepted
  *   iff every pivot was > 0 and cost(candidate) < cost(accepted) - a NaN cost rejects.  Accepted: lambda / 10; rejected:
  *   lambda * 10; lambda = 1e-3 at the start of every level.  Schedule: the levels from coarse to fine, `iters` steps each.
  *
@@ -1522,7 +1523,7 @@ int sfh_metrics_points(const float* theta_pred, const float* theta_gt, int batch
  *     A[0..2][6] = -[6, 7, 9]     A[0..2][7] = -[7, 8, 10]     A[3..5][6] = -[11, 12, 14]     A[3..5][7] = -[12, 13, 15]
  *     A[6][6] = 16   A[6][7] = 17   A[7][7] = 18   (symmetric)              g = [9, 10, 19, 14, 15, 20, -21, -22]
  *   and the algebraic cost of an h is  (h^T A h - 2 h^T g) + S23,  h^T A h = sum_i h_i (sum_k A[i][k] h_k), both sums ascending.
- * Step.  A h = g by Cholesky in fp64, the operation order of sfh_refine_step; no damping, no accept / reject: each pass is a
+ * Step.  A h = g by Cholesky in fp64, the operation order of csrc/chol8.h; no damping, no accept / reject: each pass is a
  *   linear solve.  theta_next = (fl32(h_0) .. fl32(h_7), 1).  The solve FAILS when a pivot is not > 0, when n < 4 or when one of
  *   the 27 sums is not finite; a frame whose solve failed is DEAD from then on (status < pass says so).  A frame that fails or
  *   is dead gets theta_next = theta_eval: the last solved theta, else theta0, else nine NaNs (no theta_eval).  status = the

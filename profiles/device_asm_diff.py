@@ -23,6 +23,13 @@ kernel count (.amdhsa_kernel directives) and one of
                     a section into which nothing follows (the assembler returns to the section it came from before the
                     file's own sections: .text where the file has a function outside a COMDAT group, .AMDGPU.csdata
                     where it has none) defines nothing and is left out.
+  same up to commuted operands
+                    the two texts have the same number of lines, and every pair of lines that differs is the same v_mul_f64,
+                    v_add_f64, v_mul_f32 or v_add_f32 with the same destination and its two sources - plain registers, no
+                    modifier - exchanged: the compiler met the two factors of a product in the other order.  IEEE
+                    multiplication and addition are commutative bit for bit (for two NaN operands the payload may be the
+                    other one's), so every function computes what it computed, with the same instructions in the same
+                    places.  Exit status 0.
   DIFFERENT         anything else; the first differing sections are shown.  Exit status 1.
 """
 import argparse
@@ -39,6 +46,8 @@ DROP = re.compile(r"^\s*\.(file|ident)\b|clang version|__hip_cuid_|^\s*;.*\.hip"
 # a section of a function: its code, its kernel descriptor, its size and register symbols, its resource comment, its metadata
 OF_FUNCTION = re.compile(r"@function|\.amdhsa_kernel |func_end#|codeLenInByte|^\.agpr_count")
 EMPTY = re.compile(r"\t\.(section\t.*|text)\n\s*")   # a switch to a section that nothing is put into
+REG = r"(?:[vs]\d+|[vs]\[\d+:\d+\])"
+COMMUTES = re.compile(rf"\s*(v_(?:mul|add)_f(?:32|64)(?:_e32|_e64)?)\s+({REG}),\s*({REG}),\s*({REG})\s*")
 DEFAULT = ["train_bn.hip", "train_heads.hip", "train_wgrad.hip", "train_step.hip", "wgrad_s3.hip", "conv_grouped.hip", "warp.hip",
            "det.hip"]
 
@@ -68,6 +77,18 @@ def pooled(files):
     return collections.Counter(s for s in secs if OF_FUNCTION.search(s)), {s for s in secs if not OF_FUNCTION.search(s)}
 
 
+def commuted(parent, this):
+    """every differing line pair is one commutative instruction with its two register sources exchanged"""
+    if len(parent) != len(this):
+        return False
+    for a, b in zip(parent, this):
+        if a != b:
+            ma, mb = COMMUTES.fullmatch(a), COMMUTES.fullmatch(b)
+            if not (ma and mb and ma.group(1, 2, 3, 4) == mb.group(1, 2, 4, 3)):
+                return False
+    return True
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent-tree", required=True)
@@ -93,7 +114,12 @@ def main():
             verdict = "identical"
         else:
             (p, p_own), (t, t_own) = pooled(texts[0]), pooled(texts[1])
-            verdict = "same functions, another order" if p == t and p_own == t_own else "DIFFERENT"
+            if p == t and p_own == t_own:
+                verdict = "same functions, another order"
+            elif commuted(*([ln for f in side for ln in f] for side in texts)):
+                verdict = "same up to commuted operands"
+            else:
+                verdict = "DIFFERENT"
             if verdict == "DIFFERENT":
                 bad = 1
                 for k in list((p - t).keys())[:2] + list((t - p).keys())[:2] + list(p_own ^ t_own)[:2]:

@@ -123,12 +123,6 @@ __device__ __forceinline__ void jitter_chain(const Sample& sp, float mean, float
   }
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-  return v;
-}
-
 // grid (ceil(H / 4), B), 256 threads: wave wv of block x handles row 4x + wv of frame blockIdx.y.  VEC: W % 16 == 0 and the
 // frames 16-byte aligned (checked by the launcher): a lane moves 48 bytes = 16 pixels with three 16-byte loads.
 template <bool VEC>

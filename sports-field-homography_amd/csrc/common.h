@@ -35,6 +35,19 @@ static inline int sfh_cdiv(int a, int b) { return (a + b - 1) / b; }
 // return the other operand.  A non-finite input frame then produces non-finite outputs, as it does in the reference.
 __device__ __forceinline__ float sfh_max_nan(float a, float b) { return (a > b || a != a) ? a : b; }
 
+// Sums over the 64 lanes of a wave in a fixed order.  wave_sum: the halving chain 32 .. 1, the sum arrives in lane 0 (the
+// other lanes hold partial sums).  wave_sum_all: the xor butterfly 32 .. 1, every lane receives the same bits (a + b == b + a).
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
+  return v;
+}
+__device__ __forceinline__ double wave_sum_all(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
 // Kernels that use more than 64 KB of dynamic LDS need hipFuncAttributeMaxDynamicSharedMemorySize raised once
 // per (kernel instance, device).  The template parameter gives every call site its own flag word; bit d of it
 // records device d.  The only process-wide state of the library besides the last-error string: idempotent,

@@ -131,13 +131,21 @@ SFH_DET_FN DetPlan det_warp_plan(int batch, int h, int w) {   // batch is gridDi
   return det_admit((long)det_warp_gx(w) * det_warp_gy(h), 9L * batch, sizeof(double));
 }
 
-// uvfit_accumulate_kernel (csrc/uvfit.hip): block (bx, by) covers 64 columns x 64 rows of every frame; slab = by * gx + bx,
-// elements [batch][27] (SFH_UVFIT_SUMS).  by is gridDim.y and batch gridDim.z: both at most 65535.
-#define DET_UVFIT_TILE 64
-#define DET_UVFIT_SUMS 27
-SFH_DET_FN DetPlan det_uvfit_plan(int batch, int h, int w) {
-  if (batch <= 0 || batch > 65535 || h < 2 || w < 2 || det_cdiv(h, DET_UVFIT_TILE) > 65535) return det_refuse(DET_BAD_ARG);
-  return det_admit((long)det_cdiv(w, DET_UVFIT_TILE) * det_cdiv(h, DET_UVFIT_TILE), (long)DET_UVFIT_SUMS * batch, sizeof(double));
+// refine_accumulate_kernel (csrc/refine.hip) and uvfit_accumulate_kernel (csrc/uvfit.hip): block (bx, by) covers 64 columns
+// x 64 rows of every frame; slab = by * gx + bx, elements [batch][sums], fp64.  batch is gridDim.z: at most 65535.
+#define DET_FIT_TILE 64
+#define DET_REFINE_SUMS 45   // SFH_REFINE_SUMS
+#define DET_UVFIT_SUMS 27    // SFH_UVFIT_SUMS
+SFH_DET_FN DetPlan det_fit_tiles(int batch, int h, int w, int sums) {
+  return det_admit((long)det_cdiv(w, DET_FIT_TILE) * det_cdiv(h, DET_FIT_TILE), (long)sums * batch, sizeof(double));
+}
+SFH_DET_FN DetPlan det_refine_plan(int batch, int h, int w) {   // h x w: the evidence grid of a level
+  if (batch <= 0 || batch > 65535 || h < 1 || w < 1) return det_refuse(DET_BAD_ARG);
+  return det_fit_tiles(batch, h, w, DET_REFINE_SUMS);
+}
+SFH_DET_FN DetPlan det_uvfit_plan(int batch, int h, int w) {    // by is gridDim.y: at most 65535 tile rows
+  if (batch <= 0 || batch > 65535 || h < 2 || w < 2 || det_cdiv(h, DET_FIT_TILE) > 65535) return det_refuse(DET_BAD_ARG);
+  return det_fit_tiles(batch, h, w, DET_UVFIT_SUMS);
 }
 
 // ------------------------------------------------------------------ backward-filter, fp32 MFMA (csrc/train_wgrad.hip)

@@ -69,12 +69,6 @@ __device__ __forceinline__ void eval_pixel(const float (&v)[NC], long long g, fl
   }
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-  return v;
-}
-
 // grid (ceil(H / 4), B), 256 threads: wave wv of block x handles row 4x + wv of frame blockIdx.y.  VEC = 4: W % 4 == 0 and
 // every base pointer 16-byte aligned (checked by the launcher), so each lane moves 16 bytes per logit plane and per warp row
 // and 32 bytes of mask.  logits / warp may be null (the net has no UNet / no warper).

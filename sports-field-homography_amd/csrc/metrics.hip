@@ -282,12 +282,6 @@ __global__ __launch_bounds__(256) void region_kernel(const float* __restrict__ t
 }
 
 // ------------------------------------------------------------------------------------------------------------------ points
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-  return v;
-}
-
 // the error of one point under the two matrices (g: ground truth, p: prediction); counted iff in(g, q)
 __device__ __forceinline__ bool point_error(const double* __restrict__ Mg, const double* __restrict__ Mp, double x, double y,
                                             double sx, double sy, double& err) {

@@ -5,8 +5,8 @@
 // * prep_fit_kernel: one wave per frame, four frames per workgroup.  Lanes run across the points for every sum over points
 //   (slot = point index mod 64, slots combined by an xor butterfly: every lane ends with the same bits, no atomics); the
 //   9 x 9 Jacobi eigen-solve lives in LDS with lanes 0..8 across the rows / columns of a rotation; the 8 x 8 Gauss-Newton
-//   system is solved redundantly by every lane in registers.  All fp64, individually rounded (-ffp-contract=off): the numpy
-//   restatement tests/prep_ref.py follows the same order of operations.
+//   system is solved redundantly by every lane in registers (chol8_solve, chol8.h).  All fp64, individually rounded
+//   (-ffp-contract=off): the numpy restatement tests/prep_ref.py follows the same order of operations.
 // * prep_render_kernel: the nearest warp of the uint8 id image with warp.hip's coordinate arithmetic (warp_coords.h: the
 //   same functions, so the tap is the same), four consecutive pixels per lane: one 4-byte mask store and three 8-byte uv
 //   stores per lane and row, a wave writes 256 / 1536 consecutive bytes.  Taps go through buffer descriptors: an invalid
@@ -14,6 +14,7 @@
 // * prep_rgb_to_ids_kernel: 12 bytes in, 4 bytes out per thread.
 #include "common.h"
 #include "warp_coords.h"
+#include "chol8.h"
 
 namespace {
 
@@ -22,13 +23,6 @@ typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 constexpr int kFitWaves = 4;                          // frames per workgroup
 constexpr int kPer = SFH_PREP_MAX_POINTS / 64;        // points per lane at most
 constexpr int kSums = 45;                             // upper triangle of 9 x 9 = upper triangle of 8 x 8 + 8 + 1
-
-// sum over the 64 lanes; every lane receives the same bits (a + b == b + a)
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 __global__ __launch_bounds__(64 * kFitWaves) void prep_fit_kernel(
     const double* __restrict__ court, const double* __restrict__ manual, const uint8_t* __restrict__ ignore, int batch,
@@ -61,7 +55,7 @@ __global__ __launch_bounds__(64 * kFitWaves) void prep_fit_kernel(
     flag[k] = in && !(ignore && ignore[i]) && !(mx[k] == -1.0 && my[k] == -1.0);
     cnt += use[k] ? 1.0 : 0.0;
   }
-  const double n = wave_sum(cnt);
+  const double n = wave_sum_all(cnt);
   const bool fitted = n >= 4.0;
   const double nd = fitted ? n : 1.0;
 
@@ -74,8 +68,8 @@ __global__ __launch_bounds__(64 * kFitWaves) void prep_fit_kernel(
     s4[2] += use[k] ? fx[k] : 0.0;
     s4[3] += use[k] ? fy[k] : 0.0;
   }
-  const double cx1 = wave_sum(s4[0]) / nd, cy1 = wave_sum(s4[1]) / nd;
-  const double cx2 = wave_sum(s4[2]) / nd, cy2 = wave_sum(s4[3]) / nd;
+  const double cx1 = wave_sum_all(s4[0]) / nd, cy1 = wave_sum_all(s4[1]) / nd;
+  const double cx2 = wave_sum_all(s4[2]) / nd, cy2 = wave_sum_all(s4[3]) / nd;
   double d1 = 0.0, d2 = 0.0;
 #pragma unroll
   for (int k = 0; k < kPer; ++k) {
@@ -83,7 +77,7 @@ __global__ __launch_bounds__(64 * kFitWaves) void prep_fit_kernel(
     d1 += use[k] ? sqrt(ax * ax + ay * ay) : 0.0;
     d2 += use[k] ? sqrt(bx * bx + by * by) : 0.0;
   }
-  const double sc1 = sqrt(2.0) / (wave_sum(d1) / nd), sc2 = sqrt(2.0) / (wave_sum(d2) / nd);
+  const double sc1 = sqrt(2.0) / (wave_sum_all(d1) / nd), sc2 = sqrt(2.0) / (wave_sum_all(d2) / nd);
 
   // ---- L^T L over the usable points
   double acc[kSums];
@@ -110,7 +104,7 @@ __global__ __launch_bounds__(64 * kFitWaves) void prep_fit_kernel(
     for (int i = 0; i < 9; ++i)
 #pragma unroll
       for (int j = i; j < 9; ++j, ++e) {
-        const double s = wave_sum(acc[e]);
+        const double s = wave_sum_all(acc[e]);
         if (lane == 0) {
           A[i * 9 + j] = s;
           A[j * 9 + i] = s;
@@ -194,7 +188,7 @@ __global__ __launch_bounds__(64 * kFitWaves) void prep_fit_kernel(
       const double ry = ((g[3] * tx[k] + g[4] * ty[k]) + g[5]) * iw - fy[k];
       cs += use[k] ? (rx * rx + ry * ry) : 0.0;
     }
-    return wave_sum(cs);
+    return wave_sum_all(cs);
   };
   double lambda = 1e-3;
   for (int it = 0; it < refine; ++it) {
@@ -226,8 +220,8 @@ __global__ __launch_bounds__(64 * kFitWaves) void prep_fit_kernel(
       acc[44] += use[k] ? (rx * rx + ry * ry) : 0.0;
     }
 #pragma unroll
-    for (int e = 0; e < kSums; ++e) acc[e] = wave_sum(acc[e]);
-    // (J^T J + lambda diag(J^T J)) delta = -J^T r by Cholesky; a pivot that is not positive rejects the step
+    for (int e = 0; e < kSums; ++e) acc[e] = wave_sum_all(acc[e]);
+    // (J^T J + lambda diag(J^T J)) delta = -J^T r by chol8.h; a pivot that is not positive rejects the step
     double Lm[8][8], gv[8];
     {
       int e = 0;
@@ -236,37 +230,9 @@ __global__ __launch_bounds__(64 * kFitWaves) void prep_fit_kernel(
 #pragma unroll
         for (int j = i; j < 8; ++j, ++e) Lm[j][i] = (i == j) ? acc[e] + lambda * acc[e] : acc[e];
     }
-    bool ok = true;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      double d = Lm[j][j];
-#pragma unroll
-      for (int k = 0; k < j; ++k) d -= Lm[j][k] * Lm[j][k];
-      ok = ok && (d > 0.0);
-      const double dj = sqrt(ok ? d : 1.0);
-      Lm[j][j] = dj;
-#pragma unroll
-      for (int i = j + 1; i < 8; ++i) {
-        double v = Lm[i][j];
-#pragma unroll
-        for (int k = 0; k < j; ++k) v -= Lm[i][k] * Lm[j][k];
-        Lm[i][j] = v / dj;
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {          // L y = -g
-      double v = -acc[36 + i];
-#pragma unroll
-      for (int k = 0; k < i; ++k) v -= Lm[i][k] * gv[k];
-      gv[i] = v / Lm[i][i];
-    }
-#pragma unroll
-    for (int i = 7; i >= 0; --i) {         // L^T delta = y
-      double v = gv[i];
-#pragma unroll
-      for (int k = i + 1; k < 8; ++k) v -= Lm[k][i] * gv[k];
-      gv[i] = v / Lm[i][i];
-    }
+    for (int i = 0; i < 8; ++i) gv[i] = -acc[36 + i];
+    const bool ok = chol8_solve(Lm, gv, true);
     double hc[9];
 #pragma unroll
     for (int i = 0; i < 8; ++i) hc[i] = h[i] + gv[i];
@@ -315,8 +281,8 @@ __global__ __launch_bounds__(64 * kFitWaves) void prep_fit_kernel(
       o[2] = fitted ? f : 0.0;
     }
   }
-  nz = wave_sum(nz);
-  ds = wave_sum(ds);
+  nz = wave_sum_all(nz);
+  ds = wave_sum_all(ds);
   if (active && lane < 9) {
     theta_c2f[b * 9 + lane] = fitted ? h[lane] : 0.0;
     theta[b * 9 + lane] = fitted ? inv[lane] : 0.0;

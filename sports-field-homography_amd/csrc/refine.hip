@@ -9,16 +9,17 @@
 //   warp_bwd_theta_kernel (warp.hip).  The 45 sums are reduced by wave shuffle, then across the four waves through LDS, and
 //   stored once into the workgroup's slab: the store pass of det_core.h.  No atomics, no workgroup waits for another.
 // * refine_step_kernel: one wave per frame; lanes 0..44 take the ascending chain over the slabs (det_sum), every lane then
-//   holds all 45 sums and solves the 8 x 8 system redundantly in registers, as prep_fit_kernel (prepare.hip) does - the
-//   Cholesky step is stated here a second time so that prepare.hip's instruction stream does not move.
+//   holds all 45 sums and solves the 8 x 8 system redundantly in registers, as prep_fit_kernel (prepare.hip) does: both
+//   call chol8_solve (chol8.h).
 #include "common.h"
 #include "warp_coords.h"
 #include "det_core.h"
+#include "chol8.h"
 
 namespace {
 
 constexpr int kSums = SFH_REFINE_SUMS;   // upper triangle of 8 x 8 (36) + J^T r (8) + cost (1)
-constexpr int kTileW = 64, kTileH = 64, kWaveRows = 16;
+constexpr int kTile = DET_FIT_TILE, kWaveRows = 16;   // a workgroup's 64 x 64 pixels, four waves of 64 x 16
 
 __host__ __device__ inline int refine_cp(int nc) { return nc <= 5 ? 4 : 8; }
 
@@ -104,7 +105,7 @@ __global__ __launch_bounds__(256) void refine_accumulate_kernel(const float* __r
                                                                 float cx, float ay, float cy, double* __restrict__ partial) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int b = blockIdx.z;
-  const int x = blockIdx.x * kTileW + lane;
+  const int x = blockIdx.x * kTile + lane;
   Homog H;
 #pragma unroll
   for (int k = 0; k < 9; ++k) H.t[k] = theta[b * 9 + k];
@@ -116,7 +117,7 @@ __global__ __launch_bounds__(256) void refine_accumulate_kernel(const float* __r
   if (x < we) {
     const float xn = __builtin_fmaf(ax, (float)x, cx);
     for (int r = 0; r < kWaveRows; ++r) {
-      const int y = blockIdx.y * kTileH + wv * kWaveRows + r;
+      const int y = blockIdx.y * kTile + wv * kWaveRows + r;
       if (y >= he) break;
       const float yn = __builtin_fmaf(ay, (float)y, cy);
       const float X = __fadd_rn(__fadd_rn(__fmul_rn(H.t[0], xn), __fmul_rn(H.t[1], yn)), H.t[2]);
@@ -214,7 +215,7 @@ __global__ __launch_bounds__(64) void refine_step_kernel(const double* __restric
 #pragma unroll
   for (int k = 0; k < 9; ++k) ta[k] = take ? te[k] : theta_acc[b * 9 + k];
 
-  // (J^T J + lambda diag(J^T J)) delta = -J^T r by Cholesky; a pivot that is not positive rejects the step (prep_fit_kernel)
+  // (J^T J + lambda diag(J^T J)) delta = -J^T r by chol8.h; a pivot that is not positive rejects the step
   double Lm[8][8], gv[8];
   {
     int e = 0;
@@ -223,37 +224,9 @@ __global__ __launch_bounds__(64) void refine_step_kernel(const double* __restric
 #pragma unroll
       for (int j = i; j < 8; ++j, ++e) Lm[j][i] = (i == j) ? S[e] + lam * S[e] : S[e];
   }
-  bool ok = true;
 #pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    double d = Lm[j][j];
-#pragma unroll
-    for (int k = 0; k < j; ++k) d -= Lm[j][k] * Lm[j][k];
-    ok = ok && (d > 0.0);
-    const double dj = sqrt(ok ? d : 1.0);
-    Lm[j][j] = dj;
-#pragma unroll
-    for (int i = j + 1; i < 8; ++i) {
-      double v = Lm[i][j];
-#pragma unroll
-      for (int k = 0; k < j; ++k) v -= Lm[i][k] * Lm[j][k];
-      Lm[i][j] = v / dj;
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {          // L y = -g
-    double v = -S[36 + i];
-#pragma unroll
-    for (int k = 0; k < i; ++k) v -= Lm[i][k] * gv[k];
-    gv[i] = v / Lm[i][i];
-  }
-#pragma unroll
-  for (int i = 7; i >= 0; --i) {         // L^T delta = y
-    double v = gv[i];
-#pragma unroll
-    for (int k = i + 1; k < 8; ++k) v -= Lm[k][i] * gv[k];
-    gv[i] = v / Lm[i][i];
-  }
+  for (int i = 0; i < 8; ++i) gv[i] = -S[36 + i];
+  const bool ok = chol8_solve(Lm, gv, true);
   if (lane == 0) {
 #pragma unroll
     for (int k = 0; k < 9; ++k) {
@@ -273,10 +246,8 @@ __global__ __launch_bounds__(64) void refine_step_kernel(const double* __restric
 }
 
 // what accumulate, the size query and the step's caller agree on: the slab grid of an evidence grid of h x w
-inline DetPlan refine_plan(int batch, int h, int w) {
-  if (batch <= 0 || batch > 65535 || h < 1 || w < 1) return det_refuse(DET_BAD_ARG);
-  return det_admit((long)det_cdiv(w, kTileW) * det_cdiv(h, kTileH), (long)kSums * batch, sizeof(double));
-}
+// (det_refine_plan, det_core.h)
+static_assert(kSums == DET_REFINE_SUMS, "refine sums");
 
 inline void refine_axis(int f, int n, int nl, float& a, float& c) {
   a = (float)((2.0 * f * n) / ((double)nl * (n - 1)));
@@ -324,7 +295,7 @@ extern "C" int sfh_refine_evidence_planes(const float* logits, int batch, int nc
   return sfh_check_launch("refine_evidence_planes_kernel");
 }
 
-extern "C" int64_t sfh_refine_workspace_bytes(int batch, int h, int w) { return det_bytes(refine_plan(batch, h, w)); }
+extern "C" int64_t sfh_refine_workspace_bytes(int batch, int h, int w) { return det_bytes(det_refine_plan(batch, h, w)); }
 
 extern "C" int sfh_refine_accumulate(const float* theta, const float* tplanes, int64_t tplanes_bstride, int ht, int wt,
                                      const float* eplanes, int batch, int nc, int hl, int wl, int H, int W, int f, void* workspace,
@@ -337,7 +308,7 @@ extern "C" int sfh_refine_accumulate(const float* theta, const float* tplanes, i
   SFH_REQUIRE(ht % f == 0 && wt % f == 0 && hl % f == 0 && wl % f == 0,
               "%s: level %d does not divide the template %dx%d and the logits %dx%d", who, f, wt, ht, wl, hl);
   const int htf = ht / f, wtf = wt / f, he = hl / f, we = wl / f, cp = refine_cp(nc);
-  const DetPlan p = refine_plan(batch, he, we);
+  const DetPlan p = det_refine_plan(batch, he, we);
   SFH_REQUIRE(p.ok, "%s: batch %d (1..65535)", who, batch);
   SFH_REQUIRE((long)htf * wtf * cp < (1L << 29) && (long)batch * he * we * cp < (1L << 31), "%s: planes too large", who);
   SFH_REQUIRE(tplanes_bstride == 0 || (tplanes_bstride >= (int64_t)htf * wtf * cp && tplanes_bstride % 4 == 0),
@@ -349,7 +320,7 @@ extern "C" int sfh_refine_accumulate(const float* theta, const float* tplanes, i
   float ax, cx, ay, cy;
   refine_axis(f, W, wl, ax, cx);
   refine_axis(f, H, hl, ay, cy);
-  const dim3 grid((unsigned)det_cdiv(we, kTileW), (unsigned)det_cdiv(he, kTileH), (unsigned)batch);
+  const dim3 grid((unsigned)det_cdiv(we, kTile), (unsigned)det_cdiv(he, kTile), (unsigned)batch);
   if (cp == 4)
     hipLaunchKernelGGL(refine_accumulate_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, theta, tplanes, (long)tplanes_bstride,
                        htf, wtf, eplanes, he, we, ax, cx, ay, cy, (double*)workspace);

@@ -9,14 +9,15 @@
 //   sums are reduced by wave shuffle, then across the four waves through LDS, and stored once into the workgroup's slab: the
 //   store pass of det_core.h, as refine_accumulate_kernel does it.  No atomics, no workgroup waits for another.
 // * uvfit_step_kernel: one wave per frame; lanes 0..26 take the ascending chain over the slabs (det_sum), every lane then holds
-//   all 27 sums, assembles the 8 x 8 system and solves it redundantly in registers (the Cholesky of refine_step_kernel).
+//   all 27 sums, assembles the 8 x 8 system and solves it redundantly in registers (chol8_solve, chol8.h).
 #include "common.h"
 #include "det_core.h"
+#include "chol8.h"
 
 namespace {
 
 constexpr int kSums = SFH_UVFIT_SUMS;
-constexpr int kTileW = 64, kTileH = 64, kWaveRows = 16;
+constexpr int kTile = DET_FIT_TILE, kWaveRows = 16;   // a workgroup's 64 x 64 pixels, four waves of 64 x 16
 
 template <bool HAS_THETA, bool HAS_LOGITS>
 __global__ __launch_bounds__(256) void uvfit_accumulate_kernel(const float* __restrict__ uv, const float* __restrict__ logits, int nc,
@@ -26,7 +27,7 @@ __global__ __launch_bounds__(256) void uvfit_accumulate_kernel(const float* __re
                                                                double* __restrict__ partial) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int b = blockIdx.z;
-  const int j = blockIdx.x * kTileW + lane;
+  const int j = blockIdx.x * kTile + lane;
   const long plane = (long)h * w;
   double t[9];
 #pragma unroll
@@ -40,7 +41,7 @@ __global__ __launch_bounds__(256) void uvfit_accumulate_kernel(const float* __re
     // the wave's 16 rows of u and v are loaded before any of them is used: 32 independent loads in flight per lane in place
     // of 16 dependent round trips (a row outside the grid reads nothing and holds 0, which the gate refuses); the rows are
     // still ADDED in ascending order
-    const int i0 = blockIdx.y * kTileH + wv * kWaveRows;
+    const int i0 = blockIdx.y * kTile + wv * kWaveRows;
     float ur[kWaveRows], vr[kWaveRows];
 #pragma unroll
     for (int r = 0; r < kWaveRows; ++r) {
@@ -155,38 +156,15 @@ __global__ __launch_bounds__(64) void uvfit_step_kernel(const double* __restrict
   bool ok = !dead && !last && S[24] >= 4.0;
 #pragma unroll
   for (int e = 0; e < kSums; ++e) ok = ok && fabs(S[e]) <= 1.79769313486231570815e308;
-  // A hv = g by Cholesky; a pivot that is not positive fails the solve (refine_step_kernel)
+  // A hv = g by chol8.h (A itself is read again below); a pivot that is not positive fails the solve
   double Lm[8][8], hv[8];
 #pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    double d = A[j][j];
+  for (int i = 0; i < 8; ++i) {
+    hv[i] = g[i];
 #pragma unroll
-    for (int k = 0; k < j; ++k) d -= Lm[j][k] * Lm[j][k];
-    ok = ok && (d > 0.0);
-    const double dj = sqrt(ok ? d : 1.0);
-    Lm[j][j] = dj;
-#pragma unroll
-    for (int i = j + 1; i < 8; ++i) {
-      double v = A[i][j];
-#pragma unroll
-      for (int k = 0; k < j; ++k) v -= Lm[i][k] * Lm[j][k];
-      Lm[i][j] = v / dj;
-    }
+    for (int k = 0; k <= i; ++k) Lm[i][k] = A[i][k];
   }
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {          // L y = g
-    double v = g[i];
-#pragma unroll
-    for (int k = 0; k < i; ++k) v -= Lm[i][k] * hv[k];
-    hv[i] = v / Lm[i][i];
-  }
-#pragma unroll
-  for (int i = 7; i >= 0; --i) {         // L^T h = y
-    double v = hv[i];
-#pragma unroll
-    for (int k = i + 1; k < 8; ++k) v -= Lm[k][i] * hv[k];
-    hv[i] = v / Lm[i][i];
-  }
+  ok = chol8_solve(Lm, hv, ok);
   float tn[9];
 #pragma unroll
   for (int k = 0; k < 9; ++k) tn[k] = ok ? (k < 8 ? (float)hv[k] : 1.0f) : te[k];
@@ -213,7 +191,7 @@ __global__ __launch_bounds__(64) void uvfit_step_kernel(const double* __restrict
 
 // what accumulate, the size query and the step's caller agree on: the slab grid of an h x w grid
 // (det_uvfit_plan, det_core.h)
-static_assert(kTileW == DET_UVFIT_TILE && kTileH == DET_UVFIT_TILE && kSums == DET_UVFIT_SUMS, "uvfit tile / sums");
+static_assert(kSums == DET_UVFIT_SUMS, "uvfit sums");
 
 }  // namespace
 
@@ -234,7 +212,7 @@ extern "C" int sfh_uvfit_accumulate(const float* uv, const float* logits, int nc
   SFH_REQUIRE_WS(who, workspace, workspace_bytes, p);
   float a[2], c[2];
   if (sfh_refine_axis(1, W, w, a) != SFH_OK || sfh_refine_axis(1, H, h, c) != SFH_OK) return SFH_E_ARG;
-  const dim3 grid((unsigned)det_cdiv(w, kTileW), (unsigned)det_cdiv(h, kTileH), (unsigned)batch);
+  const dim3 grid((unsigned)det_cdiv(w, kTile), (unsigned)det_cdiv(h, kTile), (unsigned)batch);
 #define SFH_UVFIT_LAUNCH(T, L)                                                                                                  \
   hipLaunchKernelGGL((uvfit_accumulate_kernel<T, L>), grid, dim3(256), 0, (hipStream_t)stream, uv, logits, nc, theta, h, w, a[0], \
                      a[1], c[0], c[1], 0.5 * wt, 0.5 * ht, u_min, v_min, kx, ky, delta, (double*)workspace)

@@ -1,6 +1,6 @@
 """The stand-alone host programs (tests/*_host_main.cpp, which include the plain-C++ headers of csrc/: the decode cores
-*_core.h, bn_math.h): found compiler and the sanitizer build that tests/test_jpegdec_host.py, tests/test_pngdec_host.py and
-tests/test_train_kernel_host.py share.  A plain module, imported by all three."""
+*_core.h, bn_math.h, chol8.h): found compiler and the sanitizer build that the tests/test_*_host.py files of these programs
+share.  A plain module."""
 import os
 import shutil
 import subprocess

@@ -5,6 +5,8 @@ sums over points in the stated fixed order (slot = index mod 64, butterfly 32 ..
 generate_uv_template, rescale_theta, preprocess_weight, rgb -> ids, and the fp64 form of transform_poi."""
 import numpy as np
 
+from chol8_ref import chol8_solve
+
 SWEEPS = 12
 _IDX = np.arange(64)
 
@@ -112,52 +114,32 @@ def dlt(src, dst, use):
     return h / h[8], eig
 
 
+def gn_system(h, src, dst, use, lam):
+    """the damped normal equations of one Gauss-Newton step at h: (L, b, cost) - the 8 x 8 list of lists J^T J + lam
+    diag(J^T J), the right-hand side -J^T r and the cost |r|^2, sums over points in the fixed order"""
+    x, y = src[:, 0], src[:, 1]
+    z = np.zeros_like(x)
+    iw = 1.0 / ((h[6] * x + h[7] * y) + 1.0)
+    px, py = ((h[0] * x + h[1] * y) + h[2]) * iw, ((h[3] * x + h[4] * y) + h[5]) * iw
+    rx, ry = px - dst[:, 0], py - dst[:, 1]
+    xi, yi = x * iw, y * iw
+    jx = np.stack([xi, yi, iw, z, z, z, -(px * xi), -(px * yi)], axis=1)
+    jy = np.stack([z, z, z, xi, yi, iw, -(py * xi), -(py * yi)], axis=1)
+    JtJ = np.zeros((8, 8))
+    for i in range(8):
+        for j in range(i, 8):
+            JtJ[i, j] = JtJ[j, i] = wave_sum(np.where(use, jx[:, i] * jx[:, j] + jy[:, i] * jy[:, j], 0.0))
+    g = [wave_sum(np.where(use, jx[:, i] * rx + jy[:, i] * ry, 0.0)) for i in range(8)]
+    L = [[JtJ[i, j] + lam * JtJ[i, j] if i == j else JtJ[i, j] for j in range(8)] for i in range(8)]
+    return L, [-v for v in g], wave_sum(np.where(use, rx * rx + ry * ry, 0.0))
+
+
 def refine_gn(h, src, dst, use, steps):
     h = h.copy()
     lam = 1e-3
-    x, y = src[:, 0], src[:, 1]
-    z = np.zeros_like(x)
     for _ in range(steps):
-        iw = 1.0 / ((h[6] * x + h[7] * y) + 1.0)
-        px, py = ((h[0] * x + h[1] * y) + h[2]) * iw, ((h[3] * x + h[4] * y) + h[5]) * iw
-        rx, ry = px - dst[:, 0], py - dst[:, 1]
-        xi, yi = x * iw, y * iw
-        jx = np.stack([xi, yi, iw, z, z, z, -(px * xi), -(px * yi)], axis=1)
-        jy = np.stack([z, z, z, xi, yi, iw, -(py * xi), -(py * yi)], axis=1)
-        JtJ = np.zeros((8, 8))
-        for i in range(8):
-            for j in range(i, 8):
-                JtJ[i, j] = JtJ[j, i] = wave_sum(np.where(use, jx[:, i] * jx[:, j] + jy[:, i] * jy[:, j], 0.0))
-        g = np.array([wave_sum(np.where(use, jx[:, i] * rx + jy[:, i] * ry, 0.0)) for i in range(8)])
-        cost0 = wave_sum(np.where(use, rx * rx + ry * ry, 0.0))
-        L = np.zeros((8, 8))
-        for i in range(8):
-            for j in range(i, 8):
-                L[j, i] = JtJ[i, j] + lam * JtJ[i, j] if i == j else JtJ[i, j]
-        ok = True
-        for j in range(8):
-            d = L[j, j]
-            for k in range(j):
-                d -= L[j, k] * L[j, k]
-            ok = ok and (d > 0.0)
-            dj = np.sqrt(d if ok else 1.0)
-            L[j, j] = dj
-            for i in range(j + 1, 8):
-                v = L[i, j]
-                for k in range(j):
-                    v -= L[i, k] * L[j, k]
-                L[i, j] = v / dj
-        yv = np.zeros(8)
-        for i in range(8):
-            v = -g[i]
-            for k in range(i):
-                v -= L[i, k] * yv[k]
-            yv[i] = v / L[i, i]
-        for i in range(7, -1, -1):
-            v = yv[i]
-            for k in range(i + 1, 8):
-                v -= L[k, i] * yv[k]
-            yv[i] = v / L[i, i]
+        L, yv, cost0 = gn_system(h, src, dst, use, lam)
+        ok = chol8_solve(L, yv, True)
         hc = h.copy()
         hc[:8] = h[:8] + yv
         c1 = forward_cost(hc, src, dst, use)

@@ -28,6 +28,7 @@ cost_margin(npix, cost).  The cost of a theta is evaluated here by one rule for 
 import numpy as np
 
 import step_tail_ref as ST
+from chol8_ref import chol8_solve
 
 F32 = np.float32
 U = 2.0 ** -24
@@ -229,8 +230,9 @@ def cost_margin(npix, cost):
 
 
 # ------------------------------------------------------------------------------------------------ step
-def lm_solve(S, lam):
-    """(delta[8], ok) of (J^T J + lam diag) delta = -J^T r from the 45 sums, in refine_step_kernel's operation order"""
+def lm_system(S, lam):
+    """(L, b): the lower triangle of J^T J + lam diag(J^T J) as an 8 x 8 list of lists and b = -J^T r, from the 45 sums, as
+    refine_step_kernel fills them"""
     S = [float(v) for v in S]
     L = [[0.0] * 8 for _ in range(8)]
     e = 0
@@ -238,31 +240,13 @@ def lm_solve(S, lam):
         for j in range(i, 8):
             L[j][i] = S[e] + lam * S[e] if i == j else S[e]
             e += 1
-    ok = True
-    with np.errstate(all="ignore"):
-        for j in range(8):
-            d = L[j][j]
-            for k in range(j):
-                d -= L[j][k] * L[j][k]
-            ok = ok and (d > 0.0)
-            dj = float(np.sqrt(np.float64(d if ok else 1.0)))
-            L[j][j] = dj
-            for i in range(j + 1, 8):
-                v = L[i][j]
-                for k in range(j):
-                    v -= L[i][k] * L[j][k]
-                L[i][j] = float(np.float64(v) / np.float64(dj))
-        g = [0.0] * 8
-        for i in range(8):
-            v = -S[36 + i]
-            for k in range(i):
-                v -= L[i][k] * g[k]
-            g[i] = float(np.float64(v) / np.float64(L[i][i]))
-        for i in range(7, -1, -1):
-            v = g[i]
-            for k in range(i + 1, 8):
-                v -= L[k][i] * g[k]
-            g[i] = float(np.float64(v) / np.float64(L[i][i]))
+    return L, [-S[36 + i] for i in range(8)]
+
+
+def lm_solve(S, lam):
+    """(delta[8], ok) of (J^T J + lam diag) delta = -J^T r from the 45 sums (chol8_ref)"""
+    L, g = lm_system(S, lam)
+    ok = chol8_solve(L, g, True)
     return g, ok
 
 

@@ -24,6 +24,8 @@ theta_margin_px(theta, wt, ht).  The court-pixel size of 64 float32 ulps of thet
 """
 import numpy as np
 
+from chol8_ref import chol8_solve
+
 F32 = np.float32
 E53 = 2.0 ** -53
 K2 = 1.01
@@ -165,35 +167,11 @@ def assemble(S):
 
 
 def solve(S, allowed=True):
-    """(h[8], ok) of A h = g in uvfit_step_kernel's operation order; ok is False for n < 4, a non-finite sum, a pivot not > 0"""
+    """(h[8], ok) of A h = g as uvfit_step_kernel solves it (chol8_ref); ok is False for n < 4, a non-finite sum, a pivot not > 0"""
     A, g = assemble(S)
     ok = bool(allowed and float(S[24]) >= 4.0 and np.isfinite(np.asarray(S, dtype=np.float64)).all())
-    L = [[0.0] * 8 for _ in range(8)]
-    with np.errstate(all="ignore"):
-        for j in range(8):
-            d = A[j][j]
-            for k in range(j):
-                d -= L[j][k] * L[j][k]
-            ok = ok and (d > 0.0)
-            dj = float(np.sqrt(np.float64(d if ok else 1.0)))
-            L[j][j] = dj
-            for i in range(j + 1, 8):
-                v = A[i][j]
-                for k in range(j):
-                    v -= L[i][k] * L[j][k]
-                L[i][j] = float(np.float64(v) / np.float64(dj))
-        hv = [0.0] * 8
-        for i in range(8):
-            v = g[i]
-            for k in range(i):
-                v -= L[i][k] * hv[k]
-            hv[i] = float(np.float64(v) / np.float64(L[i][i]))
-        for i in range(7, -1, -1):
-            v = hv[i]
-            for k in range(i + 1, 8):
-                v -= L[k][i] * hv[k]
-            hv[i] = float(np.float64(v) / np.float64(L[i][i]))
-    return hv, ok
+    ok = chol8_solve(A, g, ok)      # A and g are this call's own: overwritten by the factor and the solution
+    return g, ok
 
 
 def step(S, pass_, last, theta_eval, status_in):
