@@ -25,11 +25,12 @@ kernel count (.amdhsa_kernel directives) and one of
                     where it has none) defines nothing and is left out.
   same up to commuted operands
                     the two texts have the same number of lines, and every pair of lines that differs is the same v_mul_f64,
-                    v_add_f64, v_mul_f32 or v_add_f32 with the same destination and its two sources - plain registers, no
-                    modifier - exchanged: the compiler met the two factors of a product in the other order.  IEEE
-                    multiplication and addition are commutative bit for bit (for two NaN operands the payload may be the
-                    other one's), so every function computes what it computed, with the same instructions in the same
-                    places.  Exit status 0.
+                    v_add_f64, v_mul_f32, v_add_f32, v_mul_lo_u32 or v_mul_hi_u32 with the same destination and its two
+                    sources - plain registers, no modifier - exchanged, or the same v_mad_u64_u32 (vdst, sdst, src0, src1,
+                    src2) with its two factors src0 and src1 exchanged and everything else the same: the compiler met
+                    the two factors of a product in the other order.  IEEE multiplication and addition are commutative bit for bit (for two NaN operands
+                    the payload may be the other one's) and integer multiplication commutes exactly, so every function
+                    computes what it computed, with the same instructions in the same places.  Exit status 0.
   DIFFERENT         anything else; the first differing sections are shown.  Exit status 1.
 """
 import argparse
@@ -47,7 +48,9 @@ DROP = re.compile(r"^\s*\.(file|ident)\b|clang version|__hip_cuid_|^\s*;.*\.hip"
 OF_FUNCTION = re.compile(r"@function|\.amdhsa_kernel |func_end#|codeLenInByte|^\.agpr_count")
 EMPTY = re.compile(r"\t\.(section\t.*|text)\n\s*")   # a switch to a section that nothing is put into
 REG = r"(?:[vs]\d+|[vs]\[\d+:\d+\])"
-COMMUTES = re.compile(rf"\s*(v_(?:mul|add)_f(?:32|64)(?:_e32|_e64)?)\s+({REG}),\s*({REG}),\s*({REG})\s*")
+COMMUTES = re.compile(rf"\s*(v_(?:(?:mul|add)_f(?:32|64)|mul_(?:lo|hi)_u32)(?:_e32|_e64)?)\s+({REG}),\s*({REG}),\s*({REG})\s*")
+# the 64-bit multiply-add: vdst, sdst (carry out), src0 * src1 + src2
+COMMUTES_MAD = re.compile(rf"\s*(v_mad_u64_u32(?:_e64)?)\s+({REG}),\s*({REG}|vcc),\s*({REG}),\s*({REG}),\s*({REG}|-?\d+)\s*")
 DEFAULT = ["train_bn.hip", "train_heads.hip", "train_wgrad.hip", "train_step.hip", "wgrad_s3.hip", "conv_grouped.hip", "warp.hip",
            "det.hip"]
 
@@ -84,7 +87,9 @@ def commuted(parent, this):
     for a, b in zip(parent, this):
         if a != b:
             ma, mb = COMMUTES.fullmatch(a), COMMUTES.fullmatch(b)
-            if not (ma and mb and ma.group(1, 2, 3, 4) == mb.group(1, 2, 4, 3)):
+            mad_a, mad_b = COMMUTES_MAD.fullmatch(a), COMMUTES_MAD.fullmatch(b)
+            if not (ma and mb and ma.group(1, 2, 3, 4) == mb.group(1, 2, 4, 3)) and not (
+                    mad_a and mad_b and mad_a.group(1, 2, 3, 4, 5, 6) == mad_b.group(1, 2, 3, 5, 4, 6)):
                 return False
     return True
 

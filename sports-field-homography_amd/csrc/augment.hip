@@ -17,6 +17,7 @@
 // The arithmetic restates torchvision.transforms.functional's tensor path op by op in fp32 (augment.reference_apply is the
 // CPU yardstick); -ffp-contract=off keeps every product and sum a separate rounding, as torch's are.
 #include "common.h"
+#include "split_mfma.h"   // u32x4
 
 namespace {
 
@@ -25,7 +26,6 @@ constexpr int kSrcW = kTW + 2, kSrcH = kTH + 2;   // source rectangle of a tile:
 constexpr int kParamWords = 16;
 constexpr int kMaxK = 11;
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef long long i64x2 __attribute__((ext_vector_type(2)));
 
 struct Sample {

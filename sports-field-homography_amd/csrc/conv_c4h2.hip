@@ -15,13 +15,9 @@
 
 #include "common.h"
 #include "conv_epilogue.h"
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+#include "split_mfma.h"
 
 namespace {
-
-constexpr unsigned kOOB = 0xFFFFFFF0u;
 
 struct C4HCfg {  // tile geometry seen by the shared epilogue: 8 rows x 32 cols, 1x16 pixel groups
   static constexpr int SUBX = 2, SH = 1, SW = 16, TH = 8, TW = 32, KS = 3;
@@ -36,8 +32,6 @@ struct C4HGeom {
   unsigned bytes0;
 };
 
-__device__ __forceinline__ f16x8 as_hf(const u32x4& v) { return __builtin_bit_cast(f16x8, v); }
-
 __global__ __launch_bounds__(256, 2) void conv3x3_c4h2_kernel(const sfh_conv_desc d, const C4HGeom g) {
   // halo slots + one slot that stays zero (the padding taps and the k-step-1 lanes without a tap read it)
   __shared__ __attribute__((aligned(16))) u32x4 halo[C4HCfg::HPIX + 1];
@@ -47,10 +41,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c4h2_kernel(const sfh_conv_des
   const int wv = tid >> 6;
   const int lq = lane & 15, lg = lane >> 4;
   const int bid = blockIdx.x;
-  const int xcd = bid & 7, k = bid >> 3;
-  const int nb = k % g.nblk_n;
-  const int tile = (k / g.nblk_n) * 8 + xcd;
-  if (tile >= g.ntiles) return;
+  const SfhWg wg = sfh_wg_round_robin(bid & 7, bid >> 3, g.ntiles, g.nblk_n);
+  if (!wg.live) return;
+  const int nb = wg.nb, tile = wg.tile;
   const int ty = tile / g.tiles_x, tx = tile - ty * g.tiles_x;
   const int x0 = tx * C4HCfg::TW, r0 = ty * C4HCfg::TH;
   const int n0 = nb * 64;
@@ -63,11 +56,11 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c4h2_kernel(const sfh_conv_des
     if (p < C4HCfg::HPIX) {
       const int hy = p / C4HCfg::HW, hx = p - hy * C4HCfg::HW;
       const int r = r0 - 1 + hy, x = x0 - 1 + hx;
-      unsigned off = kOOB;
+      unsigned off = kSfhOOB;
       if (r >= 0 && x >= 0 && x < d.W) {
-        const int b = (int)__umulhi((unsigned)r, g.rows_magic);
-        const int y = r - b * g.rows_per_img;
-        if (b < d.batch && y < d.H) off = (unsigned)((b * d.H + y) * d.W + x) * 16u;
+        int b, y;
+        sfh_row_split(g, r, b, y);
+        if (b < d.batch && y < d.H) off = frame_pixel_offset(b, y, x, d.H, d.W);
       }
       halo[p] = __builtin_amdgcn_raw_buffer_load_b128(rs0, (int)off, 0, 0);
     }
@@ -95,8 +88,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c4h2_kernel(const sfh_conv_des
   for (int ni = 0; ni < 4; ++ni)
 #pragma unroll
     for (int mi = 0; mi < 4; ++mi) acc[ni][mi] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  // the kept partial products, smallest first (as conv_s3.hip): w0 x1 + w1 x0 + w0 x0
-  constexpr int PW[3] = {0, 1, 0}, PX[3] = {1, 0, 0};
+  using P = SplitProducts<2>;
 #pragma unroll
   for (int mi = 0; mi < 4; ++mi) {
     const int sg = wv * 4 + mi;
@@ -111,10 +103,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c4h2_kernel(const sfh_conv_des
 #pragma unroll
     for (int s = 0; s < 2; ++s)
 #pragma unroll
-      for (int q = 0; q < 3; ++q)
+      for (int q = 0; q < P::N; ++q)
 #pragma unroll
-        for (int ni = 0; ni < 4; ++ni)
-          acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_f16(as_hf(wr[s][PW[q]][ni]), as_hf(x[s][PX[q]]), acc[ni][mi], 0, 0, 0);
+        for (int ni = 0; ni < 4; ++ni) acc[ni][mi] = split_mfma<2>(wr[s][P::PW[q]][ni], x[s][P::PX[q]], acc[ni][mi]);
   }
   sfh_conv_epilogue<C4HCfg, 4, 4, 2>(d, g, acc, n0, wv * 4, r0, x0, lq, lg);   // H2 (or fp32) destination
 }
@@ -158,7 +149,7 @@ __global__ __launch_bounds__(256) void frame_to_h2_kernel(const float* __restric
 #pragma unroll
     for (int j = 0; j < 4; ++j) v[j] = j < C ? s[(long)j * HW] : 0.f;
     if (nhwc4) *reinterpret_cast<f32x4*>(nhwc4 + p * 4) = v;
-    sfh_u32x2 pl[2];
+    u32x2 pl[2];
     sfh_split4_h2(v, scale, pl, over);
     fh2[p] = (u32x4){pl[0][0], pl[0][1], pl[1][0], pl[1][1]};
   }
@@ -198,25 +189,16 @@ extern "C" int sfh_conv3x3_c4h2_fwd(const sfh_conv_desc* dp, void* stream_) {
               "conv3x3_c4h2_fwd: needs one FH2 frame source (sfh_frame_to_h2), 3x3 stride 1, a plain output");
   SFH_REQUIRE(d.dst_fmt == SFH_FMT_H2 || d.dst_fmt == SFH_FMT_F32, "conv3x3_c4h2_fwd: the destination is H2 or fp32 (dst_fmt=%d)", d.dst_fmt);
   SFH_REQUIRE(d.cout > 0 && d.cout % 64 == 0 && d.batch > 0 && d.H > 0 && d.W > 0, "conv3x3_c4h2_fwd: bad geometry");
-  SFH_REQUIRE(d.h2_exp_dst >= -64 && d.h2_exp_dst <= 64, "conv3x3_c4h2_fwd: h2_exp_dst=%d out of range (-64 .. 64)", d.h2_exp_dst);
-  SFH_REQUIRE(d.h2_exp_src >= -64 && d.h2_exp_src <= 64, "conv3x3_c4h2_fwd: h2_exp_src=%d out of range (-64 .. 64)", d.h2_exp_src);
+  if (!sfh_h2_exp_ok("conv3x3_c4h2_fwd", "h2_exp_dst", d.h2_exp_dst) || !sfh_h2_exp_ok("conv3x3_c4h2_fwd", "h2_exp_src", d.h2_exp_src))
+    return SFH_E_ARG;
   // the kernel hard-codes 16 bytes per source pixel (two fp16 planes of four channels): anything else would be misread silently
   SFH_REQUIRE(d.src_fmt == SFH_FMT_FH2, "conv3x3_c4h2_fwd: src_fmt=%d, expected SFH_FMT_FH2 (the frame tensor of sfh_frame_to_h2; "
               "an fp32 NHWC4 frame belongs to sfh_conv3x3_c4_fwd)", d.src_fmt);
   SFH_REQUIRE(d.c0 >= 1 && d.c0 <= 4 && d.cs0 == 4, "conv3x3_c4h2_fwd: c0=%d cs0=%d, expected 1..4 channels stored as 4", d.c0, d.cs0);
   C4HGeom g;
-  g.Ho = d.H;
-  g.Wo = d.W;
-  g.tiles_x = sfh_cdiv(g.Wo, C4HCfg::TW);
-  int zr = 1;
-  if ((g.Ho + zr) & 1) ++zr;
-  g.rows_per_img = g.Ho + zr;
-  g.rows_total = d.batch * g.rows_per_img;
-  g.rows_magic = (unsigned)((1ULL << 32) / (unsigned)g.rows_per_img) + 1u;
-  SFH_REQUIRE((unsigned long long)(g.rows_total + 64) * g.rows_per_img < (1ULL << 32), "conv3x3_c4h2_fwd: too many rows");
-  g.ntiles = g.tiles_x * sfh_cdiv(g.rows_total, C4HCfg::TH);
+  SFH_REQUIRE(sfh_conv_grid(g, d.batch, d.H, d.W, 3, 1, true, true, C4HCfg::TH, C4HCfg::TW), "conv3x3_c4h2_fwd: too many rows");
   const unsigned long long b0 = 16ULL * d.batch * d.H * d.W;
-  SFH_REQUIRE(b0 < kOOB, "conv3x3_c4h2_fwd: source exceeds the 4 GiB descriptor range");
+  SFH_REQUIRE(sfh_fits_descriptor(b0), "conv3x3_c4h2_fwd: source exceeds the 4 GiB descriptor range");
   g.bytes0 = (unsigned)b0;
   g.nblk_n = d.cout / 64;
   const long nblocks = (long)sfh_cdiv(g.ntiles, 8) * 8 * g.nblk_n;

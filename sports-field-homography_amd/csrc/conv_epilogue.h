@@ -9,19 +9,17 @@
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 
 #include "common.h"
-
-typedef unsigned int sfh_u32x2 __attribute__((ext_vector_type(2)));
+#include "split_mfma.h"
 
 typedef float sfh_f32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 sfh_bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int sfh_u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ unsigned sfh_cvt_pk(float a, float b) {  // v_cvt_pk_bf16_f32 (RNE)
   return __builtin_bit_cast(unsigned, __builtin_convertvector((sfh_f32x2){a, b}, sfh_bf16x2));
 }
 
 // three-plane split of 4 fp32 values with packed conversions: out[p] = 4 bf16 (8 bytes) of plane p
-__device__ __forceinline__ void sfh_split4(const f32x4& v, sfh_u32x2 (&out)[3]) {
+__device__ __forceinline__ void sfh_split4(const f32x4& v, u32x2 (&out)[3]) {
   f32x4 r = v;
 #pragma unroll
   for (int p = 0; p < 3; ++p) {
@@ -51,6 +49,12 @@ constexpr float kSfhH2Max = 65504.f;
 __device__ __forceinline__ bool sfh_h2_out_of_range(unsigned over) { return over > 0x477FE000u; }   // bits of 65504.f
 // 2^e for a tensor exponent -64 <= e <= 64 (exact: the bit pattern of the power of two)
 __device__ __forceinline__ float sfh_h2_pow2(int e) { return __builtin_bit_cast(float, (unsigned)(127 + e) << 23); }
+// ... which every launcher checks for the exponents its kernel reads (who / field: for the message)
+static inline bool sfh_h2_exp_ok(const char* who, const char* field, int e) {
+  if (e >= -64 && e <= 64) return true;
+  sfh_set_error("%s: %s=%d out of range (-64 .. 64)", who, field, e);
+  return false;
+}
 
 __device__ __forceinline__ unsigned sfh_cvt_pk_h(float a, float b) {  // v_cvt_pk_f16_f32 (RNE)
   return __builtin_bit_cast(unsigned, __builtin_convertvector((sfh_f32x2){a, b}, sfh_f16x2));
@@ -59,7 +63,7 @@ __device__ __forceinline__ sfh_f32x2 sfh_unpack_h(unsigned w) {
   return __builtin_convertvector(__builtin_bit_cast(sfh_f16x2, w), sfh_f32x2);
 }
 
-__device__ __forceinline__ void sfh_split4_h2(const f32x4& v, float scale, sfh_u32x2 (&out)[2], unsigned& over) {
+__device__ __forceinline__ void sfh_split4_h2(const f32x4& v, float scale, u32x2 (&out)[2], unsigned& over) {
   f32x4 u;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
@@ -137,8 +141,6 @@ struct sfh_cfg_ngrp { static constexpr int value = 1 << 30; };
 template <class CFG>
 struct sfh_cfg_ngrp<CFG, decltype((void)CFG::NGRP)> { static constexpr int value = CFG::NGRP; };
 
-constexpr unsigned kSfhOOB = 0xFFFFFFF0u;  // byte offset that the buffer range check rejects
-
 // CFG supplies SUBX, SH, SW, FLATROWS; G supplies Ho, Wo, rows_total, rows_per_img, rows_magic.
 // All global accesses are buffer loads/stores with 32-bit byte offsets: a pixel outside the frame
 // carries kSfhOOB and its stores are dropped by the descriptor's range check (no branches, no
@@ -213,10 +215,7 @@ __device__ __forceinline__ void sfh_conv_epilogue(const sfh_conv_desc& d, const 
     int b, y;
     bool ok = x < g.Wo && s < sfh_cfg_ngrp<CFG>::value;
     if (CFG::FLATROWS) {
-      const int r = r0 + oy;
-      b = (int)__umulhi((unsigned)r, g.rows_magic);
-      y = r - b * g.rows_per_img;
-      ok = ok && r < g.rows_total && y < g.Ho;
+      ok = sfh_row_split(g, r0 + oy, b, y, ok);
     } else {
       b = r0 >> 16;
       y = (r0 & 0xFFFF) + oy;
@@ -264,8 +263,8 @@ __device__ __forceinline__ void sfh_conv_epilogue(const sfh_conv_desc& d, const 
             f32x4 q = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int p = 1; p >= 0; --p) {
-              const sfh_u32x2 w = __builtin_bit_cast(
-                  sfh_u32x2, __builtin_amdgcn_raw_buffer_load_b64(rr_, (int)voff[mi], (int)(nioff + p * planeb), 0));
+              const u32x2 w = __builtin_bit_cast(
+                  u32x2, __builtin_amdgcn_raw_buffer_load_b64(rr_, (int)voff[mi], (int)(nioff + p * planeb), 0));
               const sfh_f32x2 a = sfh_unpack_h(w[0]), b = sfh_unpack_h(w[1]);
               q[0] += a[0]; q[1] += a[1]; q[2] += b[0]; q[3] += b[1];
             }
@@ -275,8 +274,8 @@ __device__ __forceinline__ void sfh_conv_epilogue(const sfh_conv_desc& d, const 
         } else if (res_s3) {
 #pragma unroll
           for (int p = 2; p >= 0; --p) {
-            const sfh_u32x2 w = __builtin_bit_cast(
-                sfh_u32x2, __builtin_amdgcn_raw_buffer_load_b64(rr_, (int)voff[mi], (int)(nioff + p * planeb), 0));
+            const u32x2 w = __builtin_bit_cast(
+                u32x2, __builtin_amdgcn_raw_buffer_load_b64(rr_, (int)voff[mi], (int)(nioff + p * planeb), 0));
             v[0] += __builtin_bit_cast(float, w[0] << 16);
             v[1] += __builtin_bit_cast(float, w[0] & 0xFFFF0000u);
             v[2] += __builtin_bit_cast(float, w[1] << 16);
@@ -307,7 +306,7 @@ __device__ __forceinline__ void sfh_conv_epilogue(const sfh_conv_desc& d, const 
       acc[ni][mi] = v;
       if (h2) {
         if constexpr ((FMTS & 2) != 0) {
-          sfh_u32x2 pl[2];
+          u32x2 pl[2];
           // lanes past the frame (tile round-up, the shared zero rows) compute a value from the taps that still reach the
           // frame and store nothing: they must not raise the tensor's words
           unsigned o = 0u;
@@ -319,13 +318,13 @@ __device__ __forceinline__ void sfh_conv_epilogue(const sfh_conv_desc& d, const 
             __builtin_amdgcn_raw_buffer_store_b64(pl[p], rd, (int)voff[mi], (int)(nioff + p * planeb), 0);
         }
       } else if (s3) {
-        sfh_u32x2 pl[3];
+        u32x2 pl[3];
         sfh_split4(v, pl);
 #pragma unroll
         for (int p = 0; p < 3; ++p)
           __builtin_amdgcn_raw_buffer_store_b64(pl[p], rd, (int)voff[mi], (int)(nioff + p * planeb), 0);
       } else {
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(sfh_u32x4, v), rd, (int)voff[mi], (int)nioff, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rd, (int)voff[mi], (int)nioff, 0);
       }
     }
   }
@@ -373,7 +372,7 @@ __device__ __forceinline__ void sfh_conv_epilogue(const sfh_conv_desc& d, const 
         const unsigned nioff = pni_off(ni);
         if (h2) {
           if constexpr ((FMTS & 2) != 0) {
-            sfh_u32x2 pl[2];
+            u32x2 pl[2];
             unsigned dummy = 0u;   // the pooled values are a subset of the values checked above
             sfh_split4_h2(m, h2_dst_scale, pl, dummy);
 #pragma unroll
@@ -381,13 +380,13 @@ __device__ __forceinline__ void sfh_conv_epilogue(const sfh_conv_desc& d, const 
               __builtin_amdgcn_raw_buffer_store_b64(pl[p], rp, (int)pv, (int)(nioff + p * pplaneb), 0);
           }
         } else if (s3) {
-          sfh_u32x2 pl[3];
+          u32x2 pl[3];
           sfh_split4(m, pl);
 #pragma unroll
           for (int p = 0; p < 3; ++p)
             __builtin_amdgcn_raw_buffer_store_b64(pl[p], rp, (int)pv, (int)(nioff + p * pplaneb), 0);
         } else {
-          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(sfh_u32x4, m), rp, (int)pv, (int)nioff, 0);
+          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, m), rp, (int)pv, (int)nioff, 0);
         }
       }
     }

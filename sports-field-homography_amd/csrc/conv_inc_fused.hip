@@ -22,14 +22,9 @@
 
 #include "common.h"
 #include "conv_epilogue.h"
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+#include "split_mfma.h"
 
 namespace {
-
-constexpr unsigned kOOB = 0xFFFFFFF0u;
 
 struct IFCfg {   // geometry as S3Cfg<3, 1, 1, 16, 8, 32, 2> (conv_s3.hip) + the frame halo
   static constexpr int KS = 3, NP = 2, NWN = 2, NWM = 2, NT = 256, NTAP = 9;
@@ -63,8 +58,6 @@ struct IFGeom {
   unsigned rows_magic;
 };
 
-__device__ __forceinline__ f16x8 as_hf(const u32x4& v) { return __builtin_bit_cast(f16x8, v); }
-
 __global__ __launch_bounds__(IFCfg::NT, 2) void conv_inc_fused_kernel(const sfh_conv_desc d, const IFProd pr, const IFGeom g) {
   using C = IFCfg;
   extern __shared__ __attribute__((aligned(16))) float smem_f[];
@@ -78,13 +71,10 @@ __global__ __launch_bounds__(IFCfg::NT, 2) void conv_inc_fused_kernel(const sfh_
   const int wm = wv / C::NWN, wn = wv % C::NWN;
   const int lq = lane & 15, lg = lane >> 4;
 
-  // tile order of conv_s3_kernel with one cout block: every XCD owns a contiguous range of tiles, walked backwards on request
   const int bid = (int)blockIdx.x;
-  const int xcd = bid & 7, rr = bid >> 3;
-  const int tpx = (g.ntiles + 7) >> 3;
-  const int tl = d.reverse_tiles ? tpx - 1 - rr : rr;
-  const int tile = xcd * tpx + tl;
-  if (tile >= g.ntiles) return;
+  const SfhWg wg = sfh_wg_xcd_range_one(bid & 7, bid >> 3, g.ntiles, d.reverse_tiles);
+  if (!wg.live) return;
+  const int tile = wg.tile;
   const int ty = tile / g.tiles_x, tx = tile - ty * g.tiles_x;
   const int x0 = tx * C::TW, r0 = ty * C::TH;
 
@@ -98,11 +88,11 @@ __global__ __launch_bounds__(IFCfg::NT, 2) void conv_inc_fused_kernel(const sfh_
       if (p < C::FPIX) {
         const int hy = p / C::FW, hx = p - hy * C::FW;
         const int r = r0 - 2 + hy, x = x0 - 2 + hx;
-        unsigned off = kOOB;
+        unsigned off = kSfhOOB;
         if (r >= 0 && x >= 0 && x < d.W) {
-          const int b = (int)__umulhi((unsigned)r, g.rows_magic);
-          const int y = r - b * g.rows_per_img;
-          if (b < d.batch && y < d.H) off = (unsigned)((b * d.H + y) * d.W + x) * 16u;
+          int b, y;
+          sfh_row_split(g, r, b, y);
+          if (b < d.batch && y < d.H) off = frame_pixel_offset(b, y, x, d.H, d.W);
         }
         fh[p] = __builtin_amdgcn_raw_buffer_load_b128(rsf, (int)off, 0, 0);
       }
@@ -115,7 +105,7 @@ __global__ __launch_bounds__(IFCfg::NT, 2) void conv_inc_fused_kernel(const sfh_
   const int ta = 2 * lg, tb = 2 * lg + 1;
   const int oa = (ta / 3) * C::FW + ta % 3, ob = (tb / 3) * C::FW + tb % 3;
   constexpr int O8 = 2 * C::FW + 2;
-  constexpr int PW[3] = {0, 1, 0}, PX[3] = {1, 0, 0};   // the kept partial products, smallest first: w0 x1 + w1 x0 + w0 x0
+  using P = SplitProducts<IFCfg::NP>;
   const float mid_scale = sfh_h2_pow2(pr.exp_mid);
   unsigned over_mid = 0u;
   auto produce = [&](int st) {
@@ -152,14 +142,13 @@ __global__ __launch_bounds__(IFCfg::NT, 2) void conv_inc_fused_kernel(const sfh_
 #pragma unroll
       for (int s = 0; s < 2; ++s)
 #pragma unroll
-        for (int k3 = 0; k3 < 3; ++k3)
+        for (int k3 = 0; k3 < P::N; ++k3)
 #pragma unroll
-          for (int ni = 0; ni < 2; ++ni)
-            pa[ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(as_hf(pw[s][PW[k3]][ni]), as_hf(x[s][PX[k3]]), pa[ni], 0, 0, 0);
+          for (int ni = 0; ni < 2; ++ni) pa[ni] = split_mfma<IFCfg::NP>(pw[s][P::PW[k3]][ni], x[s][P::PX[k3]], pa[ni]);
       // the first conv's epilogue (as sfh_conv_epilogue's pass 1 for an H2 destination) into the stage buffer
       const int r = r0 - 1 + hy, xx = x0 - 1 + hx;
-      const int b = (int)__umulhi((unsigned)r, g.rows_magic);
-      const int y = r - b * g.rows_per_img;
+      int b, y;
+      sfh_row_split(g, r, b, y);
       const bool in_frame = real && r >= 0 && b < d.batch && y < d.H && (unsigned)xx < (unsigned)d.W;
       const bool interior = real && hy >= 1 && hy <= C::TH && hx >= 1 && hx <= C::TW;
 #pragma unroll
@@ -174,7 +163,7 @@ __global__ __launch_bounds__(IFCfg::NT, 2) void conv_inc_fused_kernel(const sfh_
 #pragma unroll
           for (int j = 0; j < 4; ++j) v[j] = sfh_relu(v[j]);
         }
-        sfh_u32x2 pl[2];
+        u32x2 pl[2];
         unsigned o = 0u;
         sfh_split4_h2(v, mid_scale, pl, o);
         o = (interior && in_frame) ? o : 0u;   // (as sfh_conv_epilogue: only pixels of the tensor enter the words)
@@ -203,17 +192,18 @@ __global__ __launch_bounds__(IFCfg::NT, 2) void conv_inc_fused_kernel(const sfh_
 
   // ---- consumer: conv_s3_kernel's single-buffer H2 stage body on the stage buffer
   constexpr int NP = C::NP;
-  constexpr unsigned WTAP = (unsigned)NP * 4u * 1024u;          // bytes per (stage, tap)
+  using WS = SplitWeights<NP>;
+  constexpr unsigned WTAP = WS::TAP;
   constexpr unsigned wtotal = 2u * C::NTAP * WTAP;              // [stage 2][tap 9][plane 2][cout group 4][lane 64][8 x fp16]
   const __amdgpu_buffer_rsrc_t rsw =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(d.wpacked), 0, (int)wtotal, 0x00020000);
-  const unsigned wvoff = lane * 16u + (unsigned)(2 * wn) * 1024u;
+  const unsigned wvoff = lane * 16u + (unsigned)(2 * wn) * WS::GROUP;
   auto load_w = [&](u32x4 (&w)[NP][2], unsigned soff) {
 #pragma unroll
     for (int p = 0; p < NP; ++p)
 #pragma unroll
       for (int ni = 0; ni < 2; ++ni)
-        w[p][ni] = __builtin_amdgcn_raw_buffer_load_b128(rsw, (int)(wvoff + ni * 1024u), (int)(soff + p * 4096u), 0);
+        w[p][ni] = __builtin_amdgcn_raw_buffer_load_b128(rsw, (int)(wvoff + ni * WS::GROUP), (int)(soff + p * WS::PLANE), 0);
   };
   const int pixbase0 = lg * C::HPIXP + ((wm * C::MT_M / C::SUBX) * C::SH + lq / C::SW) * C::HW + (lq % C::SW);
   static_assert(C::MT_M % C::SUBX == 0, "a wave's pixel groups must start on a tile-row boundary");
@@ -251,10 +241,9 @@ __global__ __launch_bounds__(IFCfg::NT, 2) void conv_inc_fused_kernel(const sfh_
       if (s + XD < NSTEP) ld_x(s + XD, (s + XD) % (XD + 1));
       if (mi == 0 && t + 1 < C::NTAP) load_w(wnx, (unsigned)(ST * C::NTAP + t + 1) * WTAP);  // next tap: one tap of MFMAs ahead
 #pragma unroll
-      for (int k3 = 0; k3 < 3; ++k3)
+      for (int k3 = 0; k3 < P::N; ++k3)
 #pragma unroll
-        for (int ni = 0; ni < 2; ++ni)
-          acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_f16(as_hf(wc[PW[k3]][ni]), as_hf(xq[xb][PX[k3]]), acc[ni][mi], 0, 0, 0);
+        for (int ni = 0; ni < 2; ++ni) acc[ni][mi] = split_mfma<NP>(wc[P::PW[k3]][ni], xq[xb][P::PX[k3]], acc[ni][mi]);
       // as conv_s3_kernel: each step's memory instructions stay inside the step, the next operand reads right behind the
       // first MFMA
       __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
@@ -293,7 +282,7 @@ extern "C" int sfh_conv_inc_fused_fwd(const sfh_conv_desc* inc0, const sfh_conv_
               "the FH2 frame tensor and an H2 intermediate", a.src_fmt, a.dst_fmt);
   SFH_REQUIRE(a.c0 >= 1 && a.c0 <= 4 && a.cs0 == 4 && a.cout == 64, "conv_inc_fused_fwd: first conv: c0=%d cs0=%d cout=%d, expected "
               "1..4 channels stored as 4 and 64 output channels", a.c0, a.cs0, a.cout);
-  SFH_REQUIRE(a.h2_exp_dst >= -64 && a.h2_exp_dst <= 64, "conv_inc_fused_fwd: first conv: h2_exp_dst=%d out of range (-64 .. 64)", a.h2_exp_dst);
+  if (!sfh_h2_exp_ok("conv_inc_fused_fwd: first conv", "h2_exp_dst", a.h2_exp_dst)) return SFH_E_ARG;
   // the second conv: a plain 64 -> 64 3x3 stride-1 H2 launch of sfh_conv_s3_fwd (src0 is not used: its source never exists)
   SFH_REQUIRE(d.wpacked && d.scale && d.shift && d.dst, "conv_inc_fused_fwd: second conv: null pointer");
   SFH_REQUIRE(d.src_fmt == SFH_FMT_H2 && d.dst_fmt == SFH_FMT_H2, "conv_inc_fused_fwd: second conv: src_fmt=%d dst_fmt=%d, expected H2",
@@ -306,23 +295,14 @@ extern "C" int sfh_conv_inc_fused_fwd(const sfh_conv_desc* inc0, const sfh_conv_
               "conv_inc_fused_fwd: the two convs disagree on the frame (%d x %d x %d / %d x %d x %d)", a.batch, a.H, a.W, d.batch, d.H, d.W);
   SFH_REQUIRE(d.h2_exp_src == a.h2_exp_dst, "conv_inc_fused_fwd: the intermediate's exponent differs (%d written, %d read)",
               a.h2_exp_dst, d.h2_exp_src);
-  SFH_REQUIRE(d.h2_exp_dst >= -64 && d.h2_exp_dst <= 64, "conv_inc_fused_fwd: second conv: h2_exp_dst=%d out of range (-64 .. 64)", d.h2_exp_dst);
+  if (!sfh_h2_exp_ok("conv_inc_fused_fwd: second conv", "h2_exp_dst", d.h2_exp_dst)) return SFH_E_ARG;
   SFH_REQUIRE(d.dst_cs >= 64 && d.dst_cs % 32 == 0 && (!d.dst_pool || (d.pool_cs >= 64 && d.pool_cs % 32 == 0)),
               "conv_inc_fused_fwd: dst_cs=%d / pool_cs=%d must be multiples of 32, at least 64", d.dst_cs, d.pool_cs);
   IFGeom g;
-  g.Ho = d.H;
-  g.Wo = d.W;
-  g.tiles_x = sfh_cdiv(g.Wo, IFCfg::TW);
-  int zr = 1;
-  if ((g.Ho + zr) & 1) ++zr;   // even rows per frame: 2x2 pool windows never straddle a tile edge
-  g.rows_per_img = g.Ho + zr;
-  g.rows_total = d.batch * g.rows_per_img;
-  g.rows_magic = (unsigned)((1ULL << 32) / (unsigned)g.rows_per_img) + 1u;
-  SFH_REQUIRE((unsigned long long)(g.rows_total + 64) * g.rows_per_img < (1ULL << 32), "conv_inc_fused_fwd: too many rows");
-  g.ntiles = g.tiles_x * sfh_cdiv(g.rows_total, IFCfg::TH);
+  SFH_REQUIRE(sfh_conv_grid(g, d.batch, d.H, d.W, 3, 1, true, true, IFCfg::TH, IFCfg::TW), "conv_inc_fused_fwd: too many rows");
   const unsigned long long fb = 16ULL * d.batch * d.H * d.W;
   const unsigned long long db = 4ULL * d.batch * d.H * d.W * d.dst_cs;
-  SFH_REQUIRE(fb < kOOB && db < kOOB, "conv_inc_fused_fwd: a tensor exceeds the 4 GiB descriptor range; split the batch");
+  SFH_REQUIRE(sfh_fits_descriptor(fb) && sfh_fits_descriptor(db), "conv_inc_fused_fwd: a tensor exceeds the 4 GiB descriptor range; split the batch");
   IFProd pr;
   pr.frame = a.src0;
   pr.wpacked = a.wpacked;

@@ -61,8 +61,6 @@ struct ConvCfg {
   // padding before / after: 3x3 -> 1/1, 1x1 -> 0/0, 4x4 (space-to-depth stem) -> 2/1
   static constexpr int PAD = KS / 2;
   static constexpr int PADA = (KS - 1) / 2;
-  // zero rows shared between consecutive frames in the flattened row space (>= pad)
-  static constexpr int ZROWS = PAD;
   static constexpr int NTAP = KS * KS * NSUB;
   // taps per LDS stage: the 16-tap 4x4 stem stages its weights in two halves
   static constexpr int TPS = NTAP > 9 ? NTAP / 2 : NTAP;
@@ -93,10 +91,7 @@ struct ConvGeom {
   unsigned bytes0, bytes1;  // byte sizes of the two source tensors (buffer range check)
 };
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-constexpr unsigned kOOB = 0xFFFFFFF0u;  // voffset of a halo slot that must read zeros
-
-// 16-byte buffer load: out-of-range offsets (kOOB) return zeros without a branch; the
+// 16-byte buffer load: out-of-range offsets (kSfhOOB) return zeros without a branch; the
 // per-stage channel advance rides in the scalar offset, so staging needs no vector ALU work
 // (fp32 MFMA and VALU instructions contend for the same SIMD issue: every VALU instruction
 // in the stage loop is matrix time lost).
@@ -108,34 +103,33 @@ template <class C>
 __device__ __forceinline__ unsigned halo_voffset(const sfh_conv_desc& d, const ConvGeom& g, int which,
                                                  int slot, int r0, int x0) {
   // slot -> (channel plane, halo pixel); returns the byte offset of the pixel's channel quad
-  // of the FIRST stage in the source tensor, or kOOB.  r0: first output row of the tile (flat
+  // of the FIRST stage in the source tensor, or kSfhOOB.  r0: first output row of the tile (flat
   // row space, or img*2^16 + y for the per-image policy); x0: first output column.
-  if (slot >= C::HSLOTS) return kOOB;
+  if (slot >= C::HSLOTS) return kSfhOOB;
   const int plane = slot / C::HPIXP, p = slot - plane * C::HPIXP;
-  if (p >= C::HPIX) return kOOB;
+  if (p >= C::HPIX) return kSfhOOB;
   const int cs = which == 0 ? d.cs0 : d.cs1;
-  if (cs < C::CKS && 4 * plane >= cs) return kOOB;  // narrow source (e.g. RGB stored as 4)
+  if (cs < C::CKS && 4 * plane >= cs) return kSfhOOB;  // narrow source (e.g. RGB stored as 4)
   const int hy = p / C::HW, hx = p - hy * C::HW;
   int b, y;
   if (C::FLATROWS) {
     const int r = r0 - C::PAD + hy;
-    if (r < 0) return kOOB;
-    b = (int)__umulhi((unsigned)r, g.rows_magic);
-    y = r - b * g.rows_per_img;
-    if (b >= d.batch || y >= d.H) return kOOB;
+    if (r < 0) return kSfhOOB;
+    sfh_row_split(g, r, b, y);
+    if (b >= d.batch || y >= d.H) return kSfhOOB;
   } else {
     b = r0 >> 16;
     y = (r0 & 0xFFFF) * C::STRIDE - C::PAD + hy;
-    if (y < 0 || y >= d.H) return kOOB;
+    if (y < 0 || y >= d.H) return kSfhOOB;
   }
   const int x = x0 * C::STRIDE - C::PAD + hx;
-  if (x < 0 || x >= d.W) return kOOB;
+  if (x < 0 || x >= d.W) return kSfhOOB;
   unsigned pix;
   if (which == 0) {
     pix = d.pool0 ? (unsigned)((b * d.h0 + 2 * y) * d.w0 + 2 * x) : (unsigned)((b * d.h0 + y) * d.w0 + x);
   } else {
     const int ys = y - d.pad_top1, xs = x - d.pad_left1;
-    if (ys < 0 || ys >= d.h1 || xs < 0 || xs >= d.w1) return kOOB;
+    if (ys < 0 || ys >= d.h1 || xs < 0 || xs >= d.w1) return kSfhOOB;
     pix = (unsigned)((b * d.h1 + ys) * d.w1 + xs);
   }
   return (pix * (unsigned)cs + 4u * plane) * 4u;
@@ -146,16 +140,15 @@ struct TileCoord {
   bool live;
 };
 
-// XCD-aware block -> (tile, cout block): blocks b and b+8 share an XCD (L2); keep the cout
-// blocks of one pixel tile on one XCD so the halo is re-read from that L2.
+// block -> (tile, cout block) in the round-robin order (conv_geom.h)
 template <class C>
 __device__ __forceinline__ TileCoord decode_block(const ConvGeom& g) {
   TileCoord t;
   const int bid = blockIdx.x;
-  const int xcd = bid & 7, k = bid >> 3;
-  t.nb = k % g.nblk_n;
-  const int tile = (k / g.nblk_n) * 8 + xcd;
-  t.live = tile < g.ntiles;
+  const SfhWg wg = sfh_wg_round_robin(bid & 7, bid >> 3, g.ntiles, g.nblk_n);
+  t.nb = wg.nb;
+  const int tile = wg.tile;
+  t.live = wg.live;
   const int ty = tile / g.tiles_x, tx = tile - ty * g.tiles_x;
   t.x0 = tx * C::TW;
   if (C::FLATROWS) {
@@ -180,13 +173,10 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const sfh_conv_desc d
   const int lq = lane & 15;  // pixel (B operand col) / cout (A operand row) within a group
   const int lg = lane >> 4;  // k index of the MFMA = channel quad of the stage
 
-  // XCD-aware block -> (tile, cout block): blocks b and b+8 share an XCD (L2); keep the
-  // cout blocks of one pixel tile on one XCD so the halo is re-read from that L2.
   const int bid = blockIdx.x;
-  const int xcd = bid & 7, k = bid >> 3;
-  const int nb = k % g.nblk_n;
-  const int tile = (k / g.nblk_n) * 8 + xcd;
-  if (tile >= g.ntiles) return;
+  const SfhWg wg = sfh_wg_round_robin(bid & 7, bid >> 3, g.ntiles, g.nblk_n);
+  if (!wg.live) return;
+  const int nb = wg.nb, tile = wg.tile;
   const int ty = tile / g.tiles_x, tx = tile - ty * g.tiles_x;
   const int x0 = tx * C::TW;
   int r0;
@@ -371,10 +361,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c4_kernel(const sfh_conv_desc 
   const int wv = tid >> 6;
   const int lq = lane & 15, lg = lane >> 4;
   const int bid = blockIdx.x;
-  const int xcd = bid & 7, k = bid >> 3;
-  const int nb = k % g.nblk_n;
-  const int tile = (k / g.nblk_n) * 8 + xcd;
-  if (tile >= g.ntiles) return;
+  const SfhWg wg = sfh_wg_round_robin(bid & 7, bid >> 3, g.ntiles, g.nblk_n);
+  if (!wg.live) return;
+  const int nb = wg.nb, tile = wg.tile;
   const int ty = tile / g.tiles_x, tx = tile - ty * g.tiles_x;
   const int x0 = tx * C4Cfg::TW, r0 = ty * C4Cfg::TH;
   const int n0 = nb * 64;
@@ -388,11 +377,11 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c4_kernel(const sfh_conv_desc 
     if (p < C4Cfg::HPIX) {
       const int hy = p / C4Cfg::HW, hx = p - hy * C4Cfg::HW;
       const int r = r0 - 1 + hy, x = x0 - 1 + hx;
-      unsigned off = kOOB;
+      unsigned off = kSfhOOB;
       if (r >= 0 && x >= 0 && x < d.W) {
-        const int b = (int)__umulhi((unsigned)r, g.rows_magic);
-        const int y = r - b * g.rows_per_img;
-        if (b < d.batch && y < d.H) off = (unsigned)((b * d.H + y) * d.W + x) * 16u;
+        int b, y;
+        sfh_row_split(g, r, b, y);
+        if (b < d.batch && y < d.H) off = frame_pixel_offset(b, y, x, d.H, d.W);
       }
       halo[p] = bload(rs0, off, 0);
     }
@@ -498,28 +487,12 @@ bool ksize_ok(int k) { return k == 1 || k == 3 || k == 4; }
 template <class C>
 int launch_conv(const sfh_conv_desc& d, hipStream_t stream) {
   ConvGeom g;
-  g.Ho = (d.H + C::PAD + C::PADA - C::KS) / C::STRIDE + 1;
-  g.Wo = (d.W + C::PAD + C::PADA - C::KS) / C::STRIDE + 1;
-  g.tiles_x = sfh_cdiv(g.Wo, C::TW);
-  if (C::FLATROWS) {
-    g.rows_per_img = g.Ho + C::ZROWS;
-    g.rows_total = d.batch * g.rows_per_img;
-    g.rows_magic = (unsigned)((1ULL << 32) / (unsigned)g.rows_per_img) + 1u;
-    SFH_REQUIRE((unsigned long long)(g.rows_total + 64) * g.rows_per_img < (1ULL << 32),
-                "conv_fwd: flattened row space too large for the reciprocal division");
-    g.tiles_y = sfh_cdiv(g.rows_total, C::TH);
-    g.ntiles = g.tiles_x * g.tiles_y;
-  } else {
-    g.rows_total = 0;
-    g.rows_per_img = g.Ho;
-    g.rows_magic = 0;
-    g.tiles_y = sfh_cdiv(g.Ho, C::TH);  // per image
-    g.ntiles = g.tiles_x * g.tiles_y * d.batch;
-    SFH_REQUIRE(g.Ho < 65536 && d.batch < 32768, "stride-2 conv: geometry too large");
-  }
+  // the fp32 kernel has no fused pool output: the zero rows between frames are the padding alone (even_rows = false)
+  SFH_REQUIRE(sfh_conv_grid(g, d.batch, d.H, d.W, C::KS, C::STRIDE, C::FLATROWS, false, C::TH, C::TW),
+              "conv_fwd: geometry too large (flattened row space for the reciprocal division / stride-2 frame)");
   const unsigned long long b0 = 4ULL * d.batch * d.h0 * d.w0 * d.cs0;
   const unsigned long long b1 = d.src1 ? 4ULL * d.batch * d.h1 * d.w1 * d.cs1 : 0ULL;
-  SFH_REQUIRE(b0 < kOOB && b1 < kOOB,
+  SFH_REQUIRE(sfh_fits_descriptor(b0) && sfh_fits_descriptor(b1),
               "conv_fwd: a source tensor of %llu bytes exceeds the 4 GiB buffer-descriptor range; split the batch",
               b0 > b1 ? b0 : b1);
   g.bytes0 = (unsigned)b0;
@@ -583,19 +556,11 @@ extern "C" int sfh_conv3x3_c4_fwd(const sfh_conv_desc* dp, void* stream_) {
                   d.src_fmt == SFH_FMT_F32 && d.out_mode == SFH_OUT_NHWC && d.h0 == d.H && d.w0 == d.W,
               "conv3x3_c4_fwd: needs a single fp32 NHWC source with 4 stored channels, 3x3 stride 1");
   SFH_REQUIRE(d.cout > 0 && d.cout % 64 == 0 && d.batch > 0 && d.H > 0 && d.W > 0, "conv3x3_c4_fwd: bad geometry");
-  SFH_REQUIRE(d.h2_exp_dst >= -64 && d.h2_exp_dst <= 64, "conv3x3_c4_fwd: h2_exp_dst=%d out of range (-64 .. 64)", d.h2_exp_dst);
+  if (!sfh_h2_exp_ok("conv3x3_c4_fwd", "h2_exp_dst", d.h2_exp_dst)) return SFH_E_ARG;
   ConvGeom g;
-  g.Ho = d.H;
-  g.Wo = d.W;
-  g.tiles_x = sfh_cdiv(g.Wo, C4Cfg::TW);
-  g.rows_per_img = g.Ho + 1 + (g.Ho & 1 ? 0 : 1);  // even rows per frame
-  g.rows_total = d.batch * g.rows_per_img;
-  g.rows_magic = (unsigned)((1ULL << 32) / (unsigned)g.rows_per_img) + 1u;
-  SFH_REQUIRE((unsigned long long)(g.rows_total + 64) * g.rows_per_img < (1ULL << 32), "conv3x3_c4_fwd: too many rows");
-  g.tiles_y = sfh_cdiv(g.rows_total, C4Cfg::TH);
-  g.ntiles = g.tiles_x * g.tiles_y;
+  SFH_REQUIRE(sfh_conv_grid(g, d.batch, d.H, d.W, 3, 1, true, true, C4Cfg::TH, C4Cfg::TW), "conv3x3_c4_fwd: too many rows");
   const unsigned long long b0 = 16ULL * d.batch * d.H * d.W;
-  SFH_REQUIRE(b0 < kOOB, "conv3x3_c4_fwd: source exceeds the 4 GiB descriptor range");
+  SFH_REQUIRE(sfh_fits_descriptor(b0), "conv3x3_c4_fwd: source exceeds the 4 GiB descriptor range");
   g.bytes0 = (unsigned)b0;
   g.bytes1 = 0;
   g.nblk_n = d.cout / 64;

@@ -36,15 +36,9 @@
 
 #include "common.h"
 #include "conv_epilogue.h"
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+#include "split_mfma.h"
 
 namespace {
-
-constexpr unsigned kOOB = 0xFFFFFFF0u;
 
 // experiment knob (profiles/ab_bench.sh): wave priority inside the MFMA stages (s_setprio), 0 = leave it alone
 #ifndef SFH_STAGE_PRIO
@@ -94,54 +88,10 @@ struct S3Geom {
   int nb_group;  // cout blocks of one pixel tile that run back to back on one XCD (1 .. nblk_n)
 };
 
-__device__ __forceinline__ bf16x8 as_bf(const u32x4& v) { return __builtin_bit_cast(bf16x8, v); }
-__device__ __forceinline__ f16x8 as_hf(const u32x4& v) { return __builtin_bit_cast(f16x8, v); }
-
-// pad_y / pad_x: rows / columns before the output pixel covered by the window (C::PAD except for the
-// 2x2 up-scatter conv, whose window position depends on the output quadrant)
-template <class C>
-__device__ __forceinline__ unsigned s3_halo_voffset(const sfh_conv_desc& d, const S3Geom& g, int which,
-                                                    int slot, int r0, int x0, int pad_y, int pad_x) {
-  if (slot >= C::HSLOTS) return kOOB;
-  const int pl = slot / C::HPIXP, p = slot - pl * C::HPIXP;  // pl = plane*4 + channel group
-  if (p >= C::HPIX) return kOOB;
-  const int hy = p / C::HW, hx = p - hy * C::HW;
-  int b, y;
-  if (C::FLATROWS) {
-    const int r = r0 - pad_y + hy;
-    if (r < 0) return kOOB;
-    b = (int)__umulhi((unsigned)r, g.rows_magic);
-    y = r - b * g.rows_per_img;
-    if (b >= d.batch || y >= d.H) return kOOB;
-  } else {
-    b = r0 >> 16;
-    y = (r0 & 0xFFFF) * C::STRIDE - pad_y + hy;
-    if (y < 0 || y >= d.H) return kOOB;
-  }
-  const int x = x0 * C::STRIDE - pad_x + hx;
-  if (x < 0 || x >= d.W) return kOOB;
-  // S3 / H2 layout (B, H, cs/32, NP, 4, W, 8): byte offset of (row, channel block 0, plane/group pl, x)
-  unsigned rowi, xs_, ws_, nblk;
-  if (which == 0) {
-    if (C::KS == 2 && (y >= d.h0 || x >= d.w0)) return kOOB;  // fused Up with F.pad: the extra row / column reads 0
-    rowi = (unsigned)(b * d.h0 + y);
-    xs_ = (unsigned)x;
-    ws_ = (unsigned)d.w0;
-    nblk = (unsigned)d.cs0 >> 5;
-  } else {
-    const int ys = y - d.pad_top1, xs = x - d.pad_left1;
-    if (ys < 0 || ys >= d.h1 || xs < 0 || xs >= d.w1) return kOOB;
-    rowi = (unsigned)(b * d.h1 + ys);
-    xs_ = (unsigned)xs;
-    ws_ = (unsigned)d.w1;
-    nblk = (unsigned)d.cs1 >> 5;
-  }
-  return ((rowi * nblk * (4u * C::NP) + (unsigned)pl) * ws_ + xs_) * 16u;
-}
-
-// All NSL halo slots of a thread at once (slot = tid + NT * i), same results as s3_halo_voffset: straight-line code -
-// one validity predicate per slot instead of an early return per test (36 divergent branches in the prologue of a 3x3
-// instance), and (plane/group, halo row, halo column) of slot i + 1 follow from slot i by constant increments instead
+// Byte offsets of all NSL halo slots of a thread (slot = tid + NT * i) in source `which`, kSfhOOB where the slot must read
+// zeros.  pad_y / pad_x: rows / columns before the output pixel covered by the window (C::PAD except for the 2x2 up-scatter
+// conv, whose window position depends on the output quadrant).  Straight-line code - one validity predicate per slot instead
+// of an early return per test (36 divergent branches in the prologue of a 3x3 instance), and (plane/group, halo row, halo column) of slot i + 1 follow from slot i by constant increments instead
 // of two divisions.  The prologue runs beside the co-resident workgroup's MFMAs at half the vector issue rate and was
 // 14 % of a wave's life in the 64-channel layers (profiles/r03_diag_h2.txt).
 template <class C>
@@ -170,8 +120,7 @@ __device__ __forceinline__ void s3_halo_offsets(const sfh_conv_desc& d, const S3
     int b, y;
     if (C::FLATROWS) {
       const int r = ybase + hy;
-      b = (int)__umulhi((unsigned)r, g.rows_magic);
-      y = r - b * g.rows_per_img;
+      sfh_row_split(g, r, b, y);
       ok = ok && r >= 0 && b < d.batch && y < d.H;
     } else {
       b = bimg;
@@ -185,8 +134,9 @@ __device__ __forceinline__ void s3_halo_offsets(const sfh_conv_desc& d, const S3
     // source 0 of the fused Up conv (KS == 2) may be one row / column short of the frame; source 1 sits inside it
     if (which != 0 || C::KS == 2) ok = ok && ys >= 0 && ys < hsrc && xs >= 0 && xs < wsrc;
     const unsigned rowi = (unsigned)(b * hsrc + ys);
+    // mirrors split_pixel_offset (split_mfma.h; its own wording: the call compiles to another schedule)
     const unsigned off = ((rowi * rowmul + (unsigned)pl) * (unsigned)wsrc + (unsigned)xs) * 16u;
-    hoff[i] = ok ? off : kOOB;
+    hoff[i] = ok ? off : kSfhOOB;
     // next slot of this thread
     pl += QP;
     p += RP;
@@ -250,21 +200,16 @@ __global__ __launch_bounds__(C::NT, (C::NP == 2 && !DB) ? SFH_H2_WAVES_PER_SIMD 
   const int per_split = (int)(gridDim.x / (unsigned)ksn);
   const int ks = ksn > 1 ? (int)blockIdx.x / per_split : 0;
   const int bid = (int)blockIdx.x - ks * per_split;
+  // the tile-range-per-XCD order (conv_geom.h); weights are the dominant L2 -> CU stream of this kernel (12 KB per tap per
+  // workgroup), nb_group is chosen on the host (launch_s3)
+  // mirrors sfh_wg_xcd_range (conv_geom.h: the rationale; its own wording: the call schedules three scalar instructions
+  // elsewhere).  Weights are the dominant L2 -> CU stream of this kernel (12 KB per tap per workgroup); nb_group is chosen
+  // on the host (launch_s3).
   const int xcd = bid & 7, kk_ = bid >> 3;
-  // within an XCD the pixel tiles of ONE cout block run back to back: the ~30 workgroups resident
-  // on the XCD stream the same weight fragments, which then stay in its 4 MB L2 (weights are the
-  // dominant L2->CU stream of this kernel: 12 KB per tap per workgroup)
   const int tpx = (g.ntiles + 7) >> 3;  // tiles per XCD
-  // nb_group = G cout blocks of one pixel tile run back to back: their input tile is fetched into the
-  // XCD's L2 once instead of G times.  G is chosen on the host so that the G weight sets still fit L2
-  // next to it (transposed conv: G = all quadrants / couts, so the interleaved output rows are
-  // completed in L2 before they are written back).
   const int per = tpx * g.nb_group;
   const int gi = kk_ / per, rr = kk_ - gi * per;
   const int nb = gi * g.nb_group + rr % g.nb_group;
-  // each XCD owns a contiguous range of pixel tiles (whole tile rows), so vertically adjacent tiles
-  // share their halo rows in that XCD's L2 (the round-robin order tile = tl * 8 + xcd measured 1.4x the L2 fills)
-  // reverse_tiles: every XCD walks its range backwards, i.e. starts on what it wrote last in the previous launch
   const int tl = d.reverse_tiles ? tpx - 1 - rr / g.nb_group : rr / g.nb_group;
   const int tile = xcd * tpx + tl;
   if (tile >= g.ntiles) return;
@@ -290,12 +235,13 @@ __global__ __launch_bounds__(C::NT, (C::NP == 2 && !DB) ? SFH_H2_WAVES_PER_SIMD 
       const_cast<float*>(d.src1 ? d.src1 : d.src0), 0, (int)(d.src1 ? g.bytes1 : 0u), 0x00020000);
   // packed weights of this cout block: [stage][tap][plane NP][cout group 4][lane 64][8 x 16 bit]
   constexpr int NP = C::NP;
-  constexpr unsigned WTAP = (unsigned)NP * 4u * 1024u;  // bytes per (stage, tap)
+  using WS = SplitWeights<NP>;
+  constexpr unsigned WTAP = WS::TAP;
   const unsigned wtotal = (unsigned)nst * C::NTAP * WTAP;
   const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<char*>(reinterpret_cast<const char*>(d.wpacked)) + (size_t)(nb * (C::NWN / 2) + (wn >> 1)) * wtotal, 0,
       (int)wtotal, 0x00020000);   // weights are packed per 64 couts: waves (wn >> 1) share a block
-  const unsigned wvoff = lane * 16u + (unsigned)(2 * (wn & 1)) * 1024u;
+  const unsigned wvoff = lane * 16u + (unsigned)(2 * (wn & 1)) * WS::GROUP;
 
   // byte offsets of this thread's halo slots in the CURRENT source (recomputed once when the
   // stage loop crosses from source 0 to source 1)
@@ -330,7 +276,7 @@ __global__ __launch_bounds__(C::NT, (C::NP == 2 && !DB) ? SFH_H2_WAVES_PER_SIMD 
     for (int p = 0; p < NP; ++p)
 #pragma unroll
       for (int ni = 0; ni < 2; ++ni)
-        w[p][ni] = __builtin_amdgcn_raw_buffer_load_b128(rsw, (int)(wvoff + ni * 1024u), (int)(soff + p * 4096u), 0);
+        w[p][ni] = __builtin_amdgcn_raw_buffer_load_b128(rsw, (int)(wvoff + ni * WS::GROUP), (int)(soff + p * WS::PLANE), 0);
   };
 
   // LDS slot of this lane's pixel in pixel group 0 of the wave; group mi adds a compile-time
@@ -353,7 +299,7 @@ __global__ __launch_bounds__(C::NT, (C::NP == 2 && !DB) ? SFH_H2_WAVES_PER_SIMD 
   if constexpr (C::KS == 3 && C::STRIDE == 1) {
     if (d.acc_init) {
       const __amdgpu_buffer_rsrc_t ri =
-          __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(d.acc_init), 0, (int)kOOB, 0x00020000);
+          __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(d.acc_init), 0, (int)kSfhOOB, 0x00020000);
       const unsigned cs_i = (unsigned)d.cout;                        // channel stride of acc_init = all couts of the layer
       const unsigned c_lane_i = (unsigned)(n0 + 32 * wn + 4 * lg);
 #pragma unroll
@@ -362,10 +308,9 @@ __global__ __launch_bounds__(C::NT, (C::NP == 2 && !DB) ? SFH_H2_WAVES_PER_SIMD 
         const int sy = sgi / C::SUBX, sx = sgi - sy * C::SUBX;
         const int oy = sy * C::SH + lq / C::SW, ox = sx * C::SW + lq % C::SW;
         const int x = x0 + ox, r = r0 + oy;
-        const int b = (int)__umulhi((unsigned)r, g.rows_magic);
-        const int y = r - b * g.rows_per_img;
-        const bool ok = x < g.Wo && r < g.rows_total && y < g.Ho;
-        const unsigned off = ok ? (((unsigned)(b * g.Ho + y) * (unsigned)g.Wo + (unsigned)x) * cs_i + c_lane_i) * 4u : kOOB;
+        int b, y;
+        const bool ok = sfh_row_split(g, r, b, y, x < g.Wo);
+        const unsigned off = ok ? (((unsigned)(b * g.Ho + y) * (unsigned)g.Wo + (unsigned)x) * cs_i + c_lane_i) * 4u : kSfhOOB;
 #pragma unroll
         for (int ni = 0; ni < 2; ++ni)
           acc[ni][mi] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ri, (int)off, ni * 64, 0));
@@ -433,21 +378,14 @@ __global__ __launch_bounds__(C::NT, (C::NP == 2 && !DB) ? SFH_H2_WAVES_PER_SIMD 
         for (int q = 0; q < PPS; ++q)
           if (s * PPS + q < C::NSL) dma_piece(stn, cur ^ 1, s * PPS + q);
       }
-      // the kept partial products (six of 3 x 3 bf16 planes, three of 2 x 2 fp16 planes), smallest first; the
-      // two cout groups are interleaved so that consecutive MFMAs never depend on each other
-      constexpr int NPROD = NP == 3 ? 6 : 3;
-      constexpr int PW[6] = {0, 1, NP == 3 ? 2 : 0, 0, 1, 0}, PX[6] = {NP == 3 ? 2 : 1, NP == 3 ? 1 : 0, 0, 1, 0, 0};
+      // the kept partial products (split_mfma.h); the two cout groups are interleaved so that consecutive MFMAs never
+      // depend on each other
+      using P = SplitProducts<NP>;
+      constexpr int NPROD = P::N;
 #pragma unroll
       for (int k6 = 0; k6 < NPROD; ++k6)
 #pragma unroll
-        for (int ni = 0; ni < 2; ++ni) {
-          if constexpr (NP == 3)
-            acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf(wc[PW[k6]][ni]), as_bf(xq[xb][PX[k6]]),
-                                                                 acc[ni][mi], 0, 0, 0);
-          else
-            acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_f16(as_hf(wc[PW[k6]][ni]), as_hf(xq[xb][PX[k6]]),
-                                                                acc[ni][mi], 0, 0, 0);
-        }
+        for (int ni = 0; ni < 2; ++ni) acc[ni][mi] = split_mfma<NP>(wc[P::PW[k6]][ni], xq[xb][P::PX[k6]], acc[ni][mi]);
       // keep each step's memory instructions inside the step, operand reads of the next step
       // right behind the first MFMA so that the step's other MFMAs cover their LDS latency
       __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
@@ -559,6 +497,7 @@ __global__ __launch_bounds__(C::NT, (C::NP == 2 && !DB) ? SFH_H2_WAVES_PER_SIMD 
         const int sy = s / C::SUBX, sx = s - sy * C::SUBX;
         const int oy = sy * C::SH + q / C::SW, ox = sx * C::SW + q % C::SW;
         const int x = x0 + ox, r = r0 + oy;
+        // mirrors sfh_row_split (conv_geom.h; its own wording: the call compiles to another order of the two compares)
         const int b = (int)__umulhi((unsigned)r, g.rows_magic);
         const int y = r - b * g.rows_per_img;
         if (x < g.Wo && r < g.rows_total && y < g.Ho) {
@@ -796,7 +735,7 @@ __global__ __launch_bounds__(256) void f32_to_h2_kernel(const float* __restrict_
   if (i < total && x < W) {
     const float* sp = src + (row * W + x) * cs + cb * 32 + g * 8;
     const f32x4 a = *reinterpret_cast<const f32x4*>(sp), b = *reinterpret_cast<const f32x4*>(sp + 4);
-    sfh_u32x2 pa[2], pb[2];
+    u32x2 pa[2], pb[2];
     sfh_split4_h2(a, scale, pa, over);
     sfh_split4_h2(b, scale, pb, over);
     const long e = ((((row * (cs >> 5) + cb) * 2) * 4 + g) * W + x) * 8;
@@ -846,14 +785,14 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_split_kernel(const float* __
     }
     const long ps = 4L * Wo * 8;  // plane stride in elements
     if constexpr (DFMT == SFH_FMT_H2) {
-      sfh_u32x2 pa[2], pb[2];
+      u32x2 pa[2], pb[2];
       sfh_split4_h2(m0, scale, pa, over);
       sfh_split4_h2(m1, scale, pb, over);
       const long e = ((((row * (cs >> 5) + cb) * 2) * 4 + g) * Wo + xo) * 8;
       *reinterpret_cast<u32x4*>(dst + e) = (u32x4){pa[0][0], pa[0][1], pb[0][0], pb[0][1]};
       *reinterpret_cast<u32x4*>(dst + e + ps) = (u32x4){pa[1][0], pa[1][1], pb[1][0], pb[1][1]};
     } else {
-      sfh_u32x2 pa[3], pb[3];
+      u32x2 pa[3], pb[3];
       sfh_split4(m0, pa);
       sfh_split4(m1, pb);
       const long e = s3_elem(row, xo, cb * 32 + g * 8, 0, Wo, cs);
@@ -950,7 +889,7 @@ __global__ __launch_bounds__(256) void splitk_finish_kernel(const float* __restr
       *reinterpret_cast<f32x4*>(dp + 4) = (f32x4){v[4], v[5], v[6], v[7]};
     } else if constexpr (DFMT == SFH_FMT_H2) {
       unsigned short* dst = reinterpret_cast<unsigned short*>(dstv);
-      sfh_u32x2 pa[2], pb[2];
+      u32x2 pa[2], pb[2];
       sfh_split4_h2((f32x4){v[0], v[1], v[2], v[3]}, dst_scale, pa, over);
       sfh_split4_h2((f32x4){v[4], v[5], v[6], v[7]}, dst_scale, pb, over);
       const long e = ((((row * nb32 + cb) * 2) * 4 + g) * W + x) * 8;
@@ -983,31 +922,11 @@ __global__ __launch_bounds__(256) void splitk_finish_kernel(const float* __restr
 template <class C, bool DB>
 int launch_s3(const sfh_conv_desc& d, hipStream_t stream) {
   S3Geom g;
-  g.Ho = (d.H + C::PAD + C::PADA - C::KS) / C::STRIDE + 1;
-  g.Wo = (d.W + C::PAD + C::PADA - C::KS) / C::STRIDE + 1;
-  g.tiles_x = sfh_cdiv(g.Wo, C::TW);
-  if (C::FLATROWS) {
-    int zr = C::PAD;
-    if ((g.Ho + zr) & 1) ++zr;  // even rows per frame: 2x2 pool windows never straddle a tile edge
-    if (zr == 0) zr = (g.Ho & 1) ? 1 : 0;
-    g.rows_per_img = g.Ho + zr;
-    g.rows_total = d.batch * g.rows_per_img;
-    g.rows_magic = (unsigned)((1ULL << 32) / (unsigned)g.rows_per_img) + 1u;
-    SFH_REQUIRE((unsigned long long)(g.rows_total + 64) * g.rows_per_img < (1ULL << 32),
-                "conv_s3: flattened row space too large");
-    g.tiles_y = sfh_cdiv(g.rows_total, C::TH);
-    g.ntiles = g.tiles_x * g.tiles_y;
-  } else {
-    g.rows_total = 0;
-    g.rows_per_img = g.Ho;
-    g.rows_magic = 0;
-    g.tiles_y = sfh_cdiv(g.Ho, C::TH);
-    g.ntiles = g.tiles_x * g.tiles_y * d.batch;
-    SFH_REQUIRE(g.Ho < 65536 && d.batch < 32768, "conv_s3: geometry too large");
-  }
+  SFH_REQUIRE(sfh_conv_grid(g, d.batch, d.H, d.W, C::KS, C::STRIDE, C::FLATROWS, true, C::TH, C::TW),
+              "conv_s3: geometry too large (flattened row space / stride-2 frame)");
   const unsigned long long b0 = 2ULL * C::NP * d.batch * d.h0 * d.w0 * d.cs0;
   const unsigned long long b1 = d.src1 ? 2ULL * C::NP * d.batch * d.h1 * d.w1 * d.cs1 : 0ULL;
-  SFH_REQUIRE(b0 < kOOB && b1 < kOOB, "conv_s3: a source tensor of %llu bytes exceeds the 4 GiB descriptor range; split the batch",
+  SFH_REQUIRE(sfh_fits_descriptor(b0) && sfh_fits_descriptor(b1), "conv_s3: a source tensor of %llu bytes exceeds the 4 GiB descriptor range; split the batch",
               b0 > b1 ? b0 : b1);
   g.bytes0 = (unsigned)b0;
   g.bytes1 = (unsigned)b1;
@@ -1018,7 +937,7 @@ int launch_s3(const sfh_conv_desc& d, hipStream_t stream) {
     // 64 MB 21.61, unbounded 21.74 - re-reading the input tile once per cout block costs more than
     // streaming weights that no longer fit the 4 MB L2 (they hit the 256 MB Infinity Cache), so the budget
     // is 64 MB: every layer of this model is fully grouped.
-    const long wblock = (long)((d.c0 + (d.src1 ? d.c1 : 0)) / 32) * C::NTAP * (C::NP * 4096);
+    const long wblock = (long)((d.c0 + (d.src1 ? d.c1 : 0)) / 32) * C::NTAP * SplitWeights<C::NP>::TAP;
     const long budget = 64L << 20;
     int G = d.out_mode == SFH_OUT_UPSCATTER2 ? g.nblk_n : (int)(budget / (wblock > 0 ? wblock : 1));
     if (G < 1) G = 1;
@@ -1208,8 +1127,7 @@ extern "C" int sfh_conv_s3_fwd(const sfh_conv_desc* dp, void* stream_) {
   SFH_REQUIRE(d.dst_fmt == SFH_FMT_F32 || d.dst_fmt == d.src_fmt,
               "conv_s3_fwd: the destination is fp32 or the sources' own split format (src_fmt=%d, dst_fmt=%d)", d.src_fmt, d.dst_fmt);
   SFH_REQUIRE(d.batch > 0 && d.H > 0 && d.W > 0, "conv_s3_fwd: empty geometry");
-  SFH_REQUIRE(d.h2_exp_dst >= -64 && d.h2_exp_dst <= 64 && d.h2_exp_res >= -64 && d.h2_exp_res <= 64,
-              "conv_s3_fwd: h2_exp_dst=%d / h2_exp_res=%d out of range (-64 .. 64)", d.h2_exp_dst, d.h2_exp_res);
+  if (!sfh_h2_exp_ok("conv_s3_fwd", "h2_exp_dst", d.h2_exp_dst) || !sfh_h2_exp_ok("conv_s3_fwd", "h2_exp_res", d.h2_exp_res)) return SFH_E_ARG;
   SFH_REQUIRE(d.cout > 0 && d.cout % 64 == 0, "conv_s3_fwd: cout=%d must be a multiple of 64", d.cout);
   SFH_REQUIRE(d.c0 > 0 && d.c0 % 32 == 0 && d.cs0 >= d.c0, "conv_s3_fwd: c0=%d must be a multiple of 32 (cs0=%d)", d.c0, d.cs0);
   SFH_REQUIRE(!d.pool0, "conv_s3_fwd: pool-on-load is not available for S3 sources (use the producer's dst_pool)");
@@ -1279,12 +1197,9 @@ extern "C" int sfh_conv_s3_fwd(const sfh_conv_desc* dp, void* stream_) {
   if (w8_ok && d.ksize == KS && d.stride == ST && d.tile == TILE) {                                           \
     using CFG = S3Cfg<KS, ST, SH, SW, TH, TW, 2, 4, SFH_W128_NWM>;                                            \
     using CFGS = S3Cfg<KS, ST, SH, SW, TH, TW, 2, 4, SFH_W128_NWM, true>;                                     \
-    const int Ho_ = d.H, Wo_ = d.W;                                                                           \
-    int zr_ = CFG::PAD;                                                                                       \
-    if ((Ho_ + zr_) & 1) ++zr_;                                                                               \
-    if (zr_ == 0) zr_ = (Ho_ & 1) ? 1 : 0;                                                                    \
-    const long tiles_ = (long)sfh_cdiv(Wo_, TW) * sfh_cdiv(d.batch * (Ho_ + zr_), TH);                        \
-    if (d.wg_couts == 128 || (d.wg_couts == 0 && tiles_ * (d.cout / 128) >= SFH_W8_MIN_BLOCKS)) {            \
+    S3Geom g_;   /* the grid launch_s3 will build */                                                          \
+    const bool fits_ = sfh_conv_grid(g_, d.batch, d.H, d.W, KS, ST, true, true, TH, TW);                      \
+    if (d.wg_couts == 128 || (d.wg_couts == 0 && fits_ && (long)g_.ntiles * (d.cout / 128) >= SFH_W8_MIN_BLOCKS)) { \
       if constexpr (KS == 3) {                                                                                \
         if (d.stats_partial) return launch_s3<CFGS, (SFH_W128_NWM == 2)>(d, stream);                          \
       }                                                                                                       \

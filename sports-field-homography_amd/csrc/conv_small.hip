@@ -15,13 +15,9 @@
 // against conv_s3_kernel on one device): layer4 79 -> 50 us per launch; no gain on grids that already fill the chip.
 #include "common.h"
 #include "conv_epilogue.h"
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+#include "split_mfma.h"
 
 namespace {
-
-constexpr unsigned kOOB = 0xFFFFFFF0u;
 
 struct SmallCfg {   // what sfh_conv_epilogue needs to know about the tile
   static constexpr int KS = 3, SUBX = 5, SH = 4, SW = 4, NGRP = 15;
@@ -36,11 +32,9 @@ struct SmallGeom {
   int Ho, Wo, rows_total, rows_per_img;   // (rows_* only exist for the epilogue's flattened-row mode, unused here)
   unsigned rows_magic;
   int tiles_y, tiles_x, ntiles, nblk;
-  int tile_stationary;   // 1: an XCD owns a contiguous tile range and walks all cout blocks per tile (weights of the layer fit L2)
+  int tile_stationary;   // 1: sfh_wg_xcd_range_all (the weights of the layer fit an XCD's L2), 0: a weight-stationary order
   unsigned bytes0;
 };
-
-__device__ __forceinline__ f16x8 as_hf(const u32x4& v) { return __builtin_bit_cast(f16x8, v); }
 
 template <bool DB>
 __global__ __launch_bounds__(256, DB ? 1 : 2) void conv_small_kernel(const sfh_conv_desc d, const SmallGeom g) {
@@ -50,27 +44,21 @@ __global__ __launch_bounds__(256, DB ? 1 : 2) void conv_small_kernel(const sfh_c
   typedef __attribute__((address_space(3))) void* lds_ptr_t;
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lq = lane & 15, lg = lane >> 4;
-  // workgroup -> (32-cout block, tile): an XCD (blockIdx & 7) keeps to nblk / 8 cout blocks, so that their weights stay in its L2
+  // workgroup -> (32-cout block, tile), the orders of conv_geom.h
   const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-  int nb, tile;
-  if (g.tile_stationary) {
-    // round 6 (profiles/r06_tcc_per_launch.txt): with the weight-stationary order below every XCD reads the WHOLE input tensor
-    // (ResNet layer3: 147 MB of L2 misses per launch for 33 MB of tensors).  Where all weights of the layer fit an XCD's L2
-    // (layer3: 2.4 MB) the other order is the cheap one: an XCD owns a contiguous range of tiles, fetches their halos once and
-    // finds every cout block's weights in its L2 after the first tile.
+  SfhWg wg;
+  if (g.tile_stationary) {   // mirrors sfh_wg_xcd_range_all (its own wording: the call compiles to other scalar code)
     const int tpx = (g.ntiles + 7) >> 3;
-    nb = idx % g.nblk;
-    tile = xcd * tpx + idx / g.nblk;
+    wg.nb = idx % g.nblk;
+    wg.tile = xcd * tpx + idx / g.nblk;
     if (idx / g.nblk >= tpx) return;
   } else if (g.nblk >= 8 && (g.nblk & 7) == 0) {
-    const int per = g.nblk >> 3;
-    nb = xcd * per + idx % per;
-    tile = idx / per;
+    wg = sfh_wg_weight_stationary(xcd, idx, g.ntiles, g.nblk);
   } else {
-    nb = idx % g.nblk;
-    tile = (idx / g.nblk) * 8 + xcd;
+    wg = sfh_wg_round_robin(xcd, idx, g.ntiles, g.nblk);
   }
-  if (tile >= g.ntiles) return;
+  if (wg.tile >= g.ntiles) return;
+  const int nb = wg.nb, tile = wg.tile;
   const int tpi = g.tiles_y * g.tiles_x;
   const int b = tile / tpi, tr = tile - b * tpi;
   const int ty = tr / g.tiles_x;
@@ -79,7 +67,8 @@ __global__ __launch_bounds__(256, DB ? 1 : 2) void conv_small_kernel(const sfh_c
   const unsigned nblk_src = (unsigned)d.cs0 >> 5;
   const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(d.src0), 0, (int)g.bytes0, 0x00020000);
   // packed weights [cout block of 64][stage][tap][plane 2][cout group 4][lane 64][8 x fp16]: this workgroup's half of a block
-  const unsigned wtotal = (unsigned)nst * 9u * 8192u;
+  using WS = SplitWeights<2>;
+  const unsigned wtotal = (unsigned)nst * 9u * WS::TAP;
   const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<char*>(reinterpret_cast<const char*>(d.wpacked)) + (size_t)(nb >> 1) * wtotal, 0, (int)wtotal, 0x00020000);
   // halo slots of this thread: slot = tid + 256 * i -> (plane / channel group, halo pixel); out-of-frame pixels read zeros
@@ -92,11 +81,11 @@ __global__ __launch_bounds__(256, DB ? 1 : 2) void conv_small_kernel(const sfh_c
     const int hy = p / C::HWD, hx = p - hy * C::HWD;
     const int y = y0 - 1 + hy, x = x0 - 1 + hx;
     const bool ok = p < C::HPIX && y >= 0 && y < d.H && x >= 0 && x < d.W;
-    hoff[i] = ok ? ((((unsigned)(b * d.H + y) * nblk_src) * 8u + (unsigned)plg) * (unsigned)d.W + (unsigned)x) * 16u : kOOB;
+    hoff[i] = ok ? split_pixel_offset<2>((unsigned)(b * d.H + y), nblk_src, (unsigned)plg, (unsigned)d.W, (unsigned)x) : kSfhOOB;
   }
   // weight slots: tap i of the stage = 256 slots = [plane 2][cout group 2][lane 64]; thread tid fetches plane tid >> 7, cout
   // group (tid >> 6) & 1 of the workgroup's half
-  const unsigned woff = (unsigned)(tid >> 7) * 4096u + (unsigned)(2 * (nb & 1) + ((tid >> 6) & 1)) * 1024u + (unsigned)(tid & 63) * 16u;
+  const unsigned woff = (unsigned)(tid >> 7) * WS::PLANE + (unsigned)(2 * (nb & 1) + ((tid >> 6) & 1)) * WS::GROUP + (unsigned)(tid & 63) * 16u;
   auto dma_stage = [&](int st, int buf) {
     const unsigned cb = (unsigned)st * 128u * (unsigned)d.W;   // the row's next 32-channel block: 8 runs of W x 16 bytes
     u32x4* const base = lds + buf * C::BUF;
@@ -106,7 +95,7 @@ __global__ __launch_bounds__(256, DB ? 1 : 2) void conv_small_kernel(const sfh_c
 #pragma unroll
     for (int i = 0; i < 9; ++i)
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_ptr_t)(base + C::HSLOTS + wv * 64 + 256 * i), 16, (int)woff,
-                                               (int)(((unsigned)st * 9u + (unsigned)i) * 8192u), 0, 0);
+                                               (int)(((unsigned)st * 9u + (unsigned)i) * WS::TAP), 0, 0);
   };
   int pixbase[4];
 #pragma unroll
@@ -147,13 +136,11 @@ __global__ __launch_bounds__(256, DB ? 1 : 2) void conv_small_kernel(const sfh_c
       const int t = s_ >> 2, mi = s_ & 3;
       if (s_ + 2 < 36) ld_x(s_ + 2, (s_ + 2) % 3);
       if (mi == 0 && t + 1 < 9) ld_w(t + 1, (t + 1) & 1);
-      // the kept products in conv_s3_kernel's order (smallest first): w0*x1, w1*x0, w0*x0
-      constexpr int PW[3] = {0, 1, 0}, PX[3] = {1, 0, 0};
+      using P = SplitProducts<2>;
 #pragma unroll
-      for (int k = 0; k < 3; ++k)
+      for (int k = 0; k < P::N; ++k)
 #pragma unroll
-        for (int n = 0; n < 2; ++n)
-          acc[n][mi] = __builtin_amdgcn_mfma_f32_16x16x32_f16(as_hf(wr[t & 1][PW[k]][n]), as_hf(xq[s_ % 3][PX[k]]), acc[n][mi], 0, 0, 0);
+        for (int n = 0; n < 2; ++n) acc[n][mi] = split_mfma<2>(wr[t & 1][P::PW[k]][n], xq[s_ % 3][P::PX[k]], acc[n][mi]);
       __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
       if (mi == 0 && t + 1 < 9) __builtin_amdgcn_sched_group_barrier(0x100, 6, 0);
       else if (s_ + 2 < 36) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
@@ -197,20 +184,13 @@ extern "C" int sfh_conv_small_fwd(const sfh_conv_desc* dp, void* stream_) {
               "conv_small_fwd: bad geometry b=%d %dx%d (source %dx%d)", d.batch, d.H, d.W, d.h0, d.w0);
   SFH_REQUIRE(d.cout > 0 && d.cout % 64 == 0 && d.c0 > 0 && d.c0 % 32 == 0 && d.cs0 >= d.c0 && d.cs0 % 32 == 0,
               "conv_small_fwd: cout=%d must be a multiple of 64, c0=%d of 32 (cs0=%d)", d.cout, d.c0, d.cs0);
-  SFH_REQUIRE(d.h2_exp_dst >= -64 && d.h2_exp_dst <= 64 && d.h2_exp_res >= -64 && d.h2_exp_res <= 64,
-              "conv_small_fwd: h2_exp_dst=%d / h2_exp_res=%d out of range (-64 .. 64)", d.h2_exp_dst, d.h2_exp_res);
+  if (!sfh_h2_exp_ok("conv_small_fwd", "h2_exp_dst", d.h2_exp_dst) || !sfh_h2_exp_ok("conv_small_fwd", "h2_exp_res", d.h2_exp_res))
+    return SFH_E_ARG;
   SmallGeom g;
-  g.Ho = d.H;
-  g.Wo = d.W;
-  g.rows_per_img = d.H;
-  g.rows_total = d.batch * d.H;
-  g.rows_magic = 0u;
-  g.tiles_y = sfh_cdiv(d.H, SmallCfg::TH);
-  g.tiles_x = sfh_cdiv(d.W, SmallCfg::TW);
-  g.ntiles = d.batch * g.tiles_y * g.tiles_x;
+  SFH_REQUIRE(sfh_conv_grid(g, d.batch, d.H, d.W, 3, 1, false, true, SmallCfg::TH, SmallCfg::TW), "conv_small_fwd: geometry too large");
   g.nblk = d.cout / 32;
   const unsigned long long b0 = 4ULL * d.batch * d.H * d.W * d.cs0;
-  SFH_REQUIRE(b0 < kOOB && 4ULL * d.batch * d.H * d.W * (unsigned long long)d.dst_cs < kOOB,
+  SFH_REQUIRE(sfh_fits_descriptor(b0) && sfh_fits_descriptor(4ULL * d.batch * d.H * d.W * (unsigned long long)d.dst_cs),
               "conv_small_fwd: a tensor exceeds the 4 GiB descriptor range");
   g.bytes0 = (unsigned)b0;
   const long nblocks = (long)sfh_cdiv(g.ntiles, 8) * 8 * g.nblk;

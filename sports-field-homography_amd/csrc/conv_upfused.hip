@@ -20,13 +20,10 @@
 // bit-identical, same 2.37 ms per step for the two launches: the LDS pipe is not what they wait for.)
 #include "common.h"
 #include "conv_epilogue.h"
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+#include "split_mfma.h"
 
 namespace {
 
-constexpr unsigned kOOB = 0xFFFFFFF0u;
 constexpr int TH = 16, TW = 32;
 constexpr int LH = TH / 2 + 2, LW = TW / 2 + 2, LPIX = LH * LW, LPIXP = 192;   // low-resolution halo 10 x 18
 constexpr int SHH = TH + 2, SWW = TW + 2, SPIX = SHH * SWW, SPIXP = 624;      // skip halo 18 x 34
@@ -34,11 +31,9 @@ constexpr int LSLOTS = 8 * LPIXP, SSLOTS = 8 * SPIXP;                        // 
 
 struct UpGeom {
   int tiles_y, tiles_x, ntiles, nblk;
-  int xcd_order;   // 1: every XCD owns a contiguous range of pixel tiles and runs a tile's cout blocks back to back (round 6)
+  int xcd_order;   // 1: sfh_wg_xcd_range_all (conv_geom.h), 0: tile = blockIdx / nblk
   unsigned bytes_skip, bytes_low;
 };
-
-__device__ __forceinline__ f16x8 as_hf(const u32x4& v) { return __builtin_bit_cast(f16x8, v); }
 
 __global__ __launch_bounds__(256, 2) void conv_upfused_kernel(const sfh_conv_desc d, const UpGeom g) {
   extern __shared__ __attribute__((aligned(16))) float smem_f[];
@@ -47,18 +42,14 @@ __global__ __launch_bounds__(256, 2) void conv_upfused_kernel(const sfh_conv_des
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lq = lane & 15, lg = lane >> 4;
   const int py = wv >> 1, px = wv & 1, qd = wv;          // the wave's output parity = quadrant of the composed conv
-  // Workgroups go round-robin to the 8 XCDs, each with its own 4 MB L2.  Round 6 (profiles/r06_tcc_per_launch.txt): with
-  // tile = blockIdx / nblk the cout blocks of ONE pixel tile landed on different XCDs - its skip / low-resolution halos crossed
-  // the fabric once per cout block (u3: 3.28 GB of L2 misses for 1.18 GB of tensors) - and neighbouring tiles never shared an L2.
-  // Now, as in conv_s3_kernel: XCD x owns the contiguous tile range [x * tpx, (x + 1) * tpx) (whole tile rows next to each
-  // other, so vertically adjacent tiles meet their halo rows in that L2) and runs a tile's cout blocks back to back.
+  // (with tile = blockIdx / nblk the cout blocks of ONE pixel tile landed on different XCDs: u3 had 3.28 GB of L2 misses for
+  // 1.18 GB of tensors)
   int nb, tile;
   if (g.xcd_order) {
-    const int xcd = (int)blockIdx.x & 7, k = (int)blockIdx.x >> 3;
-    const int tpx = (g.ntiles + 7) >> 3;
-    nb = k % g.nblk;
-    tile = xcd * tpx + k / g.nblk;
-    if (tile >= g.ntiles || k / g.nblk >= tpx) return;      // (the whole workgroup leaves: uniform)
+    const SfhWg wg = sfh_wg_xcd_range_all((int)blockIdx.x & 7, (int)blockIdx.x >> 3, g.ntiles, g.nblk);
+    if (!wg.live) return;
+    nb = wg.nb;
+    tile = wg.tile;
   } else {
     nb = (int)blockIdx.x % g.nblk;
     tile = (int)blockIdx.x / g.nblk;
@@ -73,7 +64,8 @@ __global__ __launch_bounds__(256, 2) void conv_upfused_kernel(const sfh_conv_des
   const __amdgpu_buffer_rsrc_t r_skip = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(d.src0), 0, (int)g.bytes_skip, 0x00020000);
   const __amdgpu_buffer_rsrc_t r_low = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(d.src1), 0, (int)g.bytes_low, 0x00020000);
   // packed weights, per 64 couts: [stage][tap][plane 2][cout group 4][lane 64][8 x fp16]
-  const unsigned wtot_up = (unsigned)nst_low * 4u * 8192u, wtot_sk = (unsigned)nst_skip * 9u * 8192u;
+  using WS = SplitWeights<2>;
+  const unsigned wtot_up = (unsigned)nst_low * 4u * WS::TAP, wtot_sk = (unsigned)nst_skip * 9u * WS::TAP;
   const __amdgpu_buffer_rsrc_t rw_up = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<char*>(reinterpret_cast<const char*>(d.up_wpacked)) + (size_t)(qd * g.nblk + nb) * wtot_up, 0, (int)wtot_up, 0x00020000);
   const __amdgpu_buffer_rsrc_t rw_sk = __builtin_amdgcn_make_buffer_rsrc(
@@ -104,7 +96,7 @@ __global__ __launch_bounds__(256, 2) void conv_upfused_kernel(const sfh_conv_des
 #pragma unroll
           for (int n = 0; n < 4; ++n)
             wr[set][p][n] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                rw, (int)((p * 4 + n) * 1024 + lane * 16), (int)(((unsigned)st * NTAP + (unsigned)t) * 8192u), 0));
+                rw, (int)((p * 4 + n) * WS::GROUP + lane * 16), (int)(((unsigned)st * NTAP + (unsigned)t) * WS::TAP), 0));
       };
       ld_w(0, 0);
       asm volatile("s_waitcnt vmcnt(8)" ::: "memory");     // the DMA pieces (older than the eight weight loads) have landed
@@ -121,12 +113,11 @@ __global__ __launch_bounds__(256, 2) void conv_upfused_kernel(const sfh_conv_des
         const int t = s_ >> 3, i = s_ & 7;
         if (s_ + 2 < NSTEP) ld_x(s_ + 2, (s_ + 2) % 3);
         if (i == 0 && t + 1 < NTAP) ld_w(t + 1, (t + 1) & 1);
-        constexpr int PW[3] = {0, 1, 0}, PX[3] = {1, 0, 0};
+        using P = SplitProducts<2>;
 #pragma unroll
-        for (int k = 0; k < 3; ++k)
+        for (int k = 0; k < P::N; ++k)
 #pragma unroll
-          for (int n = 0; n < 4; ++n)
-            acc[n][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(as_hf(wr[t & 1][PW[k]][n]), as_hf(xq[s_ % 3][PX[k]]), acc[n][i], 0, 0, 0);
+          for (int n = 0; n < 4; ++n) acc[n][i] = split_mfma<2>(wr[t & 1][P::PW[k]][n], xq[s_ % 3][P::PX[k]], acc[n][i]);
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
         if (s_ + 2 < NSTEP) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
         if (i == 0 && t + 1 < NTAP) __builtin_amdgcn_sched_group_barrier(0x020, 8, 0);
@@ -143,7 +134,7 @@ __global__ __launch_bounds__(256, 2) void conv_upfused_kernel(const sfh_conv_des
       const int hy = p / LW, hx = p - hy * LW;
       const int y = Y0 - 1 + hy, x = X0 - 1 + hx;
       const bool ok = p < LPIX && y >= 0 && y < d.h1 && x >= 0 && x < d.w1;
-      return ok ? ((((unsigned)(b * d.h1 + y) * nblk_low) * 8u + (unsigned)plg) * (unsigned)d.w1 + (unsigned)x) * 16u : kOOB;
+      return ok ? split_pixel_offset<2>((unsigned)(b * d.h1 + y), nblk_low, (unsigned)plg, (unsigned)d.w1, (unsigned)x) : kSfhOOB;
     };
     const int base = lg * LPIXP + py * LW + lq + px;
     auto xaddr = [&](int t, int i, int p) { return base + p * 4 * LPIXP + (i + (t >> 1)) * LW + (t & 1); };
@@ -175,7 +166,7 @@ __global__ __launch_bounds__(256, 2) void conv_upfused_kernel(const sfh_conv_des
       const int hy = p / SWW, hx = p - hy * SWW;
       const int y = y0 - 1 + hy, x = x0 - 1 + hx;
       const bool ok = p < SPIX && y >= 0 && y < d.H && x >= 0 && x < d.W;
-      return ok ? ((((unsigned)(b * d.H + y) * nblk_skip) * 8u + (unsigned)plg) * (unsigned)d.W + (unsigned)x) * 16u : kOOB;
+      return ok ? split_pixel_offset<2>((unsigned)(b * d.H + y), nblk_skip, (unsigned)plg, (unsigned)d.W, (unsigned)x) : kSfhOOB;
     };
     const int base = lg * SPIXP + py * SWW + 2 * lq + px;
     auto xaddr = [&](int t, int i, int p) { return base + p * 4 * SPIXP + (2 * i + t / 3) * SWW + (t % 3); };
@@ -184,7 +175,7 @@ __global__ __launch_bounds__(256, 2) void conv_upfused_kernel(const sfh_conv_des
   // ---- BatchNorm scale / shift, ReLU, two-plane split, store (H2: (B, H, cs/32, 2, 4, W, 8))
   const float dscale = sfh_h2_pow2(d.h2_exp_dst);
   const unsigned cs = (unsigned)d.dst_cs, run = (unsigned)d.W * 16u, planeb = 4u * run;
-  const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(d.dst, 0, (int)kOOB, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(d.dst, 0, (int)kSfhOOB, 0x00020000);
   unsigned over = 0u;
 #pragma unroll
   for (int n = 0; n < 4; ++n) {
@@ -201,8 +192,8 @@ __global__ __launch_bounds__(256, 2) void conv_upfused_kernel(const sfh_conv_des
       }
       const int yo = y0 + 2 * i + py;
       const bool ok = yo < d.H && xo < d.W;
-      const unsigned voff = ok ? (unsigned)(b * d.H + yo) * ((cs >> 5) * 8u * run) + (unsigned)xo * 16u + lane_co : kOOB;
-      sfh_u32x2 pl[2];
+      const unsigned voff = ok ? (unsigned)(b * d.H + yo) * ((cs >> 5) * 8u * run) + (unsigned)xo * 16u + lane_co : kSfhOOB;
+      u32x2 pl[2];
       unsigned o = 0u;      // (as sfh_conv_epilogue: only pixels of the tensor enter the words)
       sfh_split4_h2(v, dscale, pl, o);
       o = ok ? o : 0u;
@@ -231,14 +222,14 @@ extern "C" int sfh_conv_upfused_fwd(const sfh_conv_desc* dp, void* stream_) {
               "conv_upfused_fwd: channel counts (cout %d, skip %d / %d, low %d / %d, dst %d)", d.cout, d.c0, d.cs0, d.c1, d.cs1, d.dst_cs);
   SFH_REQUIRE(!d.residual && !d.dst_pool && !d.head_w && !d.acc_init && !(d.ksplit > 1) && !d.stats_partial && !d.pool0,
               "conv_upfused_fwd: a plain launch (no residual / pooled output / head / acc_init / split-K / statistics)");
-  SFH_REQUIRE(d.h2_exp_dst >= -64 && d.h2_exp_dst <= 64, "conv_upfused_fwd: h2_exp_dst=%d out of range (-64 .. 64)", d.h2_exp_dst);
+  if (!sfh_h2_exp_ok("conv_upfused_fwd", "h2_exp_dst", d.h2_exp_dst)) return SFH_E_ARG;
   UpGeom g;
   g.tiles_y = sfh_cdiv(d.H, TH);
   g.tiles_x = sfh_cdiv(d.W, TW);
   g.ntiles = d.batch * g.tiles_y * g.tiles_x;
   g.nblk = d.cout / 64;
   const unsigned long long bs = 4ULL * d.batch * d.H * d.W * d.cs0, bl = 4ULL * d.batch * d.h1 * d.w1 * d.cs1;
-  SFH_REQUIRE(bs < kOOB && bl < kOOB && 4ULL * d.batch * d.H * d.W * (unsigned long long)d.dst_cs < kOOB,
+  SFH_REQUIRE(sfh_fits_descriptor(bs) && sfh_fits_descriptor(bl) && sfh_fits_descriptor(4ULL * d.batch * d.H * d.W * (unsigned long long)d.dst_cs),
               "conv_upfused_fwd: a tensor exceeds the 4 GiB descriptor range");
   g.bytes_skip = (unsigned)bs;
   g.bytes_low = (unsigned)bl;

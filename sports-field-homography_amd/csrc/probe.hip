@@ -2,9 +2,7 @@
 // once per rank so that every bench line carries what THIS device sustains (the pool's MI355X differ by up to 4 % in the
 // clock they hold under an MFMA-dense load, which is more than most kernel changes are worth).
 #include "common.h"
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+#include "split_mfma.h"
 
 // Register-resident v_mfma_f32_16x16x32_f16 loop: 16 independent accumulators per wave, operands = fp16 values in
 // [0.5, 1) with random mantissas (the matrix cores' power draw, and with it the clock the chip holds, follows the data).
@@ -33,8 +31,7 @@ __global__ __launch_bounds__(256, 2) void probe_mfma_f16_kernel(float* out, int 
     for (int k = 0; k < 4; ++k)
 #pragma unroll
       for (int i = 0; i < 16; ++i)
-        acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a[(i + k) & 3]),
-                                                        __builtin_bit_cast(f16x8, b[(i >> 2) ^ k]), acc[i], 0, 0, 0);
+        acc[i] = split_mfma<2>(a[(i + k) & 3], b[(i >> 2) ^ k], acc[i]);
   }
   asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(c1), "=s"(r1)::"memory");
   f32x4 t = {0, 0, 0, 0};

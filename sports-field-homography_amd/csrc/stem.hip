@@ -15,11 +15,8 @@
 // and where a packed weight lies, is stated once for both instances in stem_core.h.
 #include "common.h"
 #include "conv_epilogue.h"
+#include "split_mfma.h"
 #include "stem_core.h"
-
-typedef unsigned int st_u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 st_bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 st_f16x8 __attribute__((ext_vector_type(8)));
 
 namespace {
 
@@ -49,15 +46,13 @@ struct StemGeom {
   int tiles_x, tiles_y, ntiles;
 };
 
-__device__ __forceinline__ st_bf16x8 st_bf(const st_u32x4& v) { return __builtin_bit_cast(st_bf16x8, v); }
-
 // NP = 3: the input is split into three bf16 planes, six products (bf16x6); NP = 2: two fp16 planes of v * 2^2, three
 // products (f16x3: weights packed as planes of w * 2^wexp, the caller folds 2^-(wexp + 2) into `scale`)
 template <int NP>
 __global__ __launch_bounds__(256, 2) void stem7x7_kernel(const sfh_conv_desc d, const StemGeom g) {
   using C = StemCfg;
   extern __shared__ __attribute__((aligned(16))) float smem_f[];
-  st_u32x4* const lds = reinterpret_cast<st_u32x4*>(smem_f);   // [3 planes][HPIXP] x 16 B
+  u32x4* const lds = reinterpret_cast<u32x4*>(smem_f);   // [3 planes][HPIXP] x 16 B
   const int tid = threadIdx.x, lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wv >> 1, wn = wv & 1;
@@ -82,7 +77,7 @@ __global__ __launch_bounds__(256, 2) void stem7x7_kernel(const sfh_conv_desc d, 
       v[0] = a[0]; v[1] = a[1]; v[2] = a[2]; v[3] = a[3]; v[4] = b[0]; v[5] = b[1]; v[6] = b[2]; v[7] = b[3];
     }
     if constexpr (NP == 3) {
-      st_u32x4 pl[3];
+      u32x4 pl[3];
       float r[8];
 #pragma unroll
       for (int j = 0; j < 8; ++j) r[j] = v[j];
@@ -98,11 +93,11 @@ __global__ __launch_bounds__(256, 2) void stem7x7_kernel(const sfh_conv_desc d, 
         lds[q * C::HPIXP + p] = pl[q];
       }
     } else {
-      sfh_u32x2 pa[2], pb[2];
+      u32x2 pa[2], pb[2];
       sfh_split4_h2((f32x4){v[0], v[1], v[2], v[3]}, in_scale, pa, over);
       sfh_split4_h2((f32x4){v[4], v[5], v[6], v[7]}, in_scale, pb, over);
-      lds[p] = (st_u32x4){pa[0][0], pa[0][1], pb[0][0], pb[0][1]};
-      lds[C::HPIXP + p] = (st_u32x4){pa[1][0], pa[1][1], pb[1][0], pb[1][1]};
+      lds[p] = (u32x4){pa[0][0], pa[0][1], pb[0][0], pb[0][1]};
+      lds[C::HPIXP + p] = (u32x4){pa[1][0], pa[1][1], pb[1][0], pb[1][1]};
     }
   }
   if constexpr (NP == 2) {
@@ -110,14 +105,14 @@ __global__ __launch_bounds__(256, 2) void stem7x7_kernel(const sfh_conv_desc d, 
   }
 
   // ---- weights: packed [step 13][plane NP][cout subtile 4][lane 64] x 16 B; this wave: subtiles 2*wn, 2*wn+1
-  const st_u32x4* wp = reinterpret_cast<const st_u32x4*>(d.wpacked) + (2 * wn) * 64 + lane;
-  auto load_w = [&](st_u32x4 (&w)[NP][2], int s) {
+  const u32x4* wp = reinterpret_cast<const u32x4*>(d.wpacked) + (2 * wn) * 64 + lane;
+  auto load_w = [&](u32x4 (&w)[NP][2], int s) {
 #pragma unroll
     for (int p = 0; p < NP; ++p)
 #pragma unroll
       for (int ni = 0; ni < 2; ++ni) w[p][ni] = wp[((s * NP + p) * 4 + ni) * 64];
   };
-  st_u32x4 wa[NP][2], wb[NP][2];
+  u32x4 wa[NP][2], wb[NP][2];
   load_w(wa, 0);
 
   f32x4 acc[2][8];
@@ -130,30 +125,23 @@ __global__ __launch_bounds__(256, 2) void stem7x7_kernel(const sfh_conv_desc d, 
   // lane's pixel in pixel group mi of this wave: row wm*4 + mi/2, col 16*(mi%2) + lq; halo pixel of tap
   // (ky,kx): (2*row + ky) * HW + 2*col + kx.  The tap of a lane is 4*s + lg.
   const int pix0 = (2 * (wm * 4)) * C::HW + 2 * lq;
-  constexpr int NPROD = NP == 3 ? 6 : 3;
-  constexpr int PW[6] = {0, 1, NP == 3 ? 2 : 0, 0, 1, 0}, PX[6] = {NP == 3 ? 2 : 1, NP == 3 ? 1 : 0, 0, 1, 0, 0};
+  using P = SplitProducts<NP>;
 #pragma unroll
   for (int s = 0; s < C::NSTEP; ++s) {
-    st_u32x4 (&wc)[NP][2] = (s & 1) ? wb : wa;
-    st_u32x4 (&wn_)[NP][2] = (s & 1) ? wa : wb;
+    u32x4 (&wc)[NP][2] = (s & 1) ? wb : wa;
+    u32x4 (&wn_)[NP][2] = (s & 1) ? wa : wb;
     if (s + 1 < C::NSTEP) load_w(wn_, s + 1);
     const int toff = st_tap_off(8, st_tap(8, s, lg));   // padding taps carry zero weights: any valid address will do
 #pragma unroll
     for (int mi = 0; mi < 8; ++mi) {
       const int moff = (2 * (mi >> 1)) * C::HW + 32 * (mi & 1);
-      st_u32x4 xq[NP];
+      u32x4 xq[NP];
 #pragma unroll
       for (int p = 0; p < NP; ++p) xq[p] = lds[p * C::HPIXP + pix0 + moff + toff];
 #pragma unroll
-      for (int k6 = 0; k6 < NPROD; ++k6)
+      for (int k6 = 0; k6 < P::N; ++k6)
 #pragma unroll
-        for (int ni = 0; ni < 2; ++ni) {
-          if constexpr (NP == 3)
-            acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(st_bf(wc[PW[k6]][ni]), st_bf(xq[PX[k6]]), acc[ni][mi], 0, 0, 0);
-          else
-            acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(st_f16x8, wc[PW[k6]][ni]),
-                                                                __builtin_bit_cast(st_f16x8, xq[PX[k6]]), acc[ni][mi], 0, 0, 0);
-        }
+        for (int ni = 0; ni < 2; ++ni) acc[ni][mi] = split_mfma<NP>(wc[P::PW[k6]][ni], xq[P::PX[k6]], acc[ni][mi]);
     }
   }
   sfh_conv_epilogue<C, 2, 8>(d, g, acc, 32 * wn, wm * 8, (img << 16) | y0, x0, lq, lg);
@@ -169,7 +157,7 @@ template <int NP>
 __global__ __launch_bounds__(256, 2) void stem7x7_wide_kernel(const sfh_conv_desc d, const StemGeom g) {
   using C = StemWideCfg;
   extern __shared__ __attribute__((aligned(16))) float smem_f[];
-  st_u32x4* const lds = reinterpret_cast<st_u32x4*>(smem_f);   // st_lds_elem: [NP planes][2 halves][HPIXP] x 16 B
+  u32x4* const lds = reinterpret_cast<u32x4*>(smem_f);   // st_lds_elem: [NP planes][2 halves][HPIXP] x 16 B
   const int tid = threadIdx.x, lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wv >> 1, wn = wv & 1;
@@ -200,7 +188,7 @@ __global__ __launch_bounds__(256, 2) void stem7x7_wide_kernel(const sfh_conv_des
       float r[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
 #pragma unroll
       for (int q = 0; q < 3; ++q) {
-        st_u32x4 pl;
+        u32x4 pl;
 #pragma unroll
         for (int h = 0; h < 4; ++h) {
           const unsigned w = sfh_cvt_pk(r[2 * h], r[2 * h + 1]);
@@ -211,11 +199,11 @@ __global__ __launch_bounds__(256, 2) void stem7x7_wide_kernel(const sfh_conv_des
         lds[st_lds_elem(C::CH, q, hf, p)] = pl;
       }
     } else {
-      sfh_u32x2 pa[2], pb[2];
+      u32x2 pa[2], pb[2];
       sfh_split4_h2(a, in_scale, pa, over);
       sfh_split4_h2(b, in_scale, pb, over);
-      lds[st_lds_elem(C::CH, 0, hf, p)] = (st_u32x4){pa[0][0], pa[0][1], pb[0][0], pb[0][1]};
-      lds[st_lds_elem(C::CH, 1, hf, p)] = (st_u32x4){pa[1][0], pa[1][1], pb[1][0], pb[1][1]};
+      lds[st_lds_elem(C::CH, 0, hf, p)] = (u32x4){pa[0][0], pa[0][1], pb[0][0], pb[0][1]};
+      lds[st_lds_elem(C::CH, 1, hf, p)] = (u32x4){pa[1][0], pa[1][1], pb[1][0], pb[1][1]};
     }
   }
   if constexpr (NP == 2) {
@@ -223,14 +211,14 @@ __global__ __launch_bounds__(256, 2) void stem7x7_wide_kernel(const sfh_conv_des
   }
 
   // ---- weights: packed [step 25][plane NP][cout subtile 4][lane 64] x 16 B; this wave: subtiles 2*wn, 2*wn+1
-  const st_u32x4* wp = reinterpret_cast<const st_u32x4*>(d.wpacked) + (2 * wn) * 64 + lane;
-  auto load_w = [&](st_u32x4 (&w)[NP][2], int s) {
+  const u32x4* wp = reinterpret_cast<const u32x4*>(d.wpacked) + (2 * wn) * 64 + lane;
+  auto load_w = [&](u32x4 (&w)[NP][2], int s) {
 #pragma unroll
     for (int p = 0; p < NP; ++p)
 #pragma unroll
       for (int ni = 0; ni < 2; ++ni) w[p][ni] = wp[((s * NP + p) * 4 + ni) * 64];
   };
-  st_u32x4 wa[NP][2], wb[NP][2];
+  u32x4 wa[NP][2], wb[NP][2];
   load_w(wa, 0);
 
   f32x4 acc[2][4];
@@ -243,29 +231,22 @@ __global__ __launch_bounds__(256, 2) void stem7x7_wide_kernel(const sfh_conv_des
   // lane's pixel in pixel group mi of this wave: tile row wm*4 + mi, column lq; its channel half: st_chan0 / 8
   const int hf = st_chan0(C::CH, lg) >> 3;
   const int pix0 = st_pixel_off(C::CH, wm * 4, lq);
-  constexpr int NPROD = NP == 3 ? 6 : 3;
-  constexpr int PW[6] = {0, 1, NP == 3 ? 2 : 0, 0, 1, 0}, PX[6] = {NP == 3 ? 2 : 1, NP == 3 ? 1 : 0, 0, 1, 0, 0};
+  using P = SplitProducts<NP>;
 #pragma unroll
   for (int s = 0; s < C::NSTEP; ++s) {
-    st_u32x4 (&wc)[NP][2] = (s & 1) ? wb : wa;
-    st_u32x4 (&wn_)[NP][2] = (s & 1) ? wa : wb;
+    u32x4 (&wc)[NP][2] = (s & 1) ? wb : wa;
+    u32x4 (&wn_)[NP][2] = (s & 1) ? wa : wb;
     if (s + 1 < C::NSTEP) load_w(wn_, s + 1);
     const int toff = st_tap_off(C::CH, st_tap(C::CH, s, lg));   // padding taps carry zero weights: any valid address will do
 #pragma unroll
     for (int mi = 0; mi < 4; ++mi) {
-      st_u32x4 xq[NP];
+      u32x4 xq[NP];
 #pragma unroll
       for (int p = 0; p < NP; ++p) xq[p] = lds[st_lds_elem(C::CH, p, hf, pix0 + st_pixel_off(C::CH, mi, 0) + toff)];
 #pragma unroll
-      for (int k6 = 0; k6 < NPROD; ++k6)
+      for (int k6 = 0; k6 < P::N; ++k6)
 #pragma unroll
-        for (int ni = 0; ni < 2; ++ni) {
-          if constexpr (NP == 3)
-            acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(st_bf(wc[PW[k6]][ni]), st_bf(xq[PX[k6]]), acc[ni][mi], 0, 0, 0);
-          else
-            acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(st_f16x8, wc[PW[k6]][ni]),
-                                                                __builtin_bit_cast(st_f16x8, xq[PX[k6]]), acc[ni][mi], 0, 0, 0);
-        }
+        for (int ni = 0; ni < 2; ++ni) acc[ni][mi] = split_mfma<NP>(wc[P::PW[k6]][ni], xq[P::PX[k6]], acc[ni][mi]);
     }
   }
   sfh_conv_epilogue<C, 2, 4>(d, g, acc, 32 * wn, wm * 4, (img << 16) | y0, x0, lq, lg);
@@ -339,17 +320,11 @@ extern "C" int sfh_stem7x7_fwd(const sfh_conv_desc* dp, void* stream) {
                   !d.dst_pool && !d.src1, "stem7x7_fwd: 64 output channels, plain fp32 NHWC destination");
   SFH_REQUIRE(d.batch > 0 && d.batch < 32768 && d.H > 0 && d.W > 0 && d.h0 == d.H && d.w0 == d.W, "stem7x7_fwd: bad geometry");
   StemGeom g;
-  g.Ho = (d.H + 6 - 7) / 2 + 1;
-  g.Wo = (d.W + 6 - 7) / 2 + 1;
-  SFH_REQUIRE(g.Ho < 65536, "stem7x7_fwd: frame too tall");
-  g.rows_total = 0; g.rows_per_img = g.Ho; g.rows_magic = 0;
-  g.tiles_x = sfh_cdiv(g.Wo, wide ? StemWideCfg::TW : StemCfg::TW);
-  g.tiles_y = sfh_cdiv(g.Ho, wide ? StemWideCfg::TH : StemCfg::TH);
-  SFH_REQUIRE((long long)g.tiles_x * g.tiles_y * d.batch < 0x7FFFFFFFLL, "stem7x7_fwd: too many tiles");
-  g.ntiles = g.tiles_x * g.tiles_y * d.batch;
-  SFH_REQUIRE((unsigned long long)d.batch * g.Ho * g.Wo * d.dst_cs * 4ULL < 0xFFFFFFF0ULL, "stem7x7_fwd: destination exceeds 4 GiB");
+  SFH_REQUIRE(sfh_conv_grid(g, d.batch, d.H, d.W, 7, 2, false, false, wide ? StemWideCfg::TH : StemCfg::TH, wide ? StemWideCfg::TW : StemCfg::TW),
+              "stem7x7_fwd: frame too tall or too many tiles");
+  SFH_REQUIRE(sfh_fits_descriptor((unsigned long long)d.batch * g.Ho * g.Wo * d.dst_cs * 4ULL), "stem7x7_fwd: destination exceeds 4 GiB");
   SFH_REQUIRE(d.split_arith == 0 || d.split_arith == SFH_FMT_S3 || d.split_arith == SFH_FMT_H2, "stem7x7_fwd: split_arith=%d", d.split_arith);
-  SFH_REQUIRE(d.h2_exp_src >= -64 && d.h2_exp_src <= 64, "stem7x7_fwd: h2_exp_src=%d out of range (-64 .. 64)", d.h2_exp_src);
+  if (!sfh_h2_exp_ok("stem7x7_fwd", "h2_exp_src", d.h2_exp_src)) return SFH_E_ARG;
   if (wide) {
     if (d.split_arith == SFH_FMT_H2) {
       hipLaunchKernelGGL(stem7x7_wide_kernel<2>, dim3((unsigned)g.ntiles), dim3(256), st_lds_bytes(16, 2), (hipStream_t)stream, d, g);

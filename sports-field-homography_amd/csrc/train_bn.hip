@@ -392,7 +392,7 @@ __device__ __forceinline__ long tr_s3_elem(long row, int x, int c, int W, int C,
 // the same 8 values as two fp16 planes (H2 format, include/sfh_amd.h); `over`: see sfh_split4_h2
 __device__ __forceinline__ void tr_split8_h2(const float (&v)[8], unsigned short* __restrict__ dst, long e, long ps,
                                              unsigned& over) {
-  sfh_u32x2 pa[2], pb[2];
+  u32x2 pa[2], pb[2];
   sfh_split4_h2((f32x4){v[0], v[1], v[2], v[3]}, kSfhH2Scale, pa, over);
   sfh_split4_h2((f32x4){v[4], v[5], v[6], v[7]}, kSfhH2Scale, pb, over);
   typedef unsigned int tr_u32x4 __attribute__((ext_vector_type(4)));

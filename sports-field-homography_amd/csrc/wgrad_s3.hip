@@ -24,17 +24,13 @@
 
 #include "common.h"
 #include "det_core.h"   // the split plan and det_add: the deterministic mode's slabs
+#include "split_mfma.h"
 
 namespace {
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef __attribute__((address_space(3))) s16x4* lds_s16x4_ptr;
-
-constexpr unsigned kOOB = 0xFFFFFFF0u;
 
 struct WgS3Args {
   const void* dz; int M;               // dz S3 (B, H, M/32, 3, 4, W, 8)
@@ -123,7 +119,7 @@ __global__ __launch_bounds__(256, NP == 2 ? 3 : 2) void wgrad_s3_kernel(const Wg
         const int r = hp / HWD, c = hp - r * HWD;
         const int yy = y0 - PADK + r - a.pad_top, xx = x0 - PADK + c - a.pad_left;
         const bool ok = (unsigned)yy < (unsigned)a.xh && (unsigned)xx < (unsigned)a.xw;
-        voff[i] = ok ? (unsigned)((yy * CBX * R4 * a.xw + xx) * 16) : kOOB;
+        voff[i] = ok ? (unsigned)((yy * CBX * R4 * a.xw + xx) * 16) : kSfhOOB;
         act[i] = hp < HP;
       }
       const unsigned xsb = (unsigned)((b * a.xh * CBX + nb32) * R4) * (unsigned)a.xw * 16u;
@@ -139,7 +135,7 @@ __global__ __launch_bounds__(256, NP == 2 ? 3 : 2) void wgrad_s3_kernel(const Wg
       }
       const int py = lane / TW, px = lane - py * TW;
       const int y = y0 + py, x = x0 + px;
-      const unsigned dvoff = (y < a.H && x < a.W) ? (unsigned)((y * MB * R4 * a.W + x) * 16) : kOOB;
+      const unsigned dvoff = (y < a.H && x < a.W) ? (unsigned)((y * MB * R4 * a.W + x) * 16) : kSfhOOB;
       const unsigned dsb = (unsigned)((b * a.H * MB + mb64 * 2) * R4) * (unsigned)a.W * 16u;
 #pragma unroll
       for (int j = 0; j < 2 * NP; ++j) {
@@ -171,19 +167,11 @@ __global__ __launch_bounds__(256, NP == 2 ? 3 : 2) void wgrad_s3_kernel(const Wg
           const unsigned ad = xb + (unsigned)(((p * 4) * PX + (s * RS + ky) * HWD + kx) * 16);
           bfr[p] = frag(tr(ad), tr(ad + 64));
         }
-        // the kept partial products, smallest first (as in the forward kernel)
-        constexpr int NPROD = NP == 3 ? 6 : 3;
-        constexpr int PA[6] = {0, 1, NP == 3 ? 2 : 0, 0, 1, 0}, PB[6] = {NP == 3 ? 2 : 1, NP == 3 ? 1 : 0, 0, 1, 0, 0};
+        using P = SplitProducts<NP>;   // dz takes the weights' place (first operand), x the activations'
 #pragma unroll
-        for (int k6 = 0; k6 < NPROD; ++k6)
+        for (int k6 = 0; k6 < P::N; ++k6)
 #pragma unroll
-          for (int mb = 0; mb < 2; ++mb) {
-            if constexpr (NP == 3)
-              acc[mb][t9] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[mb][PA[k6]], bfr[PB[k6]], acc[mb][t9], 0, 0, 0);
-            else
-              acc[mb][t9] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, af[mb][PA[k6]]),
-                                                                  __builtin_bit_cast(f16x8, bfr[PB[k6]]), acc[mb][t9], 0, 0, 0);
-          }
+          for (int mb = 0; mb < 2; ++mb) acc[mb][t9] = split_mfma<NP>(af[mb][P::PW[k6]], bfr[P::PX[k6]], acc[mb][t9]);
       }
     }
     __syncthreads();   // every wave is done with the buffer before the next tile's DMA lands in it
@@ -256,7 +244,7 @@ static int conv_wgrad_s3_impl(const void* dz_s3, int M, const void* x_s3, int x_
   SFH_REQUIRE(n_off >= 0 && n_off + N <= raw_n, "%s: n_off=%d N=%d raw_n=%d", who, n_off, N, raw_n);
   SFH_REQUIRE(pad_top >= 0 && pad_left >= 0 && pad_top + xh <= H && pad_left + xw <= W, "%s: source does not fit the frame", who);
   const unsigned long long bdz = bpe * batch * H * W * M, bx = bpe * batch * xh * xw * x_channels;
-  SFH_REQUIRE(bdz < kOOB && bx < kOOB, "%s: a tensor of %llu bytes exceeds the 4 GiB descriptor range", who, bdz > bx ? bdz : bx);
+  SFH_REQUIRE(sfh_fits_descriptor(bdz) && sfh_fits_descriptor(bx), "%s: a tensor of %llu bytes exceeds the 4 GiB descriptor range", who, bdz > bx ? bdz : bx);
   SFH_REQUIRE(p.ok, "%s: grid too large", who);
   WgS3Args a;
   a.dz = dz_s3; a.M = M; a.x = x_s3; a.xc = x_channels; a.xh = xh; a.xw = xw; a.N = N;

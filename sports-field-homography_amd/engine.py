@@ -28,16 +28,29 @@ _TILES_S3_HALF = ((_lib.TILE_8x16, 8, 16), (_lib.TILE_16x8, 16, 8))
 _WG_SLOTS = 512  # workgroups resident on the chip at two per CU
 
 
+def _zero_rows(ksize, ho, split):
+    """shared zero rows per frame of the flattened row space (csrc/conv_geom.h, sfh_zero_rows): the padding before the window;
+    the split-operand kernels keep the rows per frame even (fused 2x2 pool windows never straddle a tile edge)"""
+    zr = ksize // 2
+    if split:
+        zr += (ho + zr) & 1
+    return zr
+
+
+def _ntiles(batch, ho, wo, stride, zr, th, tw):
+    """pixel tiles of th x tw outputs (csrc/conv_geom.h, sfh_conv_grid): stride 1 tiles the flattened rows of all frames,
+    stride 2 every frame for itself"""
+    ty = batch * -(-ho // th) if stride == 2 else -(-(batch * (ho + zr)) // th)
+    return ty * -(-wo // tw)
+
+
 def choose_tile(batch, ho, wo, stride, zrows=1):
     """fp32 kernel: pick the workgroup tile that wastes the fewest padded output pixels."""
     best = None
     for tid, th, tw in _TILES:
         if stride == 2:
             th //= 2
-            ty = batch * -(-ho // th)
-        else:
-            ty = -(-(batch * (ho + zrows)) // th)  # flattened rows, `zrows` shared zero rows per frame
-        cost = ty * th * (-(-wo // tw)) * tw
+        cost = _ntiles(batch, ho, wo, stride, zrows, th, tw) * th * tw
         if best is None or cost < best[0]:
             best = (cost, tid)
     return best[1]
@@ -53,11 +66,7 @@ def choose_tile_s3(batch, ho, wo, stride, zrows, nblk, ksize=3, wg_slots=_WG_SLO
     else:  # stride 1: full-size tiles (half-size tiles measured no faster on ResNet layer3/4)
         cands = _TILES
     for tid, th, tw in cands:
-        if stride == 2:
-            ty = batch * -(-ho // th)
-        else:
-            ty = -(-(batch * (ho + zrows)) // th)
-        ntiles = ty * (-(-wo // tw))
+        ntiles = _ntiles(batch, ho, wo, stride, zrows, th, tw)
         rounds = -(-(ntiles * nblk) // wg_slots)
         # equal estimates: prefer the larger tile (less per-workgroup overhead, more operand reuse)
         cost = (rounds * th * tw, ntiles * th * tw, -th * tw)
@@ -73,8 +82,8 @@ def choose_small_map(batch, ho, wo, zr, cout, tile_id, max_wgs=None):
     gives at least 1.2x the workgroups.  At batch 16 and 640x360: ResNet layer4 (192 -> 256 workgroups: 79 -> 50 us) and layer3
     (240 -> 512: equal alone, better under the pipeline); at batch 1 most of the net."""
     th, tw = next((a, b) for t_, a, b in _TILES + _TILES_S3_HALF if t_ == tile_id)
-    std = -(-(batch * (ho + zr)) // th) * -(-wo // tw) * (cout // 64)
-    fine = batch * -(-ho // 12) * -(-wo // 20) * (cout // 32)
+    std = _ntiles(batch, ho, wo, 1, zr, th, tw) * (cout // 64)
+    fine = _ntiles(batch, ho, wo, 2, 0, 12, 20) * (cout // 32)   # (tiles per frame, as at stride 2)
     return std <= (_SMALL_MAP_MAX if max_wgs is None else max_wgs) and fine * 5 >= std * 6
 
 
@@ -85,14 +94,9 @@ def choose_ksplit(batch, ho, wo, stride, cout, nstages, ksize=3, wg_slots=_WG_SL
     stages.  1 = no split.  Measured at batch 16 (profiles/r03_resnet_table_*.txt): layer3 (240 workgroups) 53 us
     unsplit against 49 + 10.5 us (conv x2 + finish), layer4 (192) 82 against 74 + 8 - grids of that size are bound
     by the weight stream every pixel tile pulls from L2, not by idle CUs, so they are left alone."""
-    zr = ksize // 2
-    zr += (ho + zr) & 1
+    zr = _zero_rows(ksize, ho, True)
     cands = _TILES_S3_HALF if stride == 2 else _TILES
-    ntiles = None
-    for tid, th, tw in cands:
-        ty = batch * -(-ho // th) if stride == 2 else -(-(batch * (ho + zr)) // th)
-        n = ty * (-(-wo // tw))
-        ntiles = n if ntiles is None else min(ntiles, n)
+    ntiles = min(_ntiles(batch, ho, wo, stride, zr, th, tw) for tid, th, tw in cands)
     wgs = ntiles * (cout // 64)
     if wgs * 4 > wg_slots:
         return 1
@@ -451,10 +455,7 @@ class PackedConv(_H2Layer):
         pad2 = self.ksize // 2 + (self.ksize - 1) // 2  # pad before + pad after
         ho = (H + pad2 - self.ksize) // self.stride + 1
         wo = (W + pad2 - self.ksize) // self.stride + 1
-        zr = self.ksize // 2
-        if self.fmt is not None:  # even rows per frame (fused 2x2 pool windows never straddle a tile edge)
-            zr += (ho + zr) & 1
-        return ho, wo, zr
+        return ho, wo, _zero_rows(self.ksize, ho, self.fmt is not None)
 
     def _pick_tile(self, batch, ho, wo, zr, wg_couts, plain):
         """-> (tile id, wg_couts) where the caller names no tile; plain: no fused head, statistics or split-K"""
@@ -464,7 +465,7 @@ class PackedConv(_H2Layer):
         # rounds (64 -> 128: +4 %), slower for longer K or few rounds (profiles/r03_conv_rate_probe_w8half.txt)
         if (plain and self.fmt == "h2" and self.ksize == 3 and self.stride == 1 and wg_couts == 0
                 and self.cout % 128 == 0 and 64 <= self.c0 + self.c1 <= 256):
-            nt = -(-(batch * (ho + zr)) // 8) * -(-wo // 16)
+            nt = _ntiles(batch, ho, wo, 1, zr, 8, 16)
             if nt * (self.cout // 128) >= _W8_HALF_ROUNDS * _WG_SLOTS:
                 return _lib.TILE_8x16, 128
         return choose_tile_s3(batch, ho, wo, self.stride, zr, self.cout // 64, self.ksize), wg_couts
