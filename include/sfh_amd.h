@@ -1552,6 +1552,91 @@ int sfh_uvfit_accumulate(const float* uv, const float* logits, int nc, const flo
 int sfh_uvfit_step(const double* partial, int64_t slabs, int batch, int pass, int last, const float* theta_eval,
                    float* theta_next, int32_t* status, double* stats, void* stream);
 
+/* -------------------------------------------------------------------------------------------------
+ * Inter-frame homography tracking (csrc/track.hip).  M_t is the homography under which frame t lines up with frame t - 1,
+ * estimated from the pixels themselves by direct photometric alignment - coarse to fine, a few robust Levenberg-Marquardt
+ * steps per pair - and theta is carried across it: theta_t = theta_{t-1} M_t (theta maps the normalised frame to the
+ * normalised court, Reconstructor.warp's matrix; M maps the normalised coordinates of the CURRENT frame of a pair to those of
+ * its PREVIOUS frame).  THE RULE, stated here once; the kernels and the numpy restatement tests/track_ref.py follow it.  The
+ * reference project has no counterpart.
+ *
+ * Planes.  Luma of a pixel: y = (19595 r + 38470 g + 7471 b + 32768) >> 16 (csrc/ycc.h, the JPEG encoder's Y); frames are
+ *   uint8 (B,H,W,3), channel 0 is r, or with bgr != 0 channel 2 is.  Plane of level f:  P_f[I][J] = fl32(S) / fl32(255 f f),
+ *   S the exact integer sum of y over the f x f block, one IEEE fp32 division; a scalar plane (B, H/f, W/f).  f in 1..16
+ *   must divide H and W (and an alignment needs planes of at least 2 x 2 pixels); otherwise the call is refused and nothing
+ *   is launched.
+ * Coordinates.  Plane column J of level f has xn = fmaf(ax, J, cx), (ax, cx) = sfh_refine_axis(f, W, W): the centre of the
+ *   averaged block on the full-resolution grid 2 j / (W-1) - 1.  Rows alike with H.  X, Y, Z, s, u = s X, v = s Y exactly as
+ *   the warp and the refinement form them from M (fp32, every operation rounded; s = 1 / (Z + 1e-8) where |Z| > 1e-8, else the
+ *   pixel is not counted).  Back to the previous frame's plane:  px = fmaf(u + 1, kx, -ox),  kx = (W-1) / (2 f),  ox = (f-1) /
+ *   (2 f), evaluated in fp64 on the host and rounded once to fp32 (sfh_track_axis; csrc/track_core.h); py alike with H.  Under
+ *   the identity px = J up to rounding, at every level.  (The refinement's (u + 1) wt / 2 - 0.5 is NOT this: it mixes the warp
+ *   grid with a template raster.)
+ * Residual.  Bilinear taps at (x0, y0) = (floor px, floor py) of the previous frame's plane.  A pixel COUNTS iff |Z| > 1e-8
+ *   and all four taps lie inside the plane: 0 <= x0, x0 + 1 <= wl - 1, 0 <= y0, y0 + 1 <= hl - 1 (fp32 comparisons; a NaN
+ *   fails).  No zero padding: outside the previous frame there is no evidence.  The weights wx1 = px - x0, wx0 = 1 - wx1 (wy
+ *   alike), the value ((t00 wy0 wx0 + t01 wy0 wx1) + t10 wy1 wx0) + t11 wy1 wx1 and the tap differences duf = wy0 (t01 - t00) +
+ *   wy1 (t11 - t10), dvf = wx0 (t10 - t00) + wx1 (t11 - t01) are fp32, operation for operation as the refinement states them;
+ *   everything behind them is fp64.  r = value - P_cur[I][J].
+ * Robust weight and cost (Geman-McClure).  q = r r / d2 with d2 = delta delta formed on the host, c = 1 + q, ic = 1 / c,
+ *   rho = (r r) ic, omega = ic ic: two fp64 divisions, no transcendental function.  du = duf kx, dv = dvf ky (the fp32 kx, ky
+ *   widened).  With a = (s xn, s yn, s, 0, 0, 0, gu xn, gu yn), b = (0, 0, 0, s xn, s yn, s, gv xn, gv yn), gu = -(X s) s, gv =
+ *   -(Y s) s, all fp64 from the widened fp32 values:  J_k = du a_k (k = 0..2),  dv b_k (k = 3..5),  du a_k + dv b_k (k = 6, 7).
+ *   SFH_TRACK_SUMS = 46 sums per pair over the counted pixels:  the upper triangle of sum (omega J_i) J_j row by row (36),
+ *   sum (omega J_i) r (8), sum rho (index 44), n = the counted pixels (index 45; exact as a double).
+ * Step.  M[8] is held as given (sfh_amd.track starts it at 1).  Solve (A + lambda diag A) d = -g by csrc/chol8.h; the
+ *   candidate is fl32(M_k + d_k), k < 8 (the accepted M itself when a pivot is not > 0).  It is accepted iff every pivot was
+ *   > 0, n_cand >= nmin, and cost_cand / n_cand < cost_acc / n_acc - two fp64 divisions; a NaN rejects.  The MEAN is compared
+ *   because the overlap changes with M: a plain sum would reward sliding the frames apart.  lambda = 1e-3 at the start of
+ *   every level, / 10 on accept, * 10 on reject.  nmin = ceil(min_overlap hl wl) per level, from the host.  A pair whose first
+ *   evaluation at a level has n < nmin or a sum that is not finite is DEAD from then on: it keeps its last accepted M (the
+ *   start of the schedule if there is none), later steps change nothing of it.  ok = 1 iff the pair is not dead, the accepted
+ *   M is finite and (max_cost <= 0 or the accepted mean cost <= max_cost): the cut / failure flag, with no read-back.
+ * Schedule per level.  sfh_track_accumulate(M) + sfh_track_step(first = 1), then `iters` times sfh_track_accumulate(
+ *   candidate) + sfh_track_step(first = 0), the last of them with last = 1.  No synchronisation.
+ * Carrying theta (sfh_track_propagate).  theta (F,9), optional score (F) with max_score, M (F,9) and link (F) int32: entry t
+ *   belongs to the pair (t - 1, t), entry 0 is not read.  Frame t is GOOD iff theta_t is usable (det of its fp64 copy finite
+ *   and != 0, the expressions stated above sfh_metrics_region) and, with a score array, score_t <= max_score (a NaN fails).
+ *   Good: the output bits are the input's, source[t] = t.  Bad: walk back to the nearest good k < t with t - k <= max_gap and
+ *   every link[k+1 .. t] != 0, walk forward alike (link[t+1 .. k]); the nearer anchor is taken, a tie goes back.  Back: P =
+ *   theta_k, then P = P M_j for j = k+1 .. t ascending.  Forward: P = theta_k, then P = P adj(M_j) for j = k .. t+1
+ *   descending (adj: the nine expressions above sfh_metrics_region).  Products in fp64, entry (i, j) = (p[i][0] m[0][j] +
+ *   p[i][1] m[1][j]) + p[i][2] m[2][j], every operation rounded.  Output fl32(P_i / P_8), entry 8 = 1, source[t] = k.  No
+ *   anchor, or a P_8 that is zero or not finite: nine NaNs, source[t] = -1.  One thread per frame, O(max_gap) work each.
+ *
+ * Every entry launches on the caller's stream, allocates nothing, keeps no pointer and overwrites its outputs; every refusal
+ * returns SFH_E_ARG before anything is launched. */
+#define SFH_TRACK_SUMS 46
+/* a[0] = kx, a[1] = ox of an axis of n frame pixels at level f (HOST pointer; no device call) */
+int sfh_track_axis(int f, int n, float* a);
+/* frames (batch,H,W,3) uint8 -> planes (batch, H/f, W/f) float */
+int sfh_track_planes(const uint8_t* frames, int batch, int H, int W, int f, int bgr, float* planes, void* stream);
+/* bytes of the partial sums of sfh_track_accumulate for planes of h x w (the finest level's serves every coarser one):
+ * ceil(w / 64) * ceil(h / 64) * pairs * 46 doubles; -1 for pairs outside 1..65535 or h, w < 2 */
+int64_t sfh_track_workspace_bytes(int pairs, int h, int w);
+/* The 46 sums of M (pairs,9) per workgroup.  planes (nframes, H/f, W/f) of level f; ia, ib (pairs) int32 DEVICE arrays: pair
+ * p aligns the current frame ib[p] with the previous frame ia[p] (a pair with an index outside [0, nframes) counts no pixel).
+ * Workgroup (x, y) covers 64 columns x 64 rows of the current plane, a lane per column, and stores its sums of pair p at
+ * workspace[((y * gx + x) * pairs + p) * 46 + e], one plain store per sum (wave shuffle, then LDS; no atomics).  delta > 0.
+ * A workspace that is NULL or short is refused. */
+int sfh_track_accumulate(const float* M, const float* planes, int nframes, const int32_t* ia, const int32_t* ib, int pairs,
+                         int H, int W, int f, double delta, void* workspace, long long workspace_bytes, void* stream);
+/* One wave per pair: sums the `slabs` partials [slab][pairs][46] of M_eval (pairs,9) in ascending slab order from 0 and
+ * applies the step rule against the per-pair state: M_acc (pairs,9) float, sums_acc (pairs,46) double, lambda (pairs) double,
+ * pivots_ok (pairs) int32, dead (pairs) int32.  first != 0: M_eval is adopted as the level's start, lambda = 1e-3,
+ * accepted[p * nlevels + level] = 0, stats[(p * nlevels + level) * 3] = its mean cost, and the dead rule is applied (dead is
+ * not read when level == 0).  Otherwise accept / reject as above.  Every call writes stats[(p * nlevels + level) * 3 + 1] =
+ * the accepted mean cost (cost / n: NaN for n = 0), [.. + 2] = the accepted n, ok (pairs) int32 as if the schedule ended
+ * here, and M_next (pairs,9): the next candidate, or the accepted M when last != 0 or the pair is dead.  M_next may be
+ * M_eval.  nmin: a whole number as a double. */
+int sfh_track_step(const double* partial, int64_t slabs, int pairs, int first, int last, const float* M_eval, float* M_acc,
+                   double* sums_acc, double* lambda, int32_t* pivots_ok, int32_t* dead, float* M_next, double* stats,
+                   int32_t* accepted, int32_t* ok, int level, int nlevels, double nmin, double max_cost, void* stream);
+/* theta, M (frames,9) float, score (frames) float or NULL, link (frames) int32 -> theta_out (frames,9) float, source
+ * (frames) int32.  max_gap >= 0.  theta_out must not overlap theta. */
+int sfh_track_propagate(const float* theta, const float* score, float max_score, const float* M, const int32_t* link,
+                        int frames, int max_gap, float* theta_out, int32_t* source, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

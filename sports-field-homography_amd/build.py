@@ -15,7 +15,7 @@ SOURCES = ["capi.hip", "conv_mfma.hip", "conv_s3.hip", "conv_c4h2.hip", "pointwi
            "train_wgrad.hip", "train_step.hip", "stem.hip", "wgrad_s3.hip", "probe.hip", "conv_small.hip", "conv_upfused.hip", "conv_inc_fused.hip", "hostprep.hip",
            "eval.hip", "augment.hip", "overlay.hip", "prepare.hip", "mapping.hip", "pngenc.hip", "jpegenc.hip", "resample.hip",
            "jpegdec.hip", "pngdec.hip", "conv_grouped.hip", "tiffdec.hip", "tiffenc.hip", "det.hip", "refine.hip", "metrics.hip",
-           "uvfit.hip"]
+           "uvfit.hip", "track.hip"]
 # warp.hip's coordinate arithmetic must not be contracted into FMAs (bit-exact nearest
 # sampling against oracle/warp_ref.py); the flag is harmless elsewhere.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off",
@@ -39,7 +39,9 @@ EXTRA_FLAGS = {"warp.hip": _NO_SLP, "conv_s3.hip": _NO_SLP, "conv_mfma.hip": _NO
                "mapping.hip": _NO_SLP,
                # refine.hip's accumulate kernel is that coordinate arithmetic plus per-class fp32 bilinear values and tap
                # differences in front of an fp64 chain: VALU-issue-bound by the same reasoning, not by measurement
-               "refine.hip": _NO_SLP}
+               "refine.hip": _NO_SLP,
+               # track.hip's accumulate kernel is refine.hip's with one scalar plane: the same reasoning, not measured either
+               "track.hip": _NO_SLP}
 
 
 def _stale(target, deps):

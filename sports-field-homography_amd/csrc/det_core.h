@@ -147,6 +147,13 @@ SFH_DET_FN DetPlan det_uvfit_plan(int batch, int h, int w) {    // by is gridDim
   if (batch <= 0 || batch > 65535 || h < 2 || w < 2 || det_cdiv(h, DET_FIT_TILE) > 65535) return det_refuse(DET_BAD_ARG);
   return det_fit_tiles(batch, h, w, DET_UVFIT_SUMS);
 }
+// track_accumulate_kernel (csrc/track.hip): the same tiles over the current frame's plane of a level; `pairs` stands where
+// the batch does (gridDim.z), a plane has at least 2 x 2 pixels
+#define DET_TRACK_SUMS 46    // SFH_TRACK_SUMS
+SFH_DET_FN DetPlan det_track_plan(int pairs, int h, int w) {
+  if (pairs <= 0 || pairs > 65535 || h < 2 || w < 2 || det_cdiv(h, DET_FIT_TILE) > 65535) return det_refuse(DET_BAD_ARG);
+  return det_fit_tiles(pairs, h, w, DET_TRACK_SUMS);
+}
 
 // ------------------------------------------------------------------ backward-filter, fp32 MFMA (csrc/train_wgrad.hip)
 // 64-pixel tiles of th x tw (the shape with the fewest tiles; ties go to the widest), tile index = (b * nty + ty) * ntx + tx.

@@ -26,6 +26,7 @@
 #include "codec_common.h"
 #include "codec_host.h"
 #include "codec_pack.h"
+#include "ycc.h"
 
 namespace {
 
@@ -264,8 +265,7 @@ __device__ __forceinline__ uint32_t walk_block(const int16_t* cf, int pred, cons
   return pos;
 }
 
-// libjpeg's rgb_ycc_convert: 16-bit fixed point, ONE_HALF on Y, CBCR_OFFSET + ONE_HALF - 1 on chroma
-__device__ __forceinline__ int ycc_y(int r, int g, int b) { return (19595 * r + 38470 * g + 7471 * b + 32768) >> 16; }
+// libjpeg's rgb_ycc_convert: 16-bit fixed point, ONE_HALF on Y (ycc_y, ycc.h), CBCR_OFFSET + ONE_HALF - 1 on chroma
 __device__ __forceinline__ int ycc_cb(int r, int g, int b) { return (-11059 * r - 21709 * g + 32768 * b + 8388608 + 32767) >> 16; }
 __device__ __forceinline__ int ycc_cr(int r, int g, int b) { return (32768 * r - 27439 * g - 5329 * b + 8388608 + 32767) >> 16; }
 

@@ -1,0 +1,379 @@
+// track.hip - inter-frame homography tracking: direct photometric alignment of a frame to the one before it by robust
+// Levenberg-Marquardt steps, coarse to fine, and the rule that carries theta across the result.  The rule (planes,
+// coordinates, residual, weight, step, propagation) is stated once in include/sfh_amd.h above the sfh_track_* entries;
+// tests/track_ref.py restates it in numpy.  A close relative of refine.hip, whose structure it keeps:
+//
+// * track_planes_kernel: one thread per averaged pixel; the luma is ycc.h's, the sum an exact integer, one IEEE division.
+// * track_accumulate_kernel: a workgroup covers 64 columns x 64 rows of the current frame's plane (a wave 64 x 16, a lane one
+//   column, so the current plane's row is one contiguous load at any width); the previous plane is a gather of four scalar
+//   taps.  fp32 staging as in refine_accumulate_kernel, fp64 behind it.  The 46 sums are reduced by wave_sum, then across the
+//   four waves through LDS, and stored once into the workgroup's slab: the store pass of det_core.h.  No atomics.
+// * track_step_kernel: one wave per pair; lanes 0..45 take the ascending chain over the slabs (det_sum), every lane then
+//   holds all 46 sums and solves the 8 x 8 system redundantly in registers through chol8_solve (chol8.h).
+// * track_propagate_kernel: one thread per frame, O(max_gap) work, no scan.
+#include <cmath>
+
+#include "common.h"
+#include "det_core.h"
+#include "chol8.h"
+#include "ycc.h"
+#include "track_core.h"
+
+namespace {
+
+constexpr int kSums = SFH_TRACK_SUMS;   // upper triangle of 8 x 8 (36) + g (8) + cost (1) + n (1)
+constexpr int kCost = 44, kN = 45;
+constexpr int kTile = DET_FIT_TILE, kWaveRows = 16;
+static_assert(kSums == DET_TRACK_SUMS, "track sums");
+static_assert(kSums <= 64, "one lane per sum in the step");
+
+// ------------------------------------------------------------------ planes
+__global__ __launch_bounds__(256) void track_planes_kernel(const uint8_t* __restrict__ frames, int batch, int H, int W, int f,
+                                                           int ro, float* __restrict__ planes) {
+  const int wo = W / f, ho = H / f;
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (long)batch * ho * wo) return;
+  const int x = (int)(idx % wo), y = (int)((idx / wo) % ho), b = (int)(idx / ((long)wo * ho));
+  const uint8_t* src = frames + (((long)b * H + (long)y * f) * W + (long)x * f) * 3;
+  int S = 0;
+  for (int dy = 0; dy < f; ++dy)
+    for (int dx = 0; dx < f; ++dx) {
+      const uint8_t* p = src + ((long)dy * W + dx) * 3;
+      S += ycc_y(p[ro], p[1], p[2 - ro]);
+    }
+  planes[idx] = __fdiv_rn((float)S, (float)(255 * f * f));
+}
+
+// ------------------------------------------------------------------ accumulate
+struct TrackGeom {
+  int hl, wl, nframes;
+  float ax, cx, ay, cy, kx, ox, ky, oy;
+  double d2;
+};
+
+__global__ __launch_bounds__(256) void track_accumulate_kernel(const float* __restrict__ M, const float* __restrict__ planes,
+                                                               const int32_t* __restrict__ ia, const int32_t* __restrict__ ib,
+                                                               TrackGeom g, double* __restrict__ partial) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int p = blockIdx.z;
+  const int x = blockIdx.x * kTile + lane;
+  const int fa = ia[p], fb = ib[p];
+  const bool pair_ok = fa >= 0 && fa < g.nframes && fb >= 0 && fb < g.nframes;   // wave-uniform
+  float m[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) m[k] = M[p * 9 + k];
+  const long plane = (long)g.hl * g.wl;
+  const float* prev = planes + (pair_ok ? fa : 0) * plane;
+  const float* cur = planes + (pair_ok ? fb : 0) * plane;
+  const float xmax = (float)(g.wl - 1), ymax = (float)(g.hl - 1);
+  const double dkx = (double)g.kx, dky = (double)g.ky;
+  double acc[kSums];
+#pragma unroll
+  for (int e = 0; e < kSums; ++e) acc[e] = 0.0;
+  if (pair_ok && x < g.wl) {
+    const float xn = __builtin_fmaf(g.ax, (float)x, g.cx);
+    for (int r = 0; r < kWaveRows; ++r) {
+      const int y = blockIdx.y * kTile + wv * kWaveRows + r;
+      if (y >= g.hl) break;
+      const float yn = __builtin_fmaf(g.ay, (float)y, g.cy);
+      const float X = __fadd_rn(__fadd_rn(__fmul_rn(m[0], xn), __fmul_rn(m[1], yn)), m[2]);
+      const float Y = __fadd_rn(__fadd_rn(__fmul_rn(m[3], xn), __fmul_rn(m[4], yn)), m[5]);
+      const float Z = __fadd_rn(__fadd_rn(__fmul_rn(m[6], xn), __fmul_rn(m[7], yn)), m[8]);
+      const bool live = fabsf(Z) > 1e-8f;
+      const float s = live ? __fdiv_rn(1.0f, __fadd_rn(Z, 1e-8f)) : 1.0f;
+      const float px = __builtin_fmaf(__fadd_rn(__fmul_rn(s, X), 1.0f), g.kx, -g.ox);
+      const float py = __builtin_fmaf(__fadd_rn(__fmul_rn(s, Y), 1.0f), g.ky, -g.oy);
+      const float x0 = floorf(px), y0 = floorf(py);
+      // all four taps inside the previous plane; a NaN or an infinity fails a comparison
+      const bool counts = live && x0 >= 0.f && __fadd_rn(x0, 1.0f) <= xmax && y0 >= 0.f && __fadd_rn(y0, 1.0f) <= ymax;
+      if (!counts) continue;
+      const float wx1 = __fsub_rn(px, x0), wx0 = __fsub_rn(1.0f, wx1), wy1 = __fsub_rn(py, y0), wy0 = __fsub_rn(1.0f, wy1);
+      const float w00 = __fmul_rn(wy0, wx0), w01 = __fmul_rn(wy0, wx1), w10 = __fmul_rn(wy1, wx0), w11 = __fmul_rn(wy1, wx1);
+      const float* tp = prev + (long)(int)y0 * g.wl + (int)x0;
+      const float t00 = tp[0], t01 = tp[1], t10 = tp[g.wl], t11 = tp[g.wl + 1];
+      const float cv = cur[(long)y * g.wl + x];
+      float val = __fmul_rn(t00, w00);
+      val = __fadd_rn(val, __fmul_rn(t01, w01));
+      val = __fadd_rn(val, __fmul_rn(t10, w10));
+      val = __fadd_rn(val, __fmul_rn(t11, w11));
+      const float duf = __fadd_rn(__fmul_rn(wy0, __fsub_rn(t01, t00)), __fmul_rn(wy1, __fsub_rn(t11, t10)));
+      const float dvf = __fadd_rn(__fmul_rn(wx0, __fsub_rn(t10, t00)), __fmul_rn(wx1, __fsub_rn(t11, t01)));
+      const double rr = (double)val - (double)cv;
+      const double du = (double)duf * dkx, dv = (double)dvf * dky;
+      const double r2 = rr * rr;
+      const double c = 1.0 + r2 / g.d2;
+      const double ic = 1.0 / c;
+      const double rho = r2 * ic, om = ic * ic;
+      const double ds = (double)s, dxn = (double)xn, dyn = (double)yn;
+      const double gu = -((double)X * ds) * ds, gv = -((double)Y * ds) * ds;
+      const double a0 = ds * dxn, a1 = ds * dyn;
+      const double J[8] = {du * a0, du * a1, du * ds, dv * a0, dv * a1, dv * ds,
+                           du * (gu * dxn) + dv * (gv * dxn), du * (gu * dyn) + dv * (gv * dyn)};
+      int e = 0;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const double wj = om * J[i];
+#pragma unroll
+        for (int j = i; j < 8; ++j, ++e) acc[e] += wj * J[j];
+        acc[36 + i] += wj * rr;
+      }
+      acc[kCost] += rho;
+      acc[kN] += 1.0;
+    }
+  }
+  __shared__ double sh[4][kSums];
+#pragma unroll
+  for (int e = 0; e < kSums; ++e) {
+    const double v = wave_sum(acc[e]);
+    if (lane == 0) sh[wv][e] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < kSums) {
+    const int e = threadIdx.x;
+    const long slab = (long)blockIdx.y * gridDim.x + blockIdx.x;
+    partial[det_slab_offset(slab, (long)kSums * gridDim.z) + (long)p * kSums + e] = ((sh[0][e] + sh[1][e]) + sh[2][e]) + sh[3][e];
+  }
+}
+
+// ------------------------------------------------------------------ step
+__device__ __forceinline__ bool finite_d(double v) { return fabs(v) <= 1.7976931348623157e308; }   // false for a NaN
+
+__global__ __launch_bounds__(64) void track_step_kernel(const double* __restrict__ partial, long slabs, int pairs, int first,
+                                                        int last, const float* M_eval, float* M_acc, double* sums_acc,
+                                                        double* lambda, int32_t* pivots_ok, int32_t* dead, float* M_next,
+                                                        double* stats, int32_t* accepted, int32_t* ok_out, int level,
+                                                        int nlevels, double nmin, double max_cost) {
+  const int lane = threadIdx.x, p = blockIdx.x;
+  const double mine = lane < kSums ? det_sum(0.0, partial, slabs, (long)kSums * pairs, (long)p * kSums + lane) : 0.0;
+  double S[kSums];
+#pragma unroll
+  for (int e = 0; e < kSums; ++e) S[e] = __shfl(mine, e);
+  float me[9], ma[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) me[k] = M_eval[p * 9 + k];
+  double lam = 1e-3;
+  int nacc = 0;
+  bool take = true, is_dead = false;
+  if (first) {
+    bool fin = true;
+#pragma unroll
+    for (int e = 0; e < kSums; ++e) fin = fin && finite_d(S[e]);
+    is_dead = (level > 0 && dead[p] != 0) || !fin || !(S[kN] >= nmin);
+  } else {
+    is_dead = dead[p] != 0;
+    const double mc = S[kCost] / S[kN], mk = sums_acc[p * kSums + kCost] / sums_acc[p * kSums + kN];
+    take = !is_dead && pivots_ok[p] != 0 && S[kN] >= nmin && mc < mk;   // false for a NaN
+    lam = is_dead ? lambda[p] : (take ? lambda[p] / 10.0 : lambda[p] * 10.0);
+    nacc = accepted[p * nlevels + level] + (take ? 1 : 0);
+  }
+  if (!take) {
+#pragma unroll
+    for (int e = 0; e < kSums; ++e) S[e] = sums_acc[p * kSums + e];
+  }
+#pragma unroll
+  for (int k = 0; k < 9; ++k) ma[k] = take ? me[k] : M_acc[p * 9 + k];
+
+  double Lm[8][8], gv[8];
+  {
+    int e = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+      for (int j = i; j < 8; ++j, ++e) Lm[j][i] = (i == j) ? S[e] + lam * S[e] : S[e];
+  }
+#pragma unroll
+  for (int i = 0; i < 8; ++i) gv[i] = -S[36 + i];
+  const bool piv = chol8_solve(Lm, gv, true);
+  if (lane == 0) {
+    bool mfin = true;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+      M_acc[p * 9 + k] = ma[k];
+      M_next[p * 9 + k] = (last || is_dead || !piv || k == 8) ? ma[k] : (float)((double)ma[k] + gv[k]);
+      mfin = mfin && fabsf(ma[k]) <= 3.4028234663852886e38f;
+    }
+    if (take) {
+#pragma unroll
+      for (int e = 0; e < kSums; ++e) sums_acc[p * kSums + e] = S[e];
+    }
+    lambda[p] = lam;
+    pivots_ok[p] = piv ? 1 : 0;
+    dead[p] = is_dead ? 1 : 0;
+    accepted[p * nlevels + level] = nacc;
+    const double mean = S[kCost] / S[kN];
+    double* st = stats + ((long)p * nlevels + level) * 3;
+    if (first) st[0] = mean;
+    st[1] = mean;
+    st[2] = S[kN];
+    ok_out[p] = (!is_dead && mfin && (!(max_cost > 0.0) || mean <= max_cost)) ? 1 : 0;
+  }
+}
+
+// ------------------------------------------------------------------ propagate
+struct M3 {
+  double v[9];
+};
+
+__device__ __forceinline__ void load3(const float* __restrict__ t, M3& m) {
+#pragma unroll
+  for (int k = 0; k < 9; ++k) m.v[k] = (double)t[k];
+}
+// the nine expressions stated above sfh_metrics_region; returns det
+__device__ __forceinline__ double adj3(const M3& m, M3& a) {
+  const double* t = m.v;
+  a.v[0] = t[4] * t[8] - t[5] * t[7];
+  a.v[1] = t[2] * t[7] - t[1] * t[8];
+  a.v[2] = t[1] * t[5] - t[2] * t[4];
+  a.v[3] = t[5] * t[6] - t[3] * t[8];
+  a.v[4] = t[0] * t[8] - t[2] * t[6];
+  a.v[5] = t[2] * t[3] - t[0] * t[5];
+  a.v[6] = t[3] * t[7] - t[4] * t[6];
+  a.v[7] = t[1] * t[6] - t[0] * t[7];
+  a.v[8] = t[0] * t[4] - t[1] * t[3];
+  return (t[0] * a.v[0] + t[1] * a.v[3]) + t[2] * a.v[6];
+}
+__device__ __forceinline__ void mul3(M3& P, const M3& m) {
+  M3 o;
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) o.v[i * 3 + j] = (P.v[i * 3] * m.v[j] + P.v[i * 3 + 1] * m.v[3 + j]) + P.v[i * 3 + 2] * m.v[6 + j];
+  P = o;
+}
+__device__ __forceinline__ bool frame_good(const float* __restrict__ theta, const float* __restrict__ score, float max_score,
+                                           int t) {
+  M3 m, a;
+  load3(theta + (long)t * 9, m);
+  const double det = adj3(m, a);
+  const bool usable = fabs(det) > 0.0 && finite_d(det);
+  return usable && (score == nullptr || score[t] <= max_score);   // a NaN score fails
+}
+
+__global__ __launch_bounds__(64) void track_propagate_kernel(const float* __restrict__ theta, const float* __restrict__ score,
+                                                             float max_score, const float* __restrict__ M,
+                                                             const int32_t* __restrict__ link, int frames, int max_gap,
+                                                             float* __restrict__ theta_out, int32_t* __restrict__ source) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= frames) return;
+  if (frame_good(theta, score, max_score, t)) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) theta_out[(long)t * 9 + k] = theta[(long)t * 9 + k];
+    source[t] = t;
+    return;
+  }
+  int back = -1, fwd = -1;
+  for (int d = 1; d <= max_gap; ++d) {       // the pairs (k, k+1) .. (t-1, t): link[k+1 .. t]
+    const int k = t - d;
+    if (k < 0 || link[k + 1] == 0) break;
+    if (frame_good(theta, score, max_score, k)) { back = k; break; }
+  }
+  for (int d = 1; d <= max_gap; ++d) {       // the pairs (t, t+1) .. (k-1, k): link[t+1 .. k]
+    const int k = t + d;
+    if (k >= frames || link[k] == 0) break;
+    if (frame_good(theta, score, max_score, k)) { fwd = k; break; }
+  }
+  const bool use_back = back >= 0 && (fwd < 0 || t - back <= fwd - t);
+  const int k = use_back ? back : fwd;
+  M3 P;
+  bool have = k >= 0;
+  if (have) {
+    load3(theta + (long)k * 9, P);
+    if (use_back) {
+      for (int j = k + 1; j <= t; ++j) {
+        M3 m;
+        load3(M + (long)j * 9, m);
+        mul3(P, m);
+      }
+    } else {
+      for (int j = k; j >= t + 1; --j) {
+        M3 m, a;
+        load3(M + (long)j * 9, m);
+        adj3(m, a);
+        mul3(P, a);
+      }
+    }
+    have = fabs(P.v[8]) > 0.0 && finite_d(P.v[8]);
+  }
+  const float nan = __builtin_nanf("");
+#pragma unroll
+  for (int i = 0; i < 9; ++i) theta_out[(long)t * 9 + i] = !have ? nan : (i == 8 ? 1.0f : (float)(P.v[i] / P.v[8]));
+  source[t] = have ? k : -1;
+}
+
+}  // namespace
+
+extern "C" int sfh_track_axis(int f, int n, float* a) {
+  SFH_REQUIRE(a, "track_axis: null pointer");
+  SFH_REQUIRE(track_level_ok(f, n), "track_axis: level %d (1..16) must divide %d pixels", f, n);
+  track_axis(f, n, a[0], a[1]);
+  return SFH_OK;
+}
+
+extern "C" int sfh_track_planes(const uint8_t* frames, int batch, int H, int W, int f, int bgr, float* planes, void* stream) {
+  SFH_REQUIRE(frames && planes, "track_planes: null pointer");
+  SFH_REQUIRE(batch > 0 && H > 0 && W > 0, "track_planes: bad geometry b=%d H=%d W=%d", batch, H, W);
+  SFH_REQUIRE(track_level_ok(f, H) && track_level_ok(f, W), "track_planes: level %d (1..16) does not divide the frame %dx%d", f, W, H);
+  SFH_REQUIRE((long)batch * H * W * 3 < (1L << 31), "track_planes: %ld bytes of frames: too large", (long)batch * H * W * 3);
+  const long total = (long)batch * (H / f) * (W / f);
+  hipLaunchKernelGGL(track_planes_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, frames, batch, H,
+                     W, f, bgr ? 2 : 0, planes);
+  return sfh_check_launch("track_planes_kernel");
+}
+
+extern "C" int64_t sfh_track_workspace_bytes(int pairs, int h, int w) { return det_bytes(det_track_plan(pairs, h, w)); }
+
+extern "C" int sfh_track_accumulate(const float* M, const float* planes, int nframes, const int32_t* ia, const int32_t* ib,
+                                    int pairs, int H, int W, int f, double delta, void* workspace, long long workspace_bytes,
+                                    void* stream) {
+  const char* who = "track_accumulate";
+  SFH_REQUIRE(M && planes && ia && ib, "%s: null pointer", who);
+  SFH_REQUIRE(nframes > 0 && H > 0 && W > 0, "%s: bad geometry frames=%d H=%d W=%d", who, nframes, H, W);
+  SFH_REQUIRE(track_level_ok(f, H) && track_level_ok(f, W), "%s: level %d (1..16) does not divide the frame %dx%d", who, f, W, H);
+  SFH_REQUIRE(delta > 0.0 && delta * delta > 0.0 && std::isfinite(delta * delta), "%s: delta=%g (> 0)", who, delta);
+  TrackGeom g;
+  g.hl = H / f;
+  g.wl = W / f;
+  g.nframes = nframes;
+  const DetPlan p = det_track_plan(pairs, g.hl, g.wl);
+  SFH_REQUIRE(p.ok, "%s: %d pairs (1..65535) of planes %dx%d", who, pairs, g.wl, g.hl);
+  SFH_REQUIRE((long)nframes * g.hl * g.wl < (1L << 31), "%s: planes too large", who);
+  SFH_REQUIRE_WS(who, workspace, workspace_bytes, p);
+  float a[2];
+  if (sfh_refine_axis(f, W, W, a) != SFH_OK) return SFH_E_ARG;
+  g.ax = a[0], g.cx = a[1];
+  if (sfh_refine_axis(f, H, H, a) != SFH_OK) return SFH_E_ARG;
+  g.ay = a[0], g.cy = a[1];
+  track_axis(f, W, g.kx, g.ox);
+  track_axis(f, H, g.ky, g.oy);
+  g.d2 = delta * delta;
+  const dim3 grid((unsigned)det_cdiv(g.wl, kTile), (unsigned)det_cdiv(g.hl, kTile), (unsigned)pairs);
+  hipLaunchKernelGGL(track_accumulate_kernel, grid, dim3(256), 0, (hipStream_t)stream, M, planes, ia, ib, g, (double*)workspace);
+  return sfh_check_launch("track_accumulate_kernel");
+}
+
+extern "C" int sfh_track_step(const double* partial, int64_t slabs, int pairs, int first, int last, const float* M_eval,
+                              float* M_acc, double* sums_acc, double* lambda, int32_t* pivots_ok, int32_t* dead, float* M_next,
+                              double* stats, int32_t* accepted, int32_t* ok, int level, int nlevels, double nmin, double max_cost,
+                              void* stream) {
+  SFH_REQUIRE(partial && M_eval && M_acc && sums_acc && lambda && pivots_ok && dead && M_next && stats && accepted && ok,
+              "track_step: null pointer");
+  SFH_REQUIRE(slabs >= 1 && pairs > 0 && pairs <= 65535 && nlevels >= 1 && level >= 0 && level < nlevels,
+              "track_step: bad geometry slabs=%lld pairs=%d level=%d of %d", (long long)slabs, pairs, level, nlevels);
+  SFH_REQUIRE(nmin >= 0.0 && max_cost == max_cost, "track_step: nmin=%g (>= 0), max_cost=%g (not a NaN)", nmin, max_cost);
+  hipLaunchKernelGGL(track_step_kernel, dim3((unsigned)pairs), dim3(64), 0, (hipStream_t)stream, partial, (long)slabs, pairs, first,
+                     last, M_eval, M_acc, sums_acc, lambda, pivots_ok, dead, M_next, stats, accepted, ok, level, nlevels, nmin,
+                     max_cost);
+  return sfh_check_launch("track_step_kernel");
+}
+
+extern "C" int sfh_track_propagate(const float* theta, const float* score, float max_score, const float* M, const int32_t* link,
+                                   int frames, int max_gap, float* theta_out, int32_t* source, void* stream) {
+  SFH_REQUIRE(theta && M && link && theta_out && source, "track_propagate: null pointer");
+  SFH_REQUIRE(frames > 0 && frames < (1 << 24) && max_gap >= 0, "track_propagate: frames=%d (1..2^24-1), max_gap=%d (>= 0)", frames,
+              max_gap);
+  SFH_REQUIRE(theta_out + (long)frames * 9 <= theta || theta + (long)frames * 9 <= theta_out,
+              "track_propagate: theta_out overlaps theta");
+  hipLaunchKernelGGL(track_propagate_kernel, dim3((unsigned)det_cdiv(frames, 64)), dim3(64), 0, (hipStream_t)stream, theta, score,
+                     max_score, M, link, frames, max_gap, theta_out, source);
+  return sfh_check_launch("track_propagate_kernel");
+}
