@@ -247,7 +247,8 @@ int sfh_pack_c4_weights(const float* w, float* packed, int cin, int cout, void* 
 /* The same first layer on the fp16 matrix cores ("f16x3": two fp16 planes per operand, three products, fp32 accumulation;
  * unet/unet_parts.py:15).  The frame is split ONCE by sfh_frame_to_h2 into the FH2 frame tensor, 16 bytes per pixel =
  * [fp16 plane 0 of channels 0..3 | fp16 plane 1 of channels 0..3] of x * 2^act_exp (format as SFH_FMT_H2: saturating,
- * `range` receives the largest |x * 2^act_exp|, `overflow` is OR-ed with 1 on saturation; both optional); dst_nhwc4
+ * `range` receives the largest |x * 2^act_exp|, `overflow` is OR-ed with 1 on saturation; both optional; +-Inf saturate to
+ * +-65504, a NaN becomes -65504 with plane 1 at +0, and `range` then reads the non-finite bit pattern, >= 0x7F800000); dst_nhwc4
  * (optional) receives the fp32 NHWC copy with 4 stored channels that sfh_nchw_to_nhwc would write.
  * sfh_conv3x3_c4h2_fwd: src0 = the FH2 tensor (B,H,W) x 16 bytes (src_fmt = SFH_FMT_FH2, c0 <= 4, cs0 = 4; a plain fp32 NHWC4
  * frame - src_fmt SFH_FMT_F32, the source of sfh_conv3x3_c4_fwd - is rejected), h2_exp_src = act_exp, wpacked from sfh_pack_c4h2_weights (planes of

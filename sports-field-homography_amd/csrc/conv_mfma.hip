@@ -552,9 +552,12 @@ extern "C" int sfh_conv3x3_c4_fwd(const sfh_conv_desc* dp, void* stream_) {
   SFH_REQUIRE(dp, "conv3x3_c4_fwd: null descriptor");
   const sfh_conv_desc& d = *dp;
   SFH_REQUIRE(d.src0 && d.wpacked && d.scale && d.shift && d.dst, "conv3x3_c4_fwd: null pointer");
-  SFH_REQUIRE(d.ksize == 3 && d.stride == 1 && d.cs0 == 4 && d.c0 <= 4 && !d.src1 && !d.pool0 && !d.dst_pool &&
+  SFH_REQUIRE(d.ksize == 3 && d.stride == 1 && d.cs0 == 4 && d.c0 >= 1 && d.c0 <= 4 && !d.src1 && !d.pool0 && !d.dst_pool &&
                   d.src_fmt == SFH_FMT_F32 && d.out_mode == SFH_OUT_NHWC && d.h0 == d.H && d.w0 == d.W,
               "conv3x3_c4_fwd: needs a single fp32 NHWC source with 4 stored channels, 3x3 stride 1");
+  // (any other value was written as fp32 without a word)
+  SFH_REQUIRE(d.dst_fmt == SFH_FMT_F32 || d.dst_fmt == SFH_FMT_S3 || d.dst_fmt == SFH_FMT_H2,
+              "conv3x3_c4_fwd: the destination is fp32, S3 or H2 (dst_fmt=%d)", d.dst_fmt);
   SFH_REQUIRE(d.cout > 0 && d.cout % 64 == 0 && d.batch > 0 && d.H > 0 && d.W > 0, "conv3x3_c4_fwd: bad geometry");
   if (!sfh_h2_exp_ok("conv3x3_c4_fwd", "h2_exp_dst", d.h2_exp_dst)) return SFH_E_ARG;
   ConvGeom g;

@@ -81,6 +81,30 @@ def out_size(n, ksize, stride):
     return (n + ksize // 2 + (ksize - 1) // 2 - ksize) // stride + 1
 
 
+# ------------------------------------------------------------------------------------------------ the split formats
+def _bf16(x):
+    return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(torch.bfloat16).to(torch.float32).numpy()
+
+
+def split_s3(v):
+    """plane0 = bf16(v), plane1 = bf16(v - plane0), plane2 = bf16(v - plane0 - plane1), the subtractions in fp32"""
+    f32 = np.float32
+    v = np.asarray(v, dtype=f32)
+    p0 = _bf16(v)
+    r1 = (v - p0).astype(f32)
+    p1 = _bf16(r1)
+    return p0, p1, _bf16((r1 - p1).astype(f32))
+
+
+def split_h2(v, e):
+    """u = v * 2^e saturated to +-65504, plane0 = f16(u), plane1 = f16(u - plane0), as fp32 arrays (the numpy statement of
+    the H2 split of include/sfh_amd.h; tests/test_dense_conv_host.py holds h2_rep() to it)"""
+    f32 = np.float32
+    u = np.clip(np.asarray(v, dtype=f32) * f32(2.0 ** e), f32(-65504.0), f32(65504.0)).astype(f32)
+    p0 = u.astype(np.float16).astype(f32)
+    return p0, (u - p0).astype(f32).astype(np.float16).astype(f32)
+
+
 # ------------------------------------------------------------------------------------------------ the linear maps
 def assemble(x0, c0, x1=None, c1=0, pad1=(0, 0), pool0=False):
     """the conv input frame: channels [0, c0) of x0 - MaxPool2d(2) (floor) applied first with pool0 - beside channels

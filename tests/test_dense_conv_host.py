@@ -12,32 +12,13 @@ import torch.nn.functional as F
 
 import dense_conv_cases as K
 import dense_conv_ref as R
+from dense_conv_ref import split_h2, split_s3
 
 f32 = np.float32
 S3_KEPT = ((0, 2), (1, 1), (2, 0), (0, 1), (1, 0), (0, 0))      # (weight plane, source plane), in the stage loop's order
 H2_KEPT = ((0, 1), (1, 0), (0, 0))
 BY_NAME = {c.name: c for c in K.FWD}
 WG_BY_NAME = {c.name: c for c in K.WGRAD}
-
-
-def _bf16(x):
-    return torch.from_numpy(np.ascontiguousarray(x, dtype=f32)).to(torch.bfloat16).to(torch.float32).numpy()
-
-
-def split_s3(v):
-    """plane0 = bf16(v), plane1 = bf16(v - plane0), plane2 = bf16(v - plane0 - plane1), the subtractions in fp32"""
-    v = np.asarray(v, dtype=f32)
-    p0 = _bf16(v)
-    r1 = (v - p0).astype(f32)
-    p1 = _bf16(r1)
-    return p0, p1, _bf16((r1 - p1).astype(f32))
-
-
-def split_h2(v, e):
-    """u = v * 2^e saturated to +-65504, plane0 = f16(u), plane1 = f16(u - plane0), as fp32 arrays"""
-    u = np.clip(np.asarray(v, dtype=f32) * f32(2.0 ** e), f32(-65504.0), f32(65504.0)).astype(f32)
-    p0 = u.astype(np.float16).astype(f32)
-    return p0, (u - p0).astype(f32).astype(np.float16).astype(f32)
 
 
 def _planes(v, fmt, e):
