@@ -1637,6 +1637,45 @@ int sfh_track_step(const double* partial, int64_t slabs, int pairs, int first, i
  * (frames) int32.  max_gap >= 0.  theta_out must not overlap theta. */
 int sfh_track_propagate(const float* theta, const float* score, float max_score, const float* M, const int32_t* link,
                         int frames, int max_gap, float* theta_out, int32_t* source, void* stream);
+/* Motion-compensated temporal smoothing of theta (sfh_track_smooth).  Under theta_t = theta_{t-1} M_t every good neighbour k of
+ * frame t holds a second, independent estimate of theta_t: theta_k carried to t.  The estimates of one frame are combined
+ * robustly - not a low-pass over time, so no lag - which averages the regression noise down, outvotes an isolated bad theta
+ * that passed the score gate, and fills gaps as sfh_track_propagate does.  THE RULE, stated here once; csrc/smooth_core.h and
+ * track_smooth_kernel run it, tests/smooth_ref.py restates it in numpy.  The reference project has no counterpart.
+ *
+ * Members.  The window of frame t is k in [t - back, t + ahead] within [0, frames), back and ahead in 0..31 (ahead = 0: the
+ *   causal form).  Frame k is a MEMBER iff it is GOOD by sfh_track_propagate's definition (usable theta, optional score gate)
+ *   and every link between k and t is non-zero: link[k+1 .. t] for a back member, link[t+1 .. k] for a forward one; frame t
+ *   itself iff it is good.
+ * Transport.  The chains and the fp64 product of sfh_track_propagate: back, P = theta_k then P = P M_j for j = k+1 .. t
+ *   ascending; forward, P = theta_k then P = P adj(M_j) for j = k .. t+1 descending.  P is not normalised.
+ * Control points.  ctrl (4,2) fp32, points (x, y) of the normalised frame; the default (ctrl = NULL) is (-1, 0.2), (1, 0.2),
+ *   (1, 1), (-1, 1): the lower three fifths of the frame, where the court is (corners above it can lie at the ground plane's
+ *   horizon).  Member k sees point p at q_k[2p], q_k[2p+1] = X / W, Y / W in normalised court units, fp64, with X, Y, W formed
+ *   from P and (x, y, 1) as the predicate in() above sfh_metrics_region forms them.  A member is DROPPED unless all eight
+ *   values are finite and its four W are non-zero and of one sign (a mixed sign: the horizon crosses the quadrilateral).
+ *   members[t] = the members that remain.
+ * Combination.  g_k = (R + 1 - |t - k|) / (R + 1), R = back for k <= t and ahead for k > t: the integers converted to fp64, one
+ *   division (g_t = 1).  The reference member is the one nearest to t, a tie goes back; c0 = its eight values, d_k = q_k - c0.
+ *   Pass 0 takes omega_k = 1; each of the `iters` passes after it takes r2_k = the eight squared components of q_k - c added
+ *   in index order from the first, omega_k = ic ic with ic = 1 / (1 + r2_k / d2), d2 = delta delta formed on the host
+ *   (sfh_track_accumulate's Geman-McClure weight).  Every pass: w_k = g_k omega_k, S = sum w_k, c_i = c0_i + (sum w_k d_k,i) /
+ *   S.  The nine sums of a pass are the xor butterfly 32 .. 1 over the 64 lanes of a wave (wave_sum_all, csrc/common.h),
+ *   lane l holding frame k = t - back + l and a lane without a member +0.0: that is the summation order.  Members that agree
+ *   exactly give c = c0 exactly.
+ * Refit.  The homography h with h8 = 1 that takes ctrl to c: rows 2p = [x y 1 0 0 0 -(u x) -(u y) | u] and 2p + 1 = [0 0 0 x y
+ *   1 -(v x) -(v y) | v] of A h = b for point p, (u, v) = (c_2p, c_2p+1).  N = A^T A (lower triangle) and A^T b in fp64, each
+ *   entry summed over the rows 0 .. 7 ascending from +0.0; N h = A^T b by csrc/chol8.h.  theta_out = (fl32(h_0) .. fl32(h_7), 1).
+ * Statistics.  stats (frames,3) fp64 = [S of the last pass;  sqrt((sum w_k r2_k) / S) with the last pass's w and r2_k against
+ *   the final c (one more butterfly);  sqrt(r2_t) of frame t's own theta against the final c, NaN when t is not a member - how
+ *   far a frame's theta disagrees with the measured motion, readable without ground truth].
+ * Nine NaNs and three NaN statistics where members[t] < min_members (>= 1), a c_i is not finite, or a pivot of the solve is
+ *   not > 0; members[t] is written all the same.
+ * One wave per frame, O(back + ahead) matrix products per lane, no workspace.  ctrl is a HOST pointer (or NULL), read before
+ * the launch.  frames = 0 launches nothing.  theta_out must not overlap theta. */
+int sfh_track_smooth(const float* theta, const float* score, float max_score, const float* M, const int32_t* link, int frames,
+                     int back, int ahead, int iters, double delta, int min_members, const float* ctrl, float* theta_out,
+                     int32_t* members, double* stats, void* stream);
 
 #ifdef __cplusplus
 }

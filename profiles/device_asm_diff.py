@@ -31,6 +31,9 @@ kernel count (.amdhsa_kernel directives) and one of
                     the two factors of a product in the other order.  IEEE multiplication and addition are commutative bit for bit (for two NaN operands
                     the payload may be the other one's) and integer multiplication commutes exactly, so every function
                     computes what it computed, with the same instructions in the same places.  Exit status 0.
+  every function of the parent unchanged; added: ...
+                    this tree's file holds every section of the parent's, the same text, and more of them: kernels were
+                    added to the file (they are named) and no existing one moved.  Exit status 0.
   DIFFERENT         anything else; the first differing sections are shown.  Exit status 1.
 """
 import argparse
@@ -123,6 +126,9 @@ def main():
                 verdict = "same functions, another order"
             elif commuted(*([ln for f in side for ln in f] for side in texts)):
                 verdict = "same up to commuted operands"
+            elif not (p - t) and p_own == t_own:
+                added = sorted({m for s in (t - p) for m in re.findall(r"\.amdhsa_kernel (\S+)", s)})
+                verdict = f"every function of the parent unchanged; added: {', '.join(added) or 'no kernel'}"
             else:
                 verdict = "DIFFERENT"
             if verdict == "DIFFERENT":

@@ -11,6 +11,8 @@
 // * track_step_kernel: one wave per pair; lanes 0..45 take the ascending chain over the slabs (det_sum), every lane then
 //   holds all 46 sums and solves the 8 x 8 system redundantly in registers through chol8_solve (chol8.h).
 // * track_propagate_kernel: one thread per frame, O(max_gap) work, no scan.
+// * track_smooth_kernel: one wave per frame, a lane per frame of its window (smooth_core.h: chain, projection, weights, refit);
+//   the nine sums of a pass through wave_sum_all, so every lane holds the combined points and solves the refit for itself.
 #include <cmath>
 
 #include "common.h"
@@ -18,6 +20,7 @@
 #include "chol8.h"
 #include "ycc.h"
 #include "track_core.h"
+#include "smooth_core.h"
 
 namespace {
 
@@ -210,45 +213,6 @@ __global__ __launch_bounds__(64) void track_step_kernel(const double* __restrict
 }
 
 // ------------------------------------------------------------------ propagate
-struct M3 {
-  double v[9];
-};
-
-__device__ __forceinline__ void load3(const float* __restrict__ t, M3& m) {
-#pragma unroll
-  for (int k = 0; k < 9; ++k) m.v[k] = (double)t[k];
-}
-// the nine expressions stated above sfh_metrics_region; returns det
-__device__ __forceinline__ double adj3(const M3& m, M3& a) {
-  const double* t = m.v;
-  a.v[0] = t[4] * t[8] - t[5] * t[7];
-  a.v[1] = t[2] * t[7] - t[1] * t[8];
-  a.v[2] = t[1] * t[5] - t[2] * t[4];
-  a.v[3] = t[5] * t[6] - t[3] * t[8];
-  a.v[4] = t[0] * t[8] - t[2] * t[6];
-  a.v[5] = t[2] * t[3] - t[0] * t[5];
-  a.v[6] = t[3] * t[7] - t[4] * t[6];
-  a.v[7] = t[1] * t[6] - t[0] * t[7];
-  a.v[8] = t[0] * t[4] - t[1] * t[3];
-  return (t[0] * a.v[0] + t[1] * a.v[3]) + t[2] * a.v[6];
-}
-__device__ __forceinline__ void mul3(M3& P, const M3& m) {
-  M3 o;
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) o.v[i * 3 + j] = (P.v[i * 3] * m.v[j] + P.v[i * 3 + 1] * m.v[3 + j]) + P.v[i * 3 + 2] * m.v[6 + j];
-  P = o;
-}
-__device__ __forceinline__ bool frame_good(const float* __restrict__ theta, const float* __restrict__ score, float max_score,
-                                           int t) {
-  M3 m, a;
-  load3(theta + (long)t * 9, m);
-  const double det = adj3(m, a);
-  const bool usable = fabs(det) > 0.0 && finite_d(det);
-  return usable && (score == nullptr || score[t] <= max_score);   // a NaN score fails
-}
-
 __global__ __launch_bounds__(64) void track_propagate_kernel(const float* __restrict__ theta, const float* __restrict__ score,
                                                              float max_score, const float* __restrict__ M,
                                                              const int32_t* __restrict__ link, int frames, int max_gap,
@@ -298,6 +262,70 @@ __global__ __launch_bounds__(64) void track_propagate_kernel(const float* __rest
 #pragma unroll
   for (int i = 0; i < 9; ++i) theta_out[(long)t * 9 + i] = !have ? nan : (i == 8 ? 1.0f : (float)(P.v[i] / P.v[8]));
   source[t] = have ? k : -1;
+}
+
+// ------------------------------------------------------------------ smooth
+struct SmoothCtrl {
+  float p[8];
+};
+
+__global__ __launch_bounds__(64) void track_smooth_kernel(const float* __restrict__ theta, const float* __restrict__ score,
+                                                          float max_score, const float* __restrict__ M,
+                                                          const int32_t* __restrict__ link, int frames, int back, int ahead,
+                                                          int iters, double d2, int min_members, SmoothCtrl ctrl,
+                                                          float* __restrict__ theta_out, int32_t* __restrict__ members,
+                                                          double* __restrict__ stats) {
+  const int lane = threadIdx.x, t = blockIdx.x;
+  const int k = t - back + lane;              // lane `back` is frame t itself
+  bool mem = lane <= back + ahead && smooth_linked(theta, score, max_score, link, frames, k, t);
+  double q[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  if (mem) {
+    M3 P;
+    smooth_chain(theta, M, k, t, P);
+    mem = smooth_project(P, ctrl.p, q);
+  }
+  const unsigned long long mask = __ballot(mem);
+  const int n = __popcll(mask);
+  int ref = -1;                               // the member nearest to t, a tie goes back
+  for (int d = 0; d <= SMOOTH_MAX_RADIUS && ref < 0; ++d) {
+    if (d <= back && ((mask >> (back - d)) & 1ull)) ref = back - d;
+    else if ((mask >> (back + d)) & 1ull) ref = back + d;
+  }
+  if (ref < 0) ref = 0;                       // no member: every sum is +0.0 and c is NaN
+  const double g = smooth_triangle(k < t ? back : ahead, k < t ? t - k : k - t);
+  double c0[8], dq[8], c[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    c0[i] = __shfl(q[i], ref);
+    dq[i] = q[i] - c0[i];
+    c[i] = c0[i];
+  }
+  double gw = 0.0, sw = 0.0;
+  for (int pass = 0; pass <= iters; ++pass) {
+    const double om = pass == 0 ? 1.0 : smooth_omega(smooth_r2(q, c), d2);
+    gw = mem ? g * om : 0.0;
+    sw = wave_sum_all(gw);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) c[i] = c0[i] + wave_sum_all(mem ? gw * dq[i] : 0.0) / sw;
+  }
+  const double r2 = smooth_r2(q, c);
+  const double srr = wave_sum_all(mem ? gw * r2 : 0.0);
+  const double own = __shfl(mem ? sqrt(r2) : (double)__builtin_nanf(""), back);
+  bool ok = n >= min_members;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) ok = ok && track_finite(c[i]);
+  double h[8];
+  ok = smooth_refit(ctrl.p, c, h, ok);
+  if (lane == 0) {
+    const float nanf_ = __builtin_nanf("");
+    const double nand = (double)nanf_;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) theta_out[(long)t * 9 + i] = !ok ? nanf_ : (i == 8 ? 1.0f : (float)h[i]);
+    members[t] = n;
+    stats[(long)t * 3] = ok ? sw : nand;
+    stats[(long)t * 3 + 1] = ok ? sqrt(srr / sw) : nand;
+    stats[(long)t * 3 + 2] = ok ? own : nand;
+  }
 }
 
 }  // namespace
@@ -376,4 +404,25 @@ extern "C" int sfh_track_propagate(const float* theta, const float* score, float
   hipLaunchKernelGGL(track_propagate_kernel, dim3((unsigned)det_cdiv(frames, 64)), dim3(64), 0, (hipStream_t)stream, theta, score,
                      max_score, M, link, frames, max_gap, theta_out, source);
   return sfh_check_launch("track_propagate_kernel");
+}
+
+extern "C" int sfh_track_smooth(const float* theta, const float* score, float max_score, const float* M, const int32_t* link,
+                                int frames, int back, int ahead, int iters, double delta, int min_members, const float* ctrl,
+                                float* theta_out, int32_t* members, double* stats, void* stream) {
+  const char* who = "track_smooth";
+  SFH_REQUIRE(frames >= 0, "%s: frames=%d (>= 0)", who, frames);
+  SFH_REQUIRE(back >= 0 && back <= SMOOTH_MAX_RADIUS && ahead >= 0 && ahead <= SMOOTH_MAX_RADIUS, "%s: back=%d, ahead=%d (0..%d)", who,
+              back, ahead, SMOOTH_MAX_RADIUS);
+  SFH_REQUIRE(iters >= 0, "%s: iters=%d (>= 0)", who, iters);
+  SFH_REQUIRE(delta > 0.0 && delta * delta > 0.0 && std::isfinite(delta * delta), "%s: delta=%g (> 0)", who, delta);
+  SFH_REQUIRE(min_members >= 1, "%s: min_members=%d (>= 1)", who, min_members);
+  SFH_REQUIRE(theta && M && link && theta_out && members && stats, "%s: null pointer", who);
+  SFH_REQUIRE(theta_out + (long)frames * 9 <= theta || theta + (long)frames * 9 <= theta_out, "%s: theta_out overlaps theta", who);
+  if (frames == 0) return SFH_OK;
+  static const float kDefault[8] = {-1.0f, 0.2f, 1.0f, 0.2f, 1.0f, 1.0f, -1.0f, 1.0f};
+  SmoothCtrl cp;
+  for (int i = 0; i < 8; ++i) cp.p[i] = (ctrl ? ctrl : kDefault)[i];
+  hipLaunchKernelGGL(track_smooth_kernel, dim3((unsigned)frames), dim3(64), 0, (hipStream_t)stream, theta, score, max_score, M, link,
+                     frames, back, ahead, iters, delta * delta, min_members, cp, theta_out, members, stats);
+  return sfh_check_launch("track_smooth_kernel");
 }

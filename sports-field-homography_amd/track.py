@@ -5,12 +5,17 @@
     M, ... = al(frames_u8, prev=last_frame_of_previous_batch)    # B pairs: a clip processed in batches loses no pair
     M, ... = al(frames_u8, pairs=(ia, ib), m0=M_start)           # arbitrary pairs (previous ia[p], current ib[p]), caller's start
     theta2, source = propagate_theta(theta, M, ok, score=score, max_score=0.1, max_gap=30)
+    theta_s, stats, members = smooth_theta(theta, M, ok, score=score, max_score=0.1, radius=12)   # radius=(12, 0): causal
 
 M (P,1,3,3) float32 maps the normalised coordinates of the current frame of a pair to those of its previous frame, so
 theta_t = theta_{t-1} M_t.  stats (P,L,3) float64 = [first mean cost, last mean cost, counted pixels] per level, accepted
 (P,L) int32, ok (P,) int32: 0 marks a cut or a failed alignment.  Direct photometric alignment on luma planes, coarse to fine,
 ``iters`` robust Levenberg-Marquardt steps per level.  The rule is stated once in include/sfh_amd.h above the ``sfh_track_*``
 entries; csrc/track.hip runs it, tests/track_ref.py restates it in numpy.  The reference project has no counterpart.
+
+``smooth_theta`` combines, per frame, the thetas of the good frames within ``radius`` carried to that frame across M: a robust
+mean of estimates of one quantity, so it has no lag; it also outvotes an isolated bad theta and fills gaps.  The rule stands
+above ``sfh_track_smooth``; tests/smooth_ref.py restates it.
 
 A call launches on the caller's current stream, synchronises nothing and reads nothing back (``pairs=`` given as host
 sequences are checked on the host; given as device tensors they are read back once for that check): 1 launch per level for
@@ -183,52 +188,110 @@ class FrameAligner:
         return out
 
 
+def _clip_checked(who, theta, M, ok, score, max_score):
+    """what propagate_theta and smooth_theta ask of a clip -> (F, device, the score to gate by or None)"""
+    for name, t in (("theta", theta), ("M", M), ("ok", ok)):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise ValueError(f"{who}: {name} must be a CUDA tensor (there is no CPU path)")
+    if theta.dtype != torch.float32 or theta.dim() not in (3, 4) or tuple(theta.shape[-2:]) != (3, 3) or theta.numel() != theta.shape[0] * 9:
+        raise ValueError(f"{who}: theta must be float32 (F,1,3,3), got {theta.dtype} {tuple(theta.shape)}")
+    F = theta.shape[0]
+    if M.dtype != torch.float32 or M.numel() % 9 or M.numel() // 9 not in (F, F - 1) or ok.dtype != torch.int32 or ok.numel() != M.numel() // 9:
+        raise ValueError(f"{who}: M float32 and ok int32 must have {F} or {F - 1} rows, got {tuple(M.shape)}, {tuple(ok.shape)}")
+    if not (theta.is_contiguous() and M.is_contiguous() and ok.is_contiguous()):
+        raise ValueError(f"{who}: theta, M and ok must be contiguous")
+    use_score = score is not None and max_score is not None
+    if use_score and (not torch.is_tensor(score) or not score.is_cuda or score.dtype != torch.float32 or score.numel() != F
+                      or not score.is_contiguous()):
+        raise ValueError(f"{who}: score must be a contiguous float32 CUDA tensor ({F},)")
+    return F, theta.device, (score if use_score else None)
+
+
+def _clip_rows(M, ok, F, dev):
+    """M and ok as the entries read them: F rows, row t belongs to the pair (t - 1, t)"""
+    M9, link = M.reshape(-1, 9), ok.reshape(-1)
+    if M9.shape[0] == F - 1:
+        M9 = torch.cat([torch.zeros((1, 9), dtype=torch.float32, device=dev), M9])
+        link = torch.cat([torch.zeros((1,), dtype=torch.int32, device=dev), link])
+    return M9, link
+
+
 def propagate_theta(theta, M, ok, score=None, max_score=None, max_gap=30):
     """theta (F,1,3,3) | (F,3,3) float32; M, ok: FrameAligner's outputs over the clip - F rows (row t: the pair (t - 1, t);
     row 0 is not read) or F - 1 rows (the consecutive pairs of the F frames).  score (F,) float32 with max_score: the gate of
     visualize / TopViewRenderer.  -> (theta2 of theta's shape, source (F,) int32): frames without a usable theta get the
     nearest good frame's theta carried across the inter-frame homographies; source[t] = the frame it came from, t itself for a
     good frame, -1 (and nine NaNs) where no anchor is within max_gap unbroken links.  One launch, no read-back."""
-    for name, t in (("theta", theta), ("M", M), ("ok", ok)):
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise ValueError(f"propagate_theta: {name} must be a CUDA tensor (there is no CPU path)")
-    if theta.dtype != torch.float32 or theta.dim() not in (3, 4) or tuple(theta.shape[-2:]) != (3, 3) or theta.numel() != theta.shape[0] * 9:
-        raise ValueError(f"propagate_theta: theta must be float32 (F,1,3,3), got {theta.dtype} {tuple(theta.shape)}")
-    F, dev = theta.shape[0], theta.device
     max_gap = int(max_gap)
     if max_gap < 0:
         raise ValueError(f"propagate_theta: max_gap={max_gap} (>= 0)")
-    if M.dtype != torch.float32 or M.numel() % 9 or M.numel() // 9 not in (F, F - 1) or ok.dtype != torch.int32 or ok.numel() != M.numel() // 9:
-        raise ValueError(f"propagate_theta: M float32 and ok int32 must have {F} or {F - 1} rows, got {tuple(M.shape)}, {tuple(ok.shape)}")
-    if not (theta.is_contiguous() and M.is_contiguous() and ok.is_contiguous()):
-        raise ValueError("propagate_theta: theta, M and ok must be contiguous")
-    use_score = score is not None and max_score is not None
-    if use_score and (not torch.is_tensor(score) or not score.is_cuda or score.dtype != torch.float32 or score.numel() != F
-                      or not score.is_contiguous()):
-        raise ValueError(f"propagate_theta: score must be a contiguous float32 CUDA tensor ({F},)")
+    F, dev, score = _clip_checked("propagate_theta", theta, M, ok, score, max_score)
     theta2 = torch.empty_like(theta)
     source = torch.empty((F,), dtype=torch.int32, device=dev)
     if F == 0:
         return theta2, source
     with torch.cuda.device(dev):
-        M9, link = M.reshape(-1, 9), ok.reshape(-1)
-        if M9.shape[0] == F - 1:      # row t of the entry belongs to the pair (t - 1, t)
-            M9 = torch.cat([torch.zeros((1, 9), dtype=torch.float32, device=dev), M9])
-            link = torch.cat([torch.zeros((1,), dtype=torch.int32, device=dev), link])
-        _lib.check(_lib.load().sfh_track_propagate(_ptr(theta), _ptr(score) if use_score else None, float(max_score) if use_score else 0.0,
-                                                   _ptr(M9), _ptr(link), F, max_gap, _ptr(theta2), _ptr(source), _stream()),
-                   "track_propagate")
+        M9, link = _clip_rows(M, ok, F, dev)
+        _lib.check(_lib.load().sfh_track_propagate(_ptr(theta), _ptr(score) if score is not None else None,
+                                                   float(max_score) if score is not None else 0.0, _ptr(M9), _ptr(link), F, max_gap,
+                                                   _ptr(theta2), _ptr(source), _stream()), "track_propagate")
     return theta2, source
 
 
+def _radius(radius):
+    r = (radius, radius) if isinstance(radius, (int, np.integer)) else tuple(radius)
+    if len(r) != 2 or not all(isinstance(v, (int, np.integer)) and 0 <= v <= 31 for v in r):
+        raise ValueError(f"smooth_theta: radius={radius!r} (an int or (back, ahead), each in 0..31)")
+    return int(r[0]), int(r[1])
+
+
+def smooth_theta(theta, M, ok, score=None, max_score=None, radius=12, iters=3, delta=0.05, ctrl=None, min_members=1):
+    """theta, M, ok, score, max_score: as propagate_theta takes them.  radius: an int, or (back, ahead) - (r, 0) is the causal
+    form; iters: the re-weightings after the plain weighted mean; delta: the scale of the Geman-McClure weight in normalised
+    court units; ctrl: four (x, y) points of the normalised frame, host values (default: the lower three fifths of the frame);
+    min_members: fewer members give nine NaNs.  -> (theta_s of theta's shape, stats (F,3) float64 = [sum of weights, robust rms
+    spread of the members, the frame's own distance from the result (NaN where it has no usable theta)] over the control
+    points in normalised court units, members (F,) int32).  One launch, no synchronisation, no read-back."""
+    back, ahead = _radius(radius)
+    iters, delta, min_members = int(iters), float(delta), int(min_members)
+    if iters < 0:
+        raise ValueError(f"smooth_theta: iters={iters} (>= 0)")
+    if not delta > 0.0 or not math.isfinite(delta):
+        raise ValueError(f"smooth_theta: delta={delta} (> 0)")
+    if min_members < 1:
+        raise ValueError(f"smooth_theta: min_members={min_members} (>= 1)")
+    pts = None
+    if ctrl is not None:
+        pts = np.ascontiguousarray(np.asarray(ctrl.detach().cpu() if torch.is_tensor(ctrl) else ctrl, dtype=np.float32))
+        if pts.shape != (4, 2) or not np.isfinite(pts).all():
+            raise ValueError(f"smooth_theta: ctrl must be four finite (x, y) points, got shape {pts.shape}")
+    F, dev, score = _clip_checked("smooth_theta", theta, M, ok, score, max_score)
+    theta_s = torch.empty_like(theta)
+    stats = torch.empty((F, 3), dtype=torch.float64, device=dev)
+    members = torch.empty((F,), dtype=torch.int32, device=dev)
+    if F == 0:
+        return theta_s, stats, members
+    with torch.cuda.device(dev):
+        M9, link = _clip_rows(M, ok, F, dev)
+        _lib.check(_lib.load().sfh_track_smooth(_ptr(theta), _ptr(score) if score is not None else None,
+                                                float(max_score) if score is not None else 0.0, _ptr(M9), _ptr(link), F, back, ahead,
+                                                iters, delta, min_members, pts.ctypes.data if pts is not None else None, _ptr(theta_s),
+                                                _ptr(members), _ptr(stats), _stream()), "track_smooth")
+    return theta_s, stats, members
+
+
 def track_game(court_json, frames, dst_json, frame_size=None, factors=(8, 4, 2), iters=6, delta=0.06, min_overlap=0.25,
-               max_cost=None, max_score=None, max_gap=30, batch=16, names=None, device="cuda", frames_format="array", bgr=False):
+               max_cost=None, max_score=None, max_gap=30, batch=16, names=None, device="cuda", frames_format="array", bgr=False,
+               smooth_radius=None, smooth_iters=3, smooth_delta=0.05, smooth_min_members=1):
     """The host driver, in the style of ``mapping.rectify_game``: frames - an iterable of host uint8 (H,W,3) arrays (or, with
     frames_format "jpeg" / "png", of files as bytes, decoded on the GPU) in the order of the predictions of ``court_json``
     (names: their frame names, checked when given).  Aligns the clip batch by batch, every batch with the last frame of the
     one before as ``prev``, propagates once over the whole clip and writes ``dst_json``: the court JSON with ``theta``
     replaced and a per-frame ``source`` (the frame the theta came from; -1: none, theta is NaN).  ``mapping.CourtMapping``
-    reads it back.  Returns dst_json."""
+    reads it back.  With smooth_radius (an int or (back, ahead)) the clip is smoothed by ``smooth_theta`` instead of
+    propagated: ``source`` is the frame itself where a theta was produced and -1 elsewhere, and ``members``, ``spread`` and
+    ``deviation`` (smooth_theta's member count and second and third statistic; NaN is written as null) stand next to it.
+    Returns dst_json."""
     from ._codec import frames_from_files
     from .mapping import CourtMapping
     if frames_format not in ("array", "jpeg", "png"):
@@ -279,14 +342,26 @@ def track_game(court_json, frames, dst_json, frame_size=None, factors=(8, 4, 2),
     F = len(cm)
     theta = tabs["theta"].reshape(F, 1, 3, 3).contiguous()
     M, ok = torch.cat(Ms).contiguous(), torch.cat(oks).contiguous()      # F - 1 rows: the first batch has no prev
-    theta2, source = propagate_theta(theta, M, ok, score=tabs["scores"] if max_score is not None else None, max_score=max_score,
-                                     max_gap=max_gap)
-    theta2, source = theta2.cpu().numpy(), source.cpu().numpy()
+    score = tabs["scores"] if max_score is not None else None
+    extra = {}
+    if smooth_radius is None:
+        theta2, source = propagate_theta(theta, M, ok, score=score, max_score=max_score, max_gap=max_gap)
+        theta2, source = theta2.cpu().numpy(), source.cpu().numpy()
+    else:
+        theta2, stats, members = smooth_theta(theta, M, ok, score=score, max_score=max_score, radius=smooth_radius,
+                                              iters=smooth_iters, delta=smooth_delta, min_members=smooth_min_members)
+        theta2, stats, members = theta2.cpu().numpy(), stats.cpu().numpy(), members.cpu().numpy()
+        source = np.where(np.isfinite(theta2.reshape(F, 9)).all(axis=1), np.arange(F), -1)
+        null = lambda v: float(v) if math.isfinite(v) else None
+        extra = {"members": [int(m) for m in members], "spread": [null(v) for v in stats[:, 1]],
+                 "deviation": [null(v) for v in stats[:, 2]]}
     with open(court_json, "r") as f:
         raw = json.load(f)
     for k, name in enumerate(cm.names):
         raw[name]["theta"] = theta2[k].tolist()
         raw[name]["source"] = int(source[k])
+        for key, vals in extra.items():
+            raw[name][key] = vals[k]
     os.makedirs(os.path.dirname(os.path.abspath(dst_json)), exist_ok=True)
     with open(dst_json, "w") as f:
         json.dump(raw, f, indent=2)
