@@ -1676,6 +1676,43 @@ int sfh_track_propagate(const float* theta, const float* score, float max_score,
 int sfh_track_smooth(const float* theta, const float* score, float max_score, const float* M, const int32_t* link, int frames,
                      int back, int ahead, int iters, double delta, int min_members, const float* ctrl, float* theta_out,
                      int32_t* members, double* stats, void* stream);
+/* Coarse shift search (sfh_track_search).  The Levenberg-Marquardt descent of the tracker converges from a start within about
+ * 20 full-resolution pixels of the truth (256 x 144, factors 8, 4, 2); a faster pan leaves it in a wrong minimum with ok = 1.
+ * The search tries every whole-pixel shift of the coarsest plane within a radius, scores each by the tracker's own robust
+ * mean cost and hands the best one to the alignment as its start.  THE RULE, stated here once; csrc/search_core.h and the two
+ * track_search kernels run it, tests/search_ref.py restates it in numpy.  The reference project has no counterpart.
+ *
+ * Inputs and candidates.  Level f, planes (nframes, hl, wl) as sfh_track_planes writes them, hl = H / f, wl = W / f; pair p =
+ *   previous ia[p], current ib[p].  Radii rx, ry in 0..32.  Candidates (dx, dy) with |dx| <= rx, |dy| <= ry; candidate index
+ *   c = (dy + ry) (2 rx + 1) + (dx + rx).
+ * Counted pixels.  The current pixels (I, J) with 0 <= I + dy < hl and 0 <= J + dx < wl.  n = max(0, hl - |dy|) max(0, wl -
+ *   |dx|): analytic, exact as a double; nothing is counted at run time.
+ * Per-pixel cost.  r = (double)P_prev[I+dy][J+dx] - (double)P_cur[I][J]; q = r r / d2 with d2 = delta delta formed on the
+ *   host, c = 1 + q, ic = 1 / c, rho = (r r) ic: sfh_track_accumulate's Geman-McClure cost, operation for operation.
+ * Summation order, part of the rule.  One wave per candidate.  Lane l starts at +0.0 and adds rho of its counted pixels for
+ *   I ascending and, within a row, J = l, l + 64, .. ascending; the 64 lane sums go through the xor butterfly 32 .. 1
+ *   (wave_sum_all, csrc/common.h); mean = cost / n, one fp64 division (n = 0: NaN).  Every candidate of a pair with an index
+ *   outside [0, nframes) has the mean NaN.  The table of means, workspace[p (2 rx + 1)(2 ry + 1) + c], is an output.
+ * Admissibility and choice.  A candidate is admissible iff n >= nmin and its mean is finite; nmin = ceil(min_overlap hl wl)
+ *   from the host, the aligner's own number.  Among the admissible candidates the smallest key (mean, dx dx + dy dy, dy, dx),
+ *   compared lexicographically, is taken: ties prefer the identity, and a flat scene gives (0, 0).
+ * Outputs per pair.  shift (2) int32 = (dx, dy); found int32 = 1; m0 (9) fp32 = [1, 0, tx, 0, 1, ty, 0, 0, 1] with tx =
+ *   fl32(dx 2 f / (W - 1)), ty = fl32(dy 2 f / (H - 1)), each evaluated in fp64 as one exact integer product and one division and
+ *   rounded once: under m0 sfh_track_accumulate's px is J + dx up to rounding.  sstats (3) fp64 = [the best mean, the mean
+ *   of (0, 0) or NaN if that candidate is inadmissible, n of the best].
+ * No admissible candidate (a pair index outside the frames, too small an overlap everywhere, a NaN plane): shift = (0, 0),
+ *   found = 0, m0 = the identity, sstats = NaN, NaN, 0. */
+/* bytes of the table of means: pairs (2 rx + 1)(2 ry + 1) doubles; -1 for pairs outside 1..65535 or a radius outside 0..32 */
+int64_t sfh_track_search_workspace_bytes(int pairs, int rx, int ry);
+/* Two launches on the caller's stream.  The cost kernel: grid (ceil(candidates / 4), pairs), a wave per candidate, an fp64
+ * accumulator per lane, one plain store per (pair, candidate) into the workspace; no atomics.  The choice kernel: one wave per
+ * pair walks the table in candidate order, each lane keeps its best key, a fixed butterfly over keys, lane 0 stores.  Refused
+ * before any launch: a NULL pointer, nframes, H or W < 1, pairs outside 1..65535, f outside 1..16 or not dividing H and W,
+ * planes below 2 x 2, a radius outside 0..32, delta not > 0 or not finite, nmin < 1 (a whole number as a double), a workspace
+ * that is NULL or short.  ia, ib (pairs) int32 DEVICE arrays as sfh_track_accumulate takes them. */
+int sfh_track_search(const float* planes, int nframes, const int32_t* ia, const int32_t* ib, int pairs, int H, int W, int f,
+                     int rx, int ry, double delta, double nmin, void* workspace, long long workspace_bytes, int32_t* shift,
+                     int32_t* found, float* m0, double* sstats, void* stream);
 
 #ifdef __cplusplus
 }

@@ -13,6 +13,9 @@
 // * track_propagate_kernel: one thread per frame, O(max_gap) work, no scan.
 // * track_smooth_kernel: one wave per frame, a lane per frame of its window (smooth_core.h: chain, projection, weights, refit);
 //   the nine sums of a pass through wave_sum_all, so every lane holds the combined points and solves the refit for itself.
+// * track_search_cost_kernel, track_search_choice_kernel (at the end of the file): the coarse shift search that gives an
+//   alignment its start.  One wave per (pair, whole-pixel shift) sums the robust cost of the coarsest planes in a fixed order
+//   and stores the mean into a table; one wave per pair then takes the smallest key (search_core.h).  No atomics.
 #include <cmath>
 
 #include "common.h"
@@ -21,6 +24,7 @@
 #include "ycc.h"
 #include "track_core.h"
 #include "smooth_core.h"
+#include "search_core.h"
 
 namespace {
 
@@ -425,4 +429,129 @@ extern "C" int sfh_track_smooth(const float* theta, const float* score, float ma
   hipLaunchKernelGGL(track_smooth_kernel, dim3((unsigned)frames), dim3(64), 0, (hipStream_t)stream, theta, score, max_score, M, link,
                      frames, back, ahead, iters, delta * delta, min_members, cp, theta_out, members, stats);
   return sfh_check_launch("track_smooth_kernel");
+}
+
+// ------------------------------------------------------------------ coarse shift search
+namespace {
+
+constexpr int kSearchWaves = 4;   // candidates per workgroup of the cost kernel: one wave each
+
+struct SearchGeom {
+  int hl, wl, nframes, rx, ry, ncand;
+  double d2;
+};
+
+// One wave per (pair, candidate).  Lane l adds the costs of its counted pixels for I ascending and, within a row, J = l, l + 64,
+// .. ascending; wave_sum_all; one division by the analytic n; one plain store.  Both planes come through plain cached loads:
+// a row of the current plane and the shifted row of the previous one are each one contiguous run per wave instruction.
+__global__ __launch_bounds__(256) void track_search_cost_kernel(const float* __restrict__ planes, const int32_t* __restrict__ ia,
+                                                                const int32_t* __restrict__ ib, SearchGeom g,
+                                                                double* __restrict__ table) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int p = blockIdx.y;
+  const int c = blockIdx.x * kSearchWaves + wv;   // wave-uniform
+  if (c >= g.ncand) return;
+  const int fa = ia[p], fb = ib[p];
+  const bool pair_ok = fa >= 0 && fa < g.nframes && fb >= 0 && fb < g.nframes;   // wave-uniform
+  int dx, dy;
+  search_candidate(c, g.rx, g.ry, dx, dy);
+  double acc = 0.0;
+  if (pair_ok) {
+    const long plane = (long)g.hl * g.wl;
+    const float* prev = planes + fa * plane;
+    const float* cur = planes + fb * plane;
+    const int i0 = dy < 0 ? -dy : 0, i1 = dy > 0 ? g.hl - dy : g.hl;   // 0 <= I + dy < hl; empty when |dy| >= hl
+    const int j0 = dx < 0 ? -dx : 0, j1 = dx > 0 ? g.wl - dx : g.wl;   // 0 <= J + dx < wl
+    for (int I = i0; I < i1; ++I) {
+      const float* pr = prev + (long)(I + dy) * g.wl + dx;
+      const float* cr = cur + (long)I * g.wl;
+      for (int J = lane; J < j1; J += 64)
+        if (J >= j0) acc += search_rho(pr[J], cr[J], g.d2);
+    }
+  }
+  const double cost = wave_sum_all(acc);
+  const double mean = pair_ok ? cost / search_count(g.hl, g.wl, dx, dy) : (double)__builtin_nanf("");
+  if (lane == 0) table[(long)p * g.ncand + c] = mean;
+}
+
+// One wave per pair walks the table in candidate order, lane l the candidates l, l + 64, ..; each lane keeps its best key,
+// then the xor butterfly 32 .. 1 over keys (search_before is a strict total order on admissible keys, so every lane ends with
+// the same one).  Lane 0 stores.
+__global__ __launch_bounds__(64) void track_search_choice_kernel(const double* __restrict__ table, SearchGeom g, int f, int H, int W,
+                                                                 double nmin, int32_t* __restrict__ shift,
+                                                                 int32_t* __restrict__ found, float* __restrict__ m0,
+                                                                 double* __restrict__ sstats) {
+  const int lane = threadIdx.x, p = blockIdx.x;
+  const double* row = table + (long)p * g.ncand;
+  SearchKey best;
+  best.mean = 0.0, best.dx = 0, best.dy = 0, best.ok = false;
+  for (int c = lane; c < g.ncand; c += 64) {
+    int dx, dy;
+    search_candidate(c, g.rx, g.ry, dx, dy);
+    const SearchKey k = search_key(row[c], search_count(g.hl, g.wl, dx, dy), nmin, dx, dy);
+    if (search_before(k, best)) best = k;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    SearchKey other;
+    other.mean = __shfl_xor(best.mean, o);
+    other.dx = __shfl_xor(best.dx, o);
+    other.dy = __shfl_xor(best.dy, o);
+    other.ok = __shfl_xor(best.ok ? 1 : 0, o) != 0;
+    if (search_before(other, best)) best = other;
+  }
+  if (lane == 0) {
+    const double nand = (double)__builtin_nanf("");
+    const SearchKey zero = search_key(row[search_index(0, 0, g.rx, g.ry)], search_count(g.hl, g.wl, 0, 0), nmin, 0, 0);
+    const int dx = best.ok ? best.dx : 0, dy = best.ok ? best.dy : 0;
+    shift[p * 2] = dx;
+    shift[p * 2 + 1] = dy;
+    found[p] = best.ok ? 1 : 0;
+    float m[9];
+    search_m0(f, W, H, dx, dy, m);
+#pragma unroll
+    for (int k = 0; k < 9; ++k) m0[(long)p * 9 + k] = m[k];
+    sstats[(long)p * 3] = best.ok ? best.mean : nand;
+    sstats[(long)p * 3 + 1] = (best.ok && zero.ok) ? zero.mean : nand;
+    sstats[(long)p * 3 + 2] = best.ok ? search_count(g.hl, g.wl, dx, dy) : 0.0;
+  }
+}
+
+}  // namespace
+
+extern "C" int64_t sfh_track_search_workspace_bytes(int pairs, int rx, int ry) {
+  if (pairs < 1 || pairs > 65535 || !search_radii_ok(rx, ry)) return -1;
+  return (int64_t)pairs * search_candidates(rx, ry) * (int64_t)sizeof(double);
+}
+
+extern "C" int sfh_track_search(const float* planes, int nframes, const int32_t* ia, const int32_t* ib, int pairs, int H, int W,
+                                int f, int rx, int ry, double delta, double nmin, void* workspace, long long workspace_bytes,
+                                int32_t* shift, int32_t* found, float* m0, double* sstats, void* stream) {
+  const char* who = "track_search";
+  SFH_REQUIRE(planes && ia && ib && shift && found && m0 && sstats, "%s: null pointer", who);
+  SFH_REQUIRE(nframes > 0 && H > 0 && W > 0, "%s: bad geometry frames=%d H=%d W=%d", who, nframes, H, W);
+  SFH_REQUIRE(pairs >= 1 && pairs <= 65535, "%s: %d pairs (1..65535)", who, pairs);
+  SFH_REQUIRE(track_level_ok(f, H) && track_level_ok(f, W), "%s: level %d (1..16) does not divide the frame %dx%d", who, f, W, H);
+  SearchGeom g;
+  g.hl = H / f;
+  g.wl = W / f;
+  g.nframes = nframes;
+  SFH_REQUIRE(g.hl >= 2 && g.wl >= 2, "%s: planes %dx%d (at least 2x2)", who, g.wl, g.hl);
+  SFH_REQUIRE((long)nframes * g.hl * g.wl < (1L << 31), "%s: planes too large", who);
+  SFH_REQUIRE(search_radii_ok(rx, ry), "%s: radius rx=%d, ry=%d (0..%d)", who, rx, ry, SEARCH_MAX_RADIUS);
+  SFH_REQUIRE(delta > 0.0 && delta * delta > 0.0 && std::isfinite(delta * delta), "%s: delta=%g (> 0)", who, delta);
+  SFH_REQUIRE(nmin >= 1.0, "%s: nmin=%g (>= 1)", who, nmin);
+  const long long need = sfh_track_search_workspace_bytes(pairs, rx, ry);
+  SFH_REQUIRE(workspace != nullptr && workspace_bytes >= need, "%s: workspace of %lld bytes, %lld needed", who,
+              workspace ? workspace_bytes : 0LL, need);
+  g.rx = rx, g.ry = ry, g.ncand = search_candidates(rx, ry);
+  g.d2 = delta * delta;
+  const dim3 grid((unsigned)det_cdiv(g.ncand, kSearchWaves), (unsigned)pairs);
+  hipLaunchKernelGGL(track_search_cost_kernel, grid, dim3(64 * kSearchWaves), 0, (hipStream_t)stream, planes, ia, ib, g,
+                     (double*)workspace);
+  const int rc = sfh_check_launch("track_search_cost_kernel");
+  if (rc != SFH_OK) return rc;
+  hipLaunchKernelGGL(track_search_choice_kernel, dim3((unsigned)pairs), dim3(64), 0, (hipStream_t)stream, (const double*)workspace, g,
+                     f, H, W, nmin, shift, found, m0, sstats);
+  return sfh_check_launch("track_search_choice_kernel");
 }

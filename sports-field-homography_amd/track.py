@@ -6,6 +6,8 @@
     M, ... = al(frames_u8, pairs=(ia, ib), m0=M_start)           # arbitrary pairs (previous ia[p], current ib[p]), caller's start
     theta2, source = propagate_theta(theta, M, ok, score=score, max_score=0.1, max_gap=30)
     theta_s, stats, members = smooth_theta(theta, M, ok, score=score, max_score=0.1, radius=12)   # radius=(12, 0): causal
+    al = FrameAligner(frame_size=(640, 360), search=(16, 8))     # a coarse shift search gives every pair its start
+    m0, shift, found, sstats = al.coarse_shift(frames_u8)        # the search alone
 
 M (P,1,3,3) float32 maps the normalised coordinates of the current frame of a pair to those of its previous frame, so
 theta_t = theta_{t-1} M_t.  stats (P,L,3) float64 = [first mean cost, last mean cost, counted pixels] per level, accepted
@@ -16,6 +18,11 @@ entries; csrc/track.hip runs it, tests/track_ref.py restates it in numpy.  The r
 ``smooth_theta`` combines, per frame, the thetas of the good frames within ``radius`` carried to that frame across M: a robust
 mean of estimates of one quantity, so it has no lag; it also outvotes an isolated bad theta and fills gaps.  The rule stands
 above ``sfh_track_smooth``; tests/smooth_ref.py restates it.
+
+``search=(rx, ry)`` widens the capture range: before the descent every whole-pixel shift (dx, dy), |dx| <= rx, |dy| <= ry, of the
+coarsest plane (``factors[0]``; the reach in frame pixels is ``rx * factors[0]``) is scored by the tracker's own robust mean
+cost, and the best one is the start.  The rule stands above ``sfh_track_search``; tests/search_ref.py restates it.  Two more
+launches per call; with ``search=None`` every launch and every bit is as without the argument.
 
 A call launches on the caller's current stream, synchronises nothing and reads nothing back (``pairs=`` given as host
 sequences are checked on the host; given as device tensors they are read back once for that check): 1 launch per level for
@@ -49,10 +56,12 @@ def _frames_checked(fr, what, H, W):
 
 
 class FrameAligner:
-    def __init__(self, frame_size=(640, 360), factors=(8, 4, 2), iters=6, delta=0.06, min_overlap=0.25, max_cost=None, bgr=False):
+    def __init__(self, frame_size=(640, 360), factors=(8, 4, 2), iters=6, delta=0.06, min_overlap=0.25, max_cost=None, bgr=False,
+                 search=None):
         """frame_size (W, H); factors: the pyramid, coarse to fine, each in 1..16 dividing W and H; delta: the scale of the
         Geman-McClure weight in luma units (0..1); min_overlap: the share of a level's pixels that must be counted;
-        max_cost: a mean cost above it clears ``ok`` (None: no such gate)"""
+        max_cost: a mean cost above it clears ``ok`` (None: no such gate); search: None, or (rx, ry), each in 0..32 - the
+        radius of the coarse shift search in pixels of the plane of ``factors[0]``"""
         W, H = int(frame_size[0]), int(frame_size[1])
         factors, iters, delta, min_overlap = tuple(int(f) for f in factors), int(iters), float(delta), float(min_overlap)
         if W < 2 or H < 2:
@@ -70,6 +79,14 @@ class FrameAligner:
             raise ValueError(f"FrameAligner: max_cost={max_cost} (> 0, or None)")
         self.frame_size, self.factors, self.iters, self.delta, self.min_overlap = (W, H), factors, iters, delta, min_overlap
         self.max_cost, self.bgr = (None if max_cost is None else float(max_cost)), bool(bgr)
+        if search is not None:
+            if not isinstance(search, (tuple, list)) or len(search) != 2 or not all(
+                    isinstance(v, (int, np.integer)) and not isinstance(v, bool) and 0 <= v <= 32 for v in search):
+                raise ValueError(f"FrameAligner: search={search!r} (None, or (rx, ry), whole numbers in 0..32)")
+            if not factors:
+                raise ValueError("FrameAligner: search needs a level to search on, factors is empty")
+            search = (int(search[0]), int(search[1]))
+        self.search = search
         self._work = {}        # (frames, pairs, device, stream) -> buffers
 
     def __getstate__(self):
@@ -101,7 +118,68 @@ class FrameAligner:
                 # the consecutive pairs (k, k + 1)
                 "ia": torch.arange(0, P, dtype=torch.int32, device=dev), "ib": torch.arange(1, P + 1, dtype=torch.int32, device=dev),
             }
+            if self.search is not None:
+                sbytes = lib.sfh_track_search_workspace_bytes(P, *self.search)
+                w["search_ws"], w["search_ws_bytes"] = torch.empty(sbytes // 8, dtype=torch.float64, device=dev), sbytes
         return w
+
+    def _planes(self, lib, st, w, frames_u8, prev, N, levels):
+        """the plane launches of the given levels: 1 per level, 2 with ``prev``"""
+        (W, H), B = self.frame_size, frames_u8.shape[0]
+        for li in levels:
+            f, pl = self.factors[li], w["planes"][li]
+            if prev is not None:
+                _lib.check(lib.sfh_track_planes(_ptr(prev), 1, H, W, f, int(self.bgr), _ptr(pl), st), "track_planes")
+            _lib.check(lib.sfh_track_planes(_ptr(frames_u8), B, H, W, f, int(self.bgr), _ptr(pl[N - B:]), st), "track_planes")
+
+    def _search(self, lib, st, w, N, P, ia, ib, m0, shift, found, sstats):
+        """the two launches of sfh_track_search on the planes of factors[0]"""
+        (W, H), f = self.frame_size, self.factors[0]
+        nmin = float(math.ceil(self.min_overlap * (H // f) * (W // f)))
+        _lib.check(lib.sfh_track_search(_ptr(w["planes"][0]), N, _ptr(ia), _ptr(ib), P, H, W, f, self.search[0], self.search[1],
+                                        self.delta, nmin, _ptr(w["search_ws"]), w["search_ws_bytes"], _ptr(shift), _ptr(found),
+                                        _ptr(m0), _ptr(sstats), st), "track_search")
+
+    def _pairs_checked(self, frames_u8, prev, pairs):
+        """what __call__ and coarse_shift ask of their frames -> (device, B, N, P, ia, ib); ia, ib None: the consecutive pairs"""
+        W, H = self.frame_size
+        _frames_checked(frames_u8, "frames_u8", H, W)
+        dev, B = frames_u8.device, frames_u8.shape[0]
+        if prev is not None:
+            if pairs is not None:
+                raise ValueError("FrameAligner: prev and pairs exclude each other")
+            _frames_checked(prev, "prev", H, W)
+            if prev.shape[0] != 1 or prev.device != dev:
+                raise ValueError(f"FrameAligner: prev must be one frame (1,{H},{W},3) on {dev}")
+        N = B + (1 if prev is not None else 0)
+        ia = ib = None
+        if pairs is not None:
+            ia, ib = self._indices(pairs, B, dev)
+            P = ia.numel()
+        else:
+            P = max(N - 1, 0)
+        return dev, B, N, P, ia, ib
+
+    def coarse_shift(self, frames_u8, prev=None, pairs=None):
+        """the search alone, on the frames and pairs as __call__ takes them -> (m0 (P,1,3,3) float32: the start the best shift
+        stands for, shift (P,2) int32 = (dx, dy) in pixels of the plane of factors[0], found (P,) int32: 0 where no shift was
+        admissible (m0 is then the identity), sstats (P,3) float64 = [the best mean cost, the mean cost of (0, 0), the counted
+        pixels of the best]).  1 plane launch (2 with ``prev``) and 2 for the search; no synchronisation, no read-back."""
+        if self.search is None:
+            raise ValueError("FrameAligner: coarse_shift needs search=(rx, ry)")
+        dev, B, N, P, ia, ib = self._pairs_checked(frames_u8, prev, pairs)
+        out = (torch.empty((P, 1, 3, 3), dtype=torch.float32, device=dev), torch.empty((P, 2), dtype=torch.int32, device=dev),
+               torch.empty((P,), dtype=torch.int32, device=dev), torch.empty((P, 3), dtype=torch.float64, device=dev))
+        if P == 0 or B == 0:
+            return out
+        with torch.cuda.device(dev):
+            lib, st = _lib.load(), _stream()
+            w = self._buffers(N, P, dev)
+            if ia is None:
+                ia, ib = w["ia"], w["ib"]
+            self._planes(lib, st, w, frames_u8, prev, N, [0])
+            self._search(lib, st, w, N, P, ia, ib, *out)
+        return out
 
     @staticmethod
     def _indices(pairs, N, dev):
@@ -122,23 +200,11 @@ class FrameAligner:
     def __call__(self, frames_u8, prev=None, pairs=None, m0=None):
         """frames_u8 (B,H,W,3) uint8; prev (1,H,W,3): the frame before frames_u8[0]; pairs (ia, ib): integer sequences or
         tensors indexing frames_u8; m0 (P,1,3,3) | (P,3,3) float32: the start (default: the identity)"""
-        W, H = self.frame_size
-        _frames_checked(frames_u8, "frames_u8", H, W)
-        dev, B, L = frames_u8.device, frames_u8.shape[0], len(self.factors)
-        if prev is not None:
-            if pairs is not None:
-                raise ValueError("FrameAligner: prev and pairs exclude each other")
-            _frames_checked(prev, "prev", H, W)
-            if prev.shape[0] != 1 or prev.device != dev:
-                raise ValueError(f"FrameAligner: prev must be one frame (1,{H},{W},3) on {dev}")
-        N = B + (1 if prev is not None else 0)
-        ia = ib = None
-        if pairs is not None:
-            ia, ib = self._indices(pairs, B, dev)
-            P = ia.numel()
-        else:
-            P = max(N - 1, 0)
+        (W, H), L = self.frame_size, len(self.factors)
+        dev, B, N, P, ia, ib = self._pairs_checked(frames_u8, prev, pairs)
         if m0 is not None:
+            if self.search is not None:
+                raise ValueError("FrameAligner: search and m0 exclude each other (the search is about the identity)")
             if not torch.is_tensor(m0) or not m0.is_cuda or m0.dtype != torch.float32 or tuple(m0.shape) not in ((P, 1, 3, 3), (P, 3, 3)):
                 raise ValueError(f"FrameAligner: m0 must be a float32 CUDA tensor ({P},1,3,3)")
             if not m0.is_contiguous():
@@ -158,11 +224,13 @@ class FrameAligner:
                 M_out.copy_(start.view(P, 1, 3, 3))
                 stats.fill_(float("nan")), accepted.zero_(), ok.fill_(1)
                 return out
-            for li, f in enumerate(self.factors):
-                pl = w["planes"][li]
-                if prev is not None:
-                    _lib.check(lib.sfh_track_planes(_ptr(prev), 1, H, W, f, int(self.bgr), _ptr(pl), st), "track_planes")
-                _lib.check(lib.sfh_track_planes(_ptr(frames_u8), B, H, W, f, int(self.bgr), _ptr(pl[N - B:]), st), "track_planes")
+            self._planes(lib, st, w, frames_u8, prev, N, range(L))
+            if self.search is not None:
+                if "search_out" not in w:
+                    w["search_out"] = (torch.empty((P, 9), dtype=torch.float32, device=dev), torch.empty((P, 2), dtype=torch.int32, device=dev),
+                                       torch.empty((P,), dtype=torch.int32, device=dev), torch.empty((P, 3), dtype=torch.float64, device=dev))
+                self._search(lib, st, w, N, P, ia, ib, *w["search_out"])
+                start = w["search_out"][0]
             max_cost = self.max_cost if self.max_cost is not None else 0.0
             cur = start
             for li, f in enumerate(self.factors):
@@ -282,7 +350,7 @@ def smooth_theta(theta, M, ok, score=None, max_score=None, radius=12, iters=3, d
 
 def track_game(court_json, frames, dst_json, frame_size=None, factors=(8, 4, 2), iters=6, delta=0.06, min_overlap=0.25,
                max_cost=None, max_score=None, max_gap=30, batch=16, names=None, device="cuda", frames_format="array", bgr=False,
-               smooth_radius=None, smooth_iters=3, smooth_delta=0.05, smooth_min_members=1):
+               smooth_radius=None, smooth_iters=3, smooth_delta=0.05, smooth_min_members=1, search=None):
     """The host driver, in the style of ``mapping.rectify_game``: frames - an iterable of host uint8 (H,W,3) arrays (or, with
     frames_format "jpeg" / "png", of files as bytes, decoded on the GPU) in the order of the predictions of ``court_json``
     (names: their frame names, checked when given).  Aligns the clip batch by batch, every batch with the last frame of the
@@ -291,7 +359,7 @@ def track_game(court_json, frames, dst_json, frame_size=None, factors=(8, 4, 2),
     reads it back.  With smooth_radius (an int or (back, ahead)) the clip is smoothed by ``smooth_theta`` instead of
     propagated: ``source`` is the frame itself where a theta was produced and -1 elsewhere, and ``members``, ``spread`` and
     ``deviation`` (smooth_theta's member count and second and third statistic; NaN is written as null) stand next to it.
-    Returns dst_json."""
+    search: FrameAligner's, None or (rx, ry).  Returns dst_json."""
     from ._codec import frames_from_files
     from .mapping import CourtMapping
     if frames_format not in ("array", "jpeg", "png"):
@@ -313,7 +381,7 @@ def track_game(court_json, frames, dst_json, frame_size=None, factors=(8, 4, 2),
             fr = torch.from_numpy(np.ascontiguousarray(np.stack(chunk))).to(dev)
         if state["al"] is None:
             size = frame_size if frame_size is not None else (fr.shape[2], fr.shape[1])
-            state["al"] = FrameAligner(size, factors, iters, delta, min_overlap, max_cost, bgr)
+            state["al"] = FrameAligner(size, factors, iters, delta, min_overlap, max_cost, bgr, search=search)
         M, _, _, ok = state["al"](fr, prev=state["prev"])
         Ms.append(M), oks.append(ok)
         state["prev"] = fr[-1:].clone()
